@@ -22,6 +22,12 @@ cpu_baseline = the oracle's C/OpenMP restatement of the reference path (per-popu
 The collective runs over RCCL through the library's own communicator (no PyTorch; WGSASSIGN_COMM=torch
 uses torch.distributed instead, WGSASSIGN_COMM=socket a TCP all-reduce).  A rank whose RCCL communicator
 cannot initialise exits with status 75 and the launcher starts the ranks again over the socket all-reduce.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (metric, value, ms_per_step, the headline
+kernel's roofline).  --full adds everything else the line can carry: the sums after one more step, the per-rank sweep
+times and collective timings, the class-coded legs, the float32 (fast) mode, the assignment sweep, the CPU baseline, the
+other configurations (extra.paths) and the shard projection -- each still switched off by its --no-* option.
+--dump-outputs DIR writes what the timed path computed (numpy files, see dump_outputs) after the timed steps.
 """
 import argparse
 import json
@@ -49,6 +55,8 @@ def parse():
     ap.add_argument("--inds", dest="n", type=int, default=1000, help="individuals")
     ap.add_argument("--pops", dest="K", type=int, default=10, help="populations")
     ap.add_argument("--arith", dest="mode", default=os.environ.get("WGSASSIGN_MODE", "exact"), choices=["exact", "fast"])
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other leg below (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed path's outputs of its last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-assign", action="store_true", help="skip the assignment sweep leg")
     ap.add_argument("--no-paths", action="store_true", help="skip extra.paths (whole-path timings of the other configurations)")
@@ -57,7 +65,10 @@ def parse():
     ap.add_argument("--cpu-snps", type=int, default=200_000, help="SNP sample for the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="minimum CPU-baseline EM timing window")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)     # one rank, started by the launcher below
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 COMM_INIT_FAILED = 75          # wgsassign_amd.comm.COMM_INIT_FAILED (the launcher must not import the package)
@@ -283,7 +294,8 @@ def main():
     kernel_ms = [run_steps(em, args.steps)]
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
-    ssq = em.step_reduced(comm if use_dist else None)       # untimed: the sums after warmup + steps + 1 updates
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, em, K, lo, m, m_total, rank, world)
     ms_per_step = elapsed / args.steps * 1e3
     value = K * m_total * args.steps / elapsed          # per-population SNP-updates/s, whole job
 
@@ -305,9 +317,11 @@ def main():
         roofline["valu_busy_frac"] = round(pmc["em_valu_busy_frac"], 4)
         roofline["effective_clock_ghz"] = round(pmc["em_clock_ghz"], 3)
 
-    extra = {"gl_pair_terms_per_s": value * n_call, "synth_seconds": round(t_gen, 2),
-             "ssq_last": [float(x) for x in np.asarray(ssq)[:3]]}
-    if use_dist:
+    extra = {"gl_pair_terms_per_s": value * n_call, "synth_seconds": round(t_gen, 2)}
+    if args.full:
+        ssq = em.step_reduced(comm if use_dist else None)       # untimed: the sums after warmup + steps + 1 updates
+        extra["ssq_last"] = [float(x) for x in np.asarray(ssq)[:3]]
+    if use_dist and args.full:
         # every rank's own sweep time (the slowest decides a step), and the device time of the collectives the sharded path uses
         slots = np.zeros(world)
         slots[rank] = k_avg * 1e3
@@ -318,7 +332,7 @@ def main():
         os.environ.pop("WGSASSIGN_CODES")
     else:
         os.environ["WGSASSIGN_CODES"] = user_codes
-    codes_on = args.mode == "exact" and os.environ.get("WGSASSIGN_CODES", "1") != "0" and not args.no_coded
+    codes_on = args.full and args.mode == "exact" and os.environ.get("WGSASSIGN_CODES", "1") != "0" and not args.no_coded
     codes = {"available": False}
     if codes_on and not use_dist:
         extra["coded"], codes = coded_em_leg(ctx, device, beagle, em, K, per, n, m, mode, args)
@@ -326,7 +340,7 @@ def main():
             extra["coded"]["steady_state_sweep"]["speedup_over_float32_sweep"] = round(k_avg * 1e3 / extra["coded"]["steady_state_sweep"]["kernel_ms_avg"], 3)
 
     # the same sweep in WGS_MODE_FAST (float32 term evaluation, ~1e-6 of the reference), for comparison
-    if args.mode == "exact":
+    if args.full and args.mode == "exact":
         em_fast = device.EMBatch(beagle, np.arange(K, dtype=np.int32), mode=MODE_FAST)
         fast_ms = []
         for i in range(4):
@@ -341,7 +355,7 @@ def main():
                                             "value above is exact mode"}
 
     # assignment log-likelihood sweep (one pass producing all n x K sums), same matrix
-    if not args.no_assign:
+    if args.full and not args.no_assign:
         afs = device.AFSet(m, K, ctx=ctx)
         for k in range(K):
             em.clamp(k, per)
@@ -421,11 +435,11 @@ def main():
                               "coded_kernel_ms": a.get("coded", {}).get("kernel_ms"), "coded_identical_sums": a.get("coded", {}).get("identical_sums")}
 
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         # rank 0's host cores; at N > 1 a shorter window (the other ranks wait at the closing barrier)
         cpu = cpu_baseline(beagle, group_of, K, min(args.cpu_snps, m), args.cpu_seconds if world == 1 else min(args.cpu_seconds, 6.0))
     paths = None
-    if rank == 0 and world == 1 and not args.no_paths:
+    if rank == 0 and world == 1 and args.full and not args.no_paths:
         # the other BASELINE.json configurations and the reference README's LOO shape, whole paths, after the 80 GB
         # of the headline workload have been released
         em.close()
@@ -433,7 +447,7 @@ def main():
         em = beagle = None
         paths = whole_paths(ctx, device, args.mode)
         extra["paths"] = paths
-    if rank == 0 and world == 1 and not use_dist and args.mode == "exact" and not args.no_projection:
+    if rank == 0 and world == 1 and not use_dist and args.mode == "exact" and args.full and not args.no_projection:
         if em is not None:
             em.close()
             beagle.close()
@@ -445,7 +459,7 @@ def main():
                 "unit": "SNP-updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
                 "dtype": "f64" if args.mode == "exact" else "f32", "data": "synthetic",
-                "config": {"workload": "%d GPU(s), SNP-sharded: synthetic Beagle %d SNPs x %d ind, K=%d, EM sweep (+ pop_like sweep)" % (world, m_total, n, K),
+                "config": {"workload": "%d GPU(s), SNP-sharded: synthetic Beagle %d SNPs x %d ind, K=%d, EM sweep%s" % (world, m_total, n, K, " (+ pop_like sweep)" if "assign" in extra else ""),
                            "mode": args.mode, "snps_per_gpu": m,
                            "gl_bytes_per_gpu": gl_bytes, "comm": comm_note,
                            "rccl_ranks_seen": comm_info["rccl_ranks_seen"] if comm_info and comm_info["native"] else None,
@@ -463,6 +477,27 @@ def main():
         comm.close()
         if dist is not None:
             dist.destroy_process_group()
+
+
+DUMP_BYTES = 48 << 20       # --dump-outputs: frequencies + SNP indices of the sample, all ranks together (under 64 MB)
+
+
+def dump_outputs(d, em, K, lo, m, m_total, rank, world):
+    """--dump-outputs DIR: what a caller of the timed path (wgs_em_fit) reads back after its last step -- every population's
+    allele frequencies (EMBatch.get_f) -- on a fixed sample of the SNPs (all of them when they fit in DUMP_BYTES; else a seeded
+    choice, the same for the same --snps / --pops): allele_frequencies.npy (SNPs of the sample x K, float32) and
+    snp_index.npy (their global SNP indices, float64).  At N > 1 each rank writes its own SNPs of the sample, with the suffix
+    _rank<r>."""
+    rows = min(m_total, DUMP_BYTES // (4 * K + 8))
+    pick = np.arange(m_total) if rows == m_total else np.sort(np.random.default_rng(SEED).choice(m_total, rows, replace=False))
+    mine = pick[(pick >= lo) & (pick < lo + m)]
+    af = np.empty((len(mine), K), dtype=np.float32)
+    for k in range(K):
+        af[:, k] = em.get_f(k)[mine - lo]
+    os.makedirs(d, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(d, "allele_frequencies%s.npy" % suffix), af)
+    np.save(os.path.join(d, "snp_index%s.npy" % suffix), mine.astype(np.float64))
 
 
 def coded_em_leg(ctx, device, beagle, em_direct, K, per, n, m, mode, args):

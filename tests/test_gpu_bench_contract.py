@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_json_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--snps", "200000", "--inds", "100", "--pops", "5",
-                        "--steps", "3", "--warmup", "1", "--cpu-snps", "20000", "--cpu-seconds", "1"],
+                        "--steps", "3", "--warmup", "1", "--cpu-snps", "20000", "--cpu-seconds", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -34,13 +34,41 @@ def test_bench_json_line():
     assert abs(d["value"] - 5 * 200000 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
 
 
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline alone; --dump-outputs writes the frequencies the timed fit left, on the
+    same seeded SNP sample and bit for bit the same from run to run, in float32 / float64 and under 64 MB."""
+    snps, K = 2_000_000, 5
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--snps", str(snps), "--inds", "100", "--pops", str(K),
+                            "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    d = lines[0]
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f64" and d["cpu_baseline"] is None
+    assert abs(d["value"] - K * snps * 4 / (d["ms_per_step"] * 4e-3)) / d["value"] < 1e-6
+    assert not {"coded", "assign", "paths", "shard_projection", "fast_mode_sweep", "ssq_last"} & set(d["extra"])
+    a, b = dumps
+    assert sorted(a) == ["allele_frequencies.npy", "snp_index.npy"] and sorted(b) == sorted(a)
+    af, idx = a["allele_frequencies.npy"], a["snp_index.npy"]
+    assert af.dtype == np.float32 and idx.dtype == np.float64 and af.shape == (len(idx), K) and 0 < len(idx) < snps
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < snps
+    assert np.all((af >= 0) & (af <= 1))
+    assert all(a[f].tobytes() == b[f].tobytes() for f in a)
+
+
 def test_bench_line_says_what_rccl_saw():
     """WGS_FORCE_DIST=1 sends the one-GPU run down the N > 1 path over a real RCCL communicator of one rank: the line carries
     RCCL's own count of the communicator's ranks (ncclCommCount -- what tells an N-rank RCCL run from a socket fall-back), every
     rank's sweep time and the device time of the collectives; the headline stays the float32 sweep with frac < 1, and the
     class-coded leg reports the fit cold, warm and over the float32 slabs."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--snps", "200000", "--inds", "100", "--pops", "5",
-                        "--steps", "3", "--warmup", "1", "--no-cpu", "--no-paths"],
+                        "--steps", "3", "--warmup", "1", "--no-cpu", "--no-paths", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, WGS_FORCE_DIST="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip().startswith("{")][0])
@@ -49,7 +77,7 @@ def test_bench_line_says_what_rccl_saw():
     assert d["extra"]["collectives"]["allreduce_us"] > 0
     assert d["roofline"]["kernel"] == "em_sweep_kernel<exact>" and 0 < d["roofline"]["frac"] < 1
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--snps", "200000", "--inds", "100", "--pops", "5",
-                          "--steps", "3", "--warmup", "1", "--no-cpu", "--no-paths"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--steps", "3", "--warmup", "1", "--no-cpu", "--no-paths", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads([l for l in one.stdout.splitlines() if l.strip().startswith("{")][0])
     assert d1["config"]["rccl_ranks_seen"] is None and "collectives" not in d1["extra"]
@@ -64,7 +92,7 @@ def test_bench_self_launches_two_ranks(comm_env):
     GPU of the test box: WGSASSIGN_DEVICE=0; the all-reduce over the TCP star, or over torch's gloo), rank 0
     prints the one JSON line; the sharded sums of squares equal the single-process ones."""
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--snps", "200000", "--inds", "100", "--pops", "5",
-            "--steps", "3", "--warmup", "1", "--no-cpu", "--no-assign"]
+            "--steps", "3", "--warmup", "1", "--no-cpu", "--no-assign", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     one = subprocess.run(base, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert one.returncode == 0, one.stderr[-2000:]
