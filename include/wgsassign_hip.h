@@ -92,6 +92,8 @@ int wgs_loglike(wgs_ctx *ctx, const float *L, int64_t m, int64_t n, const float 
  * site0 is the global index of the shard's first SNP (partition labels use global indices). */
 int wgs_beagle_create(wgs_ctx *ctx, int64_t m, int64_t n, const int32_t *group_of, int32_t n_groups,
                       int64_t site0, wgs_beagle **out);
+/* Destroying a matrix first destroys every EM batch and score made from it; a later wgs_em_destroy or wgs_score_destroy of
+ * such a handle is a no-op (as long as nothing has been created since: a new object may reuse the address). */
 void wgs_beagle_destroy(wgs_beagle *b);
 /* Copy host rows [row0, row0+nrows) of an (m, 2n) float32 matrix into the slabs. */
 int wgs_beagle_upload_rows(wgs_beagle *b, const float *L_rows, int64_t row0, int64_t nrows);
@@ -156,6 +158,8 @@ int wgs_beagle_codes_prepare(wgs_beagle *b, int em);
  * the leave-one-out re-fit of glassy.py:65-78.  All fits start at f = 0.25 (emMAF.py:17-18). */
 int wgs_em_create(wgs_beagle *b, int32_t n_fits, const int32_t *fit_group, const int32_t *fit_skip,
                   int mode, wgs_em **out);
+/* A no-op for a batch that is gone already: destroyed before, or together with its matrix (wgs_beagle_destroy) -- as long
+ * as nothing has been created since. */
 void wgs_em_destroy(wgs_em *em);
 /* One EM update (emMAF_cy.pyx:10-23) of every still-active fit in ONE sweep over the slabs,
  * fused with the float64 sum over this shard's SNPs of (f_new - f_old)^2 per fit.  After the
@@ -211,6 +215,8 @@ const float *wgs_em_f_dev(wgs_em *em, int32_t fit);
  * WGSassign.py:243,303). */
 typedef struct wgs_afset wgs_afset;
 int wgs_afset_create(wgs_ctx *ctx, int64_t m, int32_t K, wgs_afset **out);
+/* Destroying a frequency set first destroys every score made over it; a later wgs_score_destroy of such a handle is a
+ * no-op (as long as nothing has been created since). */
 void wgs_afset_destroy(wgs_afset *a);
 int wgs_afset_upload(wgs_afset *a, const float *A_mK);           /* host (m, K) -> K device vectors */
 int wgs_afset_download(wgs_afset *a, float *A_mK);               /* K device vectors -> host (m, K) */
@@ -250,6 +256,8 @@ int wgs_assign_parts_exact(wgs_beagle *b, wgs_afset *a, const float *const *colp
 typedef struct wgs_score wgs_score;
 int wgs_score_create(wgs_beagle *b, wgs_afset *a, const float *const *colptr, int32_t row_lo, int32_t row_hi,
                      wgs_score **out);
+/* A no-op for a score that is gone already: destroyed before, or together with its matrix or frequency set -- as long as
+ * nothing has been created since. */
 void wgs_score_destroy(wgs_score *sc);
 int wgs_score_sums(wgs_score *sc, int mode, double *out);
 /* ... continued from the SNP shards before this one (NumPy's running total handed from shard to shard): see api.hip. */

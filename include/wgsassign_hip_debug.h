@@ -50,6 +50,11 @@ int wgs_debug_reader_comp_text(wgs_reader *r, int64_t comp_bytes, int64_t text_c
 int wgs_debug_rmse1d(wgs_ctx *ctx, const float *v1, const float *v2, int64_t m, double *out, int serial,
                      int *serial_blocks);
 
+/* Sweeps this EM batch has enqueued so far through each of its four sweep kernels (csrc/em_api.hip: em_enqueue_sweep):
+ * counts[0] em_sweep_kernel, [1] em_sweep_group_kernel, [2] em_coded_kernel, [3] em_coded_group_kernel.  A sweep counts once
+ * however many launches it takes and however many iterations it runs. */
+int wgs_debug_em_sweep_paths(wgs_em *em, int64_t counts[4]);
+
 /* Test hook for the EM kernel's correctly rounded divide (csrc/em_kernels.hip: div_exact): number of
  * 2^20 x per_thread pseudo-random EM-shaped operand pairs whose quotient differs bitwise from the
  * compiler's IEEE double divide. */

@@ -384,6 +384,7 @@ static int em_enqueue_sweep(wgs_em *em, const std::vector<int32_t> &list, FitDes
         }
         HIP_TRY(hipMemcpyAsync(Dg, Hg, sizeof(int32_t) * 2 * n_groups, hipMemcpyHostToDevice, ctx->stream));
     }
+    ++em->sweep_paths[(codes ? 2 : 0) + (shared ? 1 : 0)];
     if (ev0) HIP_TRY(hipEventRecord(ev0, ctx->stream));
     const int64_t per_unit = ((ntiles + 3) / 4 + 7) / 8 * 8 + 8;       // workgroups per fit / per group: slices stay below 2^31
     const size_t max_units = (size_t)std::max<int64_t>(1, ((1ll << 31) - 1) / per_unit);
@@ -798,6 +799,13 @@ int wgs_em_fit_stats(wgs_em *em, int32_t *iterations, int32_t *chain_batches, do
 }
 
 int wgs_em_last_chain_serial_blocks(wgs_em *em) { return em ? em->last_chain_serial_blocks : -1; }
+
+int wgs_debug_em_sweep_paths(wgs_em *em, int64_t counts[4])
+{
+    WGS_REQUIRE(em && counts, "null argument");
+    for (int i = 0; i < 4; ++i) counts[i] = em->sweep_paths[i];
+    return 0;
+}
 
 int wgs_em_last_sweep_ms(wgs_em *em, float *ms)
 {

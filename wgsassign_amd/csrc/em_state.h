@@ -44,6 +44,8 @@ struct wgs_em {
     size_t chain_batch_jobs = 0;
     double fit_seconds = 0.0;
     int fit_iterations = 0, fit_chain_batches = 0;
+    // sweeps enqueued through em_sweep_kernel | em_sweep_group_kernel | em_coded_kernel | em_coded_group_kernel (wgs_debug_em_sweep_paths)
+    int64_t sweep_paths[4] = {0, 0, 0, 0};
 };
 
 static inline float *em_f(wgs_em *em, int fit, int which) { return em->fbuf[which] + (size_t)fit * em->b->m; }

@@ -416,6 +416,13 @@ class EMBatch:
         check(_lib.load().wgs_em_fit_stats(self._h, ctypes.byref(it), ctypes.byref(ch), ctypes.byref(sec), ctypes.byref(ms)))
         return it.value, ch.value, sec.value, ms.value
 
+    def sweep_paths(self):
+        """Test hook: sweeps enqueued so far through em_sweep_kernel, em_sweep_group_kernel, em_coded_kernel and
+        em_coded_group_kernel (wgs_debug_em_sweep_paths)."""
+        out = (ctypes.c_int64 * 4)()
+        check(_lib.load().wgs_debug_em_sweep_paths(self._h, out))
+        return [int(x) for x in out]
+
     def close(self):
         if self._h:
             _lib.load().wgs_em_destroy(self._h)
