@@ -135,9 +135,9 @@ void wgs_beagle_drop_codes(wgs_beagle *b)
     ++b->codes_generation;
 }
 
-static bool codes_switched_off()
+bool codes_switched_off()
 {
-    const char *env = getenv("WGSASSIGN_CODES");           // read at every use, so one process can compare both paths
+    const char *env = getenv("WGSASSIGN_CODES");           // read at every use (EM sweeps: once per call), so one process can compare both paths
     return env && env[0] == '0';
 }
 

@@ -12,12 +12,19 @@
 #include "common.h"
 #include "em_state.h"
 
+// Enqueues `units` fits or fit groups as launch(first, count) over slices of at most `per_launch` of them.
+template <class Launch> static int em_launch_sliced(size_t units, size_t per_launch, Launch launch)
+{
+    for (size_t off = 0; off < units; off += per_launch)
+        if (launch(off, (int)std::min(per_launch, units - off))) return 1;
+    return 0;
+}
+
 extern "C" {
 
 /* ------------------------------------------------------------------ EM */
 
 // (struct wgs_em: em_state.h)
-
 
 void wgs_em_destroy(wgs_em *em)
 {
@@ -26,16 +33,6 @@ void wgs_em_destroy(wgs_em *em)
     for (int i = 0; i < 3; ++i)
         if (em->fbuf[i]) (void)hipFree(em->fbuf[i]);
     if (em->d_part_b) (void)hipFree(em->d_part_b);
-    for (int i = 0; i < 2; ++i)
-        if (em->h_ssq[i]) (void)hipHostFree(em->h_ssq[i]);
-    if (em->d_descs) (void)hipFree(em->d_descs);
-    if (em->h_descs) (void)hipHostFree(em->h_descs);
-    if (em->d_groups) (void)hipFree(em->d_groups);
-    if (em->h_groups) (void)hipHostFree(em->h_groups);
-    for (int i = 0; i < 2; ++i) {
-        if (em->d_groups2[i]) (void)hipFree(em->d_groups2[i]);
-        if (em->h_groups2[i]) (void)hipHostFree(em->h_groups2[i]);
-    }
     if (em->d_ssq) (void)hipFree(em->d_ssq);
     if (em->d_part) (void)hipFree(em->d_part);
     if (em->d_part2) (void)hipFree(em->d_part2);
@@ -45,9 +42,12 @@ void wgs_em_destroy(wgs_em *em)
     if (em->ev1) (void)hipEventDestroy(em->ev1);
     for (hipEvent_t e : em->ev_sw) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) {
-        if (em->d_descs2[i]) (void)hipFree(em->d_descs2[i]);
-        if (em->h_descs2[i]) (void)hipHostFree(em->h_descs2[i]);
+        if (em->d_descs[i]) (void)hipFree(em->d_descs[i]);
+        if (em->h_descs[i]) (void)hipHostFree(em->h_descs[i]);
+        if (em->d_groups[i]) (void)hipFree(em->d_groups[i]);
+        if (em->h_groups[i]) (void)hipHostFree(em->h_groups[i]);
         if (em->h_state[i]) (void)hipHostFree(em->h_state[i]);
+        if (em->h_ssq[i]) (void)hipHostFree(em->h_ssq[i]);
         if (em->ev_it[i]) (void)hipEventDestroy(em->ev_it[i]);
     }
     for (void *p : {(void *)em->d_state, (void *)em->d_ssq2, (void *)em->d_jobs, (void *)em->d_chain_out, em->d_chain_batch})
@@ -104,7 +104,6 @@ int wgs_em_create(wgs_beagle *b, int32_t n_fits, const int32_t *fit_group, const
             return 1;
         }
     }
-    HIP_TRY(wgs_malloc(&em->d_descs, sizeof(FitDesc) * n_fits));
     HIP_TRY(wgs_malloc(&em->d_ssq, sizeof(double) * n_fits));
     HIP_TRY(wgs_malloc(&em->d_part, sizeof(double) * (size_t)n_fits * wgs_ntiles(b->m)));
     HIP_TRY(wgs_malloc(&em->d_part2, sizeof(double) * (size_t)n_fits * ssq_reduce_chunks()));
@@ -112,9 +111,12 @@ int wgs_em_create(wgs_beagle *b, int32_t n_fits, const int32_t *fit_group, const
     HIP_TRY(wgs_malloc(&em->d_chain_work, rmse_chain_workspace_bytes(b->m)));
     HIP_TRY(hipEventCreate(&em->ev0));
     HIP_TRY(hipEventCreate(&em->ev1));
-    HIP_TRY(hipHostMalloc(&em->h_descs, sizeof(FitDesc) * n_fits, hipHostMallocDefault));
-    HIP_TRY(wgs_malloc(&em->d_groups, sizeof(int32_t) * 2 * n_fits));
-    HIP_TRY(hipHostMalloc(&em->h_groups, sizeof(int32_t) * 2 * n_fits, hipHostMallocDefault));
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(wgs_malloc(&em->d_descs[i], sizeof(FitDesc) * n_fits));
+        HIP_TRY(hipHostMalloc(&em->h_descs[i], sizeof(FitDesc) * n_fits, hipHostMallocDefault));
+        HIP_TRY(wgs_malloc(&em->d_groups[i], sizeof(int32_t) * 2 * n_fits));
+        HIP_TRY(hipHostMalloc(&em->h_groups[i], sizeof(int32_t) * 2 * n_fits, hipHostMallocDefault));
+    }
     if (launch_fill(b->ctx, em->fbuf[0], (int64_t)n_fits * b->m, 0.25f)) return 1;   // emMAF.py:17-18
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     guard.dismiss();
@@ -146,34 +148,28 @@ static double loo_codes_saving(const wgs_codes_plan *P, double cols)
 }
 
 // The model's own numbers for a batch of fits that sweep `swept` bytes of slabs with `cols` individuals per slab on average: what a
-// sweep over the float32 slabs takes, the share of it a coded sweep saves, what the encode pass costs.  em_codes_pay decides with
-// them and wgs_codes_model hands them out, so that what is reported beside a measurement is what decided.
+// sweep over the float32 slabs takes, the share of it a coded sweep saves, what the encode pass costs.  em_codes_decide decides with
+// them for em_codes_pay and for wgs_codes_model, which hands them out, so that what is reported beside a measurement is what decided.
 struct EmCodesModel {
     double direct_ms = 0.0, saves = 0.0, build_ms = 0.0;
     bool sampled = false;          // saves / build_ms come from the matrix's own sample pass (else from the fixed-error typical)
     bool codable = false;          // the sample pass found the matrix worth coding, with the slabs' own numbering
+    bool pays = false;             // em_codes_decide: the sweeps ahead repay the encode pass
 };
 static EmCodesModel em_codes_model(wgs_beagle *b, double swept, double cols, bool shared, bool sample)
 {
     EmCodesModel M;
-    auto saves = [&](double classes_per_slab, int lrows) { return wgs_em_codes_saving(classes_per_slab, cols, lrows); };
     if (shared) {
         constexpr double LOO_MS_PER_TERM = 7.6e-10;          // em_sweep_group_kernel, per (fit, SNP, individual)
         M.direct_ms = swept / 8.0 * LOO_MS_PER_TERM;
-        const wgs_codes_plan *P = wgs_beagle_codes_plan(b);
-        M.sampled = true;
-        M.codable = P && P->state > 0 && P->lrows > 0;
-        if (!M.codable) return M;
-        M.saves = std::max(0.0, loo_codes_saving(P, cols));
-        M.build_ms = wgs_codes_build_ms_estimate(b, P->slots);
-        return M;
+    } else {
+        M.direct_ms = swept / 6.0e9;
+        // fixed-error 2x data shows ~4.6 * cols^0.25 classes per (slab, SNP): 14.7 at 100, 12.7 at 62, 10.5 at 40
+        M.saves = wgs_em_codes_saving(4.6 * pow(std::max(1.0, cols), 0.25), cols, 24);
+        M.build_ms = wgs_codes_build_ms_estimate(b, 64);
+        M.codable = true;
+        if (!sample) return M;
     }
-    M.direct_ms = swept / 6.0e9;
-    // fixed-error 2x data shows ~4.6 * cols^0.25 classes per (slab, SNP): 14.7 at 100, 12.7 at 62, 10.5 at 40
-    M.saves = saves(4.6 * pow(std::max(1.0, cols), 0.25), 24);
-    M.build_ms = wgs_codes_build_ms_estimate(b, 64);
-    M.codable = true;
-    if (!sample) return M;
     const wgs_codes_plan *P = wgs_beagle_codes_plan(b);
     M.sampled = true;
     M.codable = P && P->state > 0 && P->lrows > 0;
@@ -181,32 +177,43 @@ static EmCodesModel em_codes_model(wgs_beagle *b, double swept, double cols, boo
         M.saves = 0.0;
         return M;
     }
-    M.saves = saves(P->mean_l, P->lrows);
+    M.saves = shared ? std::max(0.0, loo_codes_saving(P, cols)) : wgs_em_codes_saving(P->mean_l, cols, P->lrows);
     M.build_ms = wgs_codes_build_ms_estimate(b, P->slots);
     return M;
 }
 
-static bool em_codes_pay(const wgs_em *em, const std::vector<int32_t> &order, int fewest_cols, int sweeps_ahead, bool shared)
+// Whether the codes pay for a batch of fits with `ahead` sweeps to come, and the model that said so: a first estimate with the
+// classes typical of fixed-error data turns small matrices away without a sample pass, else the matrix's own sample pass decides.
+static EmCodesModel em_codes_decide(wgs_beagle *b, double swept, double cols, bool shared, double ahead)
+{
+    const EmCodesModel T = em_codes_model(b, swept, cols, false, false);
+    if (!shared && ahead * T.saves * T.direct_ms <= T.build_ms) return T;
+    EmCodesModel M = em_codes_model(b, swept, cols, shared, true);
+    M.pays = M.codable && ahead * M.saves * M.direct_ms > M.build_ms;
+    return M;
+}
+
+static int env_int(const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; }
+
+// The environment switches of the sweeps' policy, read where wgs_em_step_dev / wgs_em_fit construct it (tests change them between calls)
+struct EmSwitches {
+    bool codes = !codes_switched_off();                         // WGSASSIGN_CODES=0: no codes at all -- and no sample pass to decide about them
+    bool loo_codes = env_int("WGSASSIGN_LOO_CODES", 1) != 0;    // 0: leave-one-out batches keep the float32 kernel
+    int codes_min = env_int("WGSASSIGN_EM_CODES_MIN", 28);      // smallest population swept through the codes (tests lower it)
+    bool sweeps_set = getenv("WGSASSIGN_EM_CODES_SWEEPS") != nullptr;    // =k: "k or more sweeps ahead" replaces the cost models
+    int sweeps_min = env_int("WGSASSIGN_EM_CODES_SWEEPS", 0);   //   (0: always; tests)
+    bool fuse = env_int("WGSASSIGN_EM_FUSE", 2) >= 2;           // 0 or 1: one iteration per sweep
+};
+
+static bool em_codes_pay(const wgs_em *em, double swept, double cols, int sweeps_ahead, bool shared, const EmSwitches &sw)
 {
     wgs_beagle *b = em->b;
-    if (const char *sw = getenv("WGSASSIGN_EM_CODES_SWEEPS")) return sweeps_ahead >= atoi(sw) || b->direct_sweeps >= 3;
+    if (sw.sweeps_set) return sweeps_ahead >= sw.sweeps_min || b->direct_sweeps >= 3;
     // a fit uses ~14 iterations: what this one has done already (the codes' memory may arrive in the middle of it) no longer counts --
     // but a fit that has gone past 14 is taken to need a few more
     double ahead = std::min<double>(sweeps_ahead, std::max(3, 14 - em->fit_iterations));
     if (sweeps_ahead <= 0 && b->direct_sweeps >= 3) ahead = 12;
-    double swept = 0.0, cols = 0.0;
-    for (int j : order) {
-        swept += 8.0 * (double)b->slabs[em->group[j]].ncols * (double)b->m;
-        cols += (double)b->slabs[em->group[j]].ncols;
-    }
-    cols /= (double)std::max<size_t>(1, order.size());
-    (void)fewest_cols;
-    if (!shared) {      // a first estimate with the classes typical of fixed-error data turns small matrices away without a sample pass
-        const EmCodesModel T = em_codes_model(b, swept, cols, false, false);
-        if (ahead * T.saves * T.direct_ms <= T.build_ms) return false;
-    }
-    const EmCodesModel M = em_codes_model(b, swept, cols, shared, true);
-    return M.codable && ahead * M.saves * M.direct_ms > M.build_ms;
+    return em_codes_decide(b, swept, cols, shared, ahead).pays;
 }
 
 /* The cost models' own predictions for this matrix (so that a caller can print them beside what it measures: bench.py,
@@ -229,15 +236,13 @@ int wgs_codes_model(wgs_beagle *b, int32_t K_score, double *out)
         ++groups;
     }
     cols /= std::max(1, groups);
-    const EmCodesModel T = em_codes_model(b, swept, cols, false, false);
-    const bool first_ok = 14.0 * T.saves * T.direct_ms > T.build_ms;
-    const EmCodesModel M = first_ok ? em_codes_model(b, swept, cols, false, true) : T;
+    const EmCodesModel M = em_codes_decide(b, swept, cols, false, 14.0);
     for (int i = 0; i < 12; ++i) out[i] = 0.0;
     out[0] = M.direct_ms;
     out[1] = M.saves;
     out[2] = M.build_ms;
     out[3] = 14.0;
-    out[4] = (first_ok && M.codable && 14.0 * M.saves * M.direct_ms > M.build_ms) ? 1.0 : 0.0;
+    out[4] = M.pays ? 1.0 : 0.0;
     out[9] = M.sampled ? 1.0 : 0.0;
     if (K_score > 0) {
         if (wgs_codes_scoring_model(b, K_score, &out[5], &out[6], &out[7])) out[8] = out[5] * (1.0 - out[6]) > out[7] ? 1.0 : 0.0;
@@ -265,97 +270,106 @@ static bool em_fuse_buffers(wgs_em *em)
     return true;
 }
 
-/* Enqueue one sweep (+ the fixed-order reduction of its sums) for the fits in `list`: descriptors into the pinned
- * array H and from there to D.  Fits of different populations stream their slabs once (nontemporal loads); when
- * several fits share a slab (leave-one-out batches) they are ordered by slab and swept in groups of up to
- * em_fits_per_group() per wavefront (group table Hg -> Dg), which share the tile's loads and conversions.
- * ssq_base[j] receives fit j's sum; state_base (device, may be NULL) holds the fit states a sweep honours. */
-static int em_enqueue_sweep(wgs_em *em, const std::vector<int32_t> &list, FitDesc *H, FitDesc *D, int32_t *Hg, int32_t *Dg,
-                            double *ssq_base, int32_t *state_base, hipEvent_t ev0, hipEvent_t ev1, int sweeps_ahead,
-                            const std::vector<int32_t> *may_fuse = nullptr, double *ssq_base_b = nullptr, bool fuse_agreed = true,
-                            int *can_fuse_out = nullptr)
+// What one sweep does, decided before anything of it is written or enqueued.
+struct EmSweepPlan {
+    std::vector<int32_t> order;                        // the fits in launch order: by slab when several share one
+    bool shared = false;                               // several fits per slab: the group kernels, up to fits_per_group per group
+    int fits_per_group = 1;
+    wgs_codes *codes = nullptr;                        // the coded kernels read these; nullptr: the float32 slabs
+    bool can_fuse = false;                             // this rank could run two iterations per sweep (what it tells the others)
+    bool fusing = false;                               // it does, for the fits with (*may_fuse)[j] >= 2
+    const std::vector<int32_t> *may_fuse = nullptr;
+};
+
+/* The plan of one sweep over the fits in `list`: which kernel, through the class codes or not, one iteration or two.  Fits of
+ * different populations stream their slabs once (nontemporal loads); fits that share a slab (leave-one-out batches) are ordered by
+ * slab and swept in groups per wavefront, which share the tile's loads and conversions.  May build the codes, run the sample pass and
+ * allocate the buffers of fused sweeps, enqueues no sweep.  may_fuse[j] >= 2 (NULL: none): fit j may run two iterations. */
+static EmSweepPlan em_plan_sweep(wgs_em *em, const std::vector<int32_t> &list, int sweeps_ahead, const std::vector<int32_t> *may_fuse,
+                                 bool fuse_agreed, const EmSwitches &sw)
 {
-    wgs_ctx *ctx = em->b->ctx;
-    const int64_t ntiles = wgs_ntiles(em->b->m);
-    std::vector<int32_t> order(list);
-    std::vector<char> seen(em->b->n_groups, 0);
-    bool shared = false;
-    for (int j : order) {
-        shared = shared || seen[em->group[j]];
-        seen[em->group[j]] = 1;
+    wgs_beagle *b = em->b;
+    EmSweepPlan p;
+    double swept = 0.0, cols = 0.0;                    // (sums of integers: exact in any order)
+    int fewest = INT32_MAX;
+    std::vector<char> seen(b->n_groups, 0);
+    for (int j : list) {
+        const int g = em->group[j], ncols = b->slabs[g].ncols;
+        p.shared = p.shared || seen[g];
+        seen[g] = 1;
+        swept += 8.0 * (double)ncols * (double)b->m;
+        cols += (double)ncols;
+        fewest = std::min(fewest, ncols);
     }
-    if (shared) std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return em->group[x] < em->group[y]; });
+    cols /= (double)list.size();
+    p.order = list;
+    if (p.shared) std::stable_sort(p.order.begin(), p.order.end(), [&](int32_t x, int32_t y) { return em->group[x] < em->group[y]; });
     // exact mode on a coded matrix: the sweep through the class codes (same frequencies, bit for bit)
     // -- leave-one-out batches (several fits per slab) where the table saves instructions (loo_codes_saving), else they stay with
-    // em_sweep_group_kernel and its shared loads and conversions
+    // em_sweep_group_kernel and its shared loads and conversions (also when the codes exist already: a scoring sweep may have built them)
     // -- and small populations stay with em_sweep_kernel too: below ~28 individuals the table costs more than it saves
     // (measured: 20 individuals 0.98x, 30 1.16x, 36 1.26x, 62 1.64x, 100 2.1x)
-    // -- and the codes are BUILT for it only when the sweeps still to come repay the encode pass (em_codes_pay below).
+    // -- and the codes are BUILT for it only when the sweeps still to come repay the encode pass (em_codes_pay).
     // Codes that exist already (a scoring sweep built them, or wgs_beagle_codes_prepare) are used at once.
-    const bool loo_codes = !(getenv("WGSASSIGN_LOO_CODES") && atoi(getenv("WGSASSIGN_LOO_CODES")) == 0);
-    const char *codes_env = getenv("WGSASSIGN_CODES");      // ("0": no codes at all -- and no sample pass to decide about them; codes.hip reads it the same way)
-    bool worth = em->mode == WGS_MODE_EXACT && (!shared || loo_codes) && !(codes_env && codes_env[0] == '0');
-    const char *min_env = getenv("WGSASSIGN_EM_CODES_MIN");    // tests lower it to run small populations through the codes
-    const int min_cols = min_env ? atoi(min_env) : 28;
-    int fewest = INT32_MAX;
-    for (int j : order) fewest = std::min(fewest, (int)em->b->slabs[em->group[j]].ncols);
-    worth = worth && fewest >= min_cols;
-    if (worth && shared && !getenv("WGSASSIGN_EM_CODES_SWEEPS")) {      // (also when the codes exist already: a scoring sweep may have built them)
-        double cols = 0.0;
-        for (int j : order) cols += (double)em->b->slabs[em->group[j]].ncols;
-        worth = loo_codes_saving(wgs_beagle_codes_plan(em->b), cols / (double)order.size()) > 0.03;
-    }
-    const bool build = worth && em_codes_pay(em, order, fewest, sweeps_ahead, shared);
-    wgs_codes *codes = nullptr;
+    const bool worth = em->mode == WGS_MODE_EXACT && sw.codes && (!p.shared || sw.loo_codes) && fewest >= sw.codes_min &&
+                       (!p.shared || sw.sweeps_set || loo_codes_saving(wgs_beagle_codes_plan(b), cols) > 0.03);
+    const bool build = worth && em_codes_pay(em, swept, cols, sweeps_ahead, p.shared, sw);
     {
         WGS_STALL_SCOPE("wgs_beagle_codes from the sweep");
-        codes = worth ? wgs_beagle_codes(em->b, build, false) : nullptr;     // (memory not there yet: this sweep goes direct)
-        if (codes && codes->lrows == 0 && codes->local_skipped && build) {
+        p.codes = worth ? wgs_beagle_codes(b, build, false) : nullptr;     // (memory not there yet: this sweep goes direct)
+        if (p.codes && p.codes->lrows == 0 && p.codes->local_skipped && build) {
             // built by a scoring sweep, without the slabs' own numbering: this fit repays a full build
-            const wgs_codes_plan keep = em->b->plan;
-            wgs_beagle_drop_codes(em->b);
-            em->b->plan = keep;
-            codes = wgs_beagle_codes(em->b, true, false);
+            const wgs_codes_plan keep = b->plan;
+            wgs_beagle_drop_codes(b);
+            b->plan = keep;
+            p.codes = wgs_beagle_codes(b, true, false);
         }
     }
-    WGS_STALL_SCOPE("the sweep's launches");
-    if (codes && (codes->lrows == 0 || !em_coded_usable(ctx))) codes = nullptr;
-    if (worth && !codes) ++em->b->direct_sweeps;          // (a sweep the codes could have served)
+    WGS_STALL_SCOPE("the sweep's plan");
+    if (p.codes && (p.codes->lrows == 0 || !em_coded_usable(b->ctx))) p.codes = nullptr;
+    if (worth && !p.codes) ++b->direct_sweeps;          // (a sweep the codes could have served)
     // two iterations per sweep (em_kernels.hip: fused iterations): the coded sweep only, for the fits the caller allows (iterations
     // left, a place for the second sums); needs a third frequency buffer and a second set of partial sums, allocated on first use.
     // `can_fuse` is what THIS rank could do -- every input of it is rank-local (the codes' arrival, a cost model, environment
     // switches, free memory) -- and is what the rank tells the others (wgs_em_fit puts it into the sweep's collective); what the
     // sweep DOES additionally needs `fuse_agreed`: every rank has said it can.
-    const bool fuse_on = !(getenv("WGSASSIGN_EM_FUSE") && atoi(getenv("WGSASSIGN_EM_FUSE")) < 2);   // (read at every sweep: tests compare both)
-    bool fusing = false, can_fuse = false;
-    if (codes && may_fuse && ssq_base_b && fuse_on && !shared) {    // (leave-one-out batches are bound by arithmetic: a second iteration that turns out unneeded is not free there)
-        bool wanted = false;
-        for (int j : order) wanted = wanted || (*may_fuse)[j] >= 2;
-        can_fuse = (em->fbuf[2] || wanted) && em_fuse_buffers(em);         // (no memory for the buffers: one iteration per sweep)
-        fusing = can_fuse && wanted && (fuse_agreed || wgs_hook("em_fuse_without_agreement") != 0);
+    if (p.codes && may_fuse && sw.fuse && !p.shared) {    // (leave-one-out batches are bound by arithmetic: a second iteration that turns out unneeded is not free there)
+        const bool wanted = std::any_of(p.order.begin(), p.order.end(), [&](int32_t j) { return (*may_fuse)[j] >= 2; });
+        p.can_fuse = (em->fbuf[2] || wanted) && em_fuse_buffers(em);         // (no memory for the buffers: one iteration per sweep)
+        p.fusing = p.can_fuse && wanted && (fuse_agreed || wgs_hook("em_fuse_without_agreement") != 0);
     }
-    if (can_fuse_out) *can_fuse_out = can_fuse ? 1 : 0;
+    p.may_fuse = may_fuse;
+    // groups of fits of one slab: four per wavefront for the float32 kernel (shared loads and conversions); through the codes a
+    // wavefront walks up to 16 fits one after the other (the dictionary rows stay in registers)
+    if (p.shared) p.fits_per_group = p.codes ? 16 : em_fits_per_group();
+    return p;
+}
+
+// Slot `slot` of the pinned rings from the plan: the fits' descriptors and the group table (returns its number of pairs); fuse_used,
+// pend_cur / pend_prev.  ssq[j] receives fit j's sum, ssq_b[j] (NULL: ssq[j]) that of its second iteration; state (device, may be
+// NULL) holds the fit states a sweep honours.
+static int32_t em_write_descs(wgs_em *em, const EmSweepPlan &p, int slot, double *ssq, double *ssq_b, int32_t *state)
+{
+    const int64_t ntiles = wgs_ntiles(em->b->m);
     const int nb = em->fbuf[2] ? 3 : 2;
-    int coded_rows_max = 0;
-    for (size_t i = 0; i < order.size(); ++i) {
-        const int j = order[i];
+    for (size_t i = 0; i < p.order.size(); ++i) {
+        const int j = p.order[i];
         const Slab &s = em->b->slabs[em->group[j]];
-        FitDesc &d = H[i];
-        d.lcodes = codes ? codes->slabs[em->group[j]].lcodes : nullptr;
-        d.ldict = codes ? codes->slabs[em->group[j]].ldict : nullptr;
-        d.lrows = codes ? codes->lrows : 0;
-        d.tile_rows = codes ? codes->slabs[em->group[j]].tile_rows : nullptr;
-        d.nquads = codes ? codes->slabs[em->group[j]].nquads : 0;
-        coded_rows_max = std::max(coded_rows_max, (int)d.lrows);
+        FitDesc &d = em->h_descs[slot][i];
+        d.lcodes = p.codes ? p.codes->slabs[em->group[j]].lcodes : nullptr;
+        d.ldict = p.codes ? p.codes->slabs[em->group[j]].ldict : nullptr;
+        d.lrows = p.codes ? p.codes->lrows : 0;
+        d.tile_rows = p.codes ? p.codes->slabs[em->group[j]].tile_rows : nullptr;
+        d.nquads = p.codes ? p.codes->slabs[em->group[j]].nquads : 0;
         d.slab = s.base;
         const int c = em->cur[j], n1 = (c + 1) % nb, n2 = (c + 2) % nb;
-        const int fuse = fusing && (*may_fuse)[j] >= 2 ? 2 : 1;
+        const int fuse = p.fusing && (*p.may_fuse)[j] >= 2 ? 2 : 1;
         d.f_old = em_f(em, j, c);
         d.f_new = em_f(em, j, n1);
         d.f_new2 = fuse == 2 ? em_f(em, j, n2) : d.f_new;
         d.fuse = fuse;
-        d.ssq = ssq_base + j;
-        d.ssq2 = ssq_base_b ? ssq_base_b + j : d.ssq;
+        d.ssq = ssq + j;
+        d.ssq2 = ssq_b ? ssq_b + j : d.ssq;
         d.ssq_part = em->d_part + (size_t)j * ntiles;
         d.ssq_part2 = fuse == 2 ? em->d_part_b + (size_t)j * ntiles : d.ssq_part;
         em->fuse_used[j] = (uint8_t)fuse;
@@ -365,66 +379,60 @@ static int em_enqueue_sweep(wgs_em *em, const std::vector<int32_t> &list, FitDes
         d.ncols = s.ncols;
         d.skip = em->skip_local[j];
         d.n_eff = em->n_eff[j];
-        d.state = state_base ? state_base + j : nullptr;
+        d.state = state ? state + j : nullptr;
     }
-    // H (pinned) stays untouched until the caller has waited for this sweep
-    HIP_TRY(hipMemcpyAsync(D, H, sizeof(FitDesc) * order.size(), hipMemcpyHostToDevice, ctx->stream));
-    int32_t n_groups = 0;
-    if (shared) {
-        // groups of fits of one slab: four per wavefront for the float32 kernel (shared loads and conversions); through the codes a
-        // wavefront walks up to 16 fits one after the other (the dictionary rows stay in registers)
-        const int fg = codes ? 16 : em_fits_per_group();
-        for (size_t i = 0; i < order.size();) {
-            size_t k = i + 1;
-            while (k < order.size() && (int)(k - i) < fg && em->group[order[k]] == em->group[order[i]]) ++k;
-            Hg[2 * n_groups] = (int32_t)i;
-            Hg[2 * n_groups + 1] = (int32_t)(k - i);
-            ++n_groups;
-            i = k;
-        }
-        HIP_TRY(hipMemcpyAsync(Dg, Hg, sizeof(int32_t) * 2 * n_groups, hipMemcpyHostToDevice, ctx->stream));
+    int32_t n_groups = 0, *Hg = em->h_groups[slot];
+    for (size_t i = 0; p.shared && i < p.order.size();) {
+        size_t k = i + 1;
+        while (k < p.order.size() && (int)(k - i) < p.fits_per_group && em->group[p.order[k]] == em->group[p.order[i]]) ++k;
+        Hg[2 * n_groups] = (int32_t)i;
+        Hg[2 * n_groups + 1] = (int32_t)(k - i);
+        ++n_groups;
+        i = k;
     }
-    ++em->sweep_paths[(codes ? 2 : 0) + (shared ? 1 : 0)];
-    if (ev0) HIP_TRY(hipEventRecord(ev0, ctx->stream));
-    const int64_t per_unit = ((ntiles + 3) / 4 + 7) / 8 * 8 + 8;       // workgroups per fit / per group: slices stay below 2^31
-    const size_t max_units = (size_t)std::max<int64_t>(1, ((1ll << 31) - 1) / per_unit);
-    if (codes && shared) {
-        const int64_t per_group = (ntiles + 7) / 8 * 8 + 8;
-        const size_t max_groups = (size_t)std::max<int64_t>(1, ((1ll << 31) - 1) / per_group);
-        for (size_t off = 0; off < (size_t)n_groups; off += max_groups) {
-            const int cnt = (int)std::min<size_t>(max_groups, (size_t)n_groups - off);
-            if (launch_em_coded_groups(ctx, D, Dg + 2 * off, cnt, em->b->m, coded_rows_max)) return 1;
-        }
-    } else if (codes) {
-        const int64_t per_fit = (ntiles + 7) / 8 * 8 + 8;            // at least one tile per workgroup
-        const size_t max_fits = (size_t)std::max<int64_t>(1, ((1ll << 31) - 1) / per_fit);
-        for (size_t off = 0; off < order.size(); off += max_fits) {
-            const int cnt = (int)std::min<size_t>(max_fits, order.size() - off);
-            if (launch_em_coded(ctx, D + off, cnt, em->b->m, coded_rows_max)) return 1;
-        }
-    } else if (shared) {
-        for (size_t off = 0; off < (size_t)n_groups; off += max_units) {
-            const int cnt = (int)std::min<size_t>(max_units, (size_t)n_groups - off);
-            if (launch_em_sweep_groups(ctx, D, Dg + 2 * off, cnt, em->b->m, em->mode)) return 1;
-        }
-    } else {
-        for (size_t off = 0; off < order.size(); off += max_units) {
-            const int cnt = (int)std::min<size_t>(max_units, order.size() - off);
-            if (launch_em_sweep(ctx, D + off, cnt, em->b->m, em->mode)) return 1;
-        }
-    }
-    if (ev1) HIP_TRY(hipEventRecord(ev1, ctx->stream));
-    for (size_t off = 0; off < order.size(); off += 65535) {
-        const int cnt = (int)std::min<size_t>(65535, order.size() - off);
-        if (launch_ssq_reduce(ctx, D + off, cnt, em->b->m, em->d_part2 + off * ssq_reduce_chunks())) return 1;
-        if (fusing && launch_ssq_reduce(ctx, D + off, cnt, em->b->m, em->d_part2 + off * ssq_reduce_chunks(), 1)) return 1;
-    }
-    return 0;
+    return n_groups;
 }
+
+/* Enqueue the planned sweep (+ the fixed-order reduction of its sums): descriptors into slot `slot` of the pinned rings and from
+ * there to the device, then the plan's kernel in slices of fits or groups.  ev0 / ev1 (may be NULL) bracket the sweep kernel(s). */
+static int em_enqueue_sweep(wgs_em *em, const EmSweepPlan &p, int slot, double *ssq, double *ssq_b, int32_t *state, hipEvent_t ev0,
+                            hipEvent_t ev1)
+{
+    WGS_STALL_SCOPE("the sweep's launches");
+    wgs_ctx *ctx = em->b->ctx;
+    const int64_t m = em->b->m, ntiles = wgs_ntiles(m);
+    const int32_t n_groups = em_write_descs(em, p, slot, ssq, ssq_b, state);
+    FitDesc *D = em->d_descs[slot];
+    int32_t *Dg = em->d_groups[slot];
+    // the slot's pinned memory stays untouched until the caller has waited for this sweep
+    HIP_TRY(hipMemcpyAsync(D, em->h_descs[slot], sizeof(FitDesc) * p.order.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (p.shared) HIP_TRY(hipMemcpyAsync(Dg, em->h_groups[slot], sizeof(int32_t) * 2 * n_groups, hipMemcpyHostToDevice, ctx->stream));
+    ++em->sweep_paths[(p.codes ? 2 : 0) + (p.shared ? 1 : 0)];
+    if (ev0) HIP_TRY(hipEventRecord(ev0, ctx->stream));
+    // workgroups per fit / per group (at least one tile per workgroup for the coded kernels): slices stay below 2^31
+    const int64_t per_unit = p.codes ? (ntiles + 7) / 8 * 8 + 8 : ((ntiles + 3) / 4 + 7) / 8 * 8 + 8;
+    const size_t units = p.shared ? (size_t)n_groups : p.order.size();
+    if (em_launch_sliced(units, (size_t)std::max<int64_t>(1, ((1ll << 31) - 1) / per_unit), [&](size_t off, int cnt) {
+            if (p.codes && p.shared) return launch_em_coded_groups(ctx, D, Dg + 2 * off, cnt, m, p.codes->lrows);
+            if (p.codes) return launch_em_coded(ctx, D + off, cnt, m, p.codes->lrows);
+            if (p.shared) return launch_em_sweep_groups(ctx, D, Dg + 2 * off, cnt, m, em->mode);
+            return launch_em_sweep(ctx, D + off, cnt, m, em->mode);
+        }))
+        return 1;
+    if (ev1) HIP_TRY(hipEventRecord(ev1, ctx->stream));
+    return em_launch_sliced(p.order.size(), 65535, [&](size_t off, int cnt) {
+        double *part2 = em->d_part2 + off * ssq_reduce_chunks();
+        return launch_ssq_reduce(ctx, D + off, cnt, m, part2) || (p.fusing && launch_ssq_reduce(ctx, D + off, cnt, m, part2, 1));
+    });
+}
+
+// The sweep last enqueued for fit j has run: its new frequencies are current, prev holds the ones before.
+static void em_commit_sweep(wgs_em *em, int j) { em->cur[j] = em->pend_cur[j]; em->prev[j] = em->pend_prev[j]; }
 
 int wgs_em_step_dev(wgs_em *em, double *ssq_dev)
 {
     WGS_REQUIRE(em && ssq_dev, "null argument");
+    const EmSwitches sw;
     wgs_ctx *ctx = em->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     em->last.clear();
@@ -432,13 +440,10 @@ int wgs_em_step_dev(wgs_em *em, double *ssq_dev)
         if (em->active[j]) em->last.push_back(j);
     HIP_TRY(hipMemsetAsync(ssq_dev, 0, sizeof(double) * em->n_fits, ctx->stream));
     if (em->last.empty()) return 0;
-    // h_descs / h_groups (pinned) stay untouched until the next step, which the caller only starts after
-    // consuming this step's sums
-    if (em_enqueue_sweep(em, em->last, em->h_descs, em->d_descs, em->h_groups, em->d_groups, ssq_dev, nullptr, em->ev0, em->ev1, 0)) return 1;
-    for (int j : em->last) {                  // the new frequencies are now current; prev holds the ones before
-        em->cur[j] = em->pend_cur[j];
-        em->prev[j] = em->pend_prev[j];
-    }
+    em->step_slot ^= 1;         // (the slots alternate; the caller only starts the next step after consuming this step's sums)
+    const EmSweepPlan p = em_plan_sweep(em, em->last, 0, nullptr, true, sw);
+    if (em_enqueue_sweep(em, p, em->step_slot, ssq_dev, nullptr, nullptr, em->ev0, em->ev1)) return 1;
+    for (int j : em->last) em_commit_sweep(em, j);
     return 0;
 }
 
@@ -506,10 +511,6 @@ static int em_fit_alloc(wgs_em *em)
     HIP_TRY(hipHostMalloc(&em->h_chain_out, sizeof(float) * 2 * n, hipHostMallocDefault));
     HIP_TRY(hipHostMalloc(&em->h_setstate, sizeof(int32_t) * n, hipHostMallocDefault));
     for (int i = 0; i < 2; ++i) {
-        HIP_TRY(wgs_malloc(&em->d_descs2[i], sizeof(FitDesc) * n));
-        HIP_TRY(hipHostMalloc(&em->h_descs2[i], sizeof(FitDesc) * n, hipHostMallocDefault));
-        HIP_TRY(wgs_malloc(&em->d_groups2[i], sizeof(int32_t) * 2 * n));
-        HIP_TRY(hipHostMalloc(&em->h_groups2[i], sizeof(int32_t) * 2 * n, hipHostMallocDefault));
         HIP_TRY(hipHostMalloc(&em->h_state[i], sizeof(int32_t) * n, hipHostMallocDefault));
         HIP_TRY(hipHostMalloc(&em->h_ssq[i], sizeof(double) * (2 * n + wgs_comm_tail_doubles()), hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&em->ev_it[i], hipEventDisableTiming));
@@ -560,6 +561,7 @@ int wgs_em_fit(wgs_em *em, int32_t max_iter, double tole, int64_t m_total, wgs_c
 {
     WGS_REQUIRE(em && iters_out, "null argument");
     WGS_REQUIRE(m_total >= em->b->m, "m_total (%lld) is smaller than this shard (%lld SNPs)", (long long)m_total, (long long)em->b->m);
+    const EmSwitches sw;
     wgs_ctx *ctx = em->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     if (em_fit_alloc(em)) return 1;
@@ -620,8 +622,7 @@ int wgs_em_fit(wgs_em *em, int32_t max_iter, double tole, int64_t m_total, wgs_c
         for (int j : lists[slot ^ 1]) {
             if (skipped[j]) continue;
             sweeps[j] += em->fuse_used[j];                   // one EM iteration, or the two of a fused sweep
-            em->cur[j] = em->pend_cur[j];                    // the new frequencies are current; prev holds the ones before
-            em->prev[j] = em->pend_prev[j];
+            em_commit_sweep(em, j);
             ran.push_back(j);
         }
         std::fill(skipped.begin(), skipped.end(), 0);
@@ -645,19 +646,17 @@ int wgs_em_fit(wgs_em *em, int32_t max_iter, double tole, int64_t m_total, wgs_c
                 ++em->fit_timed;
                 em->fit_sweep_pending = true;
             }
-            int can_fuse = 0;
-            if (em_enqueue_sweep(em, L, em->h_descs2[slot], em->d_descs2[slot], em->h_groups2[slot], em->d_groups2[slot], em->d_ssq2,
-                                 em->d_state, sw0, sw1, max_iter - t + 1, &may_fuse, em->d_ssq2 + n, fuse_agreed, &can_fuse))
-                return 1;
+            const EmSweepPlan p = em_plan_sweep(em, L, max_iter - t + 1, &may_fuse, fuse_agreed, sw);
+            if (em_enqueue_sweep(em, p, slot, em->d_ssq2, em->d_ssq2 + n, em->d_state, sw0, sw1)) return 1;
             // Fits that skipped this sweep have stale sums; the decision kernel ignores them, and they are stale
             // in the same way on every rank (all ranks take the same decisions).
             if (comm) {
                 int32_t iterations_run = 0;
                 for (int j : L) iterations_run += em->fuse_used[j];
-                const wgs_coll_tag tag = {WGS_OP_EM_SUMS, generation, t, (int32_t)L.size(), iterations_run, can_fuse};
+                const wgs_coll_tag tag = {WGS_OP_EM_SUMS, generation, t, (int32_t)L.size(), iterations_run, p.can_fuse ? 1 : 0};
                 if (wgs_comm_allreduce_tagged(comm, em->d_ssq2, 2 * n, &tag)) return 1;
             }
-            if (launch_em_decide(ctx, em->d_descs2[slot], (int)L.size(), lo, hi)) return 1;
+            if (launch_em_decide(ctx, em->d_descs[slot], (int)L.size(), lo, hi)) return 1;
             HIP_TRY(hipMemcpyAsync(em->h_state[slot], em->d_state, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipMemcpyAsync(em->h_ssq[slot], em->d_ssq2, sizeof(double) * (2 * n + (comm ? world * WGS_TAG_WORDS : 0)), hipMemcpyDeviceToHost,
                                    ctx->stream));

@@ -15,10 +15,11 @@ struct wgs_em {
     // per fit, of the sweep last enqueued for it: iterations it runs (1 or 2) and where cur / prev point once it has run
     std::vector<uint8_t> fuse_used, pend_cur, pend_prev;
     double *d_part_b = nullptr;           // n_fits x ntiles partial sums of a fused sweep's second iteration
-    FitDesc *d_descs = nullptr;
-    FitDesc *h_descs = nullptr;           // pinned
-    int32_t *d_groups = nullptr, *h_groups = nullptr;         // (first, count) pairs of the fit-group sweep, step path
-    int32_t *d_groups2[2] = {nullptr, nullptr}, *h_groups2[2] = {nullptr, nullptr};   // ... wgs_em_fit slots
+    // two-slot rings of a sweep's descriptors and (first, count) pairs of its fit groups, pinned on the host: a slot is not written
+    // again before the sweep that read it has been waited for (wgs_em_fit: one iteration of lookahead; step path: alternating)
+    FitDesc *d_descs[2] = {nullptr, nullptr}, *h_descs[2] = {nullptr, nullptr};
+    int32_t *d_groups[2] = {nullptr, nullptr}, *h_groups[2] = {nullptr, nullptr};
+    int step_slot = 0;                    // slot of the last wgs_em_step_dev
     double *d_ssq = nullptr;
     double *d_part = nullptr;             // n_fits x ntiles per-tile partial sums
     double *d_part2 = nullptr;            // n_fits x ssq_reduce_chunks() slice sums
@@ -27,9 +28,8 @@ struct wgs_em {
     std::vector<int32_t> last;            // fits swept by the last step
     int last_chain_serial_blocks = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // bracket the sweep kernel(s) of the last step
-    // wgs_em_fit: device-side fit states, two-slot pinned rings for the one-iteration lookahead
+    // wgs_em_fit: device-side fit states, two-slot pinned read-backs for the one-iteration lookahead
     int32_t *d_state = nullptr;           // [n_fits] EM_ACTIVE / EM_CONVERGED / EM_UNDECIDED
-    FitDesc *d_descs2[2] = {nullptr, nullptr}, *h_descs2[2] = {nullptr, nullptr};
     int32_t *h_state[2] = {nullptr, nullptr}, *h_setstate = nullptr;
     double *d_ssq2 = nullptr;             // [2 n_fits] sums of the iteration(s) in flight: first | second of a fused sweep
     double *h_ssq[2] = {nullptr, nullptr};  // pinned read-backs of them, one per slot
@@ -47,5 +47,7 @@ struct wgs_em {
     // sweeps enqueued through em_sweep_kernel | em_sweep_group_kernel | em_coded_kernel | em_coded_group_kernel (wgs_debug_em_sweep_paths)
     int64_t sweep_paths[4] = {0, 0, 0, 0};
 };
+
+bool codes_switched_off();              // WGSASSIGN_CODES=0: no class codes at all (codes.hip)
 
 static inline float *em_f(wgs_em *em, int fit, int which) { return em->fbuf[which] + (size_t)fit * em->b->m; }
