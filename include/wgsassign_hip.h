@@ -45,7 +45,8 @@ const char *wgs_last_error(void);
  * wgs_fisher_obs_ind was removed in round 3 while the number stayed 1 -- a caller built against the older header must
  * compare wgs_version() with the WGS_ABI_VERSION it was compiled with and refuse to run on a mismatch (the ctypes shim does:
  * wgsassign_amd/_lib.py); wgs_beagle_codes_info fills 20 entries; wgs_comm_info is new.  3 (round 5): self-checking
- * collectives (wgs_coll_tag, wgs_comm_check, wgs_comm_next_generation, wgs_comm_allreduce_host_tagged). */
+ * collectives (wgs_coll_tag, wgs_comm_check, wgs_comm_next_generation, wgs_comm_allreduce_host_tagged).  The z-score entry points
+ * (wgs_depth_*, wgs_zscore_*, wgs_zkeep_*, wgs_em_fit_masked) were ADDED under 3: no existing signature changed. */
 #define WGS_ABI_VERSION 3
 int wgs_version(void);
 /* sha256[:16] over every source of the library / over the sources of the EM and scoring kernels (em_kernels.hip,
@@ -434,6 +435,49 @@ const char *wgs_ingest_chunk_sites(wgs_ingest *g, int64_t *bytes);
  * WGSASSIGN_INFLATE=host); members the device left to the host's inflater; producer seconds reading compressed members; seconds inside
  * wgs_ingest_create and inside wgs_ingest_next. */
 int wgs_ingest_stats(wgs_ingest *g, double *stats);
+
+/* ------------------------------------------------------------------ z-scores (--get_reference_z_score, --get_assignment_z_score)
+ * zscore.py / zscore_cy.pyx / WGSassign.py:311-446 on device-resident data.  The host keeps what is a few dozen numbers per
+ * individual (key filter, tables: wgsassign_amd/zscore.py); everything that touches every site runs here.  A depth pair
+ * (Ar, Aa) of depth d = Ar + Aa <= wgs_zscore_max_depth() (21) has the class index d (d + 1) / 2 + Aa; WGS_Z_CLASSES of them. */
+#define WGS_Z_CLASSES 253
+typedef struct wgs_depth wgs_depth;   /* allele-depth table of a matrix: one byte pair per (individual, site), next to the slabs */
+typedef struct wgs_zkeep wgs_zkeep;   /* the kept sites (L_keep) of a batch of individuals */
+/* The AD table of WGSassign.py:321 / 409 (np.loadtxt, (m, 2n) int32: reference- and alternative-allele reads per individual) for the
+ * SNP shard of `b`.  Destroyed with its matrix; a later wgs_depth_destroy of such a handle is a no-op (as for wgs_em_destroy). */
+int wgs_depth_create(wgs_beagle *b, wgs_depth **out);
+void wgs_depth_destroy(wgs_depth *d);
+/* Host rows [row0, row0 + nrows) of the (m, 2n) int32 table.  rc 2: a count outside 0..255 (does not fit the table). */
+int wgs_depth_upload_rows(wgs_depth *d, const int32_t *AD_rows, int64_t row0, int64_t nrows);
+int wgs_zscore_max_depth(void);
+/* zscore.AD_summary, the dictionary (zscore.py:11-21), for individuals [i0, i0 + count) in ONE launch: per (individual, class)
+ * the number of sites, the float32 sums of (g0, g1, 1 - g0 - g1) in site order (np.mean's numerator; the caller divides), the
+ * first site of the class (-1: none; the dictionary's insertion order) and per individual the sites deeper than
+ * wgs_zscore_max_depth(), which have no class (the caller refuses such data unless only depth 1 is asked for).
+ * counts_out / first_out: [count][WGS_Z_CLASSES]; sums_out: [count][WGS_Z_CLASSES][3]; over_out: [count]. */
+int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_out, float *sums_out, int32_t *first_out,
+                       int32_t *over_out);
+/* zscore.get_L_keep (zscore.py:43-61) for individuals [i0, i0 + count) in one launch.  key_comp[j][class] = -1: the class did
+ * not survive the key filter; otherwise the component (0..2) at which its mean is largest, key_mean[j][class] that mean.  A site
+ * is kept when its class survived and its own value at that component is within float32(0.01) of the mean.  kept_out[j] = sites
+ * kept.  The set stays on the device (one bit per site + the positions in the compacted order) for wgs_zscore_stats and
+ * wgs_em_fit_masked; destroyed with its matrix or depth table. */
+int wgs_zkeep_create(wgs_depth *d, int32_t i0, int32_t count, const float *key_mean, const int32_t *key_comp, int64_t *kept_out,
+                     wgs_zkeep **out);
+void wgs_zkeep_destroy(wgs_zkeep *zk);
+/* L_keep of individual i0 + slot: the kept sites' indices, ascending (kept_out[slot] of them). */
+int wgs_zkeep_sites(wgs_zkeep *zk, int32_t slot, int32_t *sites_out);
+/* zscore_cy.expected_W_l / variance_W_l (zscore_cy.pyx:10-57) for every kept site of every individual of the set in one launch.
+ * tables[j][class d (d + 1) / 2 + a][0..5] = AD_like[r][0..2], AD_factorial[r][0..2] for r = AD_index[a, d - a] (the reference
+ * reads the index transposed); freq_dev[j] = DEVICE pointer to the m frequencies individual j is tested against (a column of a
+ * wgs_afset, a fit of a wgs_em).  Outputs (host): the individuals' compacted arrays one after the other, kept_out[j] floats
+ * each, in site order -- W_l_obs per site, W_l, var_W_l; the caller forms NumPy's pairwise float32 sums of them. */
+int wgs_zscore_stats(wgs_zkeep *zk, const float *tables, const float *const *freq_dev, float *wobs_out, float *wl_out, float *var_out);
+/* emMAF.emMAF on the rows L[L_keep] (WGSassign.py:361) for every fit of the batch: the per-site update does not depend on which
+ * other sites are present, so the sweeps are wgs_em_step's over all sites; the convergence metric (emMAF_cy.rmse1d, a serial
+ * float32 chain) runs over the kept sites of individual i0 + fit_slot[j] of `zk` only and divides by their number.
+ * iters_out[j] = iteration at which fit j converged, 0 if max_iter was exhausted.  One SNP shard. */
+int wgs_em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_t max_iter, double tole, int32_t *iters_out);
 
 /* Blocks of 4096 elements that fell back to the serial loop in the last wgs_em_rmse_chain of an EM batch (diagnostics). */
 int wgs_em_last_chain_serial_blocks(wgs_em *em);

@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Times the two z-score options on device-resident data and prints ONE JSON line.
+
+    python tools/bench_zscore.py [--shapes 1000000x200x5,2000000x500x8] [--inds 200] [--step-timeout 600]
+
+Per shape m x n x K: the matrix is generated on the device (wgs_beagle_synth, depth 1.5), the depth table on the host (Poisson 1.5
+split binomially; no file I/O anywhere in the timed part), then --get_assignment_z_score and --get_reference_z_score of the
+first --inds individuals with --single_read_threshold off.  Reported per flavour: wall seconds, and inside them the depth-class sweep,
+the mask sweep, the masked fits and the statistic sweep; for comparison the bytes each sweep has to read once (slabs + depth
+table).  Every shape runs in a child process of its own under a time limit, and a shape that fails ends the run: nothing further
+is started on the card."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def one_shape(m, n, K, inds):
+    import numpy as np
+    from wgsassign_amd import zscore
+    from wgsassign_amd.device import AFSet, DeviceBeagle, get_context
+    ctx = get_context()
+    rng = np.random.default_rng(1)
+    group_of = (np.arange(n) * K // n).astype(np.int32)
+    IDs = np.array([("Ind%d" % i, "pop%02d" % g) for i, g in enumerate(group_of)], dtype=str)
+    pops = np.unique(IDs[:, 1])
+    b = DeviceBeagle(m, n, group_of, K)
+    b.synth(7, 1.5)
+    depth = zscore.DepthTable(b)
+    step = max(1, (64 << 20) // (8 * n))
+    for r in range(0, m, step):
+        rows = min(step, m - r)
+        D = rng.poisson(1.5, size=(rows, n))
+        Aa = rng.binomial(D, 0.5)
+        AD = np.empty((rows, 2 * n), dtype=np.int32)
+        AD[:, 0::2], AD[:, 1::2] = D - Aa, Aa
+        depth.upload_rows(AD, r)
+    afs = AFSet.from_host(rng.uniform(0.05, 0.95, size=(m, K)).astype(np.float32))
+    inds = min(inds, n)
+    out = dict(shape=[m, n, K], individuals=inds, device=ctx.info(), slab_bytes=b.nbytes(), depth_bytes=2 * m * n)
+    quiet = lambda *_: None
+    for name in ("assignment", "reference"):
+        phases = {}
+        lib_classes, lib_keep, lib_stats = zscore.AD_summary, zscore.get_L_keep, zscore.KeepSet.stats
+
+        def timed(key, fn):
+            def run(*a, **kw):
+                t = time.perf_counter()
+                r = fn(*a, **kw)
+                ctx.sync()
+                phases[key] = phases.get(key, 0.0) + time.perf_counter() - t
+                return r
+            return run
+        zscore.AD_summary, zscore.get_L_keep = timed("class_sweep_s", lib_classes), timed("mask_sweep_s", lib_keep)
+        zscore.KeepSet.stats = timed("stat_sweep_and_download_s", lib_stats)
+        t0 = time.perf_counter()
+        if name == "assignment":
+            zscore.assignment_z_scores(b, depth, IDs, pops, afs, 0, False, 0, inds, say=quiet)
+        else:
+            zscore.reference_z_scores(b, depth, IDs, group_of, 200, 1e-4, 0, False, 0, inds, say=quiet)
+        ctx.sync()
+        phases["wall_s"] = time.perf_counter() - t0
+        zscore.AD_summary, zscore.get_L_keep, zscore.KeepSet.stats = lib_classes, lib_keep, lib_stats
+        out[name] = {k: round(v, 4) for k, v in phases.items()}
+    print(json.dumps(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="1000000x200x5,2000000x500x8")
+    ap.add_argument("--inds", type=int, default=10**9)
+    ap.add_argument("--step-timeout", type=int, default=600)
+    ap.add_argument("--child", default=None)
+    a = ap.parse_args()
+    if a.child:
+        m, n, K = (int(x) for x in a.child.split("x"))
+        return one_shape(m, n, K, a.inds)
+    results = []
+    for shape in a.shapes.split(","):
+        r = subprocess.run(["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child", shape,
+                            "--inds", str(a.inds)], capture_output=True, text=True)
+        if r.returncode != 0:
+            print(json.dumps({"bench": "zscore", "failed": shape, "rc": r.returncode, "stderr": r.stderr[-400:], "results": results}))
+            return 1
+        results.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    print(json.dumps({"bench": "zscore", "results": results}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main() or 0)

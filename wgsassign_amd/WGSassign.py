@@ -2,9 +2,9 @@
 WGSassign.py (--get_reference_af, --loo, --get_pop_like), running on an AMD MI355X.
 
 Same flags, defaults, stdout lines and output files as the reference (WGSassign.py:24-104,
-109-308), including --ne_obs (Fisher information / effective sample sizes).  Options of the
-reference that are outside this build's scope (z-scores, mixture proportions) are recognised and
-refused with a message.  Installed as the console script `WGSassign` (pyproject.toml; reference
+109-308), including --ne_obs (Fisher information / effective sample sizes) and the two z-score options
+(WGSassign.py:311-446).  Options of the reference that are outside this build's scope (mixture
+proportions) are recognised and refused with a message.  Installed as the console script `WGSassign` (pyproject.toml; reference
 setup.py:48-50).
 """
 import argparse
@@ -41,12 +41,21 @@ parser.add_argument("--ne_obs", action="store_true",
 parser.add_argument("--gpus", metavar="INT", type=int, default=1,
                     help="MI355X build: shard the SNPs over INT GPUs of this node, one process per GPU "
                          "(not needed under torchrun or any launcher that sets RANK / WORLD_SIZE)")
+parser.add_argument("--get_assignment_z_score", action="store_true", help="Calculate z-score for individuals")
+parser.add_argument("--get_reference_z_score", action="store_true", help="Calculate z-score for reference individuals")
+parser.add_argument("--ind_ad_file", metavar="FILE",
+                    help="Filepath to individual allele depths (text as np.loadtxt reads it, or .npy)")
+parser.add_argument("--allele_count_threshold", metavar="INT", type=int,
+                    help="Minimum number of loci needed to keep a specific allele count combination")
+parser.add_argument("--single_read_threshold", action="store_true",
+                    help="Use only loci with a single read. Helps reduce computational time since z-score calculation is "
+                         "computationally intensive")
+parser.add_argument("--ind_start", metavar="INT", type=int, help="Start analysis at this individual index (0-index)")
+parser.add_argument("--ind_end", metavar="INT", type=int, help="End analysis at this individual index (0-index)")
 # recognised but not provided by this build (out of the hot-path scope)
-for _flag in ("--get_assignment_z_score", "--get_reference_z_score", "--single_read_threshold",
-              "--get_em_mix", "--get_mcmc_mix"):
+for _flag in ("--get_em_mix", "--get_mcmc_mix"):
     parser.add_argument(_flag, action="store_true", help=argparse.SUPPRESS)
-for _flag in ("--ind_ad_file", "--allele_count_threshold", "--ind_start", "--ind_end", "--pop_like", "--pop_like_IDs",
-              "--mixture_iter"):
+for _flag in ("--pop_like", "--pop_like_IDs", "--mixture_iter"):
     parser.add_argument(_flag, help=argparse.SUPPRESS)
 
 
@@ -72,7 +81,7 @@ def _run(args, comm):
     assert os.path.isfile(args.beagle), "Beagle file doesn't exist!"
     IDs = pops = None
     group_of, n_groups = None, 1
-    if args.get_reference_af:
+    if args.get_reference_af or args.get_reference_z_score:      # one slab per population: the leave-one-out fits sweep their own
         assert os.path.isfile(args.pop_af_IDs), "Reference population ID file does not exist!!"
         IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
         pops = np.unique(IDs[:, 1])
@@ -210,10 +219,59 @@ def _run(args, comm):
         if root:
             np.savetxt(args.out + ".pop_like.txt", out.astype(np.float32), fmt="%.7f")
         say("Saved population assignment log likelihoods as " + str(args.out) + ".pop_like.txt (text)")
+    for flavour in ("reference", "assignment"):
+        if getattr(args, "get_%s_z_score" % flavour):
+            _z_scores(args, flavour, beagle, group_of, m, n, say, root)
     if scored is not None:
         scored.close()
     beagle.close()
     comm.barrier()
+
+
+def _z_scores(args, flavour, beagle, group_of, m, n, say, root):
+    """WGSassign.py:311-393 (reference) / 395-446 (assignment): same files read, same checks and texts, same output."""
+    import numpy as np
+
+    from . import zscore
+    from .device import AFSet
+    say("Parsing population ID file.")
+    assert os.path.isfile(args.pop_af_IDs), "Population ID file does not exist!!"
+    IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
+    afs = None
+    if flavour == "assignment":
+        say("Parsing population allele frequency file.")
+        assert os.path.isfile(args.pop_af_file), "Population allele frequency file does not exist!!"
+        A = np.ascontiguousarray(np.load(args.pop_af_file), dtype=np.float32)
+    say("Parsing individual allele depths file.")
+    assert os.path.isfile(args.ind_ad_file), "Individual allele depths file does not exist!"
+    AD = zscore.read_depths(args.ind_ad_file)
+    assert os.path.isfile(args.pop_names), "Population names file does not exist!!"
+    pops = np.loadtxt(args.pop_names, dtype="str")
+    assert (n == IDs.shape[0]), "Number of individuals in beagle and reference ID file do not match!"
+    if args.allele_count_threshold is not None:
+        assert (args.allele_count_threshold >= 0), "Allele count threshold needs to be greater than/equal to 0!"
+        allele_count_threshold = args.allele_count_threshold
+    else:
+        allele_count_threshold = 0
+    ind_start, ind_end = zscore.ind_range(n, args.ind_start, args.ind_end)
+    depth = zscore.DepthTable(beagle, AD)
+    del AD
+    if flavour == "assignment":
+        if A.shape[0] != m:
+            raise ValueError("the allele frequency file has %d sites, the Beagle file %d" % (A.shape[0], m))
+        afs = AFSet.from_host(A, ctx=beagle.ctx)
+        z_out = zscore.assignment_z_scores(beagle, depth, IDs, np.atleast_1d(pops), afs, allele_count_threshold,
+                                           args.single_read_threshold, ind_start, ind_end, say=say)
+        afs.close()
+        name = ".z_ind.txt"
+    else:
+        z_out = zscore.reference_z_scores(beagle, depth, IDs, group_of, args.maf_iter, args.maf_tole, allele_count_threshold,
+                                          args.single_read_threshold, ind_start, ind_end, say=say)
+        name = ".reference_z_ind.txt"
+    depth.close()
+    if root:
+        np.savetxt(args.out + name, z_out, fmt="%.7f")
+    say("Saved " + str(ind_end - ind_start) + " individual z-scores as " + str(args.out) + name + " (text)")
 
 
 def main(argv=None):
@@ -237,10 +295,14 @@ def main(argv=None):
 
     if args.loo_downsampled_beagle and not args.loo:
         raise ValueError("The --loo_downsampled_beagle option requires that --loo is also specified.")
-    for unsupported in ("get_assignment_z_score", "get_reference_z_score", "get_em_mix", "get_mcmc_mix"):
+    for unsupported in ("get_em_mix", "get_mcmc_mix"):
         if getattr(args, unsupported):
             raise SystemExit("--%s is outside the scope of the MI355X build (EM allele frequencies, Fisher "
                              "information, leave-one-out and assignment likelihoods only)" % unsupported)
+    if (args.get_assignment_z_score or args.get_reference_z_score) and comm.world > 1:
+        # the depth-class sums and np.sum's pairwise order are defined over ALL sites of an individual: not sharded by SNP yet
+        raise SystemExit("--get_assignment_z_score / --get_reference_z_score run on one GPU: start them without --gpus "
+                         "(the z-score path does not shard the SNPs)")
 
     if root:        # log-file of non-default arguments (WGSassign.py:127-141)
         full, deaf = vars(args), vars(parser.parse_args([]))

@@ -55,6 +55,16 @@ SIGNATURES = {
     "wgs_beagle_codes_state": (c_int, [c_vp]),
     "wgs_beagle_codes_wait": (c_int, [c_vp, c_f64p]),
     "wgs_malloc_seconds": (ctypes.c_double, []),
+    "wgs_depth_create": (c_int, [c_vp, ctypes.POINTER(c_vp)]),
+    "wgs_depth_destroy": (None, [c_vp]),
+    "wgs_depth_upload_rows": (c_int, [c_vp, c_i32p, c_i64, c_i64]),
+    "wgs_zscore_max_depth": (c_int, []),
+    "wgs_zscore_classes": (c_int, [c_vp, c_i32, c_i32, c_i32p, c_f32p, c_i32p, c_i32p]),
+    "wgs_zkeep_create": (c_int, [c_vp, c_i32, c_i32, c_f32p, c_i32p, ctypes.POINTER(c_i64), ctypes.POINTER(c_vp)]),
+    "wgs_zkeep_destroy": (None, [c_vp]),
+    "wgs_zkeep_sites": (c_int, [c_vp, c_i32, c_i32p]),
+    "wgs_zscore_stats": (c_int, [c_vp, c_f32p, ctypes.POINTER(c_vp), c_f32p, c_f32p, c_f32p]),
+    "wgs_em_fit_masked": (c_int, [c_vp, c_vp, c_i32p, c_i32, ctypes.c_double, c_i32p]),
     "wgs_em_create": (c_int, [c_vp, c_i32, c_i32p, c_i32p, c_int, ctypes.POINTER(c_vp)]),
     "wgs_em_destroy": (None, [c_vp]),
     "wgs_em_step": (c_int, [c_vp, c_f64p]),

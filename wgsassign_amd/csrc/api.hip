@@ -63,6 +63,9 @@ bool wgs_live_remove(void *obj)
 }
 extern "C" void wgs_em_destroy(wgs_em *em);
 extern "C" void wgs_score_destroy(wgs_score *sc);
+#include "zscore.h"
+extern "C" void wgs_depth_destroy(wgs_depth *d);
+extern "C" void wgs_zkeep_destroy(wgs_zkeep *zk);
 void wgs_live_destroy_children(void *parent)
 {
     for (;;) {
@@ -77,6 +80,8 @@ void wgs_live_destroy_children(void *parent)
         }
         if (!e.obj) return;
         if (e.kind == WGS_LIVE_EM) wgs_em_destroy(reinterpret_cast<wgs_em *>(e.obj));
+        else if (e.kind == WGS_LIVE_DEPTH) wgs_depth_destroy(reinterpret_cast<wgs_depth *>(e.obj));
+        else if (e.kind == WGS_LIVE_ZKEEP) wgs_zkeep_destroy(reinterpret_cast<wgs_zkeep *>(e.obj));
         else wgs_score_destroy(reinterpret_cast<wgs_score *>(e.obj));
     }
 }

@@ -1,0 +1,49 @@
+// Internal declarations of the z-score path (zscore_kernels.hip, zscore_api.hip).
+#pragma once
+#include "common.h"
+
+constexpr int WGS_Z_MAXD = 21;                                        // largest depth Ar + Aa with a class of its own
+constexpr int WGS_Z_NKEYS = (WGS_Z_MAXD + 1) * (WGS_Z_MAXD + 2) / 2;  // 253 classes: one per thread of a 256-thread workgroup
+
+// kinds of the live-object registry (common.h: WGS_LIVE_EM = 1, WGS_LIVE_SCORE = 2): the depth table and the kept-site sets
+constexpr int WGS_LIVE_DEPTH = 3, WGS_LIVE_ZKEEP = 4;
+
+struct ZInd {                  // one individual as the sweeps see it
+    const float4 *slab;
+    int32_t npairs, pair, hi;  // its column's pair inside the slab and which half of the float4
+    int32_t ind;               // global index (row of the depth table)
+};
+struct ZCompactJob {
+    const float *cur, *prev;
+    float *a_out, *b_out;      // the fit's own compacted vectors
+    int32_t slot;              // individual of the kept-site set whose mask applies
+};
+
+struct wgs_depth {
+    wgs_beagle *b = nullptr;
+    int64_t mpad = 0;
+    uchar2 *table = nullptr;   // [individual][mpad]
+    int32_t *d_bad = nullptr;
+};
+struct wgs_zkeep {
+    wgs_beagle *b = nullptr;
+    wgs_depth *d = nullptr;
+    int32_t i0 = 0, count = 0;
+    ZInd *d_inds = nullptr;
+    unsigned long long *mask = nullptr;   // [count][ntiles]
+    uint32_t *off = nullptr;              // [count][ntiles]
+    int64_t *d_total = nullptr;
+    std::vector<int64_t> total;
+};
+
+int zs_fill_inds(wgs_beagle *b, int32_t i0, int32_t count, std::vector<ZInd> &out);
+int launch_zclass(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, int32_t *cnt, float *sums,
+                  int32_t *first, int32_t *over);
+int launch_zmask(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, const float *kmean,
+                 const int32_t *kcomp, unsigned long long *mask, uint32_t *off, int64_t *total);
+int launch_zstat(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, const float *tabs,
+                 const float *const *fptr, const unsigned long long *mask, const uint32_t *off, const int64_t *obase, float *wobs,
+                 float *wl, float *var);
+int launch_zcompact(wgs_ctx *ctx, const ZCompactJob *d_jobs, int n_jobs, int64_t m, const unsigned long long *mask, const uint32_t *off);
+int launch_zdepth_scatter(wgs_ctx *ctx, const int32_t *d_rows, int64_t nrows, int64_t n, int64_t row0, int64_t mpad, uchar2 *depth, int32_t *bad);
+int launch_zsites(wgs_ctx *ctx, int64_t m, const unsigned long long *mask, const uint32_t *off, int32_t *out);

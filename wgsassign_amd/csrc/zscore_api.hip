@@ -1,0 +1,313 @@
+// C ABI of the z-score options (include/wgsassign_hip.h, "z-scores"): depth table, depth-class sweep, kept-site sets, per-site
+// statistic, and the leave-one-out fit whose convergence test runs over a site subset.  Kernels: zscore_kernels.hip.
+#include <math.h>
+#include <string.h>
+
+#include "em_state.h"
+#include "zscore.h"
+
+// Device buffers of one call, released when it returns whichever way.
+struct ZBufs {
+    std::vector<void *> p;
+    ~ZBufs() { for (void *q : p) (void)hipFree(q); }
+    template <typename T>
+    hipError_t get(T **out, size_t bytes)
+    {
+        const hipError_t e = wgs_malloc(out, bytes ? bytes : 1);
+        if (e == hipSuccess) p.push_back(*out);
+        return e;
+    }
+};
+
+int zs_fill_inds(wgs_beagle *b, int32_t i0, int32_t count, std::vector<ZInd> &out)
+{
+    WGS_REQUIRE(i0 >= 0 && count > 0 && (int64_t)i0 + count <= b->n, "individuals [%d, %d) outside 0..%lld", i0, i0 + count, (long long)b->n);
+    out.resize(count);
+    for (int j = 0; j < count; ++j) {
+        const Slab &s = b->slabs[b->group_of[i0 + j]];
+        const int col = b->col_of[i0 + j];
+        out[j] = ZInd{s.base, s.npairs, col >> 1, col & 1, i0 + j};
+    }
+    return 0;
+}
+
+extern "C" {
+
+int wgs_depth_create(wgs_beagle *b, wgs_depth **out)
+{
+    WGS_REQUIRE(b && out, "null argument");
+    WGS_REQUIRE(b->m > 0 && b->m < (int64_t)1 << 31, "the depth table needs between 1 and 2^31 - 1 sites");
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    wgs_depth *d = new wgs_depth();
+    wgs_live_add(d, WGS_LIVE_DEPTH, b);
+    auto guard = on_failure([&] { wgs_depth_destroy(d); });
+    d->b = b;
+    d->mpad = wgs_ntiles(b->m) * 64;
+    const size_t bytes = (size_t)b->n * d->mpad * sizeof(uchar2);
+    if (wgs_malloc(&d->table, bytes) != hipSuccess) {
+        wgs_set_error("hipMalloc of %zu bytes for the allele-depth table failed", bytes);
+        return 1;
+    }
+    HIP_TRY(wgs_malloc(&d->d_bad, sizeof(int32_t)));
+    HIP_TRY(hipMemsetAsync(d->table, 0, bytes, b->ctx->stream));
+    HIP_TRY(hipMemsetAsync(d->d_bad, 0, sizeof(int32_t), b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    guard.dismiss();
+    *out = d;
+    return 0;
+}
+
+void wgs_depth_destroy(wgs_depth *d)
+{
+    if (!d || !wgs_live_remove(d)) return;
+    wgs_live_destroy_children(d);             // kept-site sets made from this table go first
+    (void)hipSetDevice(d->b->ctx->device);
+    if (d->table) (void)hipFree(d->table);
+    if (d->d_bad) (void)hipFree(d->d_bad);
+    delete d;
+}
+
+int wgs_depth_upload_rows(wgs_depth *d, const int32_t *AD_rows, int64_t row0, int64_t nrows)
+{
+    WGS_REQUIRE(d && AD_rows, "null argument");
+    wgs_beagle *b = d->b;
+    WGS_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= b->m, "row range [%lld, %lld) outside 0..%lld", (long long)row0,
+                (long long)(row0 + nrows), (long long)b->m);
+    WGS_REQUIRE(nrows * b->n < (int64_t)1 << 38, "too many rows in one upload");
+    if (nrows == 0) return 0;
+    wgs_ctx *ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ZBufs bufs;
+    int32_t *d_rows = nullptr;
+    const size_t bytes = (size_t)nrows * 2 * b->n * sizeof(int32_t);
+    HIP_TRY(bufs.get(&d_rows, bytes));
+    HIP_TRY(hipMemcpyAsync(d_rows, AD_rows, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (launch_zdepth_scatter(ctx, d_rows, nrows, b->n, row0, d->mpad, d->table, d->d_bad)) return 1;
+    int32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, d->d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (bad) {
+        HIP_TRY(hipMemset(d->d_bad, 0, sizeof(int32_t)));
+        wgs_set_error("allele depths outside 0..255 do not fit the device table");
+        return 2;
+    }
+    return 0;
+}
+
+int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_out, float *sums_out, int32_t *first_out, int32_t *over_out)
+{
+    WGS_REQUIRE(d && counts_out && sums_out && first_out && over_out, "null argument");
+    wgs_beagle *b = d->b;
+    wgs_ctx *ctx = b->ctx;
+    std::vector<ZInd> inds;
+    if (int rc = zs_fill_inds(b, i0, count, inds)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ZBufs bufs;
+    ZInd *d_inds = nullptr;
+    int32_t *cnt = nullptr, *first = nullptr, *over = nullptr;
+    float *sums = nullptr;
+    const size_t cells = (size_t)count * 256;
+    HIP_TRY(bufs.get(&d_inds, sizeof(ZInd) * count));
+    HIP_TRY(bufs.get(&cnt, sizeof(int32_t) * cells));
+    HIP_TRY(bufs.get(&first, sizeof(int32_t) * cells));
+    HIP_TRY(bufs.get(&sums, sizeof(float) * 3 * cells));
+    HIP_TRY(bufs.get(&over, sizeof(int32_t) * count));
+    HIP_TRY(hipMemcpyAsync(d_inds, inds.data(), sizeof(ZInd) * count, hipMemcpyHostToDevice, ctx->stream));
+    if (launch_zclass(ctx, d_inds, count, d->table, b->m, d->mpad, cnt, sums, first, over)) return 1;
+    std::vector<int32_t> h_cnt(cells), h_first(cells);
+    std::vector<float> h_sums(3 * cells);
+    HIP_TRY(hipMemcpyAsync(h_cnt.data(), cnt, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_first.data(), first, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_sums.data(), sums, sizeof(float) * 3 * cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(over_out, over, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int j = 0; j < count; ++j) {          // (the kernel's rows have 256 entries, the caller's WGS_Z_NKEYS)
+        memcpy(counts_out + (size_t)j * WGS_Z_NKEYS, h_cnt.data() + (size_t)j * 256, sizeof(int32_t) * WGS_Z_NKEYS);
+        memcpy(first_out + (size_t)j * WGS_Z_NKEYS, h_first.data() + (size_t)j * 256, sizeof(int32_t) * WGS_Z_NKEYS);
+        memcpy(sums_out + (size_t)j * WGS_Z_NKEYS * 3, h_sums.data() + (size_t)j * 256 * 3, sizeof(float) * 3 * WGS_Z_NKEYS);
+    }
+    return 0;
+}
+
+int wgs_zscore_max_depth(void) { return WGS_Z_MAXD; }
+
+void wgs_zkeep_destroy(wgs_zkeep *zk)
+{
+    if (!zk || !wgs_live_remove(zk)) return;
+    (void)hipSetDevice(zk->b->ctx->device);
+    for (void *p : {(void *)zk->d_inds, (void *)zk->mask, (void *)zk->off, (void *)zk->d_total})
+        if (p) (void)hipFree(p);
+    delete zk;
+}
+
+int wgs_zkeep_create(wgs_depth *d, int32_t i0, int32_t count, const float *key_mean, const int32_t *key_comp, int64_t *kept_out,
+                     wgs_zkeep **out)
+{
+    WGS_REQUIRE(d && key_mean && key_comp && kept_out && out, "null argument");
+    wgs_beagle *b = d->b;
+    wgs_ctx *ctx = b->ctx;
+    std::vector<ZInd> inds;
+    if (int rc = zs_fill_inds(b, i0, count, inds)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    wgs_zkeep *zk = new wgs_zkeep();
+    wgs_live_add(zk, WGS_LIVE_ZKEEP, b, d);
+    auto guard = on_failure([&] { wgs_zkeep_destroy(zk); });
+    zk->b = b;
+    zk->d = d;
+    zk->i0 = i0;
+    zk->count = count;
+    const size_t nt = (size_t)wgs_ntiles(b->m);
+    HIP_TRY(wgs_malloc(&zk->d_inds, sizeof(ZInd) * count));
+    HIP_TRY(wgs_malloc(&zk->mask, sizeof(unsigned long long) * count * nt));
+    HIP_TRY(wgs_malloc(&zk->off, sizeof(uint32_t) * count * nt));
+    HIP_TRY(wgs_malloc(&zk->d_total, sizeof(int64_t) * count));
+    ZBufs bufs;
+    float *kmean = nullptr;
+    int32_t *kcomp = nullptr;
+    HIP_TRY(bufs.get(&kmean, sizeof(float) * 256 * count));
+    HIP_TRY(bufs.get(&kcomp, sizeof(int32_t) * 256 * count));
+    std::vector<float> h_mean((size_t)256 * count, 0.0f);
+    std::vector<int32_t> h_comp((size_t)256 * count, -1);
+    for (int j = 0; j < count; ++j)
+        for (int k = 0; k < WGS_Z_NKEYS; ++k) {
+            const int c = key_comp[(size_t)j * WGS_Z_NKEYS + k];
+            WGS_REQUIRE(c >= -1 && c <= 2, "key_comp must be -1 (class not kept) or a component 0..2");
+            h_mean[(size_t)j * 256 + k] = key_mean[(size_t)j * WGS_Z_NKEYS + k];
+            h_comp[(size_t)j * 256 + k] = c;
+        }
+    HIP_TRY(hipMemcpyAsync(zk->d_inds, inds.data(), sizeof(ZInd) * count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(kmean, h_mean.data(), sizeof(float) * 256 * count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(kcomp, h_comp.data(), sizeof(int32_t) * 256 * count, hipMemcpyHostToDevice, ctx->stream));
+    if (launch_zmask(ctx, zk->d_inds, count, d->table, b->m, d->mpad, kmean, kcomp, zk->mask, zk->off, zk->d_total)) return 1;
+    zk->total.resize(count);
+    HIP_TRY(hipMemcpyAsync(zk->total.data(), zk->d_total, sizeof(int64_t) * count, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int j = 0; j < count; ++j) kept_out[j] = zk->total[j];
+    guard.dismiss();
+    *out = zk;
+    return 0;
+}
+
+int wgs_zkeep_sites(wgs_zkeep *zk, int32_t slot, int32_t *sites_out)
+{
+    WGS_REQUIRE(zk && sites_out && slot >= 0 && slot < zk->count, "bad argument");
+    if (zk->total[slot] == 0) return 0;
+    wgs_ctx *ctx = zk->b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ZBufs bufs;
+    int32_t *d_out = nullptr;
+    HIP_TRY(bufs.get(&d_out, sizeof(int32_t) * zk->total[slot]));
+    const size_t nt = (size_t)wgs_ntiles(zk->b->m);
+    if (launch_zsites(ctx, zk->b->m, zk->mask + slot * nt, zk->off + slot * nt, d_out)) return 1;
+    HIP_TRY(hipMemcpyAsync(sites_out, d_out, sizeof(int32_t) * zk->total[slot], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int wgs_zscore_stats(wgs_zkeep *zk, const float *tables, const float *const *freq_dev, float *wobs_out, float *wl_out, float *var_out)
+{
+    WGS_REQUIRE(zk && tables && freq_dev && wobs_out && wl_out && var_out, "null argument");
+    wgs_beagle *b = zk->b;
+    wgs_ctx *ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int count = zk->count;
+    std::vector<int64_t> obase(count);
+    int64_t all = 0;
+    for (int j = 0; j < count; ++j) {
+        WGS_REQUIRE(freq_dev[j], "individual %d has no frequency vector", zk->i0 + j);
+        obase[j] = all;
+        all += zk->total[j];
+    }
+    if (all == 0) return 0;
+    ZBufs bufs;
+    float *d_tabs = nullptr, *d_out = nullptr;
+    const float **d_fptr = nullptr;
+    int64_t *d_obase = nullptr;
+    const size_t tab_bytes = sizeof(float) * 6 * WGS_Z_NKEYS * count;
+    HIP_TRY(bufs.get(&d_tabs, tab_bytes));
+    HIP_TRY(bufs.get(&d_fptr, sizeof(float *) * count));
+    HIP_TRY(bufs.get(&d_obase, sizeof(int64_t) * count));
+    if (bufs.get(&d_out, sizeof(float) * 3 * all) != hipSuccess) {
+        wgs_set_error("hipMalloc of %zu bytes for the per-site statistics failed", sizeof(float) * 3 * (size_t)all);
+        return 1;
+    }
+    HIP_TRY(hipMemcpyAsync(d_tabs, tables, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_fptr, freq_dev, sizeof(float *) * count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_obase, obase.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, ctx->stream));
+    if (launch_zstat(ctx, zk->d_inds, count, zk->d->table, b->m, zk->d->mpad, d_tabs, d_fptr, zk->mask, zk->off, d_obase, d_out, d_out + all,
+                     d_out + 2 * all))
+        return 1;
+    HIP_TRY(hipMemcpyAsync(wobs_out, d_out, sizeof(float) * all, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(wl_out, d_out + all, sizeof(float) * all, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(var_out, d_out + 2 * all, sizeof(float) * all, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int wgs_em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_t max_iter, double tole, int32_t *iters_out)
+{
+    WGS_REQUIRE(em && zk && fit_slot && iters_out, "null argument");
+    WGS_REQUIRE(em->b == zk->b, "the EM batch and the kept-site set belong to different matrices");
+    wgs_beagle *b = em->b;
+    wgs_ctx *ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int nf = em->n_fits;
+    int64_t stride = 1;
+    for (int j = 0; j < nf; ++j) {
+        WGS_REQUIRE(fit_slot[j] >= 0 && fit_slot[j] < zk->count, "fit %d: slot %d outside the kept-site set", j, fit_slot[j]);
+        WGS_REQUIRE(zk->total[fit_slot[j]] > 0, "fit %d: no site was kept", j);
+        if (zk->total[fit_slot[j]] > stride) stride = zk->total[fit_slot[j]];
+        iters_out[j] = 0;
+    }
+    ZBufs bufs;
+    float *d_a = nullptr, *d_b = nullptr, *d_out = nullptr;
+    ZCompactJob *d_cj = nullptr;
+    ChainJob *d_jobs = nullptr;
+    void *work = nullptr;
+    const size_t vec_bytes = sizeof(float) * (size_t)nf * stride;
+    if (bufs.get(&d_a, vec_bytes) != hipSuccess || bufs.get(&d_b, vec_bytes) != hipSuccess) {
+        wgs_set_error("hipMalloc of 2 x %zu bytes for the compacted frequencies failed", vec_bytes);
+        return 1;
+    }
+    HIP_TRY(bufs.get(&d_out, sizeof(float) * nf));
+    HIP_TRY(bufs.get(&d_cj, sizeof(ZCompactJob) * nf));
+    HIP_TRY(bufs.get(&d_jobs, sizeof(ChainJob) * nf));
+    HIP_TRY(bufs.get(&work, rmse_chain_workspace_bytes(stride) * nf));
+    HIP_TRY(hipMemsetAsync(d_a, 0, vec_bytes, ctx->stream));       // what lies behind a fit's kept count stays 0: (0 - 0)^2 adds nothing
+    HIP_TRY(hipMemsetAsync(d_b, 0, vec_bytes, ctx->stream));
+    std::vector<ZCompactJob> cj(nf);
+    std::vector<ChainJob> jobs(nf);
+    std::vector<float> carry(nf);
+    std::vector<int> list;
+    for (int it = 1; it <= max_iter; ++it) {
+        list.clear();
+        for (int j = 0; j < nf; ++j)
+            if (em->active[j]) list.push_back(j);
+        if (list.empty()) break;
+        if (wgs_em_step_dev(em, em->d_ssq)) return 1;               // emMAF_cy.emMAF_update of every active fit: the existing sweep
+        const int nj = (int)list.size();
+        for (int q = 0; q < nj; ++q) {
+            const int j = list[q];
+            float *va = d_a + (size_t)j * stride, *vb = d_b + (size_t)j * stride;      // the fit's own vectors: zero behind ITS kept count
+            cj[q] = ZCompactJob{em_f(em, j, em->cur[j]), em_f(em, j, em->prev[j]), va, vb, fit_slot[j]};
+            jobs[q] = ChainJob{va, vb, 0.0f};
+        }
+        HIP_TRY(hipMemcpyAsync(d_cj, cj.data(), sizeof(ZCompactJob) * nj, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(ChainJob) * nj, hipMemcpyHostToDevice, ctx->stream));
+        if (launch_zcompact(ctx, d_cj, nj, b->m, zk->mask, zk->off)) return 1;
+        if (launch_rmse_chain_batch(ctx, d_jobs, nj, stride, d_out, work, nullptr)) return 1;
+        HIP_TRY(hipMemcpyAsync(carry.data(), d_out, sizeof(float) * nj, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (int q = 0; q < nj; ++q) {
+            const int j = list[q];
+            const float res = carry[q] / (float)zk->total[fit_slot[j]];       // emMAF_cy.pyx:32 with n = the kept sites
+            if (sqrt((double)res) < tole) {                                   // emMAF_cy.pyx:33, emMAF.py:23
+                iters_out[j] = it;
+                em->active[j] = 0;
+            }
+        }
+    }
+    return 0;
+}
+
+}   // extern "C"

@@ -1,0 +1,297 @@
+"""The reference's `zscore` module (zscore.py) on device-resident data: the z-score of an individual's observed log-likelihood
+against its expectation under the population it is assigned to (WGSassign.py:311-446).
+
+Everything that touches every site runs on the GPU, a batch of individuals per launch (csrc/zscore_kernels.hip): the depth-class
+sweep (AD_summary's dictionary), the site mask (get_L_keep), the per-site statistic (zscore_cy.expected_W_l / variance_W_l) and,
+for the reference flavour, the leave-one-out EM fits whose convergence test runs over the kept sites.  What is a few dozen numbers
+per individual stays here in NumPy: the key filter, the tables, and the three float32 sums, which np.sum forms in its own pairwise
+order from the compacted per-site arrays.  There is no CPU fallback.
+"""
+import ctypes
+import math
+import weakref
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, f32p, i32p
+
+N_CLASSES = 253      # = WGS_Z_CLASSES: depth pairs (Ar, Aa) with Ar + Aa <= 21, class index d (d + 1) / 2 + Aa
+E = 0.01
+
+
+# ---------------------------------------------------------------- host side: a few dozen numbers per individual
+def read_depths(path):
+    """--ind_ad_file: text as the reference reads it (np.loadtxt, int32), or .npy as its README describes."""
+    if str(path).endswith(".npy"):
+        return np.ascontiguousarray(np.load(path), dtype=np.int32)
+    return np.ascontiguousarray(np.atleast_2d(np.loadtxt(path, dtype=np.int32)))
+
+
+def check_depths(AD, m, n):
+    if AD.ndim != 2 or AD.shape[0] != m or AD.shape[1] < 2 * n:
+        raise ValueError("allele depths have shape %s, the Beagle file has %d sites and %d individuals" % (AD.shape, m, n))
+    if AD.size and (AD.min() < 0 or AD.max() > 255):
+        raise ValueError("allele depths outside 0..255 do not fit the device table")
+
+
+def key_filter(keys, counts, n_threshold, single_read_threshold):
+    """zscore.AD_summary, lines 22-39: rows (Ar, Aa, depth, sites) of the classes that survive, in order of first appearance."""
+    S = np.column_stack((keys[:, 0], keys[:, 1], keys[:, 0] + keys[:, 1], counts)).astype(np.int32)
+    if single_read_threshold:
+        AD_filtered = S[S[:, 2] == 1]
+    else:
+        AD_filtered = S[(S[:, 3] > n_threshold) & (S[:, 2] != 0)]
+    assert (AD_filtered.shape[0] != 0), "No loci were kept! Too stringent filtering?"
+    assert (AD_filtered.shape[0] != 1), "Not enough loci were kept! Too stringent filtering?"
+    dl, dl_counts = np.unique(AD_filtered[:, 2], return_counts=True)
+    return AD_filtered[np.isin(AD_filtered[:, 2], dl[dl < dl_counts])]
+
+
+def get_factorials(AD_array, keys, means, e=E):
+    """zscore.get_factorials (zscore.py:63-80): AD_factorial, AD_like, AD_index.  (keys, means: the dictionary.)"""
+    where = {(int(a), int(b)): j for j, (a, b) in enumerate(keys)}
+    AD_factorial = np.zeros((AD_array.shape[0], 3), dtype=np.float32)
+    AD_like = np.zeros((AD_array.shape[0], 3), dtype=np.float32)
+    AD_index = np.zeros((np.max(AD_array[:, 0]) + 1, np.max(AD_array[:, 1]) + 1), dtype=np.int32)
+    for i in range(AD_array.shape[0]):
+        Ar, Aa = int(AD_array[i, 0]), int(AD_array[i, 1])
+        AD_index[Ar, Aa] = i
+        ad_factorial = math.comb(Ar + Aa, Aa) / 1
+        AD_factorial[i, :] = [ad_factorial * ((1.0 - e) ** Ar) * (e ** Aa), ad_factorial * ((0.5) ** (Ar + Aa)),
+                              ad_factorial * ((1.0 - e) ** Aa) * (e ** Ar)]
+        AD_like[i] = means[where[(Ar, Aa)]]
+    return AD_factorial, AD_like, AD_index
+
+
+def ind_range(n, ind_start, ind_end):
+    """WGSassign.py:336-345 as it stands (--ind_start 0 is refused)."""
+    if ind_start is not None:
+        assert (ind_start > 0 and ind_start <= n), "Start individual index needs to be within range of number of individuals!"
+    if ind_end is not None:
+        assert (ind_end > 0 and ind_end <= n), "End individual index needs to be within range of number of individuals!"
+    return (0 if ind_start is None else ind_start), (n if ind_end is None else ind_end)
+
+
+def class_index(Ar, Aa):
+    d = Ar + Aa
+    return d * (d + 1) // 2 + Aa
+
+
+# ---------------------------------------------------------------- device objects
+class DepthTable:
+    """The allele-depth table of a DeviceBeagle's SNP shard on the device (wgs_depth)."""
+
+    def __init__(self, beagle, AD=None, chunk_rows=None):
+        self.b = beagle
+        h = ctypes.c_void_p()
+        check(_lib.load().wgs_depth_create(beagle.handle, ctypes.byref(h)))
+        self._h = h
+        beagle._children.add(self)
+        if AD is not None:
+            check_depths(AD, beagle.m, beagle.n)
+            step = chunk_rows or max(1, (64 << 20) // (8 * beagle.n))
+            for r in range(0, beagle.m, step):
+                self.upload_rows(AD[r:r + step], r)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def upload_rows(self, rows, row0=0):
+        rows = np.ascontiguousarray(rows[:, :2 * self.b.n], dtype=np.int32)
+        check(_lib.load().wgs_depth_upload_rows(self._h, i32p(rows), int(row0), rows.shape[0]))
+
+    def close(self):
+        if self._h:
+            _lib.load().wgs_depth_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KeepSet:
+    """L_keep of individuals [i0, i0 + count) on the device (wgs_zkeep); .kept[j] = sites kept."""
+
+    def __init__(self, depth, i0, key_mean, key_comp):
+        count = key_mean.shape[0]
+        self.depth, self.i0, self.count = depth, int(i0), count
+        key_mean = np.ascontiguousarray(key_mean, dtype=np.float32)
+        key_comp = np.ascontiguousarray(key_comp, dtype=np.int32)
+        self.kept = np.zeros(count, dtype=np.int64)
+        h = ctypes.c_void_p()
+        check(_lib.load().wgs_zkeep_create(depth.handle, self.i0, count, f32p(key_mean), i32p(key_comp),
+                                           self.kept.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(h)))
+        self._h = h
+        depth.b._children.add(self)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def sites(self, slot):
+        out = np.empty(int(self.kept[slot]), dtype=np.int32)
+        check(_lib.load().wgs_zkeep_sites(self._h, int(slot), i32p(out)))
+        return out
+
+    def stats(self, tables, freq_dev):
+        """Per-site W_l_obs, W_l, var_W_l of every individual: three lists of float32 arrays (kept[j],)."""
+        tables = np.ascontiguousarray(tables, dtype=np.float32)
+        assert tables.shape == (self.count, N_CLASSES, 6)
+        ptrs = (ctypes.c_void_p * self.count)(*[int(p) for p in freq_dev])
+        total = int(self.kept.sum())
+        out = [np.empty(total, dtype=np.float32) for _ in range(3)]
+        check(_lib.load().wgs_zscore_stats(self._h, f32p(tables), ptrs, f32p(out[0]), f32p(out[1]), f32p(out[2])))
+        cuts = np.cumsum(self.kept)[:-1]
+        return [np.split(o, cuts) for o in out]
+
+    def close(self):
+        if self._h:
+            _lib.load().wgs_zkeep_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------- the reference's functions, a batch of individuals at a time
+def AD_summary(depth, i0, count, n_threshold, single_read_threshold):
+    """zscore.AD_summary (zscore.py:11-40) for individuals [i0, i0 + count): list of dict(keys, counts, means, AD_array) -- the
+    dictionary in order of first appearance and the filtered classes.  One launch (wgs_zscore_classes)."""
+    cnt = np.empty((count, N_CLASSES), dtype=np.int32)
+    first = np.empty((count, N_CLASSES), dtype=np.int32)
+    sums = np.empty((count, N_CLASSES, 3), dtype=np.float32)
+    over = np.empty(count, dtype=np.int32)
+    check(_lib.load().wgs_zscore_classes(depth.handle, int(i0), int(count), i32p(cnt), f32p(sums), i32p(first), i32p(over)))
+    maxd = _lib.load().wgs_zscore_max_depth()
+    d_of = np.repeat(np.arange(maxd + 1), np.arange(maxd + 1) + 1)
+    a_of = np.arange(N_CLASSES) - d_of * (d_of + 1) // 2
+    out = []
+    for j in range(count):
+        if over[j] and not single_read_threshold:
+            raise ValueError("individual %d has %d sites deeper than %d reads: the depth classes of this build end there "
+                             "(--single_read_threshold needs depth 1 only and accepts such data)" % (i0 + j, int(over[j]), maxd))
+        seen = np.flatnonzero(cnt[j] > 0)
+        seen = seen[np.argsort(first[j, seen], kind="stable")]
+        keys = np.column_stack((d_of[seen] - a_of[seen], a_of[seen])).astype(np.int64)
+        counts = cnt[j, seen].astype(np.int64)
+        means = (sums[j, seen].astype(np.float64) / counts[:, None]).astype(np.float32)     # np.mean: float32 sums, true_divide by the count
+        out.append(dict(keys=keys, counts=counts, means=means, AD_array=key_filter(keys, counts, n_threshold, single_read_threshold)))
+    return out
+
+
+def get_L_keep(depth, i0, summaries):
+    """zscore.get_L_keep (zscore.py:43-61) for the batch: a KeepSet (the sites stay on the device)."""
+    count = len(summaries)
+    key_mean = np.zeros((count, N_CLASSES), dtype=np.float32)
+    key_comp = np.full((count, N_CLASSES), -1, dtype=np.int32)
+    for j, s in enumerate(summaries):
+        where = {(int(a), int(b)): r for r, (a, b) in enumerate(s["keys"])}
+        for Ar, Aa in s["AD_array"][:, :2]:
+            mean = s["means"][where[(int(Ar), int(Aa))]]
+            c = int(np.argwhere(mean == np.max(mean))[0][0])
+            key_comp[j, class_index(int(Ar), int(Aa))] = c
+            key_mean[j, class_index(int(Ar), int(Aa))] = mean[c]
+    return KeepSet(depth, i0, key_mean, key_comp)
+
+
+def stat_tables(summaries):
+    """Per individual the rows the kernel reads: [class d (d + 1) / 2 + a] = AD_like[r], AD_factorial[r] with r = AD_index[a, d - a]
+    (zscore_cy.pyx:28 reads the index transposed; only depths whose classes all survived are ever looked up)."""
+    tabs = np.zeros((len(summaries), N_CLASSES, 6), dtype=np.float32)
+    parts = []
+    for j, s in enumerate(summaries):
+        fac, like, index = get_factorials(s["AD_array"], s["keys"], s["means"], E)
+        parts.append((fac, like, index))
+        for d in np.unique(s["AD_array"][:, 2]):
+            for a in range(int(d) + 1):
+                r = index[a, int(d) - a]
+                tabs[j, class_index(int(d) - a, a)] = np.concatenate((like[r], fac[r]))
+    return tabs, parts
+
+
+def _finish(i, kept, wobs, wl, var, say):
+    W_l_obs = np.sum(wobs, dtype=np.float32)
+    z_mu = np.sum(wl)
+    z_var = np.sum(var)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z_tmp = (W_l_obs - z_mu) / np.sqrt(z_var)
+    say("Finished individual " + str(i))
+    say("z_mu: " + str(z_mu))
+    say("z_var: " + str(z_var))
+    say("z_obs: " + str(W_l_obs))
+    say("Loci used: " + str(int(kept)))
+    say("Z-score: " + str(z_tmp))
+    return dict(W_l_obs=W_l_obs, z_mu=z_mu, z_var=z_var, z=z_tmp)
+
+
+def _batches(lo, hi, batch):
+    for i0 in range(lo, hi, batch):
+        yield i0, min(batch, hi - i0)
+
+
+def assignment_z_scores(beagle, depth, IDs, pops, afset, n_threshold=0, single_read_threshold=False, ind_start=0, ind_end=None,
+                        batch=64, say=print, details=None):
+    """--get_assignment_z_score (WGSassign.py:395-446): z of individuals [ind_start, ind_end) against column k of `afset`, k = the
+    position of the individual's population in `pops`.  float32 (n_sub, 1).  details (a list) receives per individual the
+    intermediate arrays (tests)."""
+    ind_end = beagle.n if ind_end is None else ind_end
+    z_out = np.empty((ind_end - ind_start, 1), dtype=np.float32)
+    for i0, count in _batches(ind_start, ind_end, batch):
+        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold)
+        keep = get_L_keep(depth, i0, summ)
+        tabs, parts = stat_tables(summ)
+        cols = [int(np.argwhere(pops == IDs[i0 + j, 1])[0][0]) for j in range(count)]
+        wobs, wl, var = keep.stats(tabs, [afset.col_dev(k) for k in cols])
+        for j in range(count):
+            r = _finish(i0 + j, keep.kept[j], wobs[j], wl[j], var[j], say)
+            z_out[i0 + j - ind_start, 0] = r["z"]
+            if details is not None:
+                details.append(dict(summ[j], keep=keep.sites(j), fac=parts[j][0], like=parts[j][1], index=parts[j][2], wobs=wobs[j],
+                                    wl=wl[j], var=var[j], **r))
+        keep.close()
+    return z_out
+
+
+def reference_z_scores(beagle, depth, IDs, group_of, maf_iter=200, maf_tole=1e-4, n_threshold=0, single_read_threshold=False,
+                       ind_start=0, ind_end=None, batch=64, say=print, details=None):
+    """--get_reference_z_score (WGSassign.py:311-393): per individual the leave-one-out EM fit of its population on ITS kept sites
+    (wgs_em_fit_masked: the existing sweeps, the convergence chain over the kept sites), the clamp, then as above.  `beagle` must
+    hold one slab per population (group_of as --get_reference_af builds it)."""
+    from .device import EMBatch
+    ind_end = beagle.n if ind_end is None else ind_end
+    sizes = np.bincount(group_of, minlength=int(np.max(group_of)) + 1)
+    z_out = np.empty((ind_end - ind_start, 1), dtype=np.float32)
+    for i0, count in _batches(ind_start, ind_end, batch):
+        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold)
+        keep = get_L_keep(depth, i0, summ)
+        tabs, parts = stat_tables(summ)
+        ids = np.arange(i0, i0 + count)
+        if np.any(sizes[group_of[ids]] < 2):
+            raise ValueError("a population with a single individual has nobody left for the leave-one-out fit")
+        em = EMBatch(beagle, group_of[ids], ids)
+        iters = np.zeros(count, dtype=np.int32)
+        slots = np.arange(count, dtype=np.int32)
+        check(_lib.load().wgs_em_fit_masked(em.handle, keep.handle, i32p(slots), int(maf_iter), float(maf_tole), i32p(iters)))
+        for j in range(count):
+            if iters[j]:
+                say("EM (MAF) converged at iteration: " + str(int(iters[j])))
+            em.clamp(j, int(sizes[group_of[i0 + j]]) - 1)
+        wobs, wl, var = keep.stats(tabs, [em.f_dev(j) for j in range(count)])
+        for j in range(count):
+            r = _finish(i0 + j, keep.kept[j], wobs[j], wl[j], var[j], say)
+            z_out[i0 + j - ind_start, 0] = r["z"]
+            if details is not None:
+                sites = keep.sites(j)
+                details.append(dict(summ[j], keep=sites, fac=parts[j][0], like=parts[j][1], index=parts[j][2], wobs=wobs[j], wl=wl[j],
+                                    var=var[j], A=em.get_f(j)[sites], it=int(iters[j]), **r))
+        em.close()
+        keep.close()
+    return z_out
