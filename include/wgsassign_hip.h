@@ -46,7 +46,9 @@ const char *wgs_last_error(void);
  * compare wgs_version() with the WGS_ABI_VERSION it was compiled with and refuse to run on a mismatch (the ctypes shim does:
  * wgsassign_amd/_lib.py); wgs_beagle_codes_info fills 20 entries; wgs_comm_info is new.  3 (round 5): self-checking
  * collectives (wgs_coll_tag, wgs_comm_check, wgs_comm_next_generation, wgs_comm_allreduce_host_tagged).  The z-score entry points
- * (wgs_depth_*, wgs_zscore_*, wgs_zkeep_*, wgs_em_fit_masked) were ADDED under 3: no existing signature changed. */
+ * (wgs_depth_*, wgs_zscore_*, wgs_zkeep_*, wgs_em_fit_masked) were ADDED under 3: no existing signature changed; so were the
+ * integer-table reader (wgs_reader_open_table), the depth ingest (wgs_depth_ingest_*), wgs_depth_create_shape and
+ * wgs_depth_download_rows. */
 #define WGS_ABI_VERSION 3
 int wgs_version(void);
 /* sha256[:16] over every source of the library / over the sources of the EM and scoring kernels (em_kernels.hip,
@@ -412,6 +414,14 @@ int wgs_reader_index_merge(const char *path, const char *index_path, const char 
                            int32_t max_points, int64_t *sites);
 int wgs_reader_open_indexed(const char *path, const char *index_path, int64_t first_row, int threads, wgs_reader **out);
 
+/* An INTEGER TABLE instead of a Beagle file: lines of whitespace-separated small integers as np.loadtxt reads them -- the
+ * allele depths of --ind_ad_file (WGSassign.py:321, skip_lines 0) or ANGSD's -dumpCounts 4 output (allele_counts_beagle.py:11,
+ * skip_lines 1).  Plain text, gzip or BGZF, told apart by the file's first bytes, not by its name.  No header is parsed and no
+ * site-name column kept; blank lines and lines that start with '#' are no rows.  Such a reader serves wgs_depth_ingest_create
+ * only (wgs_reader_next and the Beagle ingest refuse it).  wgs_reader_table_columns: columns of the first data line (0: none). */
+int wgs_reader_open_table(const char *path, int threads, int skip_lines, wgs_reader **out);
+int wgs_reader_table_columns(wgs_reader *r);
+
 /* ------------------------------------------------------------------ device-side ingest
  * reader_cy.pyx:52-66 (strtok + atof per value) on the MI355X: the reader only inflates, finds the newlines and keeps
  * the site names; the TEXT goes to the device through page-locked buffers and a HIP kernel tokenises it straight into
@@ -449,6 +459,36 @@ int wgs_depth_create(wgs_beagle *b, wgs_depth **out);
 void wgs_depth_destroy(wgs_depth *d);
 /* Host rows [row0, row0 + nrows) of the (m, 2n) int32 table.  rc 2: a count outside 0..255 (does not fit the table). */
 int wgs_depth_upload_rows(wgs_depth *d, const int32_t *AD_rows, int64_t row0, int64_t nrows);
+/* The mirror: rows [row0, row0 + nrows) of the table back into (nrows, 2n) int32 host layout (tests, tools). */
+int wgs_depth_download_rows(wgs_depth *d, int32_t *AD_rows, int64_t row0, int64_t nrows);
+/* A table of m sites x n individuals that belongs to no matrix (python -m wgsassign_amd.allele_counts: only filled and read back;
+ * wgs_zscore_classes and wgs_zkeep_create refuse it).  Destroyed by wgs_depth_destroy. */
+int wgs_depth_create_shape(wgs_ctx *ctx, int64_t m, int64_t n, wgs_depth **out);
+/* The table filled FROM A FILE on the device (csrc/ingest.hip: depth_tokenise_kernel), through the hand-overs of the Beagle
+ * ingest: plain text and plain gzip come as text through page-locked buffers (the host inflates), BGZF members are inflated on
+ * the device unless WGSASSIGN_INFLATE=host.  `r` comes from wgs_reader_open_table and is used through the ingest only, which is
+ * destroyed before the reader is closed and before the table.
+ *   WGS_DEPTH_PAIRS   individual i of a line owns tokens 2i, 2i + 1 (--ind_ad_file); columns behind 2n are ignored;
+ *   WGS_DEPTH_COUNTS  tokens 4i .. 4i + 3 (A, C, G, T reads); majmin[site][2] (host, m x 2 bytes, each 0..3) selects the pair
+ *                     (token 4i + major, token 4i + minor) -- allele_counts_beagle.py:19-23.
+ * The kernel converts runs of 1-3 digits up to 255; a line with anything else, or too few columns, is parsed on the host by
+ * np.loadtxt's rules (a decimal or exponent form is truncated, as NumPy still does with a deprecation warning): rc 2 names the 1-based line of the file for a token np.loadtxt refuses as int32, a short line, or a count
+ * outside 0..255.  limit_rows < 0: to the end of the file.  chunk_bytes <= 0: 4 MiB of text per chunk (32 MiB when the device
+ * inflates) -- host memory stays at the staging buffers, never the table.
+ * wgs_depth_ingest_next: the next chunk's data lines fill rows row0, row0 + 1, ...; *file_rows = data lines consumed (0: end),
+ * *rows_written = rows filled.  Lines beyond the table's last row are counted, not stored (*rows_written = 0 from there on): the
+ * caller compares the total with the rows it expected.
+ * wgs_depth_ingest_stats, stats[0..7]: largest single host buffer held, in bytes | device ms (copies + kernels) | lines parsed
+ * on the host | text bytes | data lines | chunks | BGZF members inflated on the device | ms of the tokeniser kernel alone
+ * (0 unless WGSASSIGN_INGEST_TIME_KERNEL is set: timing it costs a synchronisation per chunk). */
+#define WGS_DEPTH_PAIRS 0
+#define WGS_DEPTH_COUNTS 1
+typedef struct wgs_depth_ingest wgs_depth_ingest;
+int wgs_depth_ingest_create(wgs_depth *d, wgs_reader *r, int mode, const uint8_t *majmin, int64_t limit_rows, int64_t chunk_bytes,
+                            wgs_depth_ingest **out);
+void wgs_depth_ingest_destroy(wgs_depth_ingest *g);
+int wgs_depth_ingest_next(wgs_depth_ingest *g, int64_t row0, int64_t *file_rows, int64_t *rows_written);
+int wgs_depth_ingest_stats(wgs_depth_ingest *g, double *stats);
 int wgs_zscore_max_depth(void);
 /* zscore.AD_summary, the dictionary (zscore.py:11-21), for individuals [i0, i0 + count) in ONE launch: per (individual, class)
  * the number of sites, the float32 sums of (g0, g1, 1 - g0 - g1) in site order (np.mean's numerator; the caller divides), the

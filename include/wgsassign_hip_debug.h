@@ -37,6 +37,12 @@ int wgs_debug_inflate(wgs_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, con
  * parallel newline scan, row limit) with ordinary memory and the host parser in place of the device tokeniser. */
 int wgs_debug_reader_text_rows(wgs_reader *r, int64_t chunk_bytes, int64_t limit_rows, float *rows, int64_t max_rows, int64_t *nrows);
 int64_t wgs_debug_reader_text_chunks(wgs_reader *r);   /* chunks that hand-over produced */
+/* The same for an integer table (wgs_reader_open_table): every listed line through the host parser of flagged lines, `need`
+ * columns each; linenos[i] = the 1-based line of row i in the file.  rc 2: a short line or a token np.loadtxt refuses. */
+int wgs_debug_reader_table_rows(wgs_reader *r, int64_t chunk_bytes, int32_t need, int32_t *rows, int64_t max_rows, int64_t *nrows,
+                                int64_t *linenos);
+/* That parser on one line: 0 = ok, 1 = fewer than `need` columns, 3 = a token that is no int32 by np.loadtxt's rules. */
+int wgs_debug_table_parse_line(const char *line, int64_t len, int32_t need, int32_t *out);
 /* Test hook, needs no GPU: the COMPRESSED hand-over of a BGZF file (what the device-resident ingest consumes: whole members
  * in caller-allocated staging + the text the header calls had inflated already), inflated on the host into text[0 .. cap).
  * info[0..3] = chunks, members, largest text of one chunk, chunks that carried pre-inflated text. */

@@ -45,6 +45,12 @@ parser.add_argument("--get_assignment_z_score", action="store_true", help="Calcu
 parser.add_argument("--get_reference_z_score", action="store_true", help="Calculate z-score for reference individuals")
 parser.add_argument("--ind_ad_file", metavar="FILE",
                     help="Filepath to individual allele depths (text as np.loadtxt reads it, or .npy)")
+parser.add_argument("--ind_counts_file", metavar="FILE",
+                    help="ANGSD -dumpCounts 4 output (.counts.gz: one header line, A C G T reads per individual); with "
+                         "--ind_majmin_file it stands in place of --ind_ad_file")
+parser.add_argument("--ind_majmin_file", metavar="FILE",
+                    help="Major and minor allele of every site as 0..3 in columns 2 and 3, one header line (the second argument "
+                         "of the reference's allele_counts_beagle.py)")
 parser.add_argument("--allele_count_threshold", metavar="INT", type=int,
                     help="Minimum number of loci needed to keep a specific allele count combination")
 parser.add_argument("--single_read_threshold", action="store_true",
@@ -243,8 +249,11 @@ def _z_scores(args, flavour, beagle, group_of, m, n, say, root):
         assert os.path.isfile(args.pop_af_file), "Population allele frequency file does not exist!!"
         A = np.ascontiguousarray(np.load(args.pop_af_file), dtype=np.float32)
     say("Parsing individual allele depths file.")
-    assert os.path.isfile(args.ind_ad_file), "Individual allele depths file does not exist!"
-    AD = zscore.read_depths(args.ind_ad_file)
+    majmin = None
+    if args.ind_counts_file:
+        majmin = zscore.read_majmin(args.ind_majmin_file)       # (checked once before the Beagle file was opened: depth_options)
+    else:
+        assert os.path.isfile(args.ind_ad_file), "Individual allele depths file does not exist!"
     assert os.path.isfile(args.pop_names), "Population names file does not exist!!"
     pops = np.loadtxt(args.pop_names, dtype="str")
     assert (n == IDs.shape[0]), "Number of individuals in beagle and reference ID file do not match!"
@@ -254,8 +263,8 @@ def _z_scores(args, flavour, beagle, group_of, m, n, say, root):
     else:
         allele_count_threshold = 0
     ind_start, ind_end = zscore.ind_range(n, args.ind_start, args.ind_end)
-    depth = zscore.DepthTable(beagle, AD)
-    del AD
+    # streamed and tokenised on the device: no m x 2n array on the host (csrc/ingest.hip: depth_tokenise_kernel)
+    depth = zscore.DepthTable.from_file(beagle, args.ind_counts_file or args.ind_ad_file, counts=majmin is not None, majmin=majmin)
     if flavour == "assignment":
         if A.shape[0] != m:
             raise ValueError("the allele frequency file has %d sites, the Beagle file %d" % (A.shape[0], m))
@@ -272,6 +281,24 @@ def _z_scores(args, flavour, beagle, group_of, m, n, say, root):
     if root:
         np.savetxt(args.out + name, z_out, fmt="%.7f")
     say("Saved " + str(ind_end - ind_start) + " individual z-scores as " + str(args.out) + name + " (text)")
+
+
+def depth_options(args):
+    """--ind_counts_file / --ind_majmin_file against --ind_ad_file, before any large file is opened."""
+    if args.ind_counts_file and args.ind_ad_file:
+        raise SystemExit("--ind_counts_file (with --ind_majmin_file) stands in place of --ind_ad_file: give one of the two")
+    if bool(args.ind_counts_file) != bool(args.ind_majmin_file):
+        raise SystemExit("--ind_counts_file and --ind_majmin_file go together: %s is missing" %
+                         ("--ind_majmin_file" if args.ind_counts_file else "--ind_counts_file"))
+    if args.ind_counts_file:
+        for path, what in ((args.ind_counts_file, "ANGSD counts"), (args.ind_majmin_file, "major/minor allele")):
+            if not os.path.isfile(path):
+                raise SystemExit("%s file %s does not exist" % (what, path))
+        from . import zscore
+        try:
+            zscore.read_majmin(args.ind_majmin_file)
+        except ValueError as e:
+            raise SystemExit(str(e))
 
 
 def main(argv=None):
@@ -303,6 +330,9 @@ def main(argv=None):
         # the depth-class sums and np.sum's pairwise order are defined over ALL sites of an individual: not sharded by SNP yet
         raise SystemExit("--get_assignment_z_score / --get_reference_z_score run on one GPU: start them without --gpus "
                          "(the z-score path does not shard the SNPs)")
+
+    if args.get_assignment_z_score or args.get_reference_z_score:
+        depth_options(args)
 
     if root:        # log-file of non-default arguments (WGSassign.py:127-141)
         full, deaf = vars(args), vars(parser.parse_args([]))

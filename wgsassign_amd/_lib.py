@@ -58,6 +58,16 @@ SIGNATURES = {
     "wgs_depth_create": (c_int, [c_vp, ctypes.POINTER(c_vp)]),
     "wgs_depth_destroy": (None, [c_vp]),
     "wgs_depth_upload_rows": (c_int, [c_vp, c_i32p, c_i64, c_i64]),
+    "wgs_depth_download_rows": (c_int, [c_vp, c_i32p, c_i64, c_i64]),
+    "wgs_depth_create_shape": (c_int, [c_vp, c_i64, c_i64, ctypes.POINTER(c_vp)]),
+    "wgs_depth_ingest_create": (c_int, [c_vp, c_vp, c_int, c_vp, c_i64, c_i64, ctypes.POINTER(c_vp)]),
+    "wgs_depth_ingest_destroy": (None, [c_vp]),
+    "wgs_depth_ingest_next": (c_int, [c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "wgs_depth_ingest_stats": (c_int, [c_vp, c_f64p]),
+    "wgs_reader_open_table": (c_int, [ctypes.c_char_p, c_int, c_int, ctypes.POINTER(c_vp)]),
+    "wgs_reader_table_columns": (c_int, [c_vp]),
+    "wgs_debug_reader_table_rows": (c_int, [c_vp, c_i64, c_i32, c_i32p, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "wgs_debug_table_parse_line": (c_int, [ctypes.c_char_p, c_i64, c_i32, c_i32p]),
     "wgs_zscore_max_depth": (c_int, []),
     "wgs_zscore_classes": (c_int, [c_vp, c_i32, c_i32, c_i32p, c_f32p, c_i32p, c_i32p]),
     "wgs_zkeep_create": (c_int, [c_vp, c_i32, c_i32, c_f32p, c_i32p, ctypes.POINTER(c_i64), ctypes.POINTER(c_vp)]),

@@ -33,6 +33,7 @@
 
 #include "common.h"
 #include "reader_text.h"
+#include "zscore.h"
 
 size_t inflate_table_bytes(void);
 constexpr size_t INFLATE_PAD = 128;   // bytes the compressed chunk is padded by on the device (inflate.hip reads a 24-byte window ahead)
@@ -208,6 +209,154 @@ __global__ __launch_bounds__(256) void tokenise_kernel(TokArgs a)
     }
 }
 
+// ---- integer tables: allele depths (--ind_ad_file) and ANGSD counts into the depth table [individual][site] of byte pairs ------------
+// Same hand-over and token numbering as tokenise_kernel (one wavefront per line, 1 KiB per step, wave-wide prefix sum of the token
+// starts), but a line is one SITE and each of its n pairs belongs to another row of the table, mpad pairs apart: stored directly,
+// every pair would be a 2-byte store at a stride of 2 mpad bytes.  So a workgroup takes a TILE of 64 consecutive lines (16 per
+// wavefront) times a STRIP of DEPTH_STRIP individuals, collects the pairs in LDS as [individual][line] and then stores per
+// individual the 64 sites of the tile side by side: 128 bytes per wavefront store, what zclass_kernel reads per wavefront.
+//   * pairs  (tpi = 2): individual i of a line owns tokens 2i, 2i + 1;
+//   * counts (tpi = 4): tokens 4i .. 4i + 3 (A, C, G, T reads); the pair is (token 4i + major, token 4i + minor) with the
+//     site's selectors from sel[row][2] -- np.take_along_axis in the reference's allele_counts_beagle.py.
+// LDS: a row of the tile is 64 pairs + 2 of padding = 33 dwords, so the tokens of one step -- consecutive individuals, one line --
+// fall into different banks, and the read-out of a row is 64 consecutive 2-byte words.  256 individuals x 132 bytes = 33 KiB: four
+// workgroups per CU.  More than DEPTH_STRIP individuals: the strips follow one another inside the workgroup; per line the step
+// where the strip ended is kept in LDS and taken up again (that step's 1 KiB is read twice, nothing else).
+// The kernel converts runs of 1-3 digits with value <= 255; any other token among those it owns, or too few of them, flags the
+// line, whose pairs are not stored (in the strip where the flag is raised and the strips after it; the host parses a flagged line
+// and either uploads its whole row or refuses the file).
+constexpr int DEPTH_STRIP = 256, DEPTH_ROW = 132;
+
+struct DepthTokArgs {
+    const uint4 *text;
+    const uint32_t *begin, *end;
+    const int32_t *dst;
+    uint8_t *flags;
+    uint32_t *nflagged;
+    int64_t row0;
+    int32_t nlines, n_inds, tpi;
+    const uint8_t *sel;            // counts: [site][2] selectors 0..3 (checked on the host)
+    uchar2 *table;
+    int64_t mpad;
+};
+
+__global__ __launch_bounds__(256) void depth_tokenise_kernel(DepthTokArgs a)
+{
+    __shared__ __attribute__((aligned(4))) uint8_t tile[DEPTH_STRIP * DEPTH_ROW];
+    __shared__ uint32_t s_wb[64], s_tok[64], s_prev[64];
+    __shared__ int32_t s_rel[64];
+    __shared__ uint8_t s_bad[64], s_major[64], s_minor[64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int line0 = (int)blockIdx.x * 64;
+    if (threadIdx.x < 64) {
+        const int l = line0 + (int)threadIdx.x;
+        const int32_t rel = l < a.nlines ? a.dst[l] : -1;
+        s_rel[threadIdx.x] = rel;
+        s_wb[threadIdx.x] = rel >= 0 ? a.begin[l] >> 4 : 0u;
+        s_tok[threadIdx.x] = 0;
+        s_prev[threadIdx.x] = 0;
+        s_bad[threadIdx.x] = 0;
+        s_major[threadIdx.x] = a.sel && rel >= 0 ? a.sel[(a.row0 + rel) * 2] & 3 : 0;
+        s_minor[threadIdx.x] = a.sel && rel >= 0 ? a.sel[(a.row0 + rel) * 2 + 1] & 3 : 1;
+    }
+    __syncthreads();
+    const uint32_t tpi = (uint32_t)a.tpi;
+    for (int strip0 = 0; strip0 < a.n_inds; strip0 += DEPTH_STRIP) {
+        const int strip_n = min(DEPTH_STRIP, a.n_inds - strip0);
+        const uint32_t tok_lo = (uint32_t)strip0 * tpi, tok_hi = (uint32_t)(strip0 + strip_n) * tpi;
+        for (int q = 0; q < 16; ++q) {
+            const int li = wave * 16 + q;
+            if (s_rel[li] < 0 || s_bad[li]) continue;          // (the same for the whole wavefront)
+            const uint32_t b = a.begin[line0 + li], e = a.end[line0 + li];
+            const uint32_t w1 = (e + 15u) >> 4;
+            uint32_t wb = s_wb[li], tok = s_tok[li], prev_nd = s_prev[li];
+            const uint32_t major = s_major[li], minor = s_minor[li];
+            bool bad = false, enough = false;
+            while (wb < w1 && !enough) {
+                const uint32_t w = wb + (uint32_t)lane;
+                uint4 x = make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au), y = x;
+                if (w < w1) {
+                    x = a.text[w];
+                    y = a.text[w + 1];                         // in bounds: the buffer is padded by TEXT_PAD bytes
+                }
+                uint32_t nd = nondelim16(x) | (nondelim16(y) << 16);
+                const int64_t first = (int64_t)b - (int64_t)w * 16, last = (int64_t)e - (int64_t)w * 16;
+                if (first > 0) nd &= first >= 32 ? 0u : ~0u << first;
+                if (last < 32) nd &= last <= 0 ? 0u : ~0u >> (32 - last);
+                const uint32_t own = nd & 0xFFFFu;
+                uint32_t before = (uint32_t)__shfl_up((int)(own >> 15), 1);
+                if (lane == 0) before = prev_nd;
+                uint32_t starts = own & ~((own << 1) | before);
+                const int cnt = __popc(starts);
+                int incl = cnt;
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const int up = __shfl_up(incl, off);
+                    if (lane >= off) incl += up;
+                }
+                const uint64_t lo64 = x.x | ((uint64_t)x.y << 32), hi64 = x.z | ((uint64_t)x.w << 32);
+                uint32_t k = tok + (uint32_t)(incl - cnt);
+                while (starts) {
+                    const int bit = __ffs((int)starts) - 1;
+                    starts &= starts - 1;
+                    if (k >= tok_lo && k < tok_hi) {
+                        const uint32_t inv = ~(nd >> bit);
+                        const int len = inv ? __ffs((int)inv) - 1 : 32;
+                        // the token's first four bytes (it starts in this lane's word; bytes 16.. come from the next word)
+                        const uint64_t A = bit & 8 ? hi64 : lo64, B = bit & 8 ? (uint64_t)y.x : hi64;
+                        const int sh = (bit & 7) * 8;
+                        const uint32_t c4 = (uint32_t)(sh ? (A >> sh) | (B << (64 - sh)) : A);
+                        const uint32_t d0 = (c4 & 0xFFu) - '0', d1 = ((c4 >> 8) & 0xFFu) - '0', d2 = ((c4 >> 16) & 0xFFu) - '0';
+                        uint32_t v = 256;
+                        if (len == 1 && d0 <= 9) v = d0;
+                        else if (len == 2 && d0 <= 9 && d1 <= 9) v = d0 * 10 + d1;
+                        else if (len == 3 && d0 <= 9 && d1 <= 9 && d2 <= 9) v = d0 * 100 + d1 * 10 + d2;
+                        if (v <= 255) {
+                            const uint32_t j = k - tok_lo, ind = j / tpi, which = j - ind * tpi;
+                            uint8_t *cell = tile + ind * DEPTH_ROW + li * 2;
+                            if (tpi == 2) {
+                                cell[which] = (uint8_t)v;
+                            } else {
+                                if (which == major) cell[0] = (uint8_t)v;
+                                if (which == minor) cell[1] = (uint8_t)v;
+                            }
+                        } else {
+                            bad = true;
+                        }
+                    }
+                    ++k;
+                }
+                const uint32_t total = (uint32_t)__shfl(incl, 63);
+                enough = tok + total >= tok_hi;
+                if (tok + total > tok_hi && strip0 + strip_n < a.n_inds) break;     // the next strip starts inside this step: taken up there
+                tok += total;
+                prev_nd = (uint32_t)__shfl((int)(own >> 15), 63);
+                wb += 64;
+            }
+            if (!enough) bad = true;                           // too few columns
+            const bool any_bad = __any(bad);
+            if (lane == 0) {
+                s_wb[li] = wb;
+                s_tok[li] = tok;
+                s_prev[li] = prev_nd;
+                if (any_bad) s_bad[li] = 1;
+            }
+        }
+        __syncthreads();
+        const int32_t rel = s_rel[lane];
+        if (rel >= 0 && !s_bad[lane]) {
+            uchar2 *out = a.table + a.row0 + rel;
+            for (int ind = wave; ind < strip_n; ind += 4)
+                out[(int64_t)(strip0 + ind) * a.mpad] = *reinterpret_cast<const uchar2 *>(tile + ind * DEPTH_ROW + lane * 2);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 64 && s_rel[threadIdx.x] >= 0 && s_bad[threadIdx.x]) {
+        a.flags[line0 + (int)threadIdx.x] = 1;
+        if (a.nflagged) atomicAdd(a.nflagged, 1u);
+    }
+}
+
 // ---- line listing on the device (BGZF members inflated there: the text never exists on the host) -----------------------
 // What reader.cpp: list_lines does with memchr on the host: the positions of the newlines (count per 4 KiB block, scan,
 // write), then per line its extent, whether it is blank, and its first token (the site name); exclusive scans number the
@@ -316,6 +465,7 @@ struct LineArgs {
     uint32_t *nonblank;            // 1 = a data row
     uint32_t *name_start, *name_len1;   // first token; its length + 1 (0 for blank lines)
     uint32_t *totals;
+    int32_t table;                 // an integer table: a line that starts with '#' is no row (np.loadtxt)
 };
 
 __global__ __launch_bounds__(256) void line_info_kernel(LineArgs a)
@@ -329,9 +479,10 @@ __global__ __launch_bounds__(256) void line_info_kernel(LineArgs a)
     while (x < e && !is_delim_dev(a.text[x])) ++x;
     a.begin[i] = b;
     a.end[i] = e;
-    a.nonblank[i] = q < e ? 1u : 0u;
+    const bool row = q < e && !(a.table && a.text[q] == '#');
+    a.nonblank[i] = row ? 1u : 0u;
     a.name_start[i] = q;
-    a.name_len1[i] = q < e ? x - q + 1u : 0u;
+    a.name_len1[i] = !row ? 0u : a.table ? 1u : x - q + 1u;      // (a table has no names: one newline per row)
     if (i == a.nlines - 1) a.totals[T_TAIL] = e + 1u;          // where the partial last line starts
 }
 
@@ -433,7 +584,18 @@ void pinned_release(void *p, void *)
 }  // namespace
 
 struct wgs_ingest {
-    wgs_beagle *b = nullptr;
+    wgs_beagle *b = nullptr;        // the matrix the lines go to, or ...
+    wgs_depth *depth = nullptr;     // ... the depth table (wgs_depth_ingest_*: an integer table through the same hand-overs)
+    wgs_ctx *ctx = nullptr;
+    int64_t m_rows = 0;             // rows of the target
+    int32_t tpi = 2;                // depth: tokens per individual (2: pairs, 4: ANGSD counts)
+    uint8_t *d_sel = nullptr;       // counts: the sites' (major, minor) selectors
+    std::vector<int32_t> irows;     // depth: host-parsed rows of flagged lines
+    int64_t lines_before = 0;       // depth, device-resident: lines of the text in the chunks before this one
+    size_t host_peak = 0;           // depth: largest host buffer this object allocated itself
+    bool overflow = false;          // depth: the file has more data lines than the table rows
+    double tok_ms = 0.0;            // depth: the tokeniser kernel alone (WGSASSIGN_INGEST_TIME_KERNEL=1)
+    hipEvent_t kev0 = nullptr, kev1 = nullptr;
     wgs_reader *r = nullptr;
     void *d_text = nullptr;
     size_t text_cap = 0;
@@ -516,6 +678,32 @@ int ensure_line_arrays(wgs_ingest *g, hipStream_t st, size_t nl, bool resident)
 
 void launch_tokenise(wgs_ingest *g, hipStream_t st, const void *text, int64_t row0, size_t nl, uint32_t *nflagged)
 {
+    if (g->depth) {
+        DepthTokArgs d;
+        d.text = reinterpret_cast<const uint4 *>(text);
+        d.begin = g->d_begin;
+        d.end = g->d_end;
+        d.dst = g->d_dst;
+        d.flags = g->d_flags;
+        d.nflagged = nflagged;
+        d.row0 = row0;
+        d.nlines = (int32_t)nl;
+        d.n_inds = (int32_t)g->depth->n;
+        d.tpi = g->tpi;
+        d.sel = g->d_sel;
+        d.table = g->depth->table;
+        d.mpad = g->depth->mpad;
+        static const bool timed = getenv("WGSASSIGN_INGEST_TIME_KERNEL") != nullptr;
+        if (timed && !g->kev0 && (hipEventCreate(&g->kev0) != hipSuccess || hipEventCreate(&g->kev1) != hipSuccess)) g->kev0 = g->kev1 = nullptr;
+        if (timed && g->kev1) (void)hipEventRecord(g->kev0, st);
+        hipLaunchKernelGGL(depth_tokenise_kernel, dim3((unsigned)((nl + 63) / 64)), dim3(256), 0, st, d);
+        if (timed && g->kev1) {
+            float ms = 0.0f;
+            (void)hipEventRecord(g->kev1, st);
+            if (hipEventSynchronize(g->kev1) == hipSuccess && hipEventElapsedTime(&ms, g->kev0, g->kev1) == hipSuccess) g->tok_ms += ms;
+        }
+        return;
+    }
     wgs_beagle *b = g->b;
     TokArgs a;
     a.text = reinterpret_cast<const uint4 *>(text);
@@ -565,6 +753,52 @@ int host_parse_flagged(wgs_ingest *g, int64_t row0, size_t nl, const uint8_t *fl
     return 0;
 }
 
+// The same for an integer table: a flagged line by np.loadtxt's rules (reader_table_parse_line); its pairs are picked as the kernel
+// picks them and the row goes through wgs_depth_upload_rows, which refuses counts outside 0..255.  line_of(t) = the 1-based number
+// of line t in the file.
+template <class TextOf, class LineOf>
+int host_parse_flagged_depth(wgs_ingest *g, int64_t row0, size_t nl, const uint8_t *flags, const int32_t *dst, TextOf text_of, LineOf line_of)
+{
+    wgs_depth *d = g->depth;
+    const int need = (int)d->n * g->tpi;
+    std::vector<int32_t> toks((size_t)need), sel(2);
+    g->irows.resize((size_t)2 * d->n);
+    for (size_t t = 0; t < nl; ++t) {
+        if (!flags[t] || dst[t] < 0) continue;
+        const char *lb = nullptr, *le = nullptr;
+        if (int rc = text_of(t, &lb, &le)) return rc;
+        int bad_col = 0;
+        const int k = reader_table_parse_line(lb, le, need, toks.data(), &bad_col);
+        if (k == 1) {
+            wgs_set_error("line %lld has fewer than %d columns (%lld individuals)", (long long)line_of(t), need, (long long)d->n);
+            return 2;
+        }
+        if (k) {
+            wgs_set_error("line %lld, column %d: not an integer np.loadtxt reads as int32", (long long)line_of(t), bad_col);
+            return 2;
+        }
+        const int64_t row = row0 + dst[t];
+        if (g->tpi == 2) {
+            memcpy(g->irows.data(), toks.data(), sizeof(int32_t) * (size_t)need);
+        } else {
+            uint8_t mm[2];
+            HIP_TRY(hipMemcpy(mm, g->d_sel + row * 2, 2, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < d->n; ++i) {
+                g->irows[(size_t)(2 * i)] = toks[(size_t)(4 * i + (mm[0] & 3))];
+                g->irows[(size_t)(2 * i + 1)] = toks[(size_t)(4 * i + (mm[1] & 3))];
+            }
+        }
+        for (int32_t v : g->irows)
+            if (v < 0 || v > 255) {
+                wgs_set_error("line %lld: allele depths outside 0..255 do not fit the device table", (long long)line_of(t));
+                return 2;
+            }
+        if (int rc = wgs_depth_upload_rows(d, g->irows.data(), row, 1)) return rc;
+        g->host_lines += 1;
+    }
+    return 0;
+}
+
 /* BGZF, device-resident: per chunk the producer thread only READS the next members (reader.cpp: comp_producer); here
  *   H2D of the compressed bytes -> inflate_kernel (inflate.hip; one lane per member) into d_text behind the carried partial
  *   line -> newline positions (count per 4 KiB, scan, write) -> per line extent / blank / site name -> scans number the data
@@ -573,8 +807,7 @@ int host_parse_flagged(wgs_ingest *g, int64_t row0, size_t nl, const uint8_t *fl
  * The host sees three small read-backs per chunk (counts, the names, the flag count) and the text never exists there. */
 int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t keep_len, int64_t *file_rows, int64_t *rows_written)
 {
-    wgs_beagle *b = g->b;
-    hipStream_t st = b->ctx->stream;
+    hipStream_t st = g->ctx->stream;
     static const bool trace = getenv("WGSASSIGN_INGEST_TRACE") != nullptr;       // per-chunk wall times on stderr
     while (!g->done) {
         const double t_begin = now_s();
@@ -648,7 +881,7 @@ int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64
             HIP_TRY(hipMemcpyAsync(g->d_in_len, c->in_len.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(g->d_isize, c->isize.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
             HIP_TRY(hipEventRecord(g->iev0, st));
-            if (launch_inflate(b->ctx, g->d_comp, g->d_in_off, g->d_in_len, g->d_out_off, g->d_isize, text, g->d_status, g->d_tables, nb)) return 1;
+            if (launch_inflate(g->ctx, g->d_comp, g->d_in_off, g->d_in_len, g->d_out_off, g->d_isize, text, g->d_status, g->d_tables, nb)) return 1;
             HIP_TRY(hipEventRecord(g->iev1, st));
             g->status.resize((size_t)nb);
             HIP_TRY(hipMemcpyAsync(g->status.data(), g->d_status, (size_t)nb, hipMemcpyDeviceToHost, st));
@@ -723,6 +956,7 @@ int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64
         la.name_start = g->d_name_start;
         la.name_len1 = g->d_name_len1;
         la.totals = g->d_totals;
+        la.table = g->depth ? 1 : 0;
         hipLaunchKernelGGL(line_info_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, la);
         hipLaunchKernelGGL(scan_u32_kernel, dim3(1), dim3(1024), 0, st, g->d_nonblank, g->d_rank, (uint32_t)nl, g->d_totals + T_NONBLANK);
         hipLaunchKernelGGL(scan_u32_kernel, dim3(1), dim3(1024), 0, st, g->d_name_len1, g->d_name_off, (uint32_t)nl, g->d_totals + T_NAME_BYTES);
@@ -745,7 +979,11 @@ int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64
             for (size_t i = 0; i < take; ++i) g->dstmap[i] = keep[i] ? (int32_t)written++ : -1;
             if (take) HIP_TRY(hipMemcpyAsync(g->d_dstmap, g->dstmap.data(), take * sizeof(int32_t), hipMemcpyHostToDevice, st));
         }
-        WGS_REQUIRE(row0 >= 0 && row0 + written <= b->m, "rows [%lld, %lld) outside the device matrix (%lld rows)", (long long)row0, (long long)(row0 + written), (long long)b->m);
+        // a table with more data lines than the target has rows: nothing more is stored, the lines are still counted (the caller
+        // reports both numbers)
+        if (g->depth && row0 + written > g->m_rows) g->overflow = true;
+        if (g->overflow) written = 0;
+        WGS_REQUIRE(row0 >= 0 && row0 + written <= g->m_rows, "rows [%lld, %lld) outside the device matrix (%lld rows)", (long long)row0, (long long)(row0 + written), (long long)g->m_rows);
         const size_t name_bytes = g->h_totals[T_NAME_BYTES];
         if (name_bytes + 16 > g->names_cap) {
             g->names_cap = 0;
@@ -754,7 +992,7 @@ int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64
         }
         DstArgs da;
         da.nlines = (uint32_t)nl;
-        da.take = (uint32_t)take;
+        da.take = g->overflow ? 0u : (uint32_t)take;
         da.nonblank = g->d_nonblank;
         da.rank = g->d_rank;
         da.name_start = g->d_name_start;
@@ -777,7 +1015,7 @@ int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64
         float ms = 0.0f;
         HIP_TRY(hipEventElapsedTime(&ms, g->ev0, g->ev1));
         g->device_ms += ms;
-        if (take < rows_here) g->names.resize(g->h_totals[T_NAME_CUT]);
+        if (take < rows_here || g->overflow) g->names.resize(g->h_totals[T_NAME_CUT]);
         if (g->h_totals[T_FLAGGED]) {
             // rare: fetch what the host parser needs -- flags, extents, numbering -- and the flagged lines themselves
             g->flags.resize(nl);
@@ -798,7 +1036,12 @@ int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64
                 *le = g->line.data() + n;
                 return 0;
             };
-            if (int rc = host_parse_flagged(g, row0, nl, g->flags.data(), g->dst.data(), g->rows_done, text_of, [&](size_t t) { return g->h_rank[t]; })) return rc;
+            if (g->depth) {
+                const int64_t base = reader_table_skip_lines(g->r) + g->lines_before + 1;
+                if (int rc = host_parse_flagged_depth(g, row0, nl, g->flags.data(), g->dst.data(), text_of, [&](size_t t) { return base + (int64_t)t; })) return rc;
+            } else if (int rc = host_parse_flagged(g, row0, nl, g->flags.data(), g->dst.data(), g->rows_done, text_of, [&](size_t t) { return g->h_rank[t]; })) {
+                return rc;
+            }
         }
         // the partial last line moves to the front for the next chunk (through a side buffer: the two ranges may overlap);
         // queued behind the tokeniser, waited for by nobody but the next chunk's kernels
@@ -814,6 +1057,7 @@ int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64
             HIP_TRY(hipMemcpyAsync(text, g->d_carry, left, hipMemcpyDeviceToDevice, st));
         }
         g->carry = left;
+        g->lines_before += (int64_t)nl;
         g->rows_done += (int64_t)take;
         g->lines += (int64_t)take;
         if (trace)
@@ -830,13 +1074,16 @@ int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64
 
 }  // namespace
 
+int ingest_start(wgs_ingest *g, wgs_reader *r, int64_t limit_rows, int64_t chunk_bytes, int64_t resident_default, int64_t host_default,
+                 wgs_ingest **out);
+
 extern "C" {
 
 void wgs_ingest_destroy(wgs_ingest *g)
 {
     if (!g) return;
-    (void)hipSetDevice(g->b->ctx->device);
-    (void)hipStreamSynchronize(g->b->ctx->stream);
+    (void)hipSetDevice(g->ctx->device);
+    (void)hipStreamSynchronize(g->ctx->stream);
     if (g->resident) {
         reader_add_lines_read(g->r, g->rows_done);
         reader_comp_stop(g->r);
@@ -845,10 +1092,10 @@ void wgs_ingest_destroy(wgs_ingest *g)
     for (void *p : {g->d_text, (void *)g->d_begin, (void *)g->d_end, (void *)g->d_dst, (void *)g->d_flags, (void *)g->d_carry, (void *)g->d_comp,
                     (void *)g->d_in_off, (void *)g->d_out_off, (void *)g->d_in_len, (void *)g->d_isize, (void *)g->d_status, g->d_tables,
                     (void *)g->d_counts, (void *)g->d_offsets, (void *)g->d_nl_pos, (void *)g->d_nonblank, (void *)g->d_rank, (void *)g->d_name_start,
-                    (void *)g->d_name_len1, (void *)g->d_name_off, (void *)g->d_dstmap, (void *)g->d_names, (void *)g->d_totals})
+                    (void *)g->d_name_len1, (void *)g->d_name_off, (void *)g->d_dstmap, (void *)g->d_names, (void *)g->d_totals, (void *)g->d_sel})
         if (p) (void)hipFree(p);
     if (g->h_totals) (void)hipHostFree(g->h_totals);
-    for (hipEvent_t e : {g->ev0, g->ev1, g->iev0, g->iev1})
+    for (hipEvent_t e : {g->ev0, g->ev1, g->iev0, g->iev1, g->kev0, g->kev1})
         if (e) (void)hipEventDestroy(e);
     delete g;
 }
@@ -858,26 +1105,39 @@ void wgs_ingest_destroy(wgs_ingest *g)
 int wgs_ingest_create(wgs_beagle *b, wgs_reader *r, int64_t limit_rows, int64_t chunk_bytes, wgs_ingest **out)
 {
     WGS_REQUIRE(b && r && out, "null argument");
-    const double t_create = now_s();
+    WGS_REQUIRE(!reader_is_table(r), "the reader was opened for an integer table, not a Beagle file");
     WGS_REQUIRE(reader_text_n_inds(r) == b->n, "the Beagle file has %d individuals, the device matrix %lld", reader_text_n_inds(r),
                 (long long)b->n);
-    HIP_TRY(hipSetDevice(b->ctx->device));
+    wgs_ingest *g = new wgs_ingest();
+    g->b = b;
+    g->ctx = b->ctx;
+    g->m_rows = b->m;
+    return ingest_start(g, r, limit_rows, chunk_bytes, 3ll << 30, 256ll << 20, out);
+}
+
+}  // extern "C"
+
+// The part of the creation that both targets share; takes over `g` (destroyed on failure).
+int ingest_start(wgs_ingest *g, wgs_reader *r, int64_t limit_rows, int64_t chunk_bytes, int64_t resident_default, int64_t host_default,
+                 wgs_ingest **out)
+{
+    const double t_create = now_s();
+    wgs_ctx *ctx = g->ctx;
+    g->r = r;
+    g->limit = limit_rows;
+    auto guard = on_failure([&] { wgs_ingest_destroy(g); });
+    HIP_TRY(hipSetDevice(ctx->device));
     // BGZF (what ANGSD writes): inflated on the device unless WGSASSIGN_INFLATE says host / zlib
     const char *how = getenv("WGSASSIGN_INFLATE");
     const bool resident = reader_text_is_bgzf(r) && !(how && (strcmp(how, "host") == 0 || strcmp(how, "zlib") == 0));
     // (one lane per member and three wavefronts per CU: a launch of up to 49 k members takes the time of one member, so a
     // chunk is that many members -- see reader_comp_start below -- or 3 GiB of text, whichever comes first)
-    if (chunk_bytes <= 0) chunk_bytes = resident ? (3ll << 30) : (256ll << 20);
+    if (chunk_bytes <= 0) chunk_bytes = resident ? resident_default : host_default;
     chunk_bytes = std::min<int64_t>(chunk_bytes, resident ? (3ll << 30) : (1ll << 30));
-    wgs_ingest *g = new wgs_ingest();
-    g->b = b;
-    g->r = r;
-    g->limit = limit_rows;
     TextAllocator a;
     a.alloc = pinned_alloc;
     a.release = pinned_release;
-    a.user = (void *)(intptr_t)b->ctx->device;
-    auto guard = on_failure([&] { wgs_ingest_destroy(g); });
+    a.user = (void *)(intptr_t)ctx->device;
     HIP_TRY(hipEventCreate(&g->ev0));
     HIP_TRY(hipEventCreate(&g->ev1));
     if (resident) {
@@ -885,7 +1145,7 @@ int wgs_ingest_create(wgs_beagle *b, wgs_reader *r, int64_t limit_rows, int64_t 
         HIP_TRY(hipEventCreate(&g->iev1));
         HIP_TRY(wgs_malloc(reinterpret_cast<void **>(&g->d_totals), T_COUNT * sizeof(uint32_t)));
         HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g->h_totals), T_COUNT * sizeof(uint32_t), hipHostMallocDefault));
-        g->chunk_text = (size_t)std::max<int64_t>(chunk_bytes, 1 << 20);
+        g->chunk_text = (size_t)std::max<int64_t>(chunk_bytes, g->depth ? 65536 : 1 << 20);
         g->resident = true;
         if (limit_rows == 0) g->done = true;
         // page-locked staging for the compressed members: an eighth of the text (low-depth ANGSD output deflates 10 : 1 and
@@ -900,7 +1160,7 @@ int wgs_ingest_create(wgs_beagle *b, wgs_reader *r, int64_t limit_rows, int64_t 
             }
             // one lane per member and three wavefronts per CU (52 KiB of tables each): members beyond that many wait for a
             // second round of the launch
-            const size_t lanes = (size_t)std::max(1, b->ctx->cus) * 3 * 64;
+            const size_t lanes = (size_t)std::max(1, ctx->cus) * 3 * 64;
             if (int rc = reader_comp_start(r, staging, g->chunk_text, nbuf, a, lanes)) return rc;
         }
     } else if (int rc = reader_text_start(r, (size_t)chunk_bytes, 3, a, limit_rows)) {
@@ -912,18 +1172,19 @@ int wgs_ingest_create(wgs_beagle *b, wgs_reader *r, int64_t limit_rows, int64_t 
     return 0;
 }
 
+extern "C" {
+
 /* The next chunk of the file: its lines are tokenised on the device into the slab rows row0, row0 + 1, ...
  * (keep != NULL: keep[i] says whether the i-th line of THIS chunk is kept; dropped lines take no row).
  * *file_rows = lines of the chunk (0 at the end of the file / the row limit), *rows_written = rows they filled. */
 int wgs_ingest_next(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t keep_len, int64_t *file_rows, int64_t *rows_written)
 {
     WGS_REQUIRE(g && file_rows && rows_written, "null argument");
-    wgs_beagle *b = g->b;
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    hipStream_t st = b->ctx->stream;
+    HIP_TRY(hipSetDevice(g->ctx->device));
+    hipStream_t st = g->ctx->stream;
     *file_rows = *rows_written = 0;
     g->names.clear();
-    wgs_beagle_drop_codes(b);                                  // the matrix changes: its class codes are rebuilt on next use
+    if (g->b) wgs_beagle_drop_codes(g->b);                     // the matrix changes: its class codes are rebuilt on next use
     struct Clock {
         wgs_ingest *g;
         double t0;
@@ -945,8 +1206,13 @@ int wgs_ingest_next(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t ke
     g->dst.resize(nl);
     int64_t written = 0;
     for (size_t i = 0; i < nl; ++i) g->dst[i] = (!keep || keep[i]) ? (int32_t)written++ : -1;
-    WGS_REQUIRE(row0 >= 0 && row0 + written <= b->m, "rows [%lld, %lld) outside the device matrix (%lld rows)", (long long)row0,
-                (long long)(row0 + written), (long long)b->m);
+    if (g->depth && row0 + written > g->m_rows) g->overflow = true;       // (see ingest_next_resident)
+    if (g->overflow) {
+        std::fill(g->dst.begin(), g->dst.end(), -1);
+        written = 0;
+    }
+    WGS_REQUIRE(row0 >= 0 && row0 + written <= g->m_rows, "rows [%lld, %lld) outside the device matrix (%lld rows)", (long long)row0,
+                (long long)(row0 + written), (long long)g->m_rows);
     // device buffers (grow only)
     const size_t text_bytes = (c->len + TEXT_PAD + 15) & ~(size_t)15;
     if (text_bytes > g->text_cap) {
@@ -979,7 +1245,12 @@ int wgs_ingest_next(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t ke
         *le = c->data + c->end[t];
         return 0;
     };
-    if (int rc = host_parse_flagged(g, row0, nl, g->flags.data(), g->dst.data(), c->first_row, text_of, [](size_t t) { return t; })) return rc;
+    if (g->depth) {
+        const int64_t base = reader_table_skip_lines(g->r) + c->first_line + 1;
+        if (int rc = host_parse_flagged_depth(g, row0, nl, g->flags.data(), g->dst.data(), text_of, [&](size_t t) { return base + (int64_t)c->lineno[t]; })) return rc;
+    } else if (int rc = host_parse_flagged(g, row0, nl, g->flags.data(), g->dst.data(), c->first_row, text_of, [](size_t t) { return t; })) {
+        return rc;
+    }
     g->names.swap(c->names);
     g->inflate_s += c->inflate_s;
     g->scan_s += c->scan_s;
@@ -1020,6 +1291,85 @@ int wgs_ingest_stats(wgs_ingest *g, double *stats)
     stats[11] = g->read_s;
     stats[12] = g->create_s;
     stats[13] = g->next_s;
+    return 0;
+}
+
+}  // extern "C"
+
+/* ---- integer tables into the depth table (include/wgsassign_hip.h: wgs_depth_ingest_*): the ingest above with another target.
+ * Chunks are small next to the Beagle ingest's -- 4 MiB of text through the host's inflater, 32 MiB when the device inflates --
+ * because the point of this path is that the table never exists on the host: the page-locked buffers are all it holds. */
+extern "C" {
+
+int wgs_depth_ingest_create(wgs_depth *d, wgs_reader *r, int mode, const uint8_t *majmin, int64_t limit_rows, int64_t chunk_bytes,
+                            wgs_depth_ingest **out)
+{
+    WGS_REQUIRE(d && r && out, "null argument");
+    WGS_REQUIRE(reader_is_table(r), "the reader was not opened with wgs_reader_open_table");
+    WGS_REQUIRE(mode == WGS_DEPTH_PAIRS || mode == WGS_DEPTH_COUNTS, "mode must be WGS_DEPTH_PAIRS or WGS_DEPTH_COUNTS");
+    WGS_REQUIRE((mode == WGS_DEPTH_COUNTS) == (majmin != nullptr), "the (major, minor) selectors go with WGS_DEPTH_COUNTS, and only with it");
+    const int tpi = mode == WGS_DEPTH_COUNTS ? 4 : 2;
+    const int cols = reader_table_cols(r);
+    if (cols > 0 && (int64_t)cols < d->n * tpi) {
+        wgs_set_error("line %lld has %d columns, %lld individuals need %lld", (long long)(reader_table_skip_lines(r) + 1), cols, (long long)d->n,
+                      (long long)(d->n * tpi));
+        return 2;
+    }
+    if (majmin)
+        for (int64_t i = 0; i < 2 * d->m; ++i)
+            WGS_REQUIRE(majmin[i] <= 3, "site %lld: selector %d outside 0..3", (long long)(i / 2), (int)majmin[i]);
+    wgs_ingest *g = new wgs_ingest();
+    g->depth = d;
+    g->ctx = d->ctx;
+    g->m_rows = d->m;
+    g->tpi = tpi;
+    if (majmin) {
+        auto guard = on_failure([&] { delete g; });
+        HIP_TRY(hipSetDevice(d->ctx->device));
+        if (wgs_malloc(reinterpret_cast<void **>(&g->d_sel), (size_t)(2 * d->m)) != hipSuccess) {
+            wgs_set_error("hipMalloc of %lld bytes for the allele selectors failed", (long long)(2 * d->m));
+            return 1;
+        }
+        auto guard2 = on_failure([&] { (void)hipFree(g->d_sel); });
+        HIP_TRY(hipMemcpy(g->d_sel, majmin, (size_t)(2 * d->m), hipMemcpyHostToDevice));
+        guard2.dismiss();
+        guard.dismiss();
+    }
+    wgs_ingest *made = nullptr;
+    if (int rc = ingest_start(g, r, limit_rows, chunk_bytes, 32ll << 20, 4ll << 20, &made)) return rc;
+    *out = reinterpret_cast<wgs_depth_ingest *>(made);
+    return 0;
+}
+
+void wgs_depth_ingest_destroy(wgs_depth_ingest *g) { wgs_ingest_destroy(reinterpret_cast<wgs_ingest *>(g)); }
+
+int wgs_depth_ingest_next(wgs_depth_ingest *gi, int64_t row0, int64_t *file_rows, int64_t *rows_written)
+{
+    wgs_ingest *g = reinterpret_cast<wgs_ingest *>(gi);
+    WGS_REQUIRE(g && g->depth, "null argument");
+    return wgs_ingest_next(g, row0, nullptr, 0, file_rows, rows_written);
+}
+
+/* stats[0..7]: largest single host buffer held (bytes: the reader's own buffers, the page-locked staging, a flagged line's row) |
+ * device ms (copies + kernels) | lines parsed on the host | text bytes | data lines | chunks | BGZF members inflated on the device |
+ * ms of the tokeniser kernel alone, from HIP events around its launches (0 unless WGSASSIGN_INGEST_TIME_KERNEL=1: the events
+ * cost a synchronisation per chunk). */
+int wgs_depth_ingest_stats(wgs_depth_ingest *gi, double *stats)
+{
+    wgs_ingest *g = reinterpret_cast<wgs_ingest *>(gi);
+    WGS_REQUIRE(g && g->depth && stats, "null argument");
+    size_t peak = std::max(reader_host_peak(g->r), g->host_peak);
+    peak = std::max(peak, g->irows.capacity() * sizeof(int32_t));
+    peak = std::max(peak, std::max(g->flags.capacity(), g->line.capacity()));
+    peak = std::max(peak, std::max(g->dst.capacity(), g->h_begin.capacity()) * sizeof(int32_t));
+    stats[0] = (double)peak;
+    stats[1] = g->device_ms;
+    stats[2] = (double)g->host_lines;
+    stats[3] = (double)g->text_bytes;
+    stats[4] = (double)g->lines;
+    stats[5] = (double)g->chunks;
+    stats[6] = (double)g->blocks_inflated;
+    stats[7] = g->tok_ms;
     return 0;
 }
 

@@ -256,6 +256,7 @@ struct GzSource {
     FILE *fp = nullptr;
     z_stream z;
     bool z_live = false, raw = false, eof = false;
+    bool plain = false;              // not compressed at all (integer tables: wgs_reader_open_table); read() hands the file's bytes on
     std::vector<unsigned char> in;
     // BGZF mode
     bool bgzf = false;
@@ -330,7 +331,7 @@ struct GzSource {
     }
     // After open() at the start of a member: switch to parallel block inflation if the file is BGZF from here on
     // (checked block by block as they are read; a non-BGZF member later is an error, such files do not exist).
-    void try_bgzf(int nthreads)
+    void try_bgzf(int nthreads, size_t cbuf_bytes = 64u << 20)
     {
         if (raw) return;
         const off_t here = ftello(fp);
@@ -341,7 +342,7 @@ struct GzSource {
         if (bgzf_member_size(head, got, &hdr) > 0) {
             bgzf = true;
             threads = nthreads > 0 ? nthreads : 1;
-            cbuf.resize(64u << 20);
+            cbuf.resize(cbuf_bytes);
             clen = cpos = 0;
         }
     }
@@ -530,6 +531,11 @@ struct GzSource {
         }
         if (eof) return 0;
         if (bgzf) return read_bgzf(dst, cap);
+        if (plain) {
+            const size_t got = fread(dst, 1, std::min<size_t>(cap, 1u << 30), fp);
+            if (got == 0) eof = true;
+            return (long)got;
+        }
         z.next_out = reinterpret_cast<unsigned char *>(dst);
         z.avail_out = (unsigned)std::min<size_t>(cap, 1u << 30);
         const unsigned want = z.avail_out;
@@ -601,6 +607,10 @@ struct wgs_reader {
     int threads = 1;
     int64_t lines_read = 0;
     int64_t text_chunks = 0;           // chunks the last text hand-over produced
+    bool table = false;                // an integer table (wgs_reader_open_table): no site-name column, '#' comments, no header to parse
+    int table_cols = 0;                // columns of its first data line
+    int64_t skip_lines = 0;            // header lines skipped when it was opened
+    size_t host_peak = 0;              // largest single host buffer held for it (wgs_depth_ingest_stats)
     struct CompPipe *cpipe = nullptr;  // the compressed hand-over (reader_text.h: CompChunk), when started
     struct TextPipe *pipe = nullptr;   // the text hand-over to the device tokeniser (reader_text.h), when started
 };
@@ -735,6 +745,84 @@ int wgs_reader_open(const char *path, int threads, wgs_reader **out)
     *out = r;
     return 0;
 }
+
+/* An integer table (allele depths, ANGSD counts): plain text, gzip or BGZF, told apart by the file's first bytes.  The first
+ * skip_lines lines are dropped whatever they hold; the first data line behind them -- not blank, not a whole-line '#' comment, as
+ * np.loadtxt sees it -- gives the column count and stays unread. */
+int wgs_reader_open_table(const char *path, int threads, int skip_lines, wgs_reader **out)
+{
+    if (!path || !out || skip_lines < 0) {
+        wgs_set_error("bad argument");
+        return 2;
+    }
+    wgs_reader *r = new wgs_reader();
+    if (!r->src.open(path, nullptr)) {
+        wgs_set_error("cannot open %s", path);
+        delete r;
+        return 2;
+    }
+    r->table = true;
+    r->skip_lines = skip_lines;
+    r->threads = threads > 0 ? threads : 1;
+    unsigned char magic[2] = {0, 0};
+    const size_t got = fread(magic, 1, 2, r->src.fp);
+    fseeko(r->src.fp, 0, SEEK_SET);
+    if (got < 2 || magic[0] != 0x1f || magic[1] != 0x8b) {
+        r->src.plain = true;
+        std::vector<unsigned char>().swap(r->src.in);      // the gzip stream's staging buffer is not needed
+    } else {
+        r->src.try_bgzf(r->threads, 4u << 20);
+    }
+    if (!r->buf.resize(1u << 20)) {
+        wgs_set_error("out of memory");
+        delete r;
+        return 1;
+    }
+    r->fill_cap = 1u << 20;
+    // the header lines are consumed; what follows stays in the buffer (blank and comment lines before the first row too: the
+    // hand-over's line numbering counts them).  Offsets are relative to r->pos: fill() moves the unread text to the front.
+    int64_t skipped = 0;
+    for (size_t at = 0;;) {
+        const char *p = r->buf.data() + r->pos + at, *e = r->buf.data() + r->len;
+        const char *nl = p < e ? (const char *)memchr(p, '\n', (size_t)(e - p)) : nullptr;
+        if (!nl && !r->eof) {
+            if (!fill(r)) {
+                wgs_set_error("read error in %s", path);
+                delete r;
+                return 1;
+            }
+            continue;
+        }
+        if (p >= e) break;                                   // the file ends before a data line
+        const char *le = nl ? nl : e;
+        const size_t next = (size_t)(le - (r->buf.data() + r->pos)) + (nl ? 1 : 0);
+        if (skipped < skip_lines) {
+            ++skipped;
+            r->pos += next;
+            continue;
+        }
+        const char *q = p;
+        while (q < le && is_delim(*q)) ++q;
+        if (q < le && *q != '#') {
+            int cols = 0;
+            while (q < le && *q != '#') {
+                while (q < le && !is_delim(*q) && *q != '#') ++q;
+                ++cols;
+                while (q < le && is_delim(*q)) ++q;
+            }
+            r->table_cols = cols;
+            break;
+        }
+        if (!nl) break;
+        at = next;
+    }
+    r->fill_cap = (size_t)-1;
+    r->host_peak = std::max(r->buf.size(), r->src.bgzf ? r->src.cbuf.size() : r->src.in.size());
+    *out = r;
+    return 0;
+}
+
+int wgs_reader_table_columns(wgs_reader *r) { return r && r->table ? r->table_cols : 0; }
 
 void wgs_reader_close(wgs_reader *r)
 {
@@ -1707,6 +1795,10 @@ int wgs_reader_next(wgs_reader *r, float *rows, int64_t max_rows, int64_t *nrows
         wgs_set_error("bad argument");
         return 2;
     }
+    if (r->table) {
+        wgs_set_error("the reader was opened for an integer table, not a Beagle file");
+        return 2;
+    }
     r->chunk_sites.clear();
     int64_t done = 0;
     const size_t row_floats = (size_t)2 * r->n_inds;
@@ -1784,6 +1876,10 @@ static int skip_impl(wgs_reader *r, int64_t max_rows, int64_t *nrows, bool names
 {
     if (!r || !nrows || max_rows < 0) {
         wgs_set_error("bad argument");
+        return 2;
+    }
+    if (r->table) {
+        wgs_set_error("the reader was opened for an integer table, not a Beagle file");
         return 2;
     }
     if (names) r->chunk_sites.clear();
@@ -1891,11 +1987,13 @@ struct TextPipe {
     TextAllocator alloc;
     size_t chunk_bytes = 0;
     int64_t limit = -1, rows = 0;
+    int64_t file_lines = 0;     // integer tables: lines of the text handed out so far, blank and comment lines included
     bool finished = false, stop = false;
     int rc = 0;
     std::string err;
     int64_t chunks = 0;
     std::vector<char> carry;    // text not handed out yet: [carry_pos, size)
+    size_t host_peak = 0;       // largest buffer allocated (the producer thread writes it; read after reader_text_stop or between chunks)
     size_t carry_pos = 0;
 };
 
@@ -1914,18 +2012,24 @@ bool chunk_reserve(TextPipe *p, TextChunk *c, size_t want)
     if (c->data) p->alloc.release(c->data, p->alloc.user);
     c->data = q;
     c->cap = cap;
+    p->host_peak = std::max(p->host_peak, cap);
     return true;
 }
 
 // The non-blank lines of data[0 .. len) -- every line ends with a newline, or (at the end of the file) with the buffer.
-void list_lines(const char *data, size_t len, int threads, std::vector<uint32_t> &begin, std::vector<uint32_t> &end, std::string &names)
+// table: an integer table -- a line that starts with '#' is no row either (np.loadtxt), no names are kept, and lineno receives
+// each listed line's index among all lines of the text; *all_lines their number.
+void list_lines(const char *data, size_t len, int threads, std::vector<uint32_t> &begin, std::vector<uint32_t> &end, std::string &names,
+                bool table = false, std::vector<uint32_t> *lineno = nullptr, int64_t *all_lines = nullptr)
 {
     begin.clear();
     end.clear();
     names.clear();
+    if (lineno) lineno->clear();
+    if (all_lines) *all_lines = 0;
     if (len == 0) return;
     const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)threads, len >> 20));
-    std::vector<std::vector<uint32_t>> nl(T), lb(T), le(T);
+    std::vector<std::vector<uint32_t>> nl(T), lb(T), le(T), ln(T);
     std::vector<std::string> nm(T);
     run_threads(T, [&](int t) {
         const size_t a = len * (size_t)t / (size_t)T, b = len * (size_t)(t + 1) / (size_t)T;
@@ -1946,26 +2050,36 @@ void list_lines(const char *data, size_t len, int threads, std::vector<uint32_t>
         }
         if (prev < len) nl[T - 1].push_back((uint32_t)len);      // last line without a newline
     }
+    std::vector<uint32_t> line0(T, 0);                           // lines that end before thread t's range
+    for (int t = 1; t < T; ++t) line0[t] = line0[t - 1] + (uint32_t)nl[t - 1].size();
+    if (all_lines) *all_lines = (int64_t)line0[T - 1] + (int64_t)nl[T - 1].size();
     run_threads(T, [&](int t) {
         size_t b = start[t];
+        uint32_t number = line0[t];
         for (uint32_t stop : nl[t]) {
             const char *q = data + b, *e = data + stop;
             while (q < e && is_delim(*q)) ++q;
-            if (q < e) {                                         // blank lines are not rows
+            if (q < e && !(table && *q == '#')) {                // blank lines are not rows
                 lb[t].push_back((uint32_t)b);
                 le[t].push_back(stop);
-                const char *x = q;
-                while (x < e && !is_delim(*x)) ++x;
-                nm[t].append(q, x);
-                nm[t].push_back('\n');
+                if (table) {
+                    ln[t].push_back(number);
+                } else {
+                    const char *x = q;
+                    while (x < e && !is_delim(*x)) ++x;
+                    nm[t].append(q, x);
+                    nm[t].push_back('\n');
+                }
             }
             b = (size_t)stop + 1;
+            ++number;
         }
     });
     for (int t = 0; t < T; ++t) {
         begin.insert(begin.end(), lb[t].begin(), lb[t].end());
         end.insert(end.end(), le[t].begin(), le[t].end());
         names += nm[t];
+        if (lineno) lineno->insert(lineno->end(), ln[t].begin(), ln[t].end());
     }
 }
 
@@ -2041,7 +2155,10 @@ void text_producer(wgs_reader *r)
         c->len = complete;
         memset(c->data + c->len, '\n', TEXT_PAD);
         const double t1 = now_s();
-        list_lines(c->data, c->len, r->threads, c->begin, c->end, c->names);
+        int64_t all_lines = 0;
+        list_lines(c->data, c->len, r->threads, c->begin, c->end, c->names, r->table, r->table ? &c->lineno : nullptr, &all_lines);
+        c->first_line = p->file_lines;
+        p->file_lines += all_lines;
         c->inflate_s = t1 - t0;
         c->scan_s = now_s() - t1;
         bool last_chunk = r->eof && p->carry.empty();
@@ -2051,6 +2168,7 @@ void text_producer(wgs_reader *r)
             if (keep < c->begin.size()) {
                 c->begin.resize(keep);
                 c->end.resize(keep);
+                if (r->table) c->lineno.resize(keep);
                 size_t at = 0;
                 for (size_t i = 0; i < keep; ++i) at = c->names.find('\n', at) + 1;
                 c->names.resize(at);
@@ -2082,7 +2200,7 @@ int reader_text_start(wgs_reader *r, size_t chunk_bytes, int nbuf, TextAllocator
     }
     TextPipe *p = new TextPipe();
     p->alloc = a;
-    p->chunk_bytes = std::min<size_t>(std::max<size_t>(chunk_bytes, 1u << 20), (size_t)2 << 30);
+    p->chunk_bytes = std::min<size_t>(std::max<size_t>(chunk_bytes, r->table ? 16u << 10 : 1u << 20), (size_t)2 << 30);
     p->limit = limit_rows;
     // what the line-oriented calls left in the reader's buffer comes first
     p->carry.assign(r->buf.data() + r->pos, r->buf.data() + r->len);
@@ -2141,6 +2259,7 @@ void reader_text_stop(wgs_reader *r)
     if (p->th.joinable()) p->th.join();
     r->lines_read += p->rows;
     r->text_chunks = p->chunks;
+    r->host_peak = std::max(r->host_peak, p->host_peak);
     for (TextChunk *c : p->all) {
         if (c->data) p->alloc.release(c->data, p->alloc.user);
         delete c;
@@ -2294,7 +2413,7 @@ int reader_comp_start(wgs_reader *r, size_t comp_bytes, size_t text_cap, int nbu
     }
     CompPipe *p = new CompPipe();
     p->alloc = a;
-    p->text_cap = std::max<size_t>(text_cap, 1u << 20);
+    p->text_cap = std::max<size_t>(text_cap, r->table ? 65536u : 1u << 20);   // (a BGZF member holds up to 64 KiB of text)
     p->max_members = max_members;
     comp_bytes = std::max<size_t>(comp_bytes, 1u << 20);
     p->pre_pos = r->pos;
@@ -2305,6 +2424,7 @@ int reader_comp_start(wgs_reader *r, size_t comp_bytes, size_t text_cap, int nbu
         CompChunk *c = new CompChunk();
         c->comp = (unsigned char *)a.alloc(comp_bytes, a.user);
         c->cap = comp_bytes;
+        r->host_peak = std::max(r->host_peak, comp_bytes);
         p->all.push_back(c);
         if (!c->comp) {
             for (CompChunk *x : p->all) {
@@ -2406,6 +2526,61 @@ int reader_text_n_inds(const wgs_reader *r) { return r->n_inds; }
 int reader_text_gl_cols(const wgs_reader *r) { return r->gl_cols; }
 int64_t reader_text_lines_read(const wgs_reader *r) { return r->lines_read; }
 
+bool reader_is_table(const wgs_reader *r) { return r && r->table; }
+int reader_table_cols(const wgs_reader *r) { return r->table_cols; }
+int64_t reader_table_skip_lines(const wgs_reader *r) { return r->skip_lines; }
+size_t reader_host_peak(const wgs_reader *r)
+{
+    size_t peak = std::max(r->host_peak, std::max(r->buf.size(), std::max(r->src.cbuf.size(), r->src.in.size())));
+    if (r->pipe) peak = std::max(peak, r->pipe->host_peak);
+    return peak;
+}
+
+int reader_table_parse_line(const char *b, const char *e, int need, int32_t *out, int *bad_col)
+{
+    const char *hash = (const char *)memchr(b, '#', (size_t)(e - b));
+    if (hash) e = hash;
+    const char *p = b;
+    for (int col = 0; col < need; ++col) {
+        while (p < e && is_delim(*p)) ++p;
+        if (p >= e) return 1;
+        const char *q = p;
+        bool neg = false;
+        if (*q == '+' || *q == '-') neg = *q++ == '-';
+        int64_t v = 0;
+        int digits = 0;
+        for (; q < e && *q >= '0' && *q <= '9'; ++q, ++digits)
+            if (v < ((int64_t)1 << 40)) v = v * 10 + (*q - '0');
+        if (neg) v = -v;
+        if (digits == 0 || (q < e && !is_delim(*q))) {
+            // np.loadtxt still reads an integer column "via a float" (deprecated since NumPy 1.23): a plain decimal or exponent
+            // form, truncated towards zero.  Nothing with letters other than the exponent's (inf, nan, hex).
+            const char *te = p;
+            bool plain = true;
+            while (te < e && !is_delim(*te)) {
+                const char c = *te++;
+                if (!((c >= '0' && c <= '9') || c == '.' || c == 'e' || c == 'E' || c == '+' || c == '-')) plain = false;
+            }
+            const std::string tok(p, te);
+            char *stop = nullptr;
+            const double f = plain ? strtod(tok.c_str(), &stop) : 0.0;
+            if (!plain || stop != tok.c_str() + tok.size() || !(f > -2147483649.0 && f < 2147483648.0)) {
+                if (bad_col) *bad_col = col + 1;
+                return 3;
+            }
+            v = (int64_t)f;
+            q = te;
+        }
+        if (v > INT32_MAX || v < INT32_MIN) {
+            if (bad_col) *bad_col = col + 1;
+            return 3;
+        }
+        out[col] = (int32_t)v;
+        p = q;
+    }
+    return 0;
+}
+
 extern "C" {
 
 /* Test hook (needs no GPU): the rows of wgs_reader_next, but through the text hand-over -- the producer thread, the
@@ -2451,6 +2626,54 @@ int wgs_debug_reader_text_rows(wgs_reader *r, int64_t chunk_bytes, int64_t limit
     reader_text_stop(r);
     *nrows = done;
     return rc;
+}
+
+/* Test hook (needs no GPU): an integer table through the text hand-over, every listed line parsed by reader_table_parse_line:
+ * rows[max_rows][need], linenos[max_rows] = each row's 1-based line number in the file.  rc 2 with the message the device ingest
+ * gives when a line has too few columns or a token np.loadtxt refuses. */
+int wgs_debug_reader_table_rows(wgs_reader *r, int64_t chunk_bytes, int32_t need, int32_t *rows, int64_t max_rows, int64_t *nrows, int64_t *linenos)
+{
+    if (!r || !r->table || !rows || !nrows || need < 1) {
+        wgs_set_error("bad argument");
+        return 2;
+    }
+    TextAllocator a;
+    a.alloc = [](size_t n, void *) { return malloc(n); };
+    a.release = [](void *p, void *) { free(p); };
+    if (int rc = reader_text_start(r, (size_t)chunk_bytes, 2, a, -1)) return rc;
+    int64_t done = 0;
+    int rc = 0;
+    for (;;) {
+        TextChunk *c = nullptr;
+        if ((rc = reader_text_next(r, &c, nullptr)) != 0 || !c) break;
+        for (size_t i = 0; i < c->begin.size() && !rc; ++i) {
+            const long long line = (long long)(r->skip_lines + c->first_line + c->lineno[i] + 1);
+            int bad_col = 0;
+            if (done >= max_rows) {
+                rc = 2;
+                wgs_set_error("more rows than the caller has room for");
+                break;
+            }
+            const int k = reader_table_parse_line(c->data + c->begin[i], c->data + c->end[i], need, rows + (size_t)done * need, &bad_col);
+            if (k == 1) rc = 2, wgs_set_error("line %lld has fewer than %d columns", line, need);
+            else if (k) rc = 2, wgs_set_error("line %lld, column %d: not an integer np.loadtxt reads as int32", line, bad_col);
+            else {
+                if (linenos) linenos[done] = line;
+                ++done;
+            }
+        }
+        reader_text_release(r, c);
+        if (rc) break;
+    }
+    reader_text_stop(r);
+    *nrows = done;
+    return rc;
+}
+
+int wgs_debug_table_parse_line(const char *line, int64_t len, int32_t need, int32_t *out)
+{
+    int bad_col = 0;
+    return reader_table_parse_line(line, line + len, need, out, &bad_col);
 }
 
 /* Debug / tests: the COMPRESSED hand-over (reader_text.h: CompChunk -- what the device-resident ingest consumes) driven on the

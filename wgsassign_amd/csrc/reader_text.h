@@ -27,6 +27,8 @@ struct TextChunk {
     std::vector<uint32_t> begin, end;   // per non-blank line: [begin, end) without the newline
     std::string names;                  // '\n'-terminated first tokens of those lines (site names)
     int64_t first_row = 0;              // data rows handed out before this chunk (since reader_text_start)
+    std::vector<uint32_t> lineno;       // integer tables only: per listed line, its index among ALL lines of this chunk
+    int64_t first_line = 0;             // ... and the lines of the text handed out before this chunk
     double inflate_s = 0.0, scan_s = 0.0;
 };
 
@@ -67,3 +69,15 @@ int reader_text_parse_line(const wgs_reader *r, const char *b, const char *e, fl
 int reader_text_n_inds(const wgs_reader *r);
 int reader_text_gl_cols(const wgs_reader *r);
 int64_t reader_text_lines_read(const wgs_reader *r);
+
+// ---- integer tables (wgs_reader_open_table): allele depths, ANGSD counts
+bool reader_is_table(const wgs_reader *r);
+int reader_table_cols(const wgs_reader *r);
+int64_t reader_table_skip_lines(const wgs_reader *r);
+// largest single host buffer held for the reader so far: its own buffers and what the hand-overs allocated
+size_t reader_host_peak(const wgs_reader *r);
+// One line by np.loadtxt's rules for an integer dtype: '#' starts a comment, tokens are [+-]digits that fit int32 (or, as NumPy
+// still allows with a deprecation warning, a decimal / exponent form, truncated).  The first
+// `need` values go to out.  0 = ok, 1 = fewer than `need` columns, 3 = a token that is not such an integer (*bad_col = its
+// 1-based column).
+int reader_table_parse_line(const char *b, const char *e, int need, int32_t *out, int *bad_col);

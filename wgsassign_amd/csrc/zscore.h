@@ -20,7 +20,9 @@ struct ZCompactJob {
 };
 
 struct wgs_depth {
-    wgs_beagle *b = nullptr;
+    wgs_beagle *b = nullptr;   // nullptr: a table of its own shape (wgs_depth_create_shape), for nothing but filling and reading back
+    wgs_ctx *ctx = nullptr;
+    int64_t m = 0, n = 0;
     int64_t mpad = 0;
     uchar2 *table = nullptr;   // [individual][mpad]
     int32_t *d_bad = nullptr;
@@ -46,4 +48,5 @@ int launch_zstat(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *dept
                  float *wl, float *var);
 int launch_zcompact(wgs_ctx *ctx, const ZCompactJob *d_jobs, int n_jobs, int64_t m, const unsigned long long *mask, const uint32_t *off);
 int launch_zdepth_scatter(wgs_ctx *ctx, const int32_t *d_rows, int64_t nrows, int64_t n, int64_t row0, int64_t mpad, uchar2 *depth, int32_t *bad);
+int launch_zdepth_gather(wgs_ctx *ctx, const uchar2 *depth, int64_t nrows, int64_t n, int64_t row0, int64_t mpad, int32_t *d_rows);
 int launch_zsites(wgs_ctx *ctx, int64_t m, const unsigned long long *mask, const uint32_t *off, int32_t *out);

@@ -33,35 +33,50 @@ int zs_fill_inds(wgs_beagle *b, int32_t i0, int32_t count, std::vector<ZInd> &ou
 
 extern "C" {
 
-int wgs_depth_create(wgs_beagle *b, wgs_depth **out)
+static int depth_create(wgs_ctx *ctx, wgs_beagle *b, int64_t m, int64_t n, wgs_depth **out)
 {
-    WGS_REQUIRE(b && out, "null argument");
-    WGS_REQUIRE(b->m > 0 && b->m < (int64_t)1 << 31, "the depth table needs between 1 and 2^31 - 1 sites");
-    HIP_TRY(hipSetDevice(b->ctx->device));
+    WGS_REQUIRE(m > 0 && m < (int64_t)1 << 31, "the depth table needs between 1 and 2^31 - 1 sites");
+    WGS_REQUIRE(n > 0 && n < (int64_t)1 << 24, "the depth table needs between 1 and 2^24 - 1 individuals");
+    HIP_TRY(hipSetDevice(ctx->device));
     wgs_depth *d = new wgs_depth();
-    wgs_live_add(d, WGS_LIVE_DEPTH, b);
+    wgs_live_add(d, WGS_LIVE_DEPTH, b ? (void *)b : (void *)ctx);
     auto guard = on_failure([&] { wgs_depth_destroy(d); });
     d->b = b;
-    d->mpad = wgs_ntiles(b->m) * 64;
-    const size_t bytes = (size_t)b->n * d->mpad * sizeof(uchar2);
+    d->ctx = ctx;
+    d->m = m;
+    d->n = n;
+    d->mpad = wgs_ntiles(m) * 64;
+    const size_t bytes = (size_t)n * d->mpad * sizeof(uchar2);
     if (wgs_malloc(&d->table, bytes) != hipSuccess) {
         wgs_set_error("hipMalloc of %zu bytes for the allele-depth table failed", bytes);
         return 1;
     }
     HIP_TRY(wgs_malloc(&d->d_bad, sizeof(int32_t)));
-    HIP_TRY(hipMemsetAsync(d->table, 0, bytes, b->ctx->stream));
-    HIP_TRY(hipMemsetAsync(d->d_bad, 0, sizeof(int32_t), b->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    HIP_TRY(hipMemsetAsync(d->table, 0, bytes, ctx->stream));
+    HIP_TRY(hipMemsetAsync(d->d_bad, 0, sizeof(int32_t), ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     guard.dismiss();
     *out = d;
     return 0;
+}
+
+int wgs_depth_create(wgs_beagle *b, wgs_depth **out)
+{
+    WGS_REQUIRE(b && out, "null argument");
+    return depth_create(b->ctx, b, b->m, b->n, out);
+}
+
+int wgs_depth_create_shape(wgs_ctx *ctx, int64_t m, int64_t n, wgs_depth **out)
+{
+    WGS_REQUIRE(ctx && out, "null argument");
+    return depth_create(ctx, nullptr, m, n, out);
 }
 
 void wgs_depth_destroy(wgs_depth *d)
 {
     if (!d || !wgs_live_remove(d)) return;
     wgs_live_destroy_children(d);             // kept-site sets made from this table go first
-    (void)hipSetDevice(d->b->ctx->device);
+    (void)hipSetDevice(d->ctx->device);
     if (d->table) (void)hipFree(d->table);
     if (d->d_bad) (void)hipFree(d->d_bad);
     delete d;
@@ -70,12 +85,12 @@ void wgs_depth_destroy(wgs_depth *d)
 int wgs_depth_upload_rows(wgs_depth *d, const int32_t *AD_rows, int64_t row0, int64_t nrows)
 {
     WGS_REQUIRE(d && AD_rows, "null argument");
-    wgs_beagle *b = d->b;
+    const wgs_depth *b = d;                                  // (the table's own shape: it may have no matrix)
     WGS_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= b->m, "row range [%lld, %lld) outside 0..%lld", (long long)row0,
                 (long long)(row0 + nrows), (long long)b->m);
     WGS_REQUIRE(nrows * b->n < (int64_t)1 << 38, "too many rows in one upload");
     if (nrows == 0) return 0;
-    wgs_ctx *ctx = b->ctx;
+    wgs_ctx *ctx = d->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     ZBufs bufs;
     int32_t *d_rows = nullptr;
@@ -94,9 +109,29 @@ int wgs_depth_upload_rows(wgs_depth *d, const int32_t *AD_rows, int64_t row0, in
     return 0;
 }
 
+int wgs_depth_download_rows(wgs_depth *d, int32_t *AD_rows, int64_t row0, int64_t nrows)
+{
+    WGS_REQUIRE(d && AD_rows, "null argument");
+    WGS_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= d->m, "row range [%lld, %lld) outside 0..%lld", (long long)row0,
+                (long long)(row0 + nrows), (long long)d->m);
+    WGS_REQUIRE(nrows * d->n < (int64_t)1 << 38, "too many rows in one download");
+    if (nrows == 0) return 0;
+    wgs_ctx *ctx = d->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ZBufs bufs;
+    int32_t *d_rows = nullptr;
+    const size_t bytes = (size_t)nrows * 2 * d->n * sizeof(int32_t);
+    HIP_TRY(bufs.get(&d_rows, bytes));
+    if (launch_zdepth_gather(ctx, d->table, nrows, d->n, row0, d->mpad, d_rows)) return 1;
+    HIP_TRY(hipMemcpyAsync(AD_rows, d_rows, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_out, float *sums_out, int32_t *first_out, int32_t *over_out)
 {
     WGS_REQUIRE(d && counts_out && sums_out && first_out && over_out, "null argument");
+    WGS_REQUIRE(d->b, "the depth table was created without a matrix (wgs_depth_create_shape)");
     wgs_beagle *b = d->b;
     wgs_ctx *ctx = b->ctx;
     std::vector<ZInd> inds;
@@ -144,6 +179,7 @@ int wgs_zkeep_create(wgs_depth *d, int32_t i0, int32_t count, const float *key_m
                      wgs_zkeep **out)
 {
     WGS_REQUIRE(d && key_mean && key_comp && kept_out && out, "null argument");
+    WGS_REQUIRE(d->b, "the depth table was created without a matrix (wgs_depth_create_shape)");
     wgs_beagle *b = d->b;
     wgs_ctx *ctx = b->ctx;
     std::vector<ZInd> inds;

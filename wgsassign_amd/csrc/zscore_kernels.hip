@@ -269,6 +269,19 @@ __global__ void zdepth_scatter_kernel(const int32_t *__restrict__ rows, int64_t 
     depth[(size_t)i * mpad + row0 + r] = make_uchar2((unsigned char)ar, (unsigned char)aa);
 }
 
+// ... and back: rows [row0, row0 + nrows) of the table as (nrows, 2n) int32 (a thread per pair; consecutive threads read consecutive
+// sites of one individual)
+__global__ void zdepth_gather_kernel(const uchar2 *__restrict__ depth, int64_t nrows, int64_t n, int64_t row0, int64_t mpad,
+                                     int32_t *__restrict__ rows)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nrows * n) return;
+    const int64_t i = e / nrows, r = e % nrows;
+    const uchar2 v = depth[(size_t)i * mpad + row0 + r];
+    rows[r * 2 * n + 2 * i] = v.x;
+    rows[r * 2 * n + 2 * i + 1] = v.y;
+}
+
 // The selected sites' indices in ascending order (L_keep itself, for callers that want it).
 __global__ __launch_bounds__(256) void zsites_kernel(int64_t m, const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ off,
                                                      int32_t *__restrict__ out)
@@ -334,6 +347,14 @@ int launch_zdepth_scatter(wgs_ctx *ctx, const int32_t *d_rows, int64_t nrows, in
     const int64_t total = nrows * n;
     hipLaunchKernelGGL(zdepth_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_rows, nrows, n, row0, mpad,
                        depth, bad);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_zdepth_gather(wgs_ctx *ctx, const uchar2 *depth, int64_t nrows, int64_t n, int64_t row0, int64_t mpad, int32_t *d_rows)
+{
+    const int64_t total = nrows * n;
+    hipLaunchKernelGGL(zdepth_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, depth, nrows, n, row0, mpad, d_rows);
     HIP_TRY(hipGetLastError());
     return 0;
 }

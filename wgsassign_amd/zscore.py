@@ -9,6 +9,7 @@ order from the compacted per-site arrays.  There is no CPU fallback.
 """
 import ctypes
 import math
+import os
 import weakref
 
 import numpy as np
@@ -33,6 +34,57 @@ def check_depths(AD, m, n):
         raise ValueError("allele depths have shape %s, the Beagle file has %d sites and %d individuals" % (AD.shape, m, n))
     if AD.size and (AD.min() < 0 or AD.max() > 255):
         raise ValueError("allele depths outside 0..255 do not fit the device table")
+
+
+def read_majmin(path):
+    """--ind_majmin_file: the second argument of the reference's allele_counts_beagle.py (:14) -- one header line, the selectors of
+    the major and the minor allele (0..3 = A, C, G, T) in the columns at positions 1 and 2.  uint8 (m, 2)."""
+    sel = np.atleast_2d(np.loadtxt(path, dtype="int", skiprows=1, usecols=(1, 2)))
+    if sel.size and (sel.min() < 0 or sel.max() > 3):
+        row = int(np.argwhere((sel < 0) | (sel > 3))[0][0])
+        raise ValueError("%s, line %d: allele selector outside 0..3" % (path, row + 2))
+    return np.ascontiguousarray(sel, dtype=np.uint8)
+
+
+def stream_table(handle, m, path, counts=False, majmin=None, chunk_bytes=None, threads=None, row0=0, limit_rows=-1):
+    """The file `path` into the rows row0 .. of the wgs_depth `handle` on the device (wgs_depth_ingest_*).  Returns the stats of
+    the ingest.  ValueError names the file's line for anything np.loadtxt would refuse or the table cannot hold, and both numbers
+    when the file does not have exactly m - row0 (or limit_rows) data lines."""
+    from .reader_cy import host_threads
+    lib = _lib.load()
+    r, g = ctypes.c_void_p(), ctypes.c_void_p()
+    check(lib.wgs_reader_open_table(os.fsencode(path), int(threads or host_threads()), 1 if counts else 0, ctypes.byref(r)))
+    try:
+        sel = None
+        if counts:
+            sel = np.ascontiguousarray(majmin, dtype=np.uint8)
+            if sel.shape != (m, 2):
+                raise ValueError("the allele selectors have shape %s, the table %d sites" % (sel.shape, m))
+        check(lib.wgs_depth_ingest_create(handle, r, 1 if counts else 0, sel.ctypes.data if counts else None, int(limit_rows),
+                                          int(chunk_bytes or 0), ctypes.byref(g)))
+        lines, row = 0, int(row0)
+        got, wrote = ctypes.c_int64(), ctypes.c_int64()
+        while True:
+            check(lib.wgs_depth_ingest_next(g, row, ctypes.byref(got), ctypes.byref(wrote)))
+            if got.value == 0:
+                break
+            lines += got.value
+            row += wrote.value
+        want = (m - int(row0)) if limit_rows < 0 else int(limit_rows)
+        if lines != want:
+            raise ValueError("%s has %d data lines, %d sites were expected" % (path, lines, want))
+        stats = np.zeros(8, dtype=np.float64)
+        check(lib.wgs_depth_ingest_stats(g, stats.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return dict(zip(("host_peak_bytes", "device_ms", "host_lines", "text_bytes", "lines", "chunks", "members_on_device",
+                         "tokenise_ms"), stats.tolist()))
+    except ValueError as e:
+        if str(path) not in str(e):
+            raise ValueError("%s: %s" % (path, e)) from None
+        raise
+    finally:
+        if g:
+            lib.wgs_depth_ingest_destroy(g)
+        lib.wgs_reader_close(r)
 
 
 def key_filter(keys, counts, n_threshold, single_read_threshold):
@@ -94,6 +146,22 @@ class DepthTable:
             for r in range(0, beagle.m, step):
                 self.upload_rows(AD[r:r + step], r)
 
+    @classmethod
+    def from_file(cls, beagle, path, counts=False, majmin=None, chunk_bytes=None):
+        """A fresh table streamed from `path` on the device: allele depths as --ind_ad_file holds them (text, gzip or BGZF), or with
+        counts=True ANGSD's counts with the (m, 2) selectors `majmin` (read_majmin).  Nothing of size m x 2n exists on the host;
+        .ingest_stats tells what did.  .npy goes through the upload path.  ValueError (and no table) unless the file has exactly
+        beagle.m data lines of at least 2n (4n) integers in 0..255."""
+        if str(path).endswith(".npy") and not counts:
+            return cls(beagle, read_depths(path))
+        t = cls(beagle)
+        try:
+            t.ingest_stats = stream_table(t._h, beagle.m, path, counts, majmin, chunk_bytes)
+        except Exception:
+            t.close()
+            raise
+        return t
+
     @property
     def handle(self):
         return self._h
@@ -101,6 +169,12 @@ class DepthTable:
     def upload_rows(self, rows, row0=0):
         rows = np.ascontiguousarray(rows[:, :2 * self.b.n], dtype=np.int32)
         check(_lib.load().wgs_depth_upload_rows(self._h, i32p(rows), int(row0), rows.shape[0]))
+
+    def download_rows(self, row0=0, nrows=None):
+        nrows = self.b.m - row0 if nrows is None else nrows
+        out = np.empty((nrows, 2 * self.b.n), dtype=np.int32)
+        check(_lib.load().wgs_depth_download_rows(self._h, i32p(out), int(row0), int(nrows)))
+        return out
 
     def close(self):
         if self._h:
