@@ -99,8 +99,10 @@ def test_equals_loadtxt_over_shapes_formats_and_chunks(tmp_path, m, n):
 
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_more_individuals_than_a_strip_and_extra_columns(tmp_path, fmt):
-    """300 and 700 individuals: the strips of 256 follow one another inside a workgroup; columns behind 2n are ignored."""
-    for m, n, extra in ((130, 300, 0), (77, 700, 0), (200, 257, 3)):
+    """300 and 700 individuals: the strips of 256 follow one another inside a workgroup; columns behind 2n are ignored.
+    20000 individuals: a line of 80 KB and more is longer than a small device chunk (64 KiB), so every chunk is carried whole
+    into the next and the text buffer grows while it holds the carry."""
+    for m, n, extra in ((130, 300, 0), (77, 700, 0), (200, 257, 3), (40, 20000, 0)):
         AD = edge_table(m, n, seed=n)
         full = np.hstack([AD, np.full((m, extra), 7, dtype=np.int32)]) if extra else AD
         path = write_as(tmp_path / ("w%d.%s" % (n, fmt)), table_text(full), fmt)

@@ -581,6 +581,46 @@ void pinned_release(void *p, void *)
     std::thread([blk] { munmap(blk.raw, blk.raw_bytes); }).detach();
 }
 
+
+// A device array that only grows, owned by the object it is a member of.  reserve() is the one way to more room: it waits for the
+// stream (kernels in flight may still read the old array), frees, allocates (wgs_malloc: common.h on what that can cost) and
+// leaves the capacity at 0 when that fails, so that no later call trusts an array that is gone.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;                 // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    // Room for `count` elements; where that takes a new array it has `new_cap` of them, and the first keep_bytes of the old one.
+    int reserve(hipStream_t st, size_t count, size_t new_cap, size_t keep_bytes = 0)
+    {
+        if (count <= cap) return 0;
+        cap = 0;
+        HIP_TRY(hipStreamSynchronize(st));
+        T *old = p;
+        p = nullptr;
+        if (old && !keep_bytes) HIP_TRY(hipFree(old));           // first: the old and the new array need not fit side by side
+        const hipError_t made = wgs_malloc(&p, new_cap * sizeof(T));
+        const hipError_t kept = made == hipSuccess && keep_bytes ? hipMemcpy(p, old, keep_bytes, hipMemcpyDeviceToDevice) : hipSuccess;
+        if (keep_bytes) (void)hipFree(old);
+        HIP_TRY(made);
+        HIP_TRY(kept);
+        cap = new_cap;
+        return 0;
+    }
+};
+
+// Arrays that grow together, to one capacity.
+template <class... B>
+int reserve_all(hipStream_t st, size_t count, size_t new_cap, B &...bufs)
+{
+    int rc = 0;
+    ((rc = rc ? rc : bufs.reserve(st, count, new_cap)), ...);
+    return rc;
+}
+
 }  // namespace
 
 struct wgs_ingest {
@@ -588,21 +628,21 @@ struct wgs_ingest {
     wgs_depth *depth = nullptr;     // ... the depth table (wgs_depth_ingest_*: an integer table through the same hand-overs)
     wgs_ctx *ctx = nullptr;
     int64_t m_rows = 0;             // rows of the target
-    int32_t tpi = 2;                // depth: tokens per individual (2: pairs, 4: ANGSD counts)
-    uint8_t *d_sel = nullptr;       // counts: the sites' (major, minor) selectors
-    std::vector<int32_t> irows;     // depth: host-parsed rows of flagged lines
-    int64_t lines_before = 0;       // depth, device-resident: lines of the text in the chunks before this one
-    size_t host_peak = 0;           // depth: largest host buffer this object allocated itself
-    bool overflow = false;          // depth: the file has more data lines than the table rows
-    double tok_ms = 0.0;            // depth: the tokeniser kernel alone (WGSASSIGN_INGEST_TIME_KERNEL=1)
-    hipEvent_t kev0 = nullptr, kev1 = nullptr;
+    struct {                        // what only the depth table's ingest uses
+        int32_t tpi = 2;                // tokens per individual (2: pairs, 4: ANGSD counts)
+        DevBuf<uint8_t> sel;            // counts: the sites' (major, minor) selectors
+        std::vector<int32_t> irows;     // host-parsed row of a flagged line
+        int64_t lines_before = 0;       // device-resident: lines of the text in the chunks before this one
+        size_t host_peak = 0;           // largest host buffer this object allocated itself
+        bool overflow = false;          // the file has more data lines than the table rows
+        double tok_ms = 0.0;            // the tokeniser kernel alone (WGSASSIGN_INGEST_TIME_KERNEL=1)
+        hipEvent_t kev0 = nullptr, kev1 = nullptr;
+    } dp;
     wgs_reader *r = nullptr;
-    void *d_text = nullptr;
-    size_t text_cap = 0;
-    uint32_t *d_begin = nullptr, *d_end = nullptr;
-    int32_t *d_dst = nullptr;
-    uint8_t *d_flags = nullptr;
-    size_t lines_cap = 0;
+    DevBuf<uint8_t> d_text;
+    DevBuf<uint32_t> d_begin, d_end;                         // per line (ensure_line_arrays)
+    DevBuf<int32_t> d_dst;
+    DevBuf<uint8_t> d_flags;
     std::vector<int32_t> dst;
     std::vector<uint8_t> flags;
     std::vector<float> rows;        // host-parsed rows of flagged lines
@@ -614,24 +654,17 @@ struct wgs_ingest {
     // ---- BGZF: the device-resident pipeline (compressed members in, slab rows out; see wgs_ingest_next) ----
     bool resident = false, done = false;
     int64_t limit = -1, rows_done = 0;
-    size_t chunk_text = 0;          // text per chunk the producer aims at
     size_t carry = 0;               // d_text[0 .. carry) = the partial last line of the previous chunk
-    uint8_t *d_carry = nullptr;
-    size_t carry_cap = 0;
-    uint8_t *d_comp = nullptr;
-    size_t comp_cap = 0;
-    uint64_t *d_in_off = nullptr, *d_out_off = nullptr;
-    uint32_t *d_in_len = nullptr, *d_isize = nullptr;
-    uint8_t *d_status = nullptr;
-    void *d_tables = nullptr;
-    size_t blocks_cap = 0;
-    uint32_t *d_counts = nullptr, *d_offsets = nullptr;     // newlines per 4 KiB of text, and their exclusive scan
-    size_t counts_cap = 0;
-    uint32_t *d_nl_pos = nullptr, *d_nonblank = nullptr, *d_rank = nullptr, *d_name_start = nullptr, *d_name_len1 = nullptr, *d_name_off = nullptr;
-    int32_t *d_dstmap = nullptr;
-    uint8_t *d_names = nullptr;
-    size_t names_cap = 0;
-    uint32_t *d_totals = nullptr, *h_totals = nullptr;
+    DevBuf<uint8_t> d_carry, d_comp;
+    DevBuf<uint64_t> d_in_off, d_out_off;                    // per member, as are the next three
+    DevBuf<uint32_t> d_in_len, d_isize;
+    DevBuf<uint8_t> d_status, d_tables;
+    DevBuf<uint32_t> d_counts, d_offsets;                    // newlines per 4 KiB of text, and their exclusive scan
+    DevBuf<uint32_t> d_nl_pos, d_nonblank, d_rank, d_name_start, d_name_len1, d_name_off;    // per line, as is the next
+    DevBuf<int32_t> d_dstmap;
+    DevBuf<uint8_t> d_names;
+    DevBuf<uint32_t> d_totals;
+    uint32_t *h_totals = nullptr;
     std::vector<uint64_t> out_off;
     std::vector<uint8_t> status;
     std::vector<int32_t> dstmap;
@@ -644,90 +677,160 @@ struct wgs_ingest {
 
 namespace {
 
-template <class T>
-int regrow(hipStream_t st, T *&p, size_t count)
+int ensure_line_arrays(wgs_ingest *g, size_t nl)
 {
-    HIP_TRY(hipStreamSynchronize(st));
-    if (p) HIP_TRY(hipFree(p));
-    p = nullptr;
-    HIP_TRY(wgs_malloc(reinterpret_cast<void **>(&p), count * sizeof(T)));
-    return 0;
-}
-
-int ensure_line_arrays(wgs_ingest *g, hipStream_t st, size_t nl, bool resident)
-{
-    if (nl <= g->lines_cap) return 0;
+    hipStream_t st = g->ctx->stream;
     const size_t cap = nl + nl / 2 + 1024;
-    g->lines_cap = 0;
-    if (int rc = regrow(st, g->d_begin, cap)) return rc;
-    if (int rc = regrow(st, g->d_end, cap)) return rc;
-    if (int rc = regrow(st, g->d_dst, cap)) return rc;
-    if (int rc = regrow(st, g->d_flags, cap)) return rc;
-    if (resident) {
-        if (int rc = regrow(st, g->d_nl_pos, cap)) return rc;
-        if (int rc = regrow(st, g->d_nonblank, cap)) return rc;
-        if (int rc = regrow(st, g->d_rank, cap)) return rc;
-        if (int rc = regrow(st, g->d_name_start, cap)) return rc;
-        if (int rc = regrow(st, g->d_name_len1, cap)) return rc;
-        if (int rc = regrow(st, g->d_name_off, cap)) return rc;
-        if (int rc = regrow(st, g->d_dstmap, cap)) return rc;
-    }
-    g->lines_cap = cap;
+    if (int rc = reserve_all(st, nl, cap, g->d_begin, g->d_end, g->d_dst, g->d_flags)) return rc;
+    if (!g->resident) return 0;
+    return reserve_all(st, nl, cap, g->d_nl_pos, g->d_nonblank, g->d_rank, g->d_name_start, g->d_name_len1, g->d_name_off, g->d_dstmap);
+}
+
+// device_ms: from clock_start to the end of what the chunk has put on the stream by clock_stop, which waits for it.
+int clock_start(wgs_ingest *g)
+{
+    HIP_TRY(hipEventRecord(g->ev0, g->ctx->stream));
+    return 0;
+}
+int clock_stop(wgs_ingest *g)
+{
+    HIP_TRY(hipEventRecord(g->ev1, g->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(g->ctx->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, g->ev0, g->ev1));
+    g->device_ms += ms;
     return 0;
 }
 
-void launch_tokenise(wgs_ingest *g, hipStream_t st, const void *text, int64_t row0, size_t nl, uint32_t *nflagged)
+// Rows for the n data lines of a chunk: line i goes to row0 + its number among the lines `keep` keeps (keep == NULL: all), which
+// is what *map receives where one is asked for (-1: no row); *written = the rows taken.
+int place_rows(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t keep_len, size_t n, std::vector<int32_t> *map, int64_t *written)
 {
+    if (keep) WGS_REQUIRE((int64_t)n <= keep_len, "site mask shorter than the file (%lld lines left in it, %lld in the chunk)", (long long)keep_len, (long long)n);
+    *written = (int64_t)n;
+    if (map) {
+        map->resize(n);
+        *written = 0;
+        for (size_t i = 0; i < n; ++i) (*map)[i] = (!keep || keep[i]) ? (int32_t)(*written)++ : -1;
+    }
+    // a table with more data lines than the target has rows: nothing more is stored, the lines are still counted (the caller
+    // reports both numbers)
+    if (g->depth && row0 + *written > g->m_rows) g->dp.overflow = true;
+    if (g->dp.overflow) {
+        if (map) std::fill(map->begin(), map->end(), -1);
+        *written = 0;
+    }
+    WGS_REQUIRE(row0 >= 0 && row0 + *written <= g->m_rows, "rows [%lld, %lld) outside the device matrix (%lld rows)", (long long)row0,
+                (long long)(row0 + *written), (long long)g->m_rows);
+    return 0;
+}
+
+// The tokeniser of the target over the nl lines listed in d_begin / d_end / d_dst; flags what it leaves to the host's parser.
+int launch_tokenise(wgs_ingest *g, const void *text, int64_t row0, size_t nl, uint32_t *nflagged)
+{
+    hipStream_t st = g->ctx->stream;
+    HIP_TRY(hipMemsetAsync(g->d_flags.p, 0, nl, st));
+    auto lines = [&](auto &a, int64_t n_inds) {               // what the two kernels' arguments have in common
+        a.text = reinterpret_cast<const uint4 *>(text);
+        a.begin = g->d_begin.p;
+        a.end = g->d_end.p;
+        a.dst = g->d_dst.p;
+        a.flags = g->d_flags.p;
+        a.nflagged = nflagged;
+        a.row0 = row0;
+        a.nlines = (int32_t)nl;
+        a.n_inds = (int32_t)n_inds;
+    };
     if (g->depth) {
         DepthTokArgs d;
-        d.text = reinterpret_cast<const uint4 *>(text);
-        d.begin = g->d_begin;
-        d.end = g->d_end;
-        d.dst = g->d_dst;
-        d.flags = g->d_flags;
-        d.nflagged = nflagged;
-        d.row0 = row0;
-        d.nlines = (int32_t)nl;
-        d.n_inds = (int32_t)g->depth->n;
-        d.tpi = g->tpi;
-        d.sel = g->d_sel;
+        lines(d, g->depth->n);
+        d.tpi = g->dp.tpi;
+        d.sel = g->dp.sel.p;
         d.table = g->depth->table;
         d.mpad = g->depth->mpad;
         static const bool timed = getenv("WGSASSIGN_INGEST_TIME_KERNEL") != nullptr;
-        if (timed && !g->kev0 && (hipEventCreate(&g->kev0) != hipSuccess || hipEventCreate(&g->kev1) != hipSuccess)) g->kev0 = g->kev1 = nullptr;
-        if (timed && g->kev1) (void)hipEventRecord(g->kev0, st);
+        hipEvent_t &kev0 = g->dp.kev0, &kev1 = g->dp.kev1;
+        if (timed && !kev0 && (hipEventCreate(&kev0) != hipSuccess || hipEventCreate(&kev1) != hipSuccess)) kev0 = kev1 = nullptr;
+        if (timed && kev1) (void)hipEventRecord(kev0, st);
         hipLaunchKernelGGL(depth_tokenise_kernel, dim3((unsigned)((nl + 63) / 64)), dim3(256), 0, st, d);
-        if (timed && g->kev1) {
+        if (timed && kev1) {
             float ms = 0.0f;
-            (void)hipEventRecord(g->kev1, st);
-            if (hipEventSynchronize(g->kev1) == hipSuccess && hipEventElapsedTime(&ms, g->kev0, g->kev1) == hipSuccess) g->tok_ms += ms;
+            (void)hipEventRecord(kev1, st);
+            if (hipEventSynchronize(kev1) == hipSuccess && hipEventElapsedTime(&ms, kev0, kev1) == hipSuccess) g->dp.tok_ms += ms;
         }
-        return;
+    } else {
+        wgs_beagle *b = g->b;
+        TokArgs a;
+        lines(a, b->n);
+        a.group_of = b->d_group_of;
+        a.col_of = b->d_col_of;
+        a.npairs = b->d_npairs;
+        a.base = b->d_base;
+        hipLaunchKernelGGL(tokenise_kernel, dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, st, a);
     }
-    wgs_beagle *b = g->b;
-    TokArgs a;
-    a.text = reinterpret_cast<const uint4 *>(text);
-    a.begin = g->d_begin;
-    a.end = g->d_end;
-    a.dst = g->d_dst;
-    a.flags = g->d_flags;
-    a.nflagged = nflagged;
-    a.row0 = row0;
-    a.nlines = (int32_t)nl;
-    a.n_inds = (int32_t)b->n;
-    a.group_of = b->d_group_of;
-    a.col_of = b->d_col_of;
-    a.npairs = b->d_npairs;
-    a.base = b->d_base;
-    hipLaunchKernelGGL(tokenise_kernel, dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
-// Lines the device flagged (bit patterns it leaves to strtod), host-parsed and uploaded in runs of consecutive rows.
-// text_of(t) returns the line t as [b, e) in host memory; number_of(t) its index among the chunk's data lines.
-template <class TextOf, class NumberOf>
-int host_parse_flagged(wgs_ingest *g, int64_t row0, size_t nl, const uint8_t *flags, const int32_t *dst, int64_t first_row, TextOf text_of, NumberOf number_of)
+// parse_flagged for an integer table: a line by np.loadtxt's rules (reader_table_parse_line); its pairs are picked as the kernel
+// picks them and the row goes through wgs_depth_upload_rows, which refuses counts outside 0..255.  Messages name the line's
+// 1-based number in the file.
+template <class TextOf, class LineOf>
+int parse_flagged_table(wgs_ingest *g, int64_t row0, size_t nl, TextOf text_of, LineOf line_of)
 {
+    wgs_depth *d = g->depth;
+    const int tpi = g->dp.tpi, need = (int)d->n * tpi;
+    std::vector<int32_t> toks((size_t)need);
+    std::vector<int32_t> &irows = g->dp.irows;
+    irows.resize((size_t)2 * d->n);
+    for (size_t t = 0; t < nl; ++t) {
+        if (!g->flags[t] || g->dst[t] < 0) continue;
+        const char *lb = nullptr, *le = nullptr;
+        if (int rc = text_of(t, &lb, &le)) return rc;
+        const long long line = (long long)(reader_table_skip_lines(g->r) + (int64_t)line_of(t, true) + 1);
+        int bad_col = 0;
+        const int k = reader_table_parse_line(lb, le, need, toks.data(), &bad_col);
+        if (k == 1) {
+            wgs_set_error("line %lld has fewer than %d columns (%lld individuals)", line, need, (long long)d->n);
+            return 2;
+        }
+        if (k) {
+            wgs_set_error("line %lld, column %d: not an integer np.loadtxt reads as int32", line, bad_col);
+            return 2;
+        }
+        const int64_t row = row0 + g->dst[t];
+        if (tpi == 2) {
+            memcpy(irows.data(), toks.data(), sizeof(int32_t) * (size_t)need);
+        } else {
+            uint8_t mm[2];
+            HIP_TRY(hipMemcpy(mm, g->dp.sel.p + row * 2, 2, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < d->n; ++i) {
+                irows[(size_t)(2 * i)] = toks[(size_t)(4 * i + (mm[0] & 3))];
+                irows[(size_t)(2 * i + 1)] = toks[(size_t)(4 * i + (mm[1] & 3))];
+            }
+        }
+        for (int32_t v : irows)
+            if (v < 0 || v > 255) {
+                wgs_set_error("line %lld: allele depths outside 0..255 do not fit the device table", line);
+                return 2;
+            }
+        if (int rc = wgs_depth_upload_rows(d, irows.data(), row, 1)) return rc;
+        g->host_lines += 1;
+    }
+    return 0;
+}
+
+// Lines the device flagged (g->flags; bit patterns it leaves to strtod) and that have a row (g->dst), host-parsed and uploaded.
+// text_of(t, &b, &e) fetches line t as [b, e) in host memory.  line_of(t, in_text) numbers it from 0: among the data lines the
+// reader has handed out since the ingest began (what a Beagle file's messages count), or with in_text among all lines of the text
+// (a table's).  A Beagle line goes through reader_text_parse_line, in runs of consecutive rows; a table's through the function above.
+template <class TextOf, class LineOf>
+int parse_flagged(wgs_ingest *g, int64_t row0, size_t nl, TextOf text_of, LineOf line_of)
+{
+    if (g->depth) return parse_flagged_table(g, row0, nl, text_of, line_of);
     wgs_beagle *b = g->b;
+    const uint8_t *flags = g->flags.data();
+    const int32_t *dst = g->dst.data();
     const size_t row_floats = (size_t)2 * (size_t)b->n;
     for (size_t i = 0; i < nl;) {
         if (!flags[i] || dst[i] < 0) {
@@ -742,7 +845,7 @@ int host_parse_flagged(wgs_ingest *g, int64_t row0, size_t nl, const uint8_t *fl
             if (int rc = text_of(t, &lb, &le)) return rc;
             if (reader_text_parse_line(g->r, lb, le, g->rows.data() + (t - i) * row_floats)) {
                 wgs_set_error("Beagle data line %lld has fewer than %d genotype-likelihood columns",
-                              (long long)(reader_text_lines_read(g->r) + first_row + (int64_t)number_of(t) + 2), reader_text_gl_cols(g->r));
+                              (long long)(reader_text_lines_read(g->r) + (int64_t)line_of(t, false) + 2), reader_text_gl_cols(g->r));
                 return 2;
             }
         }
@@ -753,61 +856,233 @@ int host_parse_flagged(wgs_ingest *g, int64_t row0, size_t nl, const uint8_t *fl
     return 0;
 }
 
-// The same for an integer table: a flagged line by np.loadtxt's rules (reader_table_parse_line); its pairs are picked as the kernel
-// picks them and the row goes through wgs_depth_upload_rows, which refuses counts outside 0..255.  line_of(t) = the 1-based number
-// of line t in the file.
-template <class TextOf, class LineOf>
-int host_parse_flagged_depth(wgs_ingest *g, int64_t row0, size_t nl, const uint8_t *flags, const int32_t *dst, TextOf text_of, LineOf line_of)
-{
-    wgs_depth *d = g->depth;
-    const int need = (int)d->n * g->tpi;
-    std::vector<int32_t> toks((size_t)need), sel(2);
-    g->irows.resize((size_t)2 * d->n);
-    for (size_t t = 0; t < nl; ++t) {
-        if (!flags[t] || dst[t] < 0) continue;
-        const char *lb = nullptr, *le = nullptr;
-        if (int rc = text_of(t, &lb, &le)) return rc;
-        int bad_col = 0;
-        const int k = reader_table_parse_line(lb, le, need, toks.data(), &bad_col);
-        if (k == 1) {
-            wgs_set_error("line %lld has fewer than %d columns (%lld individuals)", (long long)line_of(t), need, (long long)d->n);
-            return 2;
-        }
-        if (k) {
-            wgs_set_error("line %lld, column %d: not an integer np.loadtxt reads as int32", (long long)line_of(t), bad_col);
-            return 2;
-        }
-        const int64_t row = row0 + dst[t];
-        if (g->tpi == 2) {
-            memcpy(g->irows.data(), toks.data(), sizeof(int32_t) * (size_t)need);
-        } else {
-            uint8_t mm[2];
-            HIP_TRY(hipMemcpy(mm, g->d_sel + row * 2, 2, hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < d->n; ++i) {
-                g->irows[(size_t)(2 * i)] = toks[(size_t)(4 * i + (mm[0] & 3))];
-                g->irows[(size_t)(2 * i + 1)] = toks[(size_t)(4 * i + (mm[1] & 3))];
-            }
-        }
-        for (int32_t v : g->irows)
-            if (v < 0 || v > 255) {
-                wgs_set_error("line %lld: allele depths outside 0..255 do not fit the device table", (long long)line_of(t));
-                return 2;
-            }
-        if (int rc = wgs_depth_upload_rows(d, g->irows.data(), row, 1)) return rc;
-        g->host_lines += 1;
-    }
-    return 0;
-}
-
 /* BGZF, device-resident: per chunk the producer thread only READS the next members (reader.cpp: comp_producer); here
  *   H2D of the compressed bytes -> inflate_kernel (inflate.hip; one lane per member) into d_text behind the carried partial
  *   line -> newline positions (count per 4 KiB, scan, write) -> per line extent / blank / site name -> scans number the data
  *   lines and place the names -> dst (row limit, site mask) + names blob -> tokenise_kernel -> the partial last line moves
  *   to the front for the next chunk.
- * The host sees three small read-backs per chunk (counts, the names, the flag count) and the text never exists there. */
-int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t keep_len, int64_t *file_rows, int64_t *rows_written)
+ * The host sees three small read-backs per chunk (counts, the names, the flag count) and the text never exists there.
+ * One function per stage, in the order ingest_next_resident calls them; what they hand on about the chunk: */
+struct Chunk {
+    int nb = 0;                     // compressed members
+    bool last = false;              // of the file
+    size_t lead = 0;                // text ahead of the members': the carried partial line and what the reader had inflated itself
+    size_t total = 0;               // all of the text in d_text
+    size_t padded = 0;              // ... and with the newlines behind it that the kernels may read into
+    size_t nl = 0;                  // whole lines
+    size_t rows_here = 0, take = 0; // data lines among them, and those within the row limit
+    size_t name_bytes = 0;          // of all the data lines' site names
+    int64_t written = 0;            // rows of the target the chunk fills
+    size_t nblk() const { return (total + 4095) / 4096; }
+};
+
+// The chunk's extent, and room for it in the buffers it is staged and inflated in.
+int size_chunk(wgs_ingest *g, const CompChunk *c, Chunk &k)
 {
     hipStream_t st = g->ctx->stream;
+    k.last = c->last;
+    k.nb = (int)c->isize.size();
+    k.lead = g->carry + c->pre_len;
+    k.total = k.lead + c->text_bytes + (k.last ? 1 : 0);     // a newline closes an unterminated last line
+    WGS_REQUIRE(k.total + TEXT_PAD + 64 < (1ull << 32), "a Beagle line longer than 4 GiB");
+    g->read_s += c->read_s;
+    k.padded = ((k.total + TEXT_PAD + 15) & ~(size_t)15) + 64;
+    if (int rc = g->d_text.reserve(st, k.padded, k.padded + k.padded / 8, g->carry)) return rc;      // keeps the carried partial line
+    const size_t nb = (size_t)k.nb, cap = nb + nb / 4 + 256;
+    if (int rc = reserve_all(st, nb, cap, g->d_in_off, g->d_out_off, g->d_in_len, g->d_isize, g->d_status)) return rc;
+    if (int rc = g->d_tables.reserve(st, nb * inflate_table_bytes(), cap * inflate_table_bytes())) return rc;
+    return g->d_comp.reserve(st, c->len + INFLATE_PAD, c->len + INFLATE_PAD);
+}
+
+// Compressed members to the device and through the inflate kernel, behind the text that leads the chunk.
+int copy_and_inflate(wgs_ingest *g, const CompChunk *c, const Chunk &k)
+{
+    hipStream_t st = g->ctx->stream;
+    uint8_t *text = g->d_text.p;
+    const int nb = k.nb;
+    if (int rc = clock_start(g)) return rc;
+    HIP_TRY(hipMemsetAsync(g->d_totals.p, 0, T_COUNT * sizeof(uint32_t), st));
+    if (c->pre_len) HIP_TRY(hipMemcpyAsync(text + g->carry, c->pre_text, c->pre_len, hipMemcpyHostToDevice, st));
+    if (nb) {
+        g->out_off.resize((size_t)nb);
+        uint64_t at = k.lead;
+        for (int i = 0; i < nb; ++i) {
+            g->out_off[(size_t)i] = at;
+            at += c->isize[(size_t)i];
+        }
+        HIP_TRY(hipMemcpyAsync(g->d_comp.p, c->comp, c->len, hipMemcpyHostToDevice, st));
+        // zeros behind the chunk: a damaged last member that reads on finds an invalid stored-block header there, not the
+        // stale bytes of the chunk before (the kernel stops a lane a few bytes past its stream's end anyway)
+        HIP_TRY(hipMemsetAsync(g->d_comp.p + c->len, 0, INFLATE_PAD, st));
+        HIP_TRY(hipMemcpyAsync(g->d_in_off.p, c->in_off.data(), sizeof(uint64_t) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(g->d_out_off.p, g->out_off.data(), sizeof(uint64_t) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(g->d_in_len.p, c->in_len.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(g->d_isize.p, c->isize.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(g->iev0, st));
+        if (launch_inflate(g->ctx, g->d_comp.p, g->d_in_off.p, g->d_in_len.p, g->d_out_off.p, g->d_isize.p, text, g->d_status.p, g->d_tables.p, nb)) return 1;
+        HIP_TRY(hipEventRecord(g->iev1, st));
+        g->status.resize((size_t)nb);
+        HIP_TRY(hipMemcpyAsync(g->status.data(), g->d_status.p, (size_t)nb, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemsetAsync(text + k.lead + c->text_bytes, '\n', k.padded - (k.lead + c->text_bytes), st));
+    return 0;
+}
+
+// Newlines per 4 KiB of the text and their scan; waits for the stream: k.nl, and after the first call the members' status.
+int count_newlines(wgs_ingest *g, Chunk &k)
+{
+    hipStream_t st = g->ctx->stream;
+    const size_t nblk = k.nblk();
+    if (int rc = reserve_all(st, nblk, nblk + nblk / 4 + 64, g->d_counts, g->d_offsets)) return rc;
+    if (nblk) {
+        hipLaunchKernelGGL(count_newlines_kernel, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const uint4 *>(g->d_text.p), (uint64_t)k.total, g->d_counts.p);
+        hipLaunchKernelGGL(scan_u32_kernel, dim3(1), dim3(1024), 0, st, g->d_counts.p, g->d_offsets.p, (uint32_t)nblk, g->d_totals.p + T_NEWLINES);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(g->h_totals, g->d_totals.p, T_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    k.nl = g->h_totals[T_NEWLINES];
+    return 0;
+}
+
+// Members the device did not accept: the host's inflater, patched into the device text; the newlines are counted again
+// (WGSASSIGN_DEBUG_REJECT_MEMBERS=k, tests: every k-th member is treated as rejected and its device text wiped first).
+int patch_rejected_members(wgs_ingest *g, const CompChunk *c, Chunk &k)
+{
+    uint8_t *text = g->d_text.p;
+    const char *reject_env = getenv("WGSASSIGN_DEBUG_REJECT_MEMBERS");
+    const int reject_every = reject_env ? atoi(reject_env) : 0;
+    for (int i = 0; reject_every > 0 && i < k.nb; i += reject_every) {
+        g->status[(size_t)i] = 1;
+        HIP_TRY(hipMemset(text + g->out_off[(size_t)i], '#', c->isize[(size_t)i]));
+    }
+    bool patched = false;
+    for (int i = 0; i < k.nb; ++i) {
+        if (!g->status[(size_t)i]) continue;
+        g->line.resize(65536);
+        if (!reader_inflate_member(c->comp + c->in_off[(size_t)i], c->in_len[(size_t)i], c->isize[(size_t)i], reinterpret_cast<unsigned char *>(g->line.data()))) {
+            wgs_set_error("read error in the BGZF file (corrupt block)");
+            return 1;
+        }
+        HIP_TRY(hipMemcpy(text + g->out_off[(size_t)i], g->line.data(), c->isize[(size_t)i], hipMemcpyHostToDevice));
+        ++g->blocks_host;
+        patched = true;
+    }
+    return patched ? count_newlines(g, k) : 0;
+}
+
+// Where the newlines are, and per line its extent, whether it is a data line and its site name; waits for the stream:
+// k.rows_here, k.name_bytes.
+int list_lines(wgs_ingest *g, Chunk &k)
+{
+    hipStream_t st = g->ctx->stream;
+    const size_t nl = k.nl;
+    if (int rc = ensure_line_arrays(g, nl)) return rc;
+    hipLaunchKernelGGL(write_newlines_kernel, dim3((unsigned)k.nblk()), dim3(256), 0, st, reinterpret_cast<const uint4 *>(g->d_text.p), (uint64_t)k.total, g->d_offsets.p, g->d_nl_pos.p);
+    LineArgs la;
+    la.text = g->d_text.p;
+    la.nl_pos = g->d_nl_pos.p;
+    la.nlines = (uint32_t)nl;
+    la.begin = g->d_begin.p;
+    la.end = g->d_end.p;
+    la.nonblank = g->d_nonblank.p;
+    la.name_start = g->d_name_start.p;
+    la.name_len1 = g->d_name_len1.p;
+    la.totals = g->d_totals.p;
+    la.table = g->depth ? 1 : 0;
+    hipLaunchKernelGGL(line_info_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, la);
+    hipLaunchKernelGGL(scan_u32_kernel, dim3(1), dim3(1024), 0, st, g->d_nonblank.p, g->d_rank.p, (uint32_t)nl, g->d_totals.p + T_NONBLANK);
+    hipLaunchKernelGGL(scan_u32_kernel, dim3(1), dim3(1024), 0, st, g->d_name_len1.p, g->d_name_off.p, (uint32_t)nl, g->d_totals.p + T_NAME_BYTES);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(g->h_totals, g->d_totals.p, T_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    k.rows_here = g->h_totals[T_NONBLANK];
+    k.name_bytes = g->h_totals[T_NAME_BYTES];
+    return 0;
+}
+
+// The row limit and the site mask decide which data lines get which rows (k.take, k.written); per line its row, and the names blob.
+int place_chunk_rows(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t keep_len, Chunk &k)
+{
+    hipStream_t st = g->ctx->stream;
+    k.take = k.rows_here;
+    if (g->limit >= 0 && (int64_t)k.take >= g->limit - g->rows_done) {
+        k.take = (size_t)(g->limit - g->rows_done);
+        g->done = true;
+    }
+    if (k.last) g->done = true;
+    if (int rc = place_rows(g, row0, keep, keep_len, k.take, keep ? &g->dstmap : nullptr, &k.written)) return rc;
+    if (keep && k.take) HIP_TRY(hipMemcpyAsync(g->d_dstmap.p, g->dstmap.data(), k.take * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (int rc = g->d_names.reserve(st, k.name_bytes + 16, k.name_bytes + k.name_bytes / 2 + 4096)) return rc;
+    DstArgs da;
+    da.nlines = (uint32_t)k.nl;
+    da.take = g->dp.overflow ? 0u : (uint32_t)k.take;
+    da.nonblank = g->d_nonblank.p;
+    da.rank = g->d_rank.p;
+    da.name_start = g->d_name_start.p;
+    da.name_len1 = g->d_name_len1.p;
+    da.name_off = g->d_name_off.p;
+    da.dstmap = keep ? g->d_dstmap.p : nullptr;
+    da.text = g->d_text.p;
+    da.dst = g->d_dst.p;
+    da.names = g->d_names.p;
+    da.totals = g->d_totals.p;
+    hipLaunchKernelGGL(dst_names_kernel, dim3((unsigned)((k.nl + 255) / 256)), dim3(256), 0, st, da);
+    return 0;
+}
+
+// The tokeniser over the chunk's lines; waits for the stream: the names, and the lines left to the host's parser.
+int tokenise_chunk(wgs_ingest *g, int64_t row0, const Chunk &k)
+{
+    hipStream_t st = g->ctx->stream;
+    const uint8_t *text = g->d_text.p;
+    const size_t nl = k.nl;
+    if (int rc = launch_tokenise(g, text, row0, nl, g->d_totals.p + T_FLAGGED)) return rc;
+    g->names.resize(k.name_bytes);
+    if (k.name_bytes) HIP_TRY(hipMemcpyAsync(&g->names[0], g->d_names.p, k.name_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(g->h_totals, g->d_totals.p, T_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (int rc = clock_stop(g)) return rc;
+    if (k.take < k.rows_here || g->dp.overflow) g->names.resize(g->h_totals[T_NAME_CUT]);
+    if (!g->h_totals[T_FLAGGED]) return 0;
+    // rare: fetch what the host parser needs -- flags, extents, numbering -- and the flagged lines themselves
+    auto fetch = [nl](auto &host, const auto &dev) {
+        host.resize(nl);
+        return hipMemcpy(host.data(), dev.p, nl * sizeof(*dev.p), hipMemcpyDeviceToHost);
+    };
+    HIP_TRY(fetch(g->flags, g->d_flags));
+    HIP_TRY(fetch(g->dst, g->d_dst));
+    HIP_TRY(fetch(g->h_begin, g->d_begin));
+    HIP_TRY(fetch(g->h_end, g->d_end));
+    HIP_TRY(fetch(g->h_rank, g->d_rank));
+    auto text_of = [&](size_t t, const char **lb, const char **le) -> int {
+        const size_t n = g->h_end[t] - g->h_begin[t];
+        g->line.resize(n + 1);
+        HIP_TRY(hipMemcpy(g->line.data(), text + g->h_begin[t], n, hipMemcpyDeviceToHost));
+        *lb = g->line.data();
+        *le = g->line.data() + n;
+        return 0;
+    };
+    return parse_flagged(g, row0, nl, text_of, [&](size_t t, bool in_text) { return in_text ? g->dp.lines_before + (int64_t)t : g->rows_done + (int64_t)g->h_rank[t]; });
+}
+
+// The partial last line moves to the front for the next chunk (through a side buffer: the two ranges may overlap); queued behind
+// the tokeniser, waited for by nobody but the next chunk's kernels.
+int carry_tail(wgs_ingest *g, const Chunk &k)
+{
+    hipStream_t st = g->ctx->stream;
+    const size_t tail = g->h_totals[T_TAIL];
+    const size_t left = g->done ? 0 : k.total - tail;
+    if (left) {
+        if (int rc = g->d_carry.reserve(st, left, left + left / 2 + 65536)) return rc;
+        HIP_TRY(hipMemcpyAsync(g->d_carry.p, g->d_text.p + tail, left, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(g->d_text.p, g->d_carry.p, left, hipMemcpyDeviceToDevice, st));
+    }
+    g->carry = left;
+    return 0;
+}
+
+int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t keep_len, int64_t *file_rows, int64_t *rows_written)
+{
     static const bool trace = getenv("WGSASSIGN_INGEST_TRACE") != nullptr;       // per-chunk wall times on stderr
     while (!g->done) {
         const double t_begin = now_s();
@@ -819,254 +1094,44 @@ int ingest_next_resident(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64
             g->done = true;
             break;
         }
-        struct Release {
-            wgs_ingest *g;
-            CompChunk *c;
-            ~Release() { if (c) reader_comp_release(g->r, c); }
-        } release{g, c};
-        const bool last = c->last;
-        const int nb = (int)c->isize.size();
-        const size_t lead = g->carry + c->pre_len;
-        const size_t total = lead + c->text_bytes + (last ? 1 : 0);     // a newline closes an unterminated last line
-        WGS_REQUIRE(total + TEXT_PAD + 64 < (1ull << 32), "a Beagle line longer than 4 GiB");
-        g->read_s += c->read_s;
-        const size_t need = ((total + TEXT_PAD + 15) & ~(size_t)15) + 64;
-        if (need > g->text_cap) {                                         // keeps the carried partial line
-            HIP_TRY(hipStreamSynchronize(st));
-            void *q = nullptr;
-            const size_t cap = need + need / 8;
-            HIP_TRY(wgs_malloc(&q, cap));
-            if (g->carry) HIP_TRY(hipMemcpy(q, g->d_text, g->carry, hipMemcpyDeviceToDevice));
-            if (g->d_text) HIP_TRY(hipFree(g->d_text));
-            g->d_text = q;
-            g->text_cap = cap;
-        }
-        uint8_t *text = reinterpret_cast<uint8_t *>(g->d_text);
-        if ((size_t)nb > g->blocks_cap) {
-            const size_t cap = (size_t)nb + (size_t)nb / 4 + 256;
-            g->blocks_cap = 0;
-            if (int rc = regrow(st, g->d_in_off, cap)) return rc;
-            if (int rc = regrow(st, g->d_out_off, cap)) return rc;
-            if (int rc = regrow(st, g->d_in_len, cap)) return rc;
-            if (int rc = regrow(st, g->d_isize, cap)) return rc;
-            if (int rc = regrow(st, g->d_status, cap)) return rc;
-            HIP_TRY(hipStreamSynchronize(st));
-            if (g->d_tables) HIP_TRY(hipFree(g->d_tables));
-            g->d_tables = nullptr;
-            HIP_TRY(wgs_malloc(&g->d_tables, inflate_table_bytes() * cap));
-            g->blocks_cap = cap;
-        }
-        if (c->len + INFLATE_PAD > g->comp_cap) {
-            g->comp_cap = 0;
-            if (int rc = regrow(st, g->d_comp, c->len + INFLATE_PAD)) return rc;
-            g->comp_cap = c->len + INFLATE_PAD;
-        }
+        auto guard = on_failure([&] { reader_comp_release(g->r, c); });
+        Chunk k;
+        if (int rc = size_chunk(g, c, k)) return rc;
         const double t_alloc = now_s();
-        HIP_TRY(hipEventRecord(g->ev0, st));
-        HIP_TRY(hipMemsetAsync(g->d_totals, 0, T_COUNT * sizeof(uint32_t), st));
-        if (c->pre_len) HIP_TRY(hipMemcpyAsync(text + g->carry, c->pre_text, c->pre_len, hipMemcpyHostToDevice, st));
-        if (nb) {
-            g->out_off.resize((size_t)nb);
-            uint64_t at = lead;
-            for (int i = 0; i < nb; ++i) {
-                g->out_off[(size_t)i] = at;
-                at += c->isize[(size_t)i];
-            }
-            HIP_TRY(hipMemcpyAsync(g->d_comp, c->comp, c->len, hipMemcpyHostToDevice, st));
-            // zeros behind the chunk: a damaged last member that reads on finds an invalid stored-block header there, not the
-            // stale bytes of the chunk before (the kernel stops a lane a few bytes past its stream's end anyway)
-            HIP_TRY(hipMemsetAsync(g->d_comp + c->len, 0, INFLATE_PAD, st));
-            HIP_TRY(hipMemcpyAsync(g->d_in_off, c->in_off.data(), sizeof(uint64_t) * nb, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(g->d_out_off, g->out_off.data(), sizeof(uint64_t) * nb, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(g->d_in_len, c->in_len.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(g->d_isize, c->isize.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipEventRecord(g->iev0, st));
-            if (launch_inflate(g->ctx, g->d_comp, g->d_in_off, g->d_in_len, g->d_out_off, g->d_isize, text, g->d_status, g->d_tables, nb)) return 1;
-            HIP_TRY(hipEventRecord(g->iev1, st));
-            g->status.resize((size_t)nb);
-            HIP_TRY(hipMemcpyAsync(g->status.data(), g->d_status, (size_t)nb, hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipMemsetAsync(text + lead + c->text_bytes, '\n', need - (lead + c->text_bytes), st));
-        const size_t nblk = (total + 4095) / 4096;
-        if (nblk > g->counts_cap) {
-            const size_t cap = nblk + nblk / 4 + 64;
-            g->counts_cap = 0;
-            if (int rc = regrow(st, g->d_counts, cap)) return rc;
-            if (int rc = regrow(st, g->d_offsets, cap)) return rc;
-            g->counts_cap = cap;
-        }
-        for (int pass = 0; pass < 2; ++pass) {
-            if (nblk) {
-                hipLaunchKernelGGL(count_newlines_kernel, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const uint4 *>(text), (uint64_t)total, g->d_counts);
-                hipLaunchKernelGGL(scan_u32_kernel, dim3(1), dim3(1024), 0, st, g->d_counts, g->d_offsets, (uint32_t)nblk, g->d_totals + T_NEWLINES);
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipMemcpyAsync(g->h_totals, g->d_totals, T_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (pass) break;
-            // members the device did not accept: the host's inflater, patched into the device text; the newlines are counted again
-            // (WGSASSIGN_DEBUG_REJECT_MEMBERS=k, tests: every k-th member is treated as rejected and its device text wiped first)
-            const char *reject_env = getenv("WGSASSIGN_DEBUG_REJECT_MEMBERS");
-            const int reject_every = reject_env ? atoi(reject_env) : 0;
-            for (int i = 0; reject_every > 0 && i < nb; i += reject_every) {
-                g->status[(size_t)i] = 1;
-                HIP_TRY(hipMemset(text + g->out_off[(size_t)i], '#', c->isize[(size_t)i]));
-            }
-            bool patched = false;
-            for (int i = 0; i < nb; ++i) {
-                if (!g->status[(size_t)i]) continue;
-                g->line.resize(65536);
-                if (!reader_inflate_member(c->comp + c->in_off[(size_t)i], c->in_len[(size_t)i], c->isize[(size_t)i], reinterpret_cast<unsigned char *>(g->line.data()))) {
-                    wgs_set_error("read error in the BGZF file (corrupt block)");
-                    return 1;
-                }
-                HIP_TRY(hipMemcpy(text + g->out_off[(size_t)i], g->line.data(), c->isize[(size_t)i], hipMemcpyHostToDevice));
-                ++g->blocks_host;
-                patched = true;
-            }
-            if (!patched) break;
-        }
-        if (nb) {
+        if (int rc = copy_and_inflate(g, c, k)) return rc;
+        if (int rc = count_newlines(g, k)) return rc;
+        if (int rc = patch_rejected_members(g, c, k)) return rc;
+        if (k.nb) {
             float ms = 0.0f;
             (void)hipEventElapsedTime(&ms, g->iev0, g->iev1);
             g->inflate_kernel_ms += ms;
-            g->blocks_inflated += nb;
+            g->blocks_inflated += k.nb;
         }
         const double t_inflated = now_s();
         reader_comp_release(g->r, c);                                   // the producer may refill it while the device works on
-        release.c = nullptr;
-        c = nullptr;
-        const size_t nl = g->h_totals[T_NEWLINES];
-        g->text_bytes += (int64_t)(total - g->carry);
+        guard.dismiss();
+        g->text_bytes += (int64_t)(k.total - g->carry);
         g->chunks += 1;
-        if (nl == 0) {                                                    // not one whole line yet
-            g->carry = total;
-            if (last) g->done = true;
+        if (k.nl == 0) {                                                // not one whole line yet
+            g->carry = k.total;
+            if (k.last) g->done = true;
             continue;
         }
-        if (int rc = ensure_line_arrays(g, st, nl, true)) return rc;
-        hipLaunchKernelGGL(write_newlines_kernel, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const uint4 *>(text), (uint64_t)total, g->d_offsets, g->d_nl_pos);
-        LineArgs la;
-        la.text = text;
-        la.nl_pos = g->d_nl_pos;
-        la.nlines = (uint32_t)nl;
-        la.begin = g->d_begin;
-        la.end = g->d_end;
-        la.nonblank = g->d_nonblank;
-        la.name_start = g->d_name_start;
-        la.name_len1 = g->d_name_len1;
-        la.totals = g->d_totals;
-        la.table = g->depth ? 1 : 0;
-        hipLaunchKernelGGL(line_info_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, la);
-        hipLaunchKernelGGL(scan_u32_kernel, dim3(1), dim3(1024), 0, st, g->d_nonblank, g->d_rank, (uint32_t)nl, g->d_totals + T_NONBLANK);
-        hipLaunchKernelGGL(scan_u32_kernel, dim3(1), dim3(1024), 0, st, g->d_name_len1, g->d_name_off, (uint32_t)nl, g->d_totals + T_NAME_BYTES);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(g->h_totals, g->d_totals, T_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = list_lines(g, k)) return rc;
         const double t_listed = now_s();
-        const size_t rows_here = g->h_totals[T_NONBLANK];
-        size_t take = rows_here;
-        if (g->limit >= 0 && (int64_t)take >= g->limit - g->rows_done) {
-            take = (size_t)(g->limit - g->rows_done);
-            g->done = true;
-        }
-        if (last) g->done = true;
-        int64_t written = (int64_t)take;
-        if (keep) {
-            WGS_REQUIRE((int64_t)take <= keep_len, "site mask shorter than the file (%lld lines left in it, %lld in the chunk)", (long long)keep_len, (long long)take);
-            g->dstmap.resize(take);
-            written = 0;
-            for (size_t i = 0; i < take; ++i) g->dstmap[i] = keep[i] ? (int32_t)written++ : -1;
-            if (take) HIP_TRY(hipMemcpyAsync(g->d_dstmap, g->dstmap.data(), take * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        }
-        // a table with more data lines than the target has rows: nothing more is stored, the lines are still counted (the caller
-        // reports both numbers)
-        if (g->depth && row0 + written > g->m_rows) g->overflow = true;
-        if (g->overflow) written = 0;
-        WGS_REQUIRE(row0 >= 0 && row0 + written <= g->m_rows, "rows [%lld, %lld) outside the device matrix (%lld rows)", (long long)row0, (long long)(row0 + written), (long long)g->m_rows);
-        const size_t name_bytes = g->h_totals[T_NAME_BYTES];
-        if (name_bytes + 16 > g->names_cap) {
-            g->names_cap = 0;
-            if (int rc = regrow(st, g->d_names, name_bytes + name_bytes / 2 + 4096)) return rc;
-            g->names_cap = name_bytes + name_bytes / 2 + 4096;
-        }
-        DstArgs da;
-        da.nlines = (uint32_t)nl;
-        da.take = g->overflow ? 0u : (uint32_t)take;
-        da.nonblank = g->d_nonblank;
-        da.rank = g->d_rank;
-        da.name_start = g->d_name_start;
-        da.name_len1 = g->d_name_len1;
-        da.name_off = g->d_name_off;
-        da.dstmap = keep ? g->d_dstmap : nullptr;
-        da.text = text;
-        da.dst = g->d_dst;
-        da.names = g->d_names;
-        da.totals = g->d_totals;
-        hipLaunchKernelGGL(dst_names_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, da);
-        HIP_TRY(hipMemsetAsync(g->d_flags, 0, nl, st));
-        launch_tokenise(g, st, text, row0, nl, g->d_totals + T_FLAGGED);
-        HIP_TRY(hipGetLastError());
-        g->names.resize(name_bytes);
-        if (name_bytes) HIP_TRY(hipMemcpyAsync(&g->names[0], g->d_names, name_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(g->h_totals, g->d_totals, T_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(g->ev1, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, g->ev0, g->ev1));
-        g->device_ms += ms;
-        if (take < rows_here || g->overflow) g->names.resize(g->h_totals[T_NAME_CUT]);
-        if (g->h_totals[T_FLAGGED]) {
-            // rare: fetch what the host parser needs -- flags, extents, numbering -- and the flagged lines themselves
-            g->flags.resize(nl);
-            g->dst.resize(nl);
-            g->h_begin.resize(nl);
-            g->h_end.resize(nl);
-            g->h_rank.resize(nl);
-            HIP_TRY(hipMemcpy(g->flags.data(), g->d_flags, nl, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(g->dst.data(), g->d_dst, nl * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(g->h_begin.data(), g->d_begin, nl * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(g->h_end.data(), g->d_end, nl * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(g->h_rank.data(), g->d_rank, nl * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            auto text_of = [&](size_t t, const char **lb, const char **le) -> int {
-                const size_t n = g->h_end[t] - g->h_begin[t];
-                g->line.resize(n + 1);
-                HIP_TRY(hipMemcpy(g->line.data(), text + g->h_begin[t], n, hipMemcpyDeviceToHost));
-                *lb = g->line.data();
-                *le = g->line.data() + n;
-                return 0;
-            };
-            if (g->depth) {
-                const int64_t base = reader_table_skip_lines(g->r) + g->lines_before + 1;
-                if (int rc = host_parse_flagged_depth(g, row0, nl, g->flags.data(), g->dst.data(), text_of, [&](size_t t) { return base + (int64_t)t; })) return rc;
-            } else if (int rc = host_parse_flagged(g, row0, nl, g->flags.data(), g->dst.data(), g->rows_done, text_of, [&](size_t t) { return g->h_rank[t]; })) {
-                return rc;
-            }
-        }
-        // the partial last line moves to the front for the next chunk (through a side buffer: the two ranges may overlap);
-        // queued behind the tokeniser, waited for by nobody but the next chunk's kernels
-        const size_t tail = g->h_totals[T_TAIL];
-        const size_t left = g->done ? 0 : total - tail;
-        if (left) {
-            if (left > g->carry_cap) {
-                g->carry_cap = 0;
-                if (int rc = regrow(st, g->d_carry, left + left / 2 + 65536)) return rc;
-                g->carry_cap = left + left / 2 + 65536;
-            }
-            HIP_TRY(hipMemcpyAsync(g->d_carry, text + tail, left, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(text, g->d_carry, left, hipMemcpyDeviceToDevice, st));
-        }
-        g->carry = left;
-        g->lines_before += (int64_t)nl;
-        g->rows_done += (int64_t)take;
-        g->lines += (int64_t)take;
+        if (int rc = place_chunk_rows(g, row0, keep, keep_len, k)) return rc;
+        if (int rc = tokenise_chunk(g, row0, k)) return rc;
+        if (int rc = carry_tail(g, k)) return rc;
+        g->dp.lines_before += (int64_t)k.nl;
+        g->rows_done += (int64_t)k.take;
+        g->lines += (int64_t)k.take;
         if (trace)
             fprintf(stderr, "ingest chunk %lld: %zu B text, %d members, %zu lines | wait %.1f ms, buffers %.1f, copy+inflate %.1f, list %.1f, rows+names+tokenise %.1f\n",
-                    (long long)g->chunks, total, nb, nl, waited * 1e3, (t_alloc - t_begin - waited) * 1e3, (t_inflated - t_alloc) * 1e3,
+                    (long long)g->chunks, k.total, k.nb, k.nl, waited * 1e3, (t_alloc - t_begin - waited) * 1e3, (t_inflated - t_alloc) * 1e3,
                     (t_listed - t_inflated) * 1e3, (now_s() - t_listed) * 1e3);
-        if (take == 0) continue;
-        *file_rows = (int64_t)take;
-        *rows_written = written;
+        if (k.take == 0) continue;
+        *file_rows = (int64_t)k.take;
+        *rows_written = k.written;
         return 0;
     }
     return 0;
@@ -1089,15 +1154,10 @@ void wgs_ingest_destroy(wgs_ingest *g)
         reader_comp_stop(g->r);
     }
     reader_text_stop(g->r);                                    // joins the producer, frees the pinned buffers
-    for (void *p : {g->d_text, (void *)g->d_begin, (void *)g->d_end, (void *)g->d_dst, (void *)g->d_flags, (void *)g->d_carry, (void *)g->d_comp,
-                    (void *)g->d_in_off, (void *)g->d_out_off, (void *)g->d_in_len, (void *)g->d_isize, (void *)g->d_status, g->d_tables,
-                    (void *)g->d_counts, (void *)g->d_offsets, (void *)g->d_nl_pos, (void *)g->d_nonblank, (void *)g->d_rank, (void *)g->d_name_start,
-                    (void *)g->d_name_len1, (void *)g->d_name_off, (void *)g->d_dstmap, (void *)g->d_names, (void *)g->d_totals, (void *)g->d_sel})
-        if (p) (void)hipFree(p);
     if (g->h_totals) (void)hipHostFree(g->h_totals);
-    for (hipEvent_t e : {g->ev0, g->ev1, g->iev0, g->iev1, g->kev0, g->kev1})
+    for (hipEvent_t e : {g->ev0, g->ev1, g->iev0, g->iev1, g->dp.kev0, g->dp.kev1})
         if (e) (void)hipEventDestroy(e);
-    delete g;
+    delete g;                                                  // frees the device arrays
 }
 
 /* chunk_bytes: text per chunk (<= 0: the default -- 256 MiB through the host inflater; 3 GiB -- or the members one launch has lanes for -- when the device inflates, one
@@ -1143,15 +1203,15 @@ int ingest_start(wgs_ingest *g, wgs_reader *r, int64_t limit_rows, int64_t chunk
     if (resident) {
         HIP_TRY(hipEventCreate(&g->iev0));
         HIP_TRY(hipEventCreate(&g->iev1));
-        HIP_TRY(wgs_malloc(reinterpret_cast<void **>(&g->d_totals), T_COUNT * sizeof(uint32_t)));
+        if (int rc = g->d_totals.reserve(ctx->stream, T_COUNT, T_COUNT)) return rc;
         HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&g->h_totals), T_COUNT * sizeof(uint32_t), hipHostMallocDefault));
-        g->chunk_text = (size_t)std::max<int64_t>(chunk_bytes, g->depth ? 65536 : 1 << 20);
+        const size_t chunk_text = (size_t)std::max<int64_t>(chunk_bytes, g->depth ? 65536 : 1 << 20);
         g->resident = true;
         if (limit_rows == 0) g->done = true;
         // page-locked staging for the compressed members: an eighth of the text (low-depth ANGSD output deflates 10 : 1 and
         // more; where a file compresses less a chunk simply ends early), one buffer when the rest of the file fits into it
         else {
-            size_t staging = std::max<size_t>(g->chunk_text / 8, 1u << 20);
+            size_t staging = std::max<size_t>(chunk_text / 8, 1u << 20);
             const int64_t left = reader_comp_bytes_left(r);
             int nbuf = 2;
             if (left >= 0 && (size_t)left + 4096 <= staging) {
@@ -1161,7 +1221,7 @@ int ingest_start(wgs_ingest *g, wgs_reader *r, int64_t limit_rows, int64_t chunk
             // one lane per member and three wavefronts per CU (52 KiB of tables each): members beyond that many wait for a
             // second round of the launch
             const size_t lanes = (size_t)std::max(1, ctx->cus) * 3 * 64;
-            if (int rc = reader_comp_start(r, staging, g->chunk_text, nbuf, a, lanes)) return rc;
+            if (int rc = reader_comp_start(r, staging, chunk_text, nbuf, a, lanes)) return rc;
         }
     } else if (int rc = reader_text_start(r, (size_t)chunk_bytes, 3, a, limit_rows)) {
         return rc;
@@ -1196,67 +1256,37 @@ int wgs_ingest_next(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t ke
     if (int rc = reader_text_next(g->r, &c, &waited)) return rc;
     g->wait_s += waited;
     if (!c) return 0;
-    struct Release {
-        wgs_ingest *g;
-        TextChunk *c;
-        ~Release() { reader_text_release(g->r, c); }
-    } release{g, c};
+    auto guard = on_failure([&] { reader_text_release(g->r, c); });
     const size_t nl = c->begin.size();
-    if (keep) WGS_REQUIRE((int64_t)nl <= keep_len, "site mask shorter than the file (%lld lines left in it, %lld in the chunk)", (long long)keep_len, (long long)nl);
-    g->dst.resize(nl);
     int64_t written = 0;
-    for (size_t i = 0; i < nl; ++i) g->dst[i] = (!keep || keep[i]) ? (int32_t)written++ : -1;
-    if (g->depth && row0 + written > g->m_rows) g->overflow = true;       // (see ingest_next_resident)
-    if (g->overflow) {
-        std::fill(g->dst.begin(), g->dst.end(), -1);
-        written = 0;
-    }
-    WGS_REQUIRE(row0 >= 0 && row0 + written <= g->m_rows, "rows [%lld, %lld) outside the device matrix (%lld rows)", (long long)row0,
-                (long long)(row0 + written), (long long)g->m_rows);
-    // device buffers (grow only)
+    if (int rc = place_rows(g, row0, keep, keep_len, nl, &g->dst, &written)) return rc;
     const size_t text_bytes = (c->len + TEXT_PAD + 15) & ~(size_t)15;
-    if (text_bytes > g->text_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (g->d_text) HIP_TRY(hipFree(g->d_text));
-        g->d_text = nullptr;
-        g->text_cap = 0;
-        const size_t cap = std::max(text_bytes, c->cap);
-        HIP_TRY(wgs_malloc(&g->d_text, cap));
-        g->text_cap = cap;
-    }
-    if (int rc = ensure_line_arrays(g, st, nl, false)) return rc;
-    HIP_TRY(hipEventRecord(g->ev0, st));
-    HIP_TRY(hipMemcpyAsync(g->d_text, c->data, text_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(g->d_begin, c->begin.data(), nl * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(g->d_end, c->end.data(), nl * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(g->d_dst, g->dst.data(), nl * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(g->d_flags, 0, nl, st));
-    launch_tokenise(g, st, g->d_text, row0, nl, nullptr);
-    HIP_TRY(hipGetLastError());
+    if (int rc = g->d_text.reserve(st, text_bytes, std::max(text_bytes, c->cap))) return rc;
+    if (int rc = ensure_line_arrays(g, nl)) return rc;
+    if (int rc = clock_start(g)) return rc;
+    HIP_TRY(hipMemcpyAsync(g->d_text.p, c->data, text_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(g->d_begin.p, c->begin.data(), nl * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(g->d_end.p, c->end.data(), nl * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(g->d_dst.p, g->dst.data(), nl * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (int rc = launch_tokenise(g, g->d_text.p, row0, nl, nullptr)) return rc;
     g->flags.resize(nl);
-    HIP_TRY(hipMemcpyAsync(g->flags.data(), g->d_flags, nl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(g->ev1, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, g->ev0, g->ev1));
-    g->device_ms += ms;
+    HIP_TRY(hipMemcpyAsync(g->flags.data(), g->d_flags.p, nl, hipMemcpyDeviceToHost, st));
+    if (int rc = clock_stop(g)) return rc;
     auto text_of = [&](size_t t, const char **lb, const char **le) -> int {
         *lb = c->data + c->begin[t];
         *le = c->data + c->end[t];
         return 0;
     };
-    if (g->depth) {
-        const int64_t base = reader_table_skip_lines(g->r) + c->first_line + 1;
-        if (int rc = host_parse_flagged_depth(g, row0, nl, g->flags.data(), g->dst.data(), text_of, [&](size_t t) { return base + (int64_t)c->lineno[t]; })) return rc;
-    } else if (int rc = host_parse_flagged(g, row0, nl, g->flags.data(), g->dst.data(), c->first_row, text_of, [](size_t t) { return t; })) {
-        return rc;
-    }
+    auto line_of = [&](size_t t, bool in_text) { return in_text ? c->first_line + (int64_t)c->lineno[t] : c->first_row + (int64_t)t; };
+    if (int rc = parse_flagged(g, row0, nl, text_of, line_of)) return rc;
     g->names.swap(c->names);
     g->inflate_s += c->inflate_s;
     g->scan_s += c->scan_s;
     g->text_bytes += (int64_t)c->len;
     g->lines += (int64_t)nl;
     g->chunks += 1;
+    reader_text_release(g->r, c);
+    guard.dismiss();
     *file_rows = (int64_t)nl;
     *rows_written = written;
     return 0;
@@ -1322,17 +1352,15 @@ int wgs_depth_ingest_create(wgs_depth *d, wgs_reader *r, int mode, const uint8_t
     g->depth = d;
     g->ctx = d->ctx;
     g->m_rows = d->m;
-    g->tpi = tpi;
+    g->dp.tpi = tpi;
     if (majmin) {
         auto guard = on_failure([&] { delete g; });
         HIP_TRY(hipSetDevice(d->ctx->device));
-        if (wgs_malloc(reinterpret_cast<void **>(&g->d_sel), (size_t)(2 * d->m)) != hipSuccess) {
+        if (g->dp.sel.reserve(d->ctx->stream, (size_t)(2 * d->m), (size_t)(2 * d->m))) {
             wgs_set_error("hipMalloc of %lld bytes for the allele selectors failed", (long long)(2 * d->m));
             return 1;
         }
-        auto guard2 = on_failure([&] { (void)hipFree(g->d_sel); });
-        HIP_TRY(hipMemcpy(g->d_sel, majmin, (size_t)(2 * d->m), hipMemcpyHostToDevice));
-        guard2.dismiss();
+        HIP_TRY(hipMemcpy(g->dp.sel.p, majmin, (size_t)(2 * d->m), hipMemcpyHostToDevice));
         guard.dismiss();
     }
     wgs_ingest *made = nullptr;
@@ -1358,8 +1386,8 @@ int wgs_depth_ingest_stats(wgs_depth_ingest *gi, double *stats)
 {
     wgs_ingest *g = reinterpret_cast<wgs_ingest *>(gi);
     WGS_REQUIRE(g && g->depth && stats, "null argument");
-    size_t peak = std::max(reader_host_peak(g->r), g->host_peak);
-    peak = std::max(peak, g->irows.capacity() * sizeof(int32_t));
+    size_t peak = std::max(reader_host_peak(g->r), g->dp.host_peak);
+    peak = std::max(peak, g->dp.irows.capacity() * sizeof(int32_t));
     peak = std::max(peak, std::max(g->flags.capacity(), g->line.capacity()));
     peak = std::max(peak, std::max(g->dst.capacity(), g->h_begin.capacity()) * sizeof(int32_t));
     stats[0] = (double)peak;
@@ -1369,7 +1397,7 @@ int wgs_depth_ingest_stats(wgs_depth_ingest *gi, double *stats)
     stats[4] = (double)g->lines;
     stats[5] = (double)g->chunks;
     stats[6] = (double)g->blocks_inflated;
-    stats[7] = g->tok_ms;
+    stats[7] = g->dp.tok_ms;
     return 0;
 }
 
