@@ -48,7 +48,7 @@ const char *wgs_last_error(void);
  * collectives (wgs_coll_tag, wgs_comm_check, wgs_comm_next_generation, wgs_comm_allreduce_host_tagged).  The z-score entry points
  * (wgs_depth_*, wgs_zscore_*, wgs_zkeep_*, wgs_em_fit_masked) were ADDED under 3: no existing signature changed; so were the
  * integer-table reader (wgs_reader_open_table), the depth ingest (wgs_depth_ingest_*), wgs_depth_create_shape and
- * wgs_depth_download_rows. */
+ * wgs_depth_download_rows, and the deep tier of the z-scores (wgs_zscore_deep_sites, wgs_zkeep_create_deep). */
 #define WGS_ABI_VERSION 3
 int wgs_version(void);
 /* sha256[:16] over every source of the library / over the sources of the EM and scoring kernels (em_kernels.hip,
@@ -449,7 +449,11 @@ int wgs_ingest_stats(wgs_ingest *g, double *stats);
 /* ------------------------------------------------------------------ z-scores (--get_reference_z_score, --get_assignment_z_score)
  * zscore.py / zscore_cy.pyx / WGSassign.py:311-446 on device-resident data.  The host keeps what is a few dozen numbers per
  * individual (key filter, tables: wgsassign_amd/zscore.py); everything that touches every site runs here.  A depth pair
- * (Ar, Aa) of depth d = Ar + Aa <= wgs_zscore_max_depth() (21) has the class index d (d + 1) / 2 + Aa; WGS_Z_CLASSES of them. */
+ * (Ar, Aa) of depth d = Ar + Aa <= wgs_zscore_max_depth() (21) has the class index d (d + 1) / 2 + Aa; WGS_Z_CLASSES of them: the
+ * dense tier, one class per thread of the class sweep.  Deeper pairs -- up to 255 reads per allele, what the table's bytes hold,
+ * i.e. depth 510 -- form a sparse second tier: the class sweep counts them, wgs_zscore_deep_sites lists them for the host's
+ * dictionary, and a kept-site set made by wgs_zkeep_create_deep carries the rows of the deep depths that survived the key
+ * filter.  Data without such sites never enters the second tier. */
 #define WGS_Z_CLASSES 253
 typedef struct wgs_depth wgs_depth;   /* allele-depth table of a matrix: one byte pair per (individual, site), next to the slabs */
 typedef struct wgs_zkeep wgs_zkeep;   /* the kept sites (L_keep) of a batch of individuals */
@@ -493,10 +497,17 @@ int wgs_zscore_max_depth(void);
 /* zscore.AD_summary, the dictionary (zscore.py:11-21), for individuals [i0, i0 + count) in ONE launch: per (individual, class)
  * the number of sites, the float32 sums of (g0, g1, 1 - g0 - g1) in site order (np.mean's numerator; the caller divides), the
  * first site of the class (-1: none; the dictionary's insertion order) and per individual the sites deeper than
- * wgs_zscore_max_depth(), which have no class (the caller refuses such data unless only depth 1 is asked for).
+ * wgs_zscore_max_depth(), which have no class here (the caller lists them with wgs_zscore_deep_sites, or refuses such data).
  * counts_out / first_out: [count][WGS_Z_CLASSES]; sums_out: [count][WGS_Z_CLASSES][3]; over_out: [count]. */
 int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_out, float *sums_out, int32_t *first_out,
                        int32_t *over_out);
+/* The sites deeper than wgs_zscore_max_depth() of individuals [i0, i0 + count), per individual in site order, the individuals one
+ * after the other: over[j] = the number wgs_zscore_classes reported for individual j (the sizes of the outputs; rc 2 if the
+ * table says otherwise).  site_out[e] = site index, depth_out[e][0..1] = (Ar, Aa), g_out[e][0..1] = (g0, g1) of the matrix.  One
+ * ballot word per (individual, tile) from the depth table, a scan, and a gather that reads the slabs only where a word is set. */
+#define WGS_Z_DEEP_MAX 510
+int wgs_zscore_deep_sites(wgs_depth *d, int32_t i0, int32_t count, const int32_t *over, int32_t *site_out, int32_t *depth_out,
+                          float *g_out);
 /* zscore.get_L_keep (zscore.py:43-61) for individuals [i0, i0 + count) in one launch.  key_comp[j][class] = -1: the class did
  * not survive the key filter; otherwise the component (0..2) at which its mean is largest, key_mean[j][class] that mean.  A site
  * is kept when its class survived and its own value at that component is within float32(0.01) of the mean.  kept_out[j] = sites
@@ -504,6 +515,14 @@ int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_
  * wgs_em_fit_masked; destroyed with its matrix or depth table. */
 int wgs_zkeep_create(wgs_depth *d, int32_t i0, int32_t count, const float *key_mean, const int32_t *key_comp, int64_t *kept_out,
                      wgs_zkeep **out);
+/* ... with a deep table: deep_map[j][d], d = 0 .. WGS_Z_DEEP_MAX, = the first of the d + 1 rows of depth d in deep_rows, or -1
+ * (depth not kept; always -1 for d <= wgs_zscore_max_depth()); deep_rows[r][0..7], row r = deep_map[j][d] + a for a = 0 .. d:
+ * [0] the component (0, 1 or 2) at which the mean of class (Ar = d - a, Aa = a) is largest, [1] that mean, [2..4] AD_like and
+ * [5..7] AD_factorial at AD_index[a, d - a] (transposed, as in wgs_zscore_stats' tables).  A site of a kept deep depth is then
+ * filtered like any other, and wgs_zscore_stats runs its loops over these rows, which stay in global memory.  deep_map = NULL:
+ * wgs_zkeep_create.  rc 2 for a map that points outside the n_deep_rows rows. */
+int wgs_zkeep_create_deep(wgs_depth *d, int32_t i0, int32_t count, const float *key_mean, const int32_t *key_comp,
+                          const int32_t *deep_map, const float *deep_rows, int64_t n_deep_rows, int64_t *kept_out, wgs_zkeep **out);
 void wgs_zkeep_destroy(wgs_zkeep *zk);
 /* L_keep of individual i0 + slot: the kept sites' indices, ascending (kept_out[slot] of them). */
 int wgs_zkeep_sites(wgs_zkeep *zk, int32_t slot, int32_t *sites_out);

@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """Times the two z-score options on device-resident data and prints ONE JSON line.
 
-    python tools/bench_zscore.py [--shapes 1000000x200x5,2000000x500x8] [--inds 200] [--step-timeout 600]
+    python tools/bench_zscore.py [--shapes 1000000x200x5,2000000x500x8] [--inds 200] [--step-timeout 600] [--deep-share 0.001]
 
 Per shape m x n x K: the matrix is generated on the device (wgs_beagle_synth, depth 1.5), the depth table on the host (Poisson 1.5
 split binomially; no file I/O anywhere in the timed part), then --get_assignment_z_score and --get_reference_z_score of the
 first --inds individuals with --single_read_threshold off.  Reported per flavour: wall seconds, and inside them the depth-class sweep,
 the mask sweep, the masked fits and the statistic sweep; for comparison the bytes each sweep has to read once (slabs + depth
 table).  Every shape runs in a child process of its own under a time limit, and a shape that fails ends the run: nothing further
-is started on the card."""
+is started on the card.
+
+--deep-share S (off by default; the output without it is unchanged) adds one leg, "deep": the first shape once more with the share S
+of the table's cells overwritten by deep sites -- depth uniform in 22..30, alternative count uniform in 0..depth, so that with a few
+hundred deep sites per individual some depths have all their classes and are kept (deep table on the device) and the others are
+dropped; the likelihoods stay independent of the depth, as in the other legs.  Its "deep_list_s" is the part of the class phase
+spent listing the deep sites and building their dictionary."""
 import argparse
 import json
 import os
@@ -20,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def one_shape(m, n, K, inds):
+def one_shape(m, n, K, inds, deep_share=0.0):
     import numpy as np
     from wgsassign_amd import zscore
     from wgsassign_amd.device import AFSet, DeviceBeagle, get_context
@@ -33,20 +39,29 @@ def one_shape(m, n, K, inds):
     b.synth(7, 1.5)
     depth = zscore.DepthTable(b)
     step = max(1, (64 << 20) // (8 * n))
+    deep_rng, n_deep = np.random.default_rng(2), 0
     for r in range(0, m, step):
         rows = min(step, m - r)
         D = rng.poisson(1.5, size=(rows, n))
         Aa = rng.binomial(D, 0.5)
         AD = np.empty((rows, 2 * n), dtype=np.int32)
         AD[:, 0::2], AD[:, 1::2] = D - Aa, Aa
+        if deep_share > 0:
+            at = np.nonzero(deep_rng.random((rows, n)) < deep_share)
+            dd = deep_rng.integers(22, 31, size=len(at[0]))
+            da = deep_rng.integers(0, dd + 1)
+            AD[at[0], 2 * at[1]], AD[at[0], 2 * at[1] + 1] = dd - da, da
+            n_deep += len(dd)
         depth.upload_rows(AD, r)
     afs = AFSet.from_host(rng.uniform(0.05, 0.95, size=(m, K)).astype(np.float32))
     inds = min(inds, n)
     out = dict(shape=[m, n, K], individuals=inds, device=ctx.info(), slab_bytes=b.nbytes(), depth_bytes=2 * m * n)
+    if deep_share > 0:
+        out.update(deep_share=deep_share, deep_sites_per_individual=round(n_deep / n, 1))
     quiet = lambda *_: None
     for name in ("assignment", "reference"):
         phases = {}
-        lib_classes, lib_keep, lib_stats = zscore.AD_summary, zscore.get_L_keep, zscore.KeepSet.stats
+        lib_classes, lib_keep, lib_stats, lib_deep = zscore.AD_summary, zscore.get_L_keep, zscore.KeepSet.stats, zscore.deep_classes
 
         def timed(key, fn):
             def run(*a, **kw):
@@ -58,6 +73,8 @@ def one_shape(m, n, K, inds):
             return run
         zscore.AD_summary, zscore.get_L_keep = timed("class_sweep_s", lib_classes), timed("mask_sweep_s", lib_keep)
         zscore.KeepSet.stats = timed("stat_sweep_and_download_s", lib_stats)
+        if deep_share > 0:
+            zscore.deep_classes = timed("deep_dictionary_s", lib_deep)
         t0 = time.perf_counter()
         if name == "assignment":
             zscore.assignment_z_scores(b, depth, IDs, pops, afs, 0, False, 0, inds, say=quiet)
@@ -65,7 +82,7 @@ def one_shape(m, n, K, inds):
             zscore.reference_z_scores(b, depth, IDs, group_of, 200, 1e-4, 0, False, 0, inds, say=quiet)
         ctx.sync()
         phases["wall_s"] = time.perf_counter() - t0
-        zscore.AD_summary, zscore.get_L_keep, zscore.KeepSet.stats = lib_classes, lib_keep, lib_stats
+        zscore.AD_summary, zscore.get_L_keep, zscore.KeepSet.stats, zscore.deep_classes = lib_classes, lib_keep, lib_stats, lib_deep
         out[name] = {k: round(v, 4) for k, v in phases.items()}
     print(json.dumps(out))
 
@@ -76,19 +93,26 @@ def main():
     ap.add_argument("--inds", type=int, default=10**9)
     ap.add_argument("--step-timeout", type=int, default=600)
     ap.add_argument("--child", default=None)
+    ap.add_argument("--deep-share", type=float, default=0.0, help="add a leg with this share of deep sites (e.g. 0.001) on the first shape")
+    ap.add_argument("--child-deep-share", type=float, default=0.0)
     a = ap.parse_args()
     if a.child:
         m, n, K = (int(x) for x in a.child.split("x"))
-        return one_shape(m, n, K, a.inds)
-    results = []
-    for shape in a.shapes.split(","):
+        return one_shape(m, n, K, a.inds, a.child_deep_share)
+    results, legs = [], [(shape, 0.0) for shape in a.shapes.split(",")]
+    if a.deep_share > 0:
+        legs.append((legs[0][0], a.deep_share))
+    for shape, share in legs:
         r = subprocess.run(["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child", shape,
-                            "--inds", str(a.inds)], capture_output=True, text=True)
+                            "--inds", str(a.inds), "--child-deep-share", str(share)], capture_output=True, text=True)
         if r.returncode != 0:
             print(json.dumps({"bench": "zscore", "failed": shape, "rc": r.returncode, "stderr": r.stderr[-400:], "results": results}))
             return 1
         results.append(json.loads(r.stdout.strip().splitlines()[-1]))
-    print(json.dumps({"bench": "zscore", "results": results}))
+    if a.deep_share > 0:
+        print(json.dumps({"bench": "zscore", "results": results[:-1], "deep": results[-1]}))
+    else:
+        print(json.dumps({"bench": "zscore", "results": results}))
     return 0
 
 

@@ -71,6 +71,8 @@ SIGNATURES = {
     "wgs_zscore_max_depth": (c_int, []),
     "wgs_zscore_classes": (c_int, [c_vp, c_i32, c_i32, c_i32p, c_f32p, c_i32p, c_i32p]),
     "wgs_zkeep_create": (c_int, [c_vp, c_i32, c_i32, c_f32p, c_i32p, ctypes.POINTER(c_i64), ctypes.POINTER(c_vp)]),
+    "wgs_zscore_deep_sites": (c_int, [c_vp, c_i32, c_i32, c_i32p, c_i32p, c_i32p, c_f32p]),
+    "wgs_zkeep_create_deep": (c_int, [c_vp, c_i32, c_i32, c_f32p, c_i32p, c_i32p, c_f32p, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_vp)]),
     "wgs_zkeep_destroy": (None, [c_vp]),
     "wgs_zkeep_sites": (c_int, [c_vp, c_i32, c_i32p]),
     "wgs_zscore_stats": (c_int, [c_vp, c_f32p, ctypes.POINTER(c_vp), c_f32p, c_f32p, c_f32p]),

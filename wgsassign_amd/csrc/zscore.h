@@ -5,6 +5,11 @@
 constexpr int WGS_Z_MAXD = 21;                                        // largest depth Ar + Aa with a class of its own
 constexpr int WGS_Z_NKEYS = (WGS_Z_MAXD + 1) * (WGS_Z_MAXD + 2) / 2;  // 253 classes: one per thread of a 256-thread workgroup
 
+// The deep tier: depth pairs with WGS_Z_MAXD < Ar + Aa <= 255 + 255 (what the table's bytes hold) have no class of the dense 253.  A
+// kept-site set may carry a deep table in global memory: per individual a map depth -> first row (-1: depth not kept), and per kept
+// depth d the rows a = 0 .. d of {component, mean of class (d - a, a) | AD_like[0..2], AD_factorial[0..2] at AD_index[a, d - a]}.
+constexpr int WGS_Z_DEEP_MAP = 511, WGS_Z_DEEP_ROW = 8;
+
 // kinds of the live-object registry (common.h: WGS_LIVE_EM = 1, WGS_LIVE_SCORE = 2): the depth table and the kept-site sets
 constexpr int WGS_LIVE_DEPTH = 3, WGS_LIVE_ZKEEP = 4;
 
@@ -36,16 +41,22 @@ struct wgs_zkeep {
     uint32_t *off = nullptr;              // [count][ntiles]
     int64_t *d_total = nullptr;
     std::vector<int64_t> total;
+    int32_t *d_deep_map = nullptr;        // [count][WGS_Z_DEEP_MAP], nullptr: no individual of the set kept a deep depth
+    float *d_deep_rows = nullptr;         // [rows][WGS_Z_DEEP_ROW]
 };
 
 int zs_fill_inds(wgs_beagle *b, int32_t i0, int32_t count, std::vector<ZInd> &out);
 int launch_zclass(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, int32_t *cnt, float *sums,
                   int32_t *first, int32_t *over);
 int launch_zmask(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, const float *kmean,
-                 const int32_t *kcomp, unsigned long long *mask, uint32_t *off, int64_t *total);
+                 const int32_t *kcomp, const int32_t *dmap, const float *drows, unsigned long long *mask, uint32_t *off, int64_t *total);
 int launch_zstat(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, const float *tabs,
-                 const float *const *fptr, const unsigned long long *mask, const uint32_t *off, const int64_t *obase, float *wobs,
-                 float *wl, float *var);
+                 const float *const *fptr, const int32_t *dmap, const float *drows, const unsigned long long *mask, const uint32_t *off,
+                 const int64_t *obase, float *wobs, float *wl, float *var);
+int launch_zdeep_flag(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, unsigned long long *words,
+                      uint32_t *off, int64_t *total);
+int launch_zdeep_gather(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad,
+                        const unsigned long long *words, const uint32_t *off, const int64_t *obase, int32_t *site, int32_t *ad, float *g);
 int launch_zcompact(wgs_ctx *ctx, const ZCompactJob *d_jobs, int n_jobs, int64_t m, const unsigned long long *mask, const uint32_t *off);
 int launch_zdepth_scatter(wgs_ctx *ctx, const int32_t *d_rows, int64_t nrows, int64_t n, int64_t row0, int64_t mpad, uchar2 *depth, int32_t *bad);
 int launch_zdepth_gather(wgs_ctx *ctx, const uchar2 *depth, int64_t nrows, int64_t n, int64_t row0, int64_t mpad, int32_t *d_rows);

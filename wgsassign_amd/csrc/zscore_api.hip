@@ -166,11 +166,61 @@ int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_
 
 int wgs_zscore_max_depth(void) { return WGS_Z_MAXD; }
 
+int wgs_zscore_deep_sites(wgs_depth *d, int32_t i0, int32_t count, const int32_t *over, int32_t *site_out, int32_t *depth_out, float *g_out)
+{
+    WGS_REQUIRE(d && over && site_out && depth_out && g_out, "null argument");
+    WGS_REQUIRE(d->b, "the depth table was created without a matrix (wgs_depth_create_shape)");
+    wgs_beagle *b = d->b;
+    wgs_ctx *ctx = b->ctx;
+    std::vector<ZInd> inds;
+    if (int rc = zs_fill_inds(b, i0, count, inds)) return rc;
+    std::vector<int64_t> obase(count);
+    int64_t all = 0;
+    for (int j = 0; j < count; ++j) {
+        WGS_REQUIRE(over[j] >= 0, "individual %d: a negative number of deep sites", i0 + j);
+        obase[j] = all;
+        all += over[j];
+    }
+    if (all == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ZBufs bufs;
+    ZInd *d_inds = nullptr;
+    unsigned long long *words = nullptr;
+    uint32_t *off = nullptr;
+    int64_t *d_total = nullptr, *d_obase = nullptr;
+    int32_t *d_site = nullptr, *d_ad = nullptr;
+    float *d_g = nullptr;
+    const size_t nt = (size_t)wgs_ntiles(b->m);
+    HIP_TRY(bufs.get(&d_inds, sizeof(ZInd) * count));
+    HIP_TRY(bufs.get(&words, sizeof(unsigned long long) * count * nt));
+    HIP_TRY(bufs.get(&off, sizeof(uint32_t) * count * nt));
+    HIP_TRY(bufs.get(&d_total, sizeof(int64_t) * count));
+    HIP_TRY(bufs.get(&d_obase, sizeof(int64_t) * count));
+    HIP_TRY(bufs.get(&d_site, sizeof(int32_t) * all));
+    HIP_TRY(bufs.get(&d_ad, sizeof(int32_t) * 2 * all));
+    HIP_TRY(bufs.get(&d_g, sizeof(float) * 2 * all));
+    HIP_TRY(hipMemcpyAsync(d_inds, inds.data(), sizeof(ZInd) * count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_obase, obase.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, ctx->stream));
+    if (launch_zdeep_flag(ctx, d_inds, count, d->table, b->m, d->mpad, words, off, d_total)) return 1;
+    std::vector<int64_t> total(count);
+    HIP_TRY(hipMemcpyAsync(total.data(), d_total, sizeof(int64_t) * count, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int j = 0; j < count; ++j)         // the gather writes total[j] entries behind obase[j]: the caller's sizes must be the table's
+        WGS_REQUIRE(total[j] == over[j], "individual %d has %lld sites deeper than %d reads, the caller expects %d", i0 + j,
+                    (long long)total[j], WGS_Z_MAXD, over[j]);
+    if (launch_zdeep_gather(ctx, d_inds, count, d->table, b->m, d->mpad, words, off, d_obase, d_site, d_ad, d_g)) return 1;
+    HIP_TRY(hipMemcpyAsync(site_out, d_site, sizeof(int32_t) * all, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(depth_out, d_ad, sizeof(int32_t) * 2 * all, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(g_out, d_g, sizeof(float) * 2 * all, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 void wgs_zkeep_destroy(wgs_zkeep *zk)
 {
     if (!zk || !wgs_live_remove(zk)) return;
     (void)hipSetDevice(zk->b->ctx->device);
-    for (void *p : {(void *)zk->d_inds, (void *)zk->mask, (void *)zk->off, (void *)zk->d_total})
+    for (void *p : {(void *)zk->d_inds, (void *)zk->mask, (void *)zk->off, (void *)zk->d_total, (void *)zk->d_deep_map, (void *)zk->d_deep_rows})
         if (p) (void)hipFree(p);
     delete zk;
 }
@@ -178,7 +228,24 @@ void wgs_zkeep_destroy(wgs_zkeep *zk)
 int wgs_zkeep_create(wgs_depth *d, int32_t i0, int32_t count, const float *key_mean, const int32_t *key_comp, int64_t *kept_out,
                      wgs_zkeep **out)
 {
+    return wgs_zkeep_create_deep(d, i0, count, key_mean, key_comp, nullptr, nullptr, 0, kept_out, out);
+}
+
+int wgs_zkeep_create_deep(wgs_depth *d, int32_t i0, int32_t count, const float *key_mean, const int32_t *key_comp, const int32_t *deep_map,
+                          const float *deep_rows, int64_t n_deep_rows, int64_t *kept_out, wgs_zkeep **out)
+{
     WGS_REQUIRE(d && key_mean && key_comp && kept_out && out, "null argument");
+    WGS_REQUIRE(!deep_map || (deep_rows && n_deep_rows > 0 && n_deep_rows < (int64_t)1 << 31), "a deep map needs its rows");
+    if (deep_map)                       // the kernels index the rows by what the map says: every kept depth has its d + 1 rows
+        for (int64_t e = 0; e < (int64_t)count * WGS_Z_DEEP_MAP; ++e) {
+            const int64_t r = deep_map[e], dl = e % WGS_Z_DEEP_MAP;
+            WGS_REQUIRE(r == -1 || (dl > WGS_Z_MAXD && r >= 0 && r + dl + 1 <= n_deep_rows), "deep map: depth %lld points outside the rows",
+                        (long long)dl);
+            for (int64_t a = 0; r >= 0 && a <= dl; ++a) {
+                const float c = deep_rows[(r + a) * WGS_Z_DEEP_ROW];
+                WGS_REQUIRE(c == 0.0f || c == 1.0f || c == 2.0f, "deep rows: the component must be 0, 1 or 2");
+            }
+        }
     WGS_REQUIRE(d->b, "the depth table was created without a matrix (wgs_depth_create_shape)");
     wgs_beagle *b = d->b;
     wgs_ctx *ctx = b->ctx;
@@ -214,7 +281,15 @@ int wgs_zkeep_create(wgs_depth *d, int32_t i0, int32_t count, const float *key_m
     HIP_TRY(hipMemcpyAsync(zk->d_inds, inds.data(), sizeof(ZInd) * count, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(kmean, h_mean.data(), sizeof(float) * 256 * count, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(kcomp, h_comp.data(), sizeof(int32_t) * 256 * count, hipMemcpyHostToDevice, ctx->stream));
-    if (launch_zmask(ctx, zk->d_inds, count, d->table, b->m, d->mpad, kmean, kcomp, zk->mask, zk->off, zk->d_total)) return 1;
+    if (deep_map) {
+        HIP_TRY(wgs_malloc(&zk->d_deep_map, sizeof(int32_t) * WGS_Z_DEEP_MAP * count));
+        HIP_TRY(wgs_malloc(&zk->d_deep_rows, sizeof(float) * WGS_Z_DEEP_ROW * n_deep_rows));
+        HIP_TRY(hipMemcpyAsync(zk->d_deep_map, deep_map, sizeof(int32_t) * WGS_Z_DEEP_MAP * count, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(zk->d_deep_rows, deep_rows, sizeof(float) * WGS_Z_DEEP_ROW * n_deep_rows, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (launch_zmask(ctx, zk->d_inds, count, d->table, b->m, d->mpad, kmean, kcomp, zk->d_deep_map, zk->d_deep_rows, zk->mask, zk->off,
+                     zk->d_total))
+        return 1;
     zk->total.resize(count);
     HIP_TRY(hipMemcpyAsync(zk->total.data(), zk->d_total, sizeof(int64_t) * count, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -270,8 +345,8 @@ int wgs_zscore_stats(wgs_zkeep *zk, const float *tables, const float *const *fre
     HIP_TRY(hipMemcpyAsync(d_tabs, tables, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_fptr, freq_dev, sizeof(float *) * count, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_obase, obase.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, ctx->stream));
-    if (launch_zstat(ctx, zk->d_inds, count, zk->d->table, b->m, zk->d->mpad, d_tabs, d_fptr, zk->mask, zk->off, d_obase, d_out, d_out + all,
-                     d_out + 2 * all))
+    if (launch_zstat(ctx, zk->d_inds, count, zk->d->table, b->m, zk->d->mpad, d_tabs, d_fptr, zk->d_deep_map, zk->d_deep_rows, zk->mask, zk->off, d_obase,
+                     d_out, d_out + all, d_out + 2 * all))
         return 1;
     HIP_TRY(hipMemcpyAsync(wobs_out, d_out, sizeof(float) * all, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(wl_out, d_out + all, sizeof(float) * all, hipMemcpyDeviceToHost, ctx->stream));

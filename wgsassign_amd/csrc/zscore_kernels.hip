@@ -43,7 +43,8 @@ __device__ __forceinline__ const double2 *zs_load_log_table(double2 *tab)
     return tab;
 }
 
-// Class of a depth pair: d (d + 1) / 2 + Aa for depth d = Ar + Aa <= WGS_Z_MAXD; ZK_OVER beyond, ZK_NONE for a lane past the last site.
+// Class of a depth pair: d (d + 1) / 2 + Aa for depth d = Ar + Aa <= WGS_Z_MAXD; ZK_OVER beyond (the deep tier: zscore.h), ZK_NONE for a
+// lane past the last site.
 constexpr int ZK_OVER = 254, ZK_NONE = 255;
 __device__ __forceinline__ int zs_key(uchar2 d, bool valid)
 {
@@ -117,9 +118,14 @@ __global__ __launch_bounds__(256) void zclass_kernel(const ZInd *__restrict__ in
 
 // zscore.py:get_L_keep -- the site's class survived the key filter (kcomp >= 0: the component where the class mean is largest) and
 // the site's own value there is within float32(0.01) of the mean.  One 64-bit word per (individual, tile).
+// DEEP: the individuals have a deep table (zscore.h) -- a site of depth > WGS_Z_MAXD whose depth d survived whole (dmap[d] >= 0) finds
+// the component and the mean of its class in row dmap[d] + Aa of that table, in global memory; without a table (the instantiation
+// that data without deep sites launches) such a site has no class and is dropped.
 constexpr int ZS_TILES_PER_BLOCK = 64;
+template <bool DEEP>
 __global__ __launch_bounds__(256) void zmask_kernel(const ZInd *__restrict__ inds, const uchar2 *__restrict__ depth, int64_t m, int64_t mpad,
                                                     const float *__restrict__ kmean, const int32_t *__restrict__ kcomp,
+                                                    const int32_t *__restrict__ dmap, const float *__restrict__ drows,
                                                     unsigned long long *__restrict__ mask)
 {
     __shared__ float mean_s[256];
@@ -140,6 +146,16 @@ __global__ __launch_bounds__(256) void zmask_kernel(const ZInd *__restrict__ ind
             const float g2 = (1.0f - s.g0) - s.g1;
             const float v = c == 0 ? s.g0 : c == 1 ? s.g1 : g2;
             keep = c >= 0 && !(fabsf(mean_s[k] - v) > 0.01f);
+        }
+        if (DEEP && k == ZK_OVER) {
+            const int r = dmap[(size_t)blockIdx.y * WGS_Z_DEEP_MAP + (int)s.d.x + (int)s.d.y];
+            if (r >= 0) {
+                const float *row = drows + ((size_t)r + s.d.y) * WGS_Z_DEEP_ROW;
+                const int c = (int)row[0];
+                const float g2 = (1.0f - s.g0) - s.g1;
+                const float v = c == 0 ? s.g0 : c == 1 ? s.g1 : g2;
+                keep = !(fabsf(row[1] - v) > 0.01f);
+            }
         }
         const unsigned long long w = __ballot(keep);
         if (lane == 0) mask[(size_t)blockIdx.y * ntiles + t] = w;
@@ -182,8 +198,35 @@ __global__ __launch_bounds__(256) void zscan_kernel(const unsigned long long *__
 // Aa = 0 .. Dl in float32, three terms per step, one rounding per product and per sum (built with -ffp-contract=off).
 // tab: per class row d (d + 1) / 2 + Aa the values the reference reads at AD_index[Aa, Dl - Aa] -- AD_like[0..2], AD_factorial[0..2].
 // The results go to the individual's compacted arrays in site order.
+// The two loops over Aa = 0 .. dl of a site; row a of the table at row + a * STRIDE: AD_like[0..2], AD_factorial[0..2].
+template <int STRIDE>
+__device__ __forceinline__ void zs_loops(const float *row, int dl, float P0, float P1, float P2, const double2 *lt, float &wl_out, float &var_out)
+{
+    float wl = 0.0f;
+    for (int a = 0; a <= dl; ++a) {
+        const float *r = row + a * STRIDE;
+        const float lg = zs_logf((r[0] * P0 + r[1] * P1) + r[2] * P2, lt);
+        wl = wl + (lg * P0) * r[3];
+        wl = wl + (lg * P1) * r[4];
+        wl = wl + (lg * P2) * r[5];
+    }
+    float var = 0.0f;
+    for (int a = 0; a <= dl; ++a) {
+        const float *r = row + a * STRIDE;
+        const float lg = zs_logf((r[0] * P0 + r[1] * P1) + r[2] * P2, lt);
+        const float d = wl - lg;
+        var = var + ((d * d) * P0) * r[3];
+        var = var + ((d * d) * P1) * r[4];
+        var = var + ((d * d) * P2) * r[5];
+    }
+    wl_out = wl;
+    var_out = var;
+}
+
+template <bool DEEP>
 __global__ __launch_bounds__(256) void zstat_kernel(const ZInd *__restrict__ inds, const uchar2 *__restrict__ depth, int64_t m, int64_t mpad,
                                                     const float *__restrict__ tabs, const float *const *__restrict__ fptr,
+                                                    const int32_t *__restrict__ dmap, const float *__restrict__ drows,
                                                     const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ off,
                                                     const int64_t *__restrict__ obase, float *__restrict__ wobs_out,
                                                     float *__restrict__ wl_out, float *__restrict__ var_out)
@@ -210,29 +253,55 @@ __global__ __launch_bounds__(256) void zstat_kernel(const ZInd *__restrict__ ind
         const float f0 = s.g0 * P0, f1 = s.g1 * P1;
         const float f2 = (float)(((1.0 - (double)s.g0) - (double)s.g1) * (double)P2);
         const float wobs = zs_logf((f0 + f1) + f2, lt);
-        const int dl = (int)s.d.x + (int)s.d.y;              // <= WGS_Z_MAXD: the site's class was kept
-        const float *row = tab_s + dl * (dl + 1) / 2 * 6;
-        float wl = 0.0f;
-        for (int a = 0; a <= dl; ++a) {
-            const float *r = row + a * 6;
-            const float lg = zs_logf((r[0] * P0 + r[1] * P1) + r[2] * P2, lt);
-            wl = wl + (lg * P0) * r[3];
-            wl = wl + (lg * P1) * r[4];
-            wl = wl + (lg * P2) * r[5];
-        }
-        float var = 0.0f;
-        for (int a = 0; a <= dl; ++a) {
-            const float *r = row + a * 6;
-            const float lg = zs_logf((r[0] * P0 + r[1] * P1) + r[2] * P2, lt);
-            const float d = wl - lg;
-            var = var + ((d * d) * P0) * r[3];
-            var = var + ((d * d) * P1) * r[4];
-            var = var + ((d * d) * P2) * r[5];
-        }
+        const int dl = (int)s.d.x + (int)s.d.y;              // the site's class was kept: <= WGS_Z_MAXD, or a kept depth of the deep table
+        float wl, var;
+        if (DEEP && dl > WGS_Z_MAXD)                         // (the mask kept it: its depth has rows)
+            zs_loops<WGS_Z_DEEP_ROW>(drows + (size_t)dmap[(size_t)blockIdx.y * WGS_Z_DEEP_MAP + dl] * WGS_Z_DEEP_ROW + 2, dl, P0, P1, P2, lt, wl, var);
+        else
+            zs_loops<6>(tab_s + dl * (dl + 1) / 2 * 6, dl, P0, P1, P2, lt, wl, var);
         const size_t pos = (size_t)ob + off[(size_t)blockIdx.y * ntiles + t] + (unsigned int)__popcll(w & ((1ull << lane) - 1ull));
         wobs_out[pos] = wobs;
         wl_out[pos] = wl;
         var_out[pos] = var;
+    }
+}
+
+// The deep-site list (sites of depth > WGS_Z_MAXD, which zclass_kernel only counts): one 64-bit word per (individual, tile) from the
+// depth table alone, zscan_kernel for the offsets, then the sites of the non-empty tiles in site order -- index, (Ar, Aa), (g0, g1).
+__global__ __launch_bounds__(256) void zdeepflag_kernel(const ZInd *__restrict__ inds, const uchar2 *__restrict__ depth, int64_t m, int64_t mpad,
+                                                        unsigned long long *__restrict__ words)
+{
+    const int32_t ind = inds[blockIdx.y].ind;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t ntiles = (m + 63) >> 6;
+    const int64_t t0 = (int64_t)blockIdx.x * ZS_TILES_PER_BLOCK;
+    for (int64_t t = t0 + wave; t < t0 + ZS_TILES_PER_BLOCK && t < ntiles; t += 4) {
+        const uchar2 d = depth[(size_t)ind * mpad + (size_t)t * 64 + lane];
+        const unsigned long long w = __ballot(zs_key(d, t * 64 + lane < m) == ZK_OVER);
+        if (lane == 0) words[(size_t)blockIdx.y * ntiles + t] = w;
+    }
+}
+
+__global__ __launch_bounds__(256) void zdeepgather_kernel(const ZInd *__restrict__ inds, const uchar2 *__restrict__ depth, int64_t m, int64_t mpad,
+                                                          const unsigned long long *__restrict__ words, const uint32_t *__restrict__ off,
+                                                          const int64_t *__restrict__ obase, int32_t *__restrict__ site_out,
+                                                          int32_t *__restrict__ ad_out, float *__restrict__ g_out)
+{
+    const ZInd I = inds[blockIdx.y];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t ntiles = (m + 63) >> 6;
+    const int64_t t0 = (int64_t)blockIdx.x * ZS_TILES_PER_BLOCK;
+    const int64_t ob = obase[blockIdx.y];
+    for (int64_t t = t0 + wave; t < t0 + ZS_TILES_PER_BLOCK && t < ntiles; t += 4) {
+        const unsigned long long w = words[(size_t)blockIdx.y * ntiles + t];
+        if (!((w >> lane) & 1ull)) continue;
+        const ZSite s = zs_load(I, depth, mpad, t, lane);
+        const size_t pos = (size_t)ob + off[(size_t)blockIdx.y * ntiles + t] + (unsigned int)__popcll(w & ((1ull << lane) - 1ull));
+        site_out[pos] = (int32_t)(t * 64 + lane);
+        ad_out[2 * pos] = s.d.x;
+        ad_out[2 * pos + 1] = s.d.y;
+        g_out[2 * pos] = s.g0;
+        g_out[2 * pos + 1] = s.g1;
     }
 }
 
@@ -316,21 +385,48 @@ int launch_zclass(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *dep
 }
 
 int launch_zmask(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, const float *kmean,
-                 const int32_t *kcomp, unsigned long long *mask, uint32_t *off, int64_t *total)
+                 const int32_t *kcomp, const int32_t *dmap, const float *drows, unsigned long long *mask, uint32_t *off, int64_t *total)
 {
-    hipLaunchKernelGGL(zmask_kernel, dim3(zs_blocks(m), count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, kmean, kcomp, mask);
+    if (dmap)
+        hipLaunchKernelGGL(zmask_kernel<true>, dim3(zs_blocks(m), count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, kmean, kcomp, dmap,
+                           drows, mask);
+    else
+        hipLaunchKernelGGL(zmask_kernel<false>, dim3(zs_blocks(m), count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, kmean, kcomp, dmap,
+                           drows, mask);
     hipLaunchKernelGGL(zscan_kernel, dim3(count), dim3(256), 0, ctx->stream, mask, wgs_ntiles(m), off, total);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 int launch_zstat(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, const float *tabs,
-                 const float *const *fptr, const unsigned long long *mask, const uint32_t *off, const int64_t *obase, float *wobs,
-                 float *wl, float *var)
+                 const float *const *fptr, const int32_t *dmap, const float *drows, const unsigned long long *mask, const uint32_t *off,
+                 const int64_t *obase, float *wobs, float *wl, float *var)
 {
     if (zs_ensure_log_table(ctx)) return 1;
-    hipLaunchKernelGGL(zstat_kernel, dim3(zs_blocks(m), count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, tabs, fptr, mask, off,
-                       obase, wobs, wl, var);
+    if (dmap)
+        hipLaunchKernelGGL(zstat_kernel<true>, dim3(zs_blocks(m), count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, tabs, fptr, dmap,
+                           drows, mask, off, obase, wobs, wl, var);
+    else
+        hipLaunchKernelGGL(zstat_kernel<false>, dim3(zs_blocks(m), count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, tabs, fptr, dmap,
+                           drows, mask, off, obase, wobs, wl, var);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_zdeep_flag(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, unsigned long long *words,
+                      uint32_t *off, int64_t *total)
+{
+    hipLaunchKernelGGL(zdeepflag_kernel, dim3(zs_blocks(m), count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, words);
+    hipLaunchKernelGGL(zscan_kernel, dim3(count), dim3(256), 0, ctx->stream, words, wgs_ntiles(m), off, total);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_zdeep_gather(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad,
+                        const unsigned long long *words, const uint32_t *off, const int64_t *obase, int32_t *site, int32_t *ad, float *g)
+{
+    hipLaunchKernelGGL(zdeepgather_kernel, dim3(zs_blocks(m), count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, words, off, obase,
+                       site, ad, g);
     HIP_TRY(hipGetLastError());
     return 0;
 }

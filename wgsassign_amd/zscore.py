@@ -6,6 +6,13 @@ sweep (AD_summary's dictionary), the site mask (get_L_keep), the per-site statis
 for the reference flavour, the leave-one-out EM fits whose convergence test runs over the kept sites.  What is a few dozen numbers
 per individual stays here in NumPy: the key filter, the tables, and the three float32 sums, which np.sum forms in its own pairwise
 order from the compacted per-site arrays.  There is no CPU fallback.
+
+Depth pairs come in two tiers.  Ar + Aa <= 21: the 253 classes of the class sweep, one per thread.  Deeper pairs, up to the 255
+reads per allele the device table holds, are rare (collapsed repeats): the device lists those sites (wgs_zscore_deep_sites), their
+dictionary entries are formed here, and both tiers merge into one dictionary in order of first appearance.  A deep depth survives
+the key filter only with all its d + 1 classes; then its rows travel to the device in a table of their own (deep_tables) and the
+mask and statistic sweeps read them there.  Data without deep sites launches nothing of this.  The host part is a loop over the
+deep classes of an individual: fine for a few per thousand sites, slow where deep sites are the majority.
 """
 import ctypes
 import math
@@ -17,7 +24,10 @@ import numpy as np
 from . import _lib
 from ._lib import check, f32p, i32p
 
-N_CLASSES = 253      # = WGS_Z_CLASSES: depth pairs (Ar, Aa) with Ar + Aa <= 21, class index d (d + 1) / 2 + Aa
+N_CLASSES = 253      # = WGS_Z_CLASSES: depth pairs (Ar, Aa) with Ar + Aa <= 21, class index d (d + 1) / 2 + Aa -- the dense tier
+MAX_DENSE = 21       # = wgs_zscore_max_depth()
+DEEP_MAX = 510       # = WGS_Z_DEEP_MAX: 255 reads per allele, what the device table's bytes hold -- the sparse second tier
+DEEP_ROW = 8         # floats per row of a deep table (wgs_zkeep_create_deep)
 E = 0.01
 
 
@@ -191,15 +201,22 @@ class DepthTable:
 class KeepSet:
     """L_keep of individuals [i0, i0 + count) on the device (wgs_zkeep); .kept[j] = sites kept."""
 
-    def __init__(self, depth, i0, key_mean, key_comp):
+    def __init__(self, depth, i0, key_mean, key_comp, deep_map=None, deep_rows=None):
         count = key_mean.shape[0]
         self.depth, self.i0, self.count = depth, int(i0), count
         key_mean = np.ascontiguousarray(key_mean, dtype=np.float32)
         key_comp = np.ascontiguousarray(key_comp, dtype=np.int32)
         self.kept = np.zeros(count, dtype=np.int64)
+        kept_p = self.kept.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
         h = ctypes.c_void_p()
-        check(_lib.load().wgs_zkeep_create(depth.handle, self.i0, count, f32p(key_mean), i32p(key_comp),
-                                           self.kept.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(h)))
+        if deep_map is None:
+            check(_lib.load().wgs_zkeep_create(depth.handle, self.i0, count, f32p(key_mean), i32p(key_comp), kept_p, ctypes.byref(h)))
+        else:                                             # (deep_tables: some individual kept a depth beyond the dense classes)
+            deep_map = np.ascontiguousarray(deep_map, dtype=np.int32)
+            deep_rows = np.ascontiguousarray(deep_rows, dtype=np.float32)
+            assert deep_map.shape == (count, DEEP_MAX + 1) and deep_rows.ndim == 2 and deep_rows.shape[1] == DEEP_ROW
+            check(_lib.load().wgs_zkeep_create_deep(depth.handle, self.i0, count, f32p(key_mean), i32p(key_comp), i32p(deep_map),
+                                                    f32p(deep_rows), deep_rows.shape[0], kept_p, ctypes.byref(h)))
         self._h = h
         depth.b._children.add(self)
 
@@ -236,55 +253,126 @@ class KeepSet:
 
 
 # ---------------------------------------------------------------- the reference's functions, a batch of individuals at a time
-def AD_summary(depth, i0, count, n_threshold, single_read_threshold):
+def deep_classes(site, ad, g):
+    """The dictionary entries of one individual's deep sites (site order): keys (nk, 2), counts, first sites, float32 sums (nk, 3)
+    of (g0, g1, (1 - g0) - g1) -- the literal serial chain in site order, as the class sweep forms it for the dense tier."""
+    code = ad[:, 0].astype(np.int64) * 256 + ad[:, 1]
+    uniq, start, counts = np.unique(code, return_index=True, return_counts=True)
+    order = np.argsort(code, kind="stable")                  # class by class, site order inside a class
+    T = np.stack((g[:, 0], g[:, 1], (np.float32(1) - g[:, 0]) - g[:, 1]), axis=1)[order]
+    sums = np.empty((len(uniq), 3), dtype=np.float32)
+    for j, (lo, c) in enumerate(zip(np.cumsum(counts) - counts, counts)):
+        sums[j] = np.cumsum(T[lo:lo + c], axis=0, dtype=np.float32)[-1]            # one float32 addition per site
+    return np.column_stack((uniq // 256, uniq % 256)).astype(np.int64), counts.astype(np.int64), site[start], sums
+
+
+def merge_tiers(dense, deep):
+    """(keys, counts, first, sums) of the two tiers -> the reference's dictionary: keys, counts, means in order of first
+    appearance (every site has one class, so the first sites are distinct)."""
+    keys, counts, first, sums = (np.concatenate((a, b)) for a, b in zip(dense, deep))
+    order = np.argsort(first, kind="stable")
+    keys, counts, sums = keys[order], counts[order], sums[order]
+    means = (sums.astype(np.float64) / counts[:, None]).astype(np.float32)     # np.mean: float32 sums, true_divide by the count
+    return keys, counts, means
+
+
+def AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep=False):
     """zscore.AD_summary (zscore.py:11-40) for individuals [i0, i0 + count): list of dict(keys, counts, means, AD_array) -- the
-    dictionary in order of first appearance and the filtered classes.  One launch (wgs_zscore_classes)."""
+    dictionary in order of first appearance and the filtered classes.  One launch (wgs_zscore_classes); with deep=True one more
+    group of launches (wgs_zscore_deep_sites) if an individual of the batch has sites deeper than 21 reads, whose classes then
+    enter the dictionary like any other.  deep=False: such data is refused, except under single_read_threshold."""
+    lib = _lib.load()
     cnt = np.empty((count, N_CLASSES), dtype=np.int32)
     first = np.empty((count, N_CLASSES), dtype=np.int32)
     sums = np.empty((count, N_CLASSES, 3), dtype=np.float32)
     over = np.empty(count, dtype=np.int32)
-    check(_lib.load().wgs_zscore_classes(depth.handle, int(i0), int(count), i32p(cnt), f32p(sums), i32p(first), i32p(over)))
-    maxd = _lib.load().wgs_zscore_max_depth()
+    check(lib.wgs_zscore_classes(depth.handle, int(i0), int(count), i32p(cnt), f32p(sums), i32p(first), i32p(over)))
+    maxd = lib.wgs_zscore_max_depth()
     d_of = np.repeat(np.arange(maxd + 1), np.arange(maxd + 1) + 1)
     a_of = np.arange(N_CLASSES) - d_of * (d_of + 1) // 2
+    if deep and over.any():
+        total = int(over.sum())
+        site, ad, g = np.empty(total, dtype=np.int32), np.empty((total, 2), dtype=np.int32), np.empty((total, 2), dtype=np.float32)
+        check(lib.wgs_zscore_deep_sites(depth.handle, int(i0), int(count), i32p(over), i32p(site), i32p(ad), f32p(g)))
+        cuts = np.cumsum(over)[:-1]
+        listed = list(zip(np.split(site, cuts), np.split(ad, cuts), np.split(g, cuts)))
     out = []
     for j in range(count):
-        if over[j] and not single_read_threshold:
+        if over[j] and not deep and not single_read_threshold:
             raise ValueError("individual %d has %d sites deeper than %d reads: the depth classes of this build end there "
                              "(--single_read_threshold needs depth 1 only and accepts such data)" % (i0 + j, int(over[j]), maxd))
         seen = np.flatnonzero(cnt[j] > 0)
-        seen = seen[np.argsort(first[j, seen], kind="stable")]
-        keys = np.column_stack((d_of[seen] - a_of[seen], a_of[seen])).astype(np.int64)
-        counts = cnt[j, seen].astype(np.int64)
-        means = (sums[j, seen].astype(np.float64) / counts[:, None]).astype(np.float32)     # np.mean: float32 sums, true_divide by the count
+        dense = (np.column_stack((d_of[seen] - a_of[seen], a_of[seen])).astype(np.int64), cnt[j, seen].astype(np.int64), first[j, seen],
+                 sums[j, seen])
+        if deep and over[j]:
+            keys, counts, means = merge_tiers(dense, deep_classes(*listed[j]))
+        else:
+            keys, counts, means = merge_tiers(dense, (np.empty((0, 2), dtype=np.int64), np.empty(0, dtype=np.int64),
+                                                     np.empty(0, dtype=np.int32), np.empty((0, 3), dtype=np.float32)))
         out.append(dict(keys=keys, counts=counts, means=means, AD_array=key_filter(keys, counts, n_threshold, single_read_threshold)))
     return out
 
 
-def get_L_keep(depth, i0, summaries):
-    """zscore.get_L_keep (zscore.py:43-61) for the batch: a KeepSet (the sites stay on the device)."""
+def deep_tables(summaries):
+    """The deep table of a batch (wgs_zkeep_create_deep): map int32 (count, 511) from depth to the first of its rows, rows float32
+    (rows, 8) -- per kept depth d > 21 and a = 0 .. d: component and mean of class (d - a, a), then AD_like and AD_factorial at
+    AD_index[a, d - a].  (None, None) when no individual kept a deep depth."""
+    dmap = np.full((len(summaries), DEEP_MAX + 1), -1, dtype=np.int32)
+    rows = []
+    for j, s in enumerate(summaries):
+        depths = np.unique(s["AD_array"][:, 2])
+        depths = depths[depths > MAX_DENSE]
+        if not len(depths):
+            continue
+        fac, like, index = get_factorials(s["AD_array"], s["keys"], s["means"], E)
+        where = {(int(a), int(b)): r for r, (a, b) in enumerate(s["keys"])}
+        for d in (int(x) for x in depths):
+            dmap[j, d] = len(rows)
+            for a in range(d + 1):
+                mean = s["means"][where[(d - a, a)]]
+                c = int(np.argwhere(mean == np.max(mean))[0][0])
+                r = index[a, d - a]
+                rows.append(np.concatenate(([np.float32(c), mean[c]], like[r], fac[r])).astype(np.float32))
+    if not rows:
+        return None, None
+    return dmap, np.ascontiguousarray(np.stack(rows), dtype=np.float32)
+
+
+def mask_tables(summaries):
+    """Per individual and dense class what the mask sweep reads: the component at which the class mean is largest (-1: the class
+    did not survive the key filter) and that mean."""
     count = len(summaries)
     key_mean = np.zeros((count, N_CLASSES), dtype=np.float32)
     key_comp = np.full((count, N_CLASSES), -1, dtype=np.int32)
     for j, s in enumerate(summaries):
         where = {(int(a), int(b)): r for r, (a, b) in enumerate(s["keys"])}
         for Ar, Aa in s["AD_array"][:, :2]:
+            if int(Ar) + int(Aa) > MAX_DENSE:
+                continue                                  # (a kept deep depth: deep_tables)
             mean = s["means"][where[(int(Ar), int(Aa))]]
             c = int(np.argwhere(mean == np.max(mean))[0][0])
             key_comp[j, class_index(int(Ar), int(Aa))] = c
             key_mean[j, class_index(int(Ar), int(Aa))] = mean[c]
-    return KeepSet(depth, i0, key_mean, key_comp)
+    return key_mean, key_comp
+
+
+def get_L_keep(depth, i0, summaries):
+    """zscore.get_L_keep (zscore.py:43-61) for the batch: a KeepSet (the sites stay on the device)."""
+    return KeepSet(depth, i0, *mask_tables(summaries), *deep_tables(summaries))
 
 
 def stat_tables(summaries):
     """Per individual the rows the kernel reads: [class d (d + 1) / 2 + a] = AD_like[r], AD_factorial[r] with r = AD_index[a, d - a]
-    (zscore_cy.pyx:28 reads the index transposed; only depths whose classes all survived are ever looked up)."""
+    (zscore_cy.pyx:28 reads the index transposed; only depths whose classes all survived are ever looked up).  The rows of kept
+    depths beyond 21 are in the KeepSet's deep table."""
     tabs = np.zeros((len(summaries), N_CLASSES, 6), dtype=np.float32)
     parts = []
     for j, s in enumerate(summaries):
         fac, like, index = get_factorials(s["AD_array"], s["keys"], s["means"], E)
         parts.append((fac, like, index))
         for d in np.unique(s["AD_array"][:, 2]):
+            if d > MAX_DENSE:
+                continue
             for a in range(int(d) + 1):
                 r = index[a, int(d) - a]
                 tabs[j, class_index(int(d) - a, a)] = np.concatenate((like[r], fac[r]))
@@ -312,14 +400,14 @@ def _batches(lo, hi, batch):
 
 
 def assignment_z_scores(beagle, depth, IDs, pops, afset, n_threshold=0, single_read_threshold=False, ind_start=0, ind_end=None,
-                        batch=64, say=print, details=None):
+                        batch=64, say=print, details=None, deep=True):
     """--get_assignment_z_score (WGSassign.py:395-446): z of individuals [ind_start, ind_end) against column k of `afset`, k = the
     position of the individual's population in `pops`.  float32 (n_sub, 1).  details (a list) receives per individual the
-    intermediate arrays (tests)."""
+    intermediate arrays (tests).  deep: as for AD_summary -- sites deeper than 21 reads are computed with, as the reference does."""
     ind_end = beagle.n if ind_end is None else ind_end
     z_out = np.empty((ind_end - ind_start, 1), dtype=np.float32)
     for i0, count in _batches(ind_start, ind_end, batch):
-        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold)
+        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep)
         keep = get_L_keep(depth, i0, summ)
         tabs, parts = stat_tables(summ)
         cols = [int(np.argwhere(pops == IDs[i0 + j, 1])[0][0]) for j in range(count)]
@@ -335,7 +423,7 @@ def assignment_z_scores(beagle, depth, IDs, pops, afset, n_threshold=0, single_r
 
 
 def reference_z_scores(beagle, depth, IDs, group_of, maf_iter=200, maf_tole=1e-4, n_threshold=0, single_read_threshold=False,
-                       ind_start=0, ind_end=None, batch=64, say=print, details=None):
+                       ind_start=0, ind_end=None, batch=64, say=print, details=None, deep=True):
     """--get_reference_z_score (WGSassign.py:311-393): per individual the leave-one-out EM fit of its population on ITS kept sites
     (wgs_em_fit_masked: the existing sweeps, the convergence chain over the kept sites), the clamp, then as above.  `beagle` must
     hold one slab per population (group_of as --get_reference_af builds it)."""
@@ -344,7 +432,7 @@ def reference_z_scores(beagle, depth, IDs, group_of, maf_iter=200, maf_tole=1e-4
     sizes = np.bincount(group_of, minlength=int(np.max(group_of)) + 1)
     z_out = np.empty((ind_end - ind_start, 1), dtype=np.float32)
     for i0, count in _batches(ind_start, ind_end, batch):
-        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold)
+        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep)
         keep = get_L_keep(depth, i0, summ)
         tabs, parts = stat_tables(summ)
         ids = np.arange(i0, i0 + count)
