@@ -48,7 +48,8 @@ const char *wgs_last_error(void);
  * collectives (wgs_coll_tag, wgs_comm_check, wgs_comm_next_generation, wgs_comm_allreduce_host_tagged).  The z-score entry points
  * (wgs_depth_*, wgs_zscore_*, wgs_zkeep_*, wgs_em_fit_masked) were ADDED under 3: no existing signature changed; so were the
  * integer-table reader (wgs_reader_open_table), the depth ingest (wgs_depth_ingest_*), wgs_depth_create_shape and
- * wgs_depth_download_rows, and the deep tier of the z-scores (wgs_zscore_deep_sites, wgs_zkeep_create_deep). */
+ * wgs_depth_download_rows, the deep tier of the z-scores (wgs_zscore_deep_sites, wgs_zkeep_create_deep), and the z-scores over SNP
+ * shards (wgs_zscore_classes_sharded, wgs_em_fit_masked_sharded, wgs_depth_ingest_set_first_row, WGS_OP_Z_CLASS, WGS_OP_Z_CHAIN). */
 #define WGS_ABI_VERSION 3
 int wgs_version(void);
 /* sha256[:16] over every source of the library / over the sources of the EM and scoring kernels (em_kernels.hip,
@@ -323,7 +324,7 @@ typedef struct wgs_coll_tag {
     int32_t aux;                /* not compared */
 } wgs_coll_tag;
 enum { WGS_OP_GENERIC = 0, WGS_OP_EM_SUMS = 1, WGS_OP_EM_CHAIN = 2, WGS_OP_EM_FIT_END = 3, WGS_OP_SCORE_TOTALS = 4,
-       WGS_OP_PART_CHAINS = 5, WGS_OP_LOO_BATCH = 6, WGS_OP_TIMING = 7, WGS_OP_HOST = 8 };
+       WGS_OP_PART_CHAINS = 5, WGS_OP_LOO_BATCH = 6, WGS_OP_TIMING = 7, WGS_OP_HOST = 8, WGS_OP_Z_CLASS = 9, WGS_OP_Z_CHAIN = 10 };
 int32_t wgs_comm_next_generation(wgs_comm *c);
 int wgs_comm_check(wgs_comm *c);
 /* Sum all-reduce of n host float64 with a caller-given tag; rows_out (NULL or world * 8 float64) receives every rank's row
@@ -482,6 +483,11 @@ int wgs_depth_create_shape(wgs_ctx *ctx, int64_t m, int64_t n, wgs_depth **out);
  * wgs_depth_ingest_next: the next chunk's data lines fill rows row0, row0 + 1, ...; *file_rows = data lines consumed (0: end),
  * *rows_written = rows filled.  Lines beyond the table's last row are counted, not stored (*rows_written = 0 from there on): the
  * caller compares the total with the rows it expected.
+ * wgs_depth_ingest_set_first_row (before the first wgs_depth_ingest_next, or rc 2): the table holds the file's data rows
+ * [first_row, first_row + m) -- a SNP shard's -- instead of the first m.  Data lines before the range are read and checked like any
+ * other (a token np.loadtxt refuses, or a short line, is still reported with its line of the file; in pairs mode a count outside
+ * 0..255 too), take no row and count in *file_rows; lines behind the range are counted and dropped, as lines beyond the table always
+ * were, but no longer stop the rows of the same chunk from being stored.  majmin then holds the selectors of the range's m rows.
  * wgs_depth_ingest_stats, stats[0..7]: largest single host buffer held, in bytes | device ms (copies + kernels) | lines parsed
  * on the host | text bytes | data lines | chunks | BGZF members inflated on the device | ms of the tokeniser kernel alone
  * (0 unless WGSASSIGN_INGEST_TIME_KERNEL is set: timing it costs a synchronisation per chunk). */
@@ -491,6 +497,7 @@ typedef struct wgs_depth_ingest wgs_depth_ingest;
 int wgs_depth_ingest_create(wgs_depth *d, wgs_reader *r, int mode, const uint8_t *majmin, int64_t limit_rows, int64_t chunk_bytes,
                             wgs_depth_ingest **out);
 void wgs_depth_ingest_destroy(wgs_depth_ingest *g);
+int wgs_depth_ingest_set_first_row(wgs_depth_ingest *g, int64_t first_row);
 int wgs_depth_ingest_next(wgs_depth_ingest *g, int64_t row0, int64_t *file_rows, int64_t *rows_written);
 int wgs_depth_ingest_stats(wgs_depth_ingest *g, double *stats);
 int wgs_zscore_max_depth(void);
@@ -501,6 +508,19 @@ int wgs_zscore_max_depth(void);
  * counts_out / first_out: [count][WGS_Z_CLASSES]; sums_out: [count][WGS_Z_CLASSES][3]; over_out: [count]. */
 int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_out, float *sums_out, int32_t *first_out,
                        int32_t *over_out);
+/* The same dictionary when the sites are cut into SNP shards, one per rank of `comm` (collective: every rank calls it with the same
+ * i0 and count; comm = NULL: one shard).  The three float32 sums are serial chains in site order and do not associate, so the sweep
+ * goes from shard to shard: for r = 0 .. world - 1 rank r walks its shard -- from 0 when r = 0, else from the running sums hop r - 1
+ * left on the device (a class without a site in the shard hands them on untouched) -- and broadcasts count x 256 x 3 float32 on the
+ * context's stream (op WGS_OP_Z_CLASS, iteration = the hop, shape_a = i0; the broadcast's own row carries the root and the payload
+ * size, i.e. count).  One host all-reduce (same op, iteration = world, shapes i0 / count) then adds the counts and gathers first
+ * sites and `over`.  On every rank: counts_out = sites of ALL shards, sums_out = the sums after the last shard, first_out = the
+ * smallest GLOBAL site number (site0 + local) of a class, -1: none; over_out[r][j] = rank r's sites deeper than
+ * wgs_zscore_max_depth() of individual i0 + j ([world][count]; each rank lists its own with wgs_zscore_deep_sites).  The sweep is
+ * serial across ranks: rank r waits for hop r - 1; a (batch, hop) step depends on nothing but that, so batches could be skewed over
+ * the ranks -- not done here.  A rank out of step fails with "collective mismatch". */
+int wgs_zscore_classes_sharded(wgs_depth *d, int32_t i0, int32_t count, wgs_comm *comm, int32_t *counts_out, float *sums_out,
+                               int64_t *first_out, int32_t *over_out);
 /* The sites deeper than wgs_zscore_max_depth() of individuals [i0, i0 + count), per individual in site order, the individuals one
  * after the other: over[j] = the number wgs_zscore_classes reported for individual j (the sizes of the outputs; rc 2 if the
  * table says otherwise).  site_out[e] = site index, depth_out[e][0..1] = (Ar, Aa), g_out[e][0..1] = (g0, g1) of the matrix.  One
@@ -537,6 +557,14 @@ int wgs_zscore_stats(wgs_zkeep *zk, const float *tables, const float *const *fre
  * float32 chain) runs over the kept sites of individual i0 + fit_slot[j] of `zk` only and divides by their number.
  * iters_out[j] = iteration at which fit j converged, 0 if max_iter was exhausted.  One SNP shard. */
 int wgs_em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_t max_iter, double tole, int32_t *iters_out);
+/* ... across SNP shards (collective; comm = NULL: one shard).  `em` and `zk` are this rank's shard; the sweeps are local and no sum is
+ * all-reduced, since every iteration is decided by the exact chain: it crosses the shards in rank order on the stream as wgs_em_fit's
+ * chains do (rank r sets its carries from hop r - 1's and broadcasts nj float32: op WGS_OP_Z_CHAIN, iteration = the EM iteration,
+ * shape_a = fits still active), and the divisor is kept_total[slot], the individual's kept sites over ALL ranks ([zk's count]).  Every
+ * rank takes the same decision from the same broadcast value.  An individual that kept no site in this shard hands its carry on;
+ * rc 2 only when kept_total[slot] is 0. */
+int wgs_em_fit_masked_sharded(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_t max_iter, double tole,
+                              const int64_t *kept_total, wgs_comm *comm, int32_t *iters_out);
 
 /* Blocks of 4096 elements that fell back to the serial loop in the last wgs_em_rmse_chain of an EM batch (diagnostics). */
 int wgs_em_last_chain_serial_blocks(wgs_em *em);

@@ -227,19 +227,23 @@ def _run(args, comm):
         say("Saved population assignment log likelihoods as " + str(args.out) + ".pop_like.txt (text)")
     for flavour in ("reference", "assignment"):
         if getattr(args, "get_%s_z_score" % flavour):
-            _z_scores(args, flavour, beagle, group_of, m, n, say, root)
+            _z_scores(args, flavour, beagle, group_of, m, n, say, root, comm)
     if scored is not None:
         scored.close()
     beagle.close()
     comm.barrier()
 
 
-def _z_scores(args, flavour, beagle, group_of, m, n, say, root):
-    """WGSassign.py:311-393 (reference) / 395-446 (assignment): same files read, same checks and texts, same output."""
+def _z_scores(args, flavour, beagle, group_of, m, n, say, root, comm):
+    """WGSassign.py:311-393 (reference) / 395-446 (assignment): same files read, same checks and texts, same output.  Several
+    ranks: each takes the rows of its SNP shard from the frequency, depth and selector files (m: the sites of all shards); rank 0
+    receives the z-scores and writes the file."""
     import numpy as np
 
     from . import zscore
+    from .comm import shard_range
     from .device import AFSet
+    lo, hi = shard_range(m, comm.rank, comm.world)
     say("Parsing population ID file.")
     assert os.path.isfile(args.pop_af_IDs), "Population ID file does not exist!!"
     IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
@@ -247,11 +251,15 @@ def _z_scores(args, flavour, beagle, group_of, m, n, say, root):
     if flavour == "assignment":
         say("Parsing population allele frequency file.")
         assert os.path.isfile(args.pop_af_file), "Population allele frequency file does not exist!!"
-        A = np.ascontiguousarray(np.load(args.pop_af_file), dtype=np.float32)
+        A = np.load(args.pop_af_file, mmap_mode="r")
     say("Parsing individual allele depths file.")
     majmin = None
     if args.ind_counts_file:
         majmin = zscore.read_majmin(args.ind_majmin_file)       # (checked once before the Beagle file was opened: depth_options)
+        if comm.world > 1:
+            if majmin.shape[0] != m:
+                raise ValueError("%s has the selectors of %d sites, the Beagle file %d" % (args.ind_majmin_file, majmin.shape[0], m))
+            majmin = np.ascontiguousarray(majmin[lo:hi])
     else:
         assert os.path.isfile(args.ind_ad_file), "Individual allele depths file does not exist!"
     assert os.path.isfile(args.pop_names), "Population names file does not exist!!"
@@ -264,18 +272,23 @@ def _z_scores(args, flavour, beagle, group_of, m, n, say, root):
         allele_count_threshold = 0
     ind_start, ind_end = zscore.ind_range(n, args.ind_start, args.ind_end)
     # streamed and tokenised on the device: no m x 2n array on the host (csrc/ingest.hip: depth_tokenise_kernel)
-    depth = zscore.DepthTable.from_file(beagle, args.ind_counts_file or args.ind_ad_file, counts=majmin is not None, majmin=majmin)
+    if comm.world > 1:
+        depth = zscore.DepthTable.from_file(beagle, args.ind_counts_file or args.ind_ad_file, counts=majmin is not None, majmin=majmin,
+                                            first_row=lo, m_total=m)
+    else:
+        depth = zscore.DepthTable.from_file(beagle, args.ind_counts_file or args.ind_ad_file, counts=majmin is not None, majmin=majmin)
+    shards = comm if comm.world > 1 else None
     if flavour == "assignment":
         if A.shape[0] != m:
             raise ValueError("the allele frequency file has %d sites, the Beagle file %d" % (A.shape[0], m))
-        afs = AFSet.from_host(A, ctx=beagle.ctx)
+        afs = AFSet.from_host(np.ascontiguousarray(A[lo:hi], dtype=np.float32), ctx=beagle.ctx)
         z_out = zscore.assignment_z_scores(beagle, depth, IDs, np.atleast_1d(pops), afs, allele_count_threshold,
-                                           args.single_read_threshold, ind_start, ind_end, say=say)
+                                           args.single_read_threshold, ind_start, ind_end, say=say, comm=shards)
         afs.close()
         name = ".z_ind.txt"
     else:
         z_out = zscore.reference_z_scores(beagle, depth, IDs, group_of, args.maf_iter, args.maf_tole, allele_count_threshold,
-                                          args.single_read_threshold, ind_start, ind_end, say=say)
+                                          args.single_read_threshold, ind_start, ind_end, say=say, comm=shards)
         name = ".reference_z_ind.txt"
     depth.close()
     if root:
@@ -326,13 +339,12 @@ def main(argv=None):
         if getattr(args, unsupported):
             raise SystemExit("--%s is outside the scope of the MI355X build (EM allele frequencies, Fisher "
                              "information, leave-one-out and assignment likelihoods only)" % unsupported)
-    if (args.get_assignment_z_score or args.get_reference_z_score) and comm.world > 1:
-        # the depth-class sums and np.sum's pairwise order are defined over ALL sites of an individual: not sharded by SNP yet
-        raise SystemExit("--get_assignment_z_score / --get_reference_z_score run on one GPU: start them without --gpus "
-                         "(the z-score path does not shard the SNPs)")
-
     if args.get_assignment_z_score or args.get_reference_z_score:
         depth_options(args)
+        if comm.world > 1 and getattr(comm, "handle", None) is None:
+            # the class sums and the masked chain cross the SNP shards inside the library: before any file is opened
+            raise SystemExit("--get_assignment_z_score / --get_reference_z_score over several ranks need the library's own communicator "
+                             "(WGSASSIGN_COMM=rccl or socket); %s has none" % type(comm).__name__)
 
     if root:        # log-file of non-default arguments (WGSassign.py:127-141)
         full, deaf = vars(args), vars(parser.parse_args([]))

@@ -62,6 +62,7 @@ SIGNATURES = {
     "wgs_depth_create_shape": (c_int, [c_vp, c_i64, c_i64, ctypes.POINTER(c_vp)]),
     "wgs_depth_ingest_create": (c_int, [c_vp, c_vp, c_int, c_vp, c_i64, c_i64, ctypes.POINTER(c_vp)]),
     "wgs_depth_ingest_destroy": (None, [c_vp]),
+    "wgs_depth_ingest_set_first_row": (c_int, [c_vp, c_i64]),
     "wgs_depth_ingest_next": (c_int, [c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "wgs_depth_ingest_stats": (c_int, [c_vp, c_f64p]),
     "wgs_reader_open_table": (c_int, [ctypes.c_char_p, c_int, c_int, ctypes.POINTER(c_vp)]),
@@ -70,6 +71,7 @@ SIGNATURES = {
     "wgs_debug_table_parse_line": (c_int, [ctypes.c_char_p, c_i64, c_i32, c_i32p]),
     "wgs_zscore_max_depth": (c_int, []),
     "wgs_zscore_classes": (c_int, [c_vp, c_i32, c_i32, c_i32p, c_f32p, c_i32p, c_i32p]),
+    "wgs_zscore_classes_sharded": (c_int, [c_vp, c_i32, c_i32, c_vp, c_i32p, c_f32p, ctypes.POINTER(c_i64), c_i32p]),
     "wgs_zkeep_create": (c_int, [c_vp, c_i32, c_i32, c_f32p, c_i32p, ctypes.POINTER(c_i64), ctypes.POINTER(c_vp)]),
     "wgs_zscore_deep_sites": (c_int, [c_vp, c_i32, c_i32, c_i32p, c_i32p, c_i32p, c_f32p]),
     "wgs_zkeep_create_deep": (c_int, [c_vp, c_i32, c_i32, c_f32p, c_i32p, c_i32p, c_f32p, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_vp)]),
@@ -77,6 +79,7 @@ SIGNATURES = {
     "wgs_zkeep_sites": (c_int, [c_vp, c_i32, c_i32p]),
     "wgs_zscore_stats": (c_int, [c_vp, c_f32p, ctypes.POINTER(c_vp), c_f32p, c_f32p, c_f32p]),
     "wgs_em_fit_masked": (c_int, [c_vp, c_vp, c_i32p, c_i32, ctypes.c_double, c_i32p]),
+    "wgs_em_fit_masked_sharded": (c_int, [c_vp, c_vp, c_i32p, c_i32, ctypes.c_double, ctypes.POINTER(c_i64), c_vp, c_i32p]),
     "wgs_em_create": (c_int, [c_vp, c_i32, c_i32p, c_i32p, c_int, ctypes.POINTER(c_vp)]),
     "wgs_em_destroy": (None, [c_vp]),
     "wgs_em_step": (c_int, [c_vp, c_f64p]),

@@ -45,7 +45,7 @@ class CollectiveMismatch(RuntimeError):
 # one issued at device.py line 458 is op 8 (WGS_OP_HOST), shape a = 100000 * (index of "device.py") + 458.
 TAG_WORDS = 8
 OP_HOST = 8
-_SITE_FILES = ["device.py", "glassy.py", "fisher.py", "reader_cy.py", "WGSassign.py", "comm.py", "emMAF.py", "bench.py", "utils.py"]
+_SITE_FILES = ["device.py", "glassy.py", "fisher.py", "reader_cy.py", "WGSassign.py", "comm.py", "emMAF.py", "bench.py", "utils.py", "zscore.py"]
 
 
 def _call_site(depth=1):

@@ -224,8 +224,10 @@ __global__ __launch_bounds__(256) void tokenise_kernel(TokArgs a)
 // where the strip ended is kept in LDS and taken up again (that step's 1 KiB is read twice, nothing else).
 // The kernel converts runs of 1-3 digits with value <= 255; any other token among those it owns, or too few of them, flags the
 // line, whose pairs are not stored (in the strip where the flag is raised and the strips after it; the host parses a flagged line
-// and either uploads its whole row or refuses the file).
+// and either uploads its whole row or refuses the file).  dst = -1: the line has no row and is not looked at; dst = DEPTH_CHECK_ONLY:
+// no row either, but its tokens are read and a bad one flags it (a data line before the row range of a SNP shard).
 constexpr int DEPTH_STRIP = 256, DEPTH_ROW = 132;
+constexpr int32_t DEPTH_CHECK_ONLY = -2;
 
 struct DepthTokArgs {
     const uint4 *text;
@@ -252,7 +254,7 @@ __global__ __launch_bounds__(256) void depth_tokenise_kernel(DepthTokArgs a)
         const int l = line0 + (int)threadIdx.x;
         const int32_t rel = l < a.nlines ? a.dst[l] : -1;
         s_rel[threadIdx.x] = rel;
-        s_wb[threadIdx.x] = rel >= 0 ? a.begin[l] >> 4 : 0u;
+        s_wb[threadIdx.x] = rel != -1 ? a.begin[l] >> 4 : 0u;
         s_tok[threadIdx.x] = 0;
         s_prev[threadIdx.x] = 0;
         s_bad[threadIdx.x] = 0;
@@ -266,7 +268,7 @@ __global__ __launch_bounds__(256) void depth_tokenise_kernel(DepthTokArgs a)
         const uint32_t tok_lo = (uint32_t)strip0 * tpi, tok_hi = (uint32_t)(strip0 + strip_n) * tpi;
         for (int q = 0; q < 16; ++q) {
             const int li = wave * 16 + q;
-            if (s_rel[li] < 0 || s_bad[li]) continue;          // (the same for the whole wavefront)
+            if (s_rel[li] == -1 || s_bad[li]) continue;        // (the same for the whole wavefront)
             const uint32_t b = a.begin[line0 + li], e = a.end[line0 + li];
             const uint32_t w1 = (e + 15u) >> 4;
             uint32_t wb = s_wb[li], tok = s_tok[li], prev_nd = s_prev[li];
@@ -351,7 +353,7 @@ __global__ __launch_bounds__(256) void depth_tokenise_kernel(DepthTokArgs a)
         }
         __syncthreads();
     }
-    if (threadIdx.x < 64 && s_rel[threadIdx.x] >= 0 && s_bad[threadIdx.x]) {
+    if (threadIdx.x < 64 && s_rel[threadIdx.x] != -1 && s_bad[threadIdx.x]) {
         a.flags[line0 + (int)threadIdx.x] = 1;
         if (a.nflagged) atomicAdd(a.nflagged, 1u);
     }
@@ -635,6 +637,8 @@ struct wgs_ingest {
         int64_t lines_before = 0;       // device-resident: lines of the text in the chunks before this one
         size_t host_peak = 0;           // largest host buffer this object allocated itself
         bool overflow = false;          // the file has more data lines than the table rows
+        bool ranged = false;            // wgs_depth_ingest_set_first_row: the table holds the file's rows [first_row, first_row + m_rows)
+        int64_t before = 0;             // ... data lines still to come before that range: checked, no row
         double tok_ms = 0.0;            // the tokeniser kernel alone (WGSASSIGN_INGEST_TIME_KERNEL=1)
         hipEvent_t kev0 = nullptr, kev1 = nullptr;
     } dp;
@@ -707,6 +711,22 @@ int clock_stop(wgs_ingest *g)
 int place_rows(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t keep_len, size_t n, std::vector<int32_t> *map, int64_t *written)
 {
     if (keep) WGS_REQUIRE((int64_t)n <= keep_len, "site mask shorter than the file (%lld lines left in it, %lld in the chunk)", (long long)keep_len, (long long)n);
+    if (g->dp.ranged) {
+        // a row range of the file: lines before it are checked and take no row, the next m_rows - row0 fill the table, the rest
+        // is counted only -- the caller compares the total with the whole file's rows
+        WGS_REQUIRE(map && row0 >= 0 && row0 <= g->m_rows, "row %lld outside the device table (%lld rows)", (long long)row0, (long long)g->m_rows);
+        map->resize(n);
+        *written = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if (g->dp.before > 0) {
+                (*map)[i] = DEPTH_CHECK_ONLY;
+                --g->dp.before;
+            } else {
+                (*map)[i] = row0 + *written < g->m_rows ? (int32_t)(*written)++ : -1;
+            }
+        }
+        return 0;
+    }
     *written = (int64_t)n;
     if (map) {
         map->resize(n);
@@ -784,7 +804,8 @@ int parse_flagged_table(wgs_ingest *g, int64_t row0, size_t nl, TextOf text_of, 
     std::vector<int32_t> &irows = g->dp.irows;
     irows.resize((size_t)2 * d->n);
     for (size_t t = 0; t < nl; ++t) {
-        if (!g->flags[t] || g->dst[t] < 0) continue;
+        if (!g->flags[t] || g->dst[t] == -1) continue;
+        const bool check_only = g->dst[t] == DEPTH_CHECK_ONLY;      // before the row range: the same refusals, no row
         const char *lb = nullptr, *le = nullptr;
         if (int rc = text_of(t, &lb, &le)) return rc;
         const long long line = (long long)(reader_table_skip_lines(g->r) + (int64_t)line_of(t, true) + 1);
@@ -798,6 +819,7 @@ int parse_flagged_table(wgs_ingest *g, int64_t row0, size_t nl, TextOf text_of, 
             wgs_set_error("line %lld, column %d: not an integer np.loadtxt reads as int32", line, bad_col);
             return 2;
         }
+        if (check_only && tpi != 2) continue;      // (counts: which two of a line's tokens matter is the row's owner's to say)
         const int64_t row = row0 + g->dst[t];
         if (tpi == 2) {
             memcpy(irows.data(), toks.data(), sizeof(int32_t) * (size_t)need);
@@ -814,8 +836,9 @@ int parse_flagged_table(wgs_ingest *g, int64_t row0, size_t nl, TextOf text_of, 
                 wgs_set_error("line %lld: allele depths outside 0..255 do not fit the device table", line);
                 return 2;
             }
-        if (int rc = wgs_depth_upload_rows(d, irows.data(), row, 1)) return rc;
         g->host_lines += 1;
+        if (check_only) continue;
+        if (int rc = wgs_depth_upload_rows(d, irows.data(), row, 1)) return rc;
     }
     return 0;
 }
@@ -1011,8 +1034,9 @@ int place_chunk_rows(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t k
         g->done = true;
     }
     if (k.last) g->done = true;
-    if (int rc = place_rows(g, row0, keep, keep_len, k.take, keep ? &g->dstmap : nullptr, &k.written)) return rc;
-    if (keep && k.take) HIP_TRY(hipMemcpyAsync(g->d_dstmap.p, g->dstmap.data(), k.take * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const bool mapped = keep || g->dp.ranged;
+    if (int rc = place_rows(g, row0, keep, keep_len, k.take, mapped ? &g->dstmap : nullptr, &k.written)) return rc;
+    if (mapped && k.take) HIP_TRY(hipMemcpyAsync(g->d_dstmap.p, g->dstmap.data(), k.take * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (int rc = g->d_names.reserve(st, k.name_bytes + 16, k.name_bytes + k.name_bytes / 2 + 4096)) return rc;
     DstArgs da;
     da.nlines = (uint32_t)k.nl;
@@ -1022,7 +1046,7 @@ int place_chunk_rows(wgs_ingest *g, int64_t row0, const uint8_t *keep, int64_t k
     da.name_start = g->d_name_start.p;
     da.name_len1 = g->d_name_len1.p;
     da.name_off = g->d_name_off.p;
-    da.dstmap = keep ? g->d_dstmap.p : nullptr;
+    da.dstmap = mapped ? g->d_dstmap.p : nullptr;
     da.text = g->d_text.p;
     da.dst = g->d_dst.p;
     da.names = g->d_names.p;
@@ -1370,6 +1394,20 @@ int wgs_depth_ingest_create(wgs_depth *d, wgs_reader *r, int mode, const uint8_t
 }
 
 void wgs_depth_ingest_destroy(wgs_depth_ingest *g) { wgs_ingest_destroy(reinterpret_cast<wgs_ingest *>(g)); }
+
+int wgs_depth_ingest_set_first_row(wgs_depth_ingest *gi, int64_t first_row)
+{
+    wgs_ingest *g = reinterpret_cast<wgs_ingest *>(gi);
+    WGS_REQUIRE(g && g->depth, "null argument");
+    WGS_REQUIRE(first_row >= 0, "first_row must not be negative");
+    if (g->chunks || g->lines || g->dp.ranged) {
+        wgs_set_error("the row range of a depth ingest is set once, before its first chunk");
+        return 2;
+    }
+    g->dp.ranged = true;
+    g->dp.before = first_row;
+    return 0;
+}
 
 int wgs_depth_ingest_next(wgs_depth_ingest *gi, int64_t row0, int64_t *file_rows, int64_t *rows_written)
 {

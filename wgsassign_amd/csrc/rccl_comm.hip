@@ -113,6 +113,8 @@ static const char *op_name(int op)
     case WGS_OP_LOO_BATCH: return "leave-one-out batch size";
     case WGS_OP_TIMING: return "collective timing";
     case WGS_OP_HOST: return "host all-reduce";
+    case WGS_OP_Z_CLASS: return "z-score depth-class sums";
+    case WGS_OP_Z_CHAIN: return "z-score masked-chain carry";
     default: return "collective";
     }
 }

@@ -46,8 +46,9 @@ struct wgs_zkeep {
 };
 
 int zs_fill_inds(wgs_beagle *b, int32_t i0, int32_t count, std::vector<ZInd> &out);
+// carry: the chains go on from what `sums` holds (a later SNP shard) instead of starting at 0
 int launch_zclass(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, int32_t *cnt, float *sums,
-                  int32_t *first, int32_t *over);
+                  int32_t *first, int32_t *over, bool carry = false);
 int launch_zmask(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, const float *kmean,
                  const int32_t *kcomp, const int32_t *dmap, const float *drows, unsigned long long *mask, uint32_t *off, int64_t *total);
 int launch_zstat(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, const float *tabs,

@@ -128,15 +128,32 @@ int wgs_depth_download_rows(wgs_depth *d, int32_t *AD_rows, int64_t row0, int64_
     return 0;
 }
 
-int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_out, float *sums_out, int32_t *first_out, int32_t *over_out)
+// One (batch, rank) step of the sharded class sweep: hop r of the batch.  Rank r walks its shard -- from 0 on the first hop, else from
+// the running sums the hop before left in `sums` -- and its sums are broadcast into every rank's `sums`.  Nothing here waits for the
+// host; a caller may issue the hops of different batches in any order that keeps a batch's own hops in rank order.
+static int zclass_hop(wgs_ctx *ctx, wgs_comm *comm, int r, int rank, int world, int32_t generation, const ZInd *d_inds, int32_t i0, int count,
+                      const wgs_depth *d, int32_t *cnt, float *sums, int32_t *first, int32_t *over)
+{
+    if (r == rank && launch_zclass(ctx, d_inds, count, d->table, d->b->m, d->mpad, cnt, sums, first, over, r > 0)) return 1;
+    if (world == 1) return 0;
+    // (the broadcast's own row says who sends -- shape_b -- and how many bytes: count x 256 x 3 float32)
+    const wgs_coll_tag tag = {WGS_OP_Z_CLASS, generation, r, i0, 0, 0};       // (shape_b: wgs_comm_bcast_tagged writes the root there)
+    return wgs_comm_bcast_tagged(comm, sums, (int64_t)sizeof(float) * 3 * 256 * count, r, &tag);
+}
+
+int wgs_zscore_classes_sharded(wgs_depth *d, int32_t i0, int32_t count, wgs_comm *comm, int32_t *counts_out, float *sums_out,
+                               int64_t *first_out, int32_t *over_out)
 {
     WGS_REQUIRE(d && counts_out && sums_out && first_out && over_out, "null argument");
     WGS_REQUIRE(d->b, "the depth table was created without a matrix (wgs_depth_create_shape)");
     wgs_beagle *b = d->b;
     wgs_ctx *ctx = b->ctx;
+    int world = 1, rank = 0;
+    if (comm) wgs_comm_rank(comm, &rank, &world);
     std::vector<ZInd> inds;
     if (int rc = zs_fill_inds(b, i0, count, inds)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
+    const int32_t generation = comm ? wgs_comm_next_generation(comm) : 0;
     ZBufs bufs;
     ZInd *d_inds = nullptr;
     int32_t *cnt = nullptr, *first = nullptr, *over = nullptr;
@@ -145,22 +162,61 @@ int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_
     HIP_TRY(bufs.get(&d_inds, sizeof(ZInd) * count));
     HIP_TRY(bufs.get(&cnt, sizeof(int32_t) * cells));
     HIP_TRY(bufs.get(&first, sizeof(int32_t) * cells));
-    HIP_TRY(bufs.get(&sums, sizeof(float) * 3 * cells));
+    HIP_TRY(bufs.get(&sums, ((sizeof(float) * 3 * cells + 7) & ~(size_t)7) + wgs_comm_tail_bytes()));     // (+ the root's tag row)
     HIP_TRY(bufs.get(&over, sizeof(int32_t) * count));
     HIP_TRY(hipMemcpyAsync(d_inds, inds.data(), sizeof(ZInd) * count, hipMemcpyHostToDevice, ctx->stream));
-    if (launch_zclass(ctx, d_inds, count, d->table, b->m, d->mpad, cnt, sums, first, over)) return 1;
-    std::vector<int32_t> h_cnt(cells), h_first(cells);
+    for (int r = 0; r < world; ++r)
+        if (zclass_hop(ctx, comm, r, rank, world, generation, d_inds, i0, count, d, cnt, sums, first, over)) return 1;
+    std::vector<int32_t> h_cnt(cells), h_first(cells), h_over(count);
     std::vector<float> h_sums(3 * cells);
     HIP_TRY(hipMemcpyAsync(h_cnt.data(), cnt, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(h_first.data(), first, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(h_sums.data(), sums, sizeof(float) * 3 * cells, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(over_out, over, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_over.data(), over, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int j = 0; j < count; ++j) {          // (the kernel's rows have 256 entries, the caller's WGS_Z_NKEYS)
-        memcpy(counts_out + (size_t)j * WGS_Z_NKEYS, h_cnt.data() + (size_t)j * 256, sizeof(int32_t) * WGS_Z_NKEYS);
-        memcpy(first_out + (size_t)j * WGS_Z_NKEYS, h_first.data() + (size_t)j * 256, sizeof(int32_t) * WGS_Z_NKEYS);
-        memcpy(sums_out + (size_t)j * WGS_Z_NKEYS * 3, h_sums.data() + (size_t)j * 256 * 3, sizeof(float) * 3 * WGS_Z_NKEYS);
+    if (wgs_comm_check(comm)) return 1;               // (a receiver's view of the senders' rows)
+    // counts add; a first site is the smallest global number among the shards that have the class; `over` stays per rank.  One sum
+    // all-reduce gathers all three: every rank fills its own row of [world][first + 1 | over] (0: none) behind the counts.
+    const size_t nk = (size_t)count * WGS_Z_NKEYS, row = nk + count;
+    std::vector<double> wire(nk + (size_t)world * row, 0.0);
+    for (int j = 0; j < count; ++j) {
+        for (int k = 0; k < WGS_Z_NKEYS; ++k) {
+            const size_t e = (size_t)j * WGS_Z_NKEYS + k, o = (size_t)j * 256 + k;
+            wire[e] = (double)h_cnt[o];
+            wire[nk + (size_t)rank * row + e] = h_first[o] < 0 ? 0.0 : (double)(b->site0 + h_first[o] + 1);
+        }
+        wire[nk + (size_t)rank * row + nk + j] = (double)h_over[j];
     }
+    if (world > 1) {
+        const wgs_coll_tag tag = {WGS_OP_Z_CLASS, generation, world, i0, count, 0};
+        if (wgs_comm_allreduce_host_tagged(comm, wire.data(), (int64_t)wire.size(), &tag, nullptr)) return 1;
+    }
+    for (int j = 0; j < count; ++j) {
+        for (int k = 0; k < WGS_Z_NKEYS; ++k) {
+            const size_t e = (size_t)j * WGS_Z_NKEYS + k;
+            counts_out[e] = (int32_t)wire[e];
+            int64_t f = -1;
+            for (int r = 0; r < world; ++r) {
+                const int64_t g = (int64_t)wire[nk + (size_t)r * row + e] - 1;
+                if (g >= 0 && (f < 0 || g < f)) f = g;
+            }
+            first_out[e] = f;
+        }
+        memcpy(sums_out + (size_t)j * WGS_Z_NKEYS * 3, h_sums.data() + (size_t)j * 256 * 3, sizeof(float) * 3 * WGS_Z_NKEYS);
+        for (int r = 0; r < world; ++r) over_out[(size_t)r * count + j] = (int32_t)wire[nk + (size_t)r * row + nk + j];
+    }
+    return 0;
+}
+
+// One shard: the same body without a communicator -- one launch of zclass_kernel<false>, no collective; first sites stay local numbers.
+int wgs_zscore_classes(wgs_depth *d, int32_t i0, int32_t count, int32_t *counts_out, float *sums_out, int32_t *first_out, int32_t *over_out)
+{
+    WGS_REQUIRE(d && counts_out && sums_out && first_out && over_out, "null argument");
+    WGS_REQUIRE(d->b, "the depth table was created without a matrix (wgs_depth_create_shape)");
+    WGS_REQUIRE(count > 0, "individuals [%d, %d) outside 0..%lld", i0, i0 + count, (long long)d->b->n);
+    std::vector<int64_t> first((size_t)count * WGS_Z_NKEYS);
+    if (int rc = wgs_zscore_classes_sharded(d, i0, count, nullptr, counts_out, sums_out, first.data(), over_out)) return rc;
+    for (size_t e = 0; e < first.size(); ++e) first_out[e] = first[e] < 0 ? -1 : (int32_t)(first[e] - d->b->site0);
     return 0;
 }
 
@@ -355,18 +411,25 @@ int wgs_zscore_stats(wgs_zkeep *zk, const float *tables, const float *const *fre
     return 0;
 }
 
-int wgs_em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_t max_iter, double tole, int32_t *iters_out)
+// The masked fit of one shard (kept_total = NULL, comm = NULL: the divisor is the set's own kept count, no hop) and of many.
+static int em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_t max_iter, double tole, const int64_t *kept_total,
+                         wgs_comm *comm, int32_t *iters_out)
 {
     WGS_REQUIRE(em && zk && fit_slot && iters_out, "null argument");
+    if (!kept_total) kept_total = zk->total.data();
     WGS_REQUIRE(em->b == zk->b, "the EM batch and the kept-site set belong to different matrices");
     wgs_beagle *b = em->b;
     wgs_ctx *ctx = b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
+    int world = 1, rank = 0;
+    if (comm) wgs_comm_rank(comm, &rank, &world);
+    const int32_t generation = comm ? wgs_comm_next_generation(comm) : 0;
     const int nf = em->n_fits;
-    int64_t stride = 1;
+    int64_t stride = 1;                      // (an individual may have kept nothing in THIS shard: its chain hands the carry on)
     for (int j = 0; j < nf; ++j) {
         WGS_REQUIRE(fit_slot[j] >= 0 && fit_slot[j] < zk->count, "fit %d: slot %d outside the kept-site set", j, fit_slot[j]);
-        WGS_REQUIRE(zk->total[fit_slot[j]] > 0, "fit %d: no site was kept", j);
+        WGS_REQUIRE(kept_total[fit_slot[j]] > 0, "fit %d: no site was kept", j);
+        WGS_REQUIRE(kept_total[fit_slot[j]] >= zk->total[fit_slot[j]], "fit %d: kept_total is smaller than this shard's kept count", j);
         if (zk->total[fit_slot[j]] > stride) stride = zk->total[fit_slot[j]];
         iters_out[j] = 0;
     }
@@ -380,7 +443,7 @@ int wgs_em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_
         wgs_set_error("hipMalloc of 2 x %zu bytes for the compacted frequencies failed", vec_bytes);
         return 1;
     }
-    HIP_TRY(bufs.get(&d_out, sizeof(float) * nf));
+    HIP_TRY(bufs.get(&d_out, ((sizeof(float) * nf + 7) & ~(size_t)7) + wgs_comm_tail_bytes()));           // (+ the root's tag row)
     HIP_TRY(bufs.get(&d_cj, sizeof(ZCompactJob) * nf));
     HIP_TRY(bufs.get(&d_jobs, sizeof(ChainJob) * nf));
     HIP_TRY(bufs.get(&work, rmse_chain_workspace_bytes(stride) * nf));
@@ -395,30 +458,51 @@ int wgs_em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_
         for (int j = 0; j < nf; ++j)
             if (em->active[j]) list.push_back(j);
         if (list.empty()) break;
-        if (wgs_em_step_dev(em, em->d_ssq)) return 1;               // emMAF_cy.emMAF_update of every active fit: the existing sweep
+        if (wgs_em_step_dev(em, em->d_ssq)) return 1;               // the existing sweep over this shard: no sum crosses the ranks
         const int nj = (int)list.size();
         for (int q = 0; q < nj; ++q) {
             const int j = list[q];
-            float *va = d_a + (size_t)j * stride, *vb = d_b + (size_t)j * stride;      // the fit's own vectors: zero behind ITS kept count
+            float *va = d_a + (size_t)j * stride, *vb = d_b + (size_t)j * stride;
             cj[q] = ZCompactJob{em_f(em, j, em->cur[j]), em_f(em, j, em->prev[j]), va, vb, fit_slot[j]};
             jobs[q] = ChainJob{va, vb, 0.0f};
         }
         HIP_TRY(hipMemcpyAsync(d_cj, cj.data(), sizeof(ZCompactJob) * nj, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(ChainJob) * nj, hipMemcpyHostToDevice, ctx->stream));
         if (launch_zcompact(ctx, d_cj, nj, b->m, zk->mask, zk->off)) return 1;
-        if (launch_rmse_chain_batch(ctx, d_jobs, nj, stride, d_out, work, nullptr)) return 1;
+        // the chain over the kept sites crosses the shards in rank order on the stream, as em_resolve_chains hands its carries on
+        for (int r = 0; r < world; ++r) {
+            if (r == rank) {
+                if (r > 0 && launch_chain_set_carry(ctx, d_jobs, d_out, nj)) return 1;
+                if (launch_rmse_chain_batch(ctx, d_jobs, nj, stride, d_out, work, nullptr)) return 1;
+            }
+            const wgs_coll_tag tag = {WGS_OP_Z_CHAIN, generation, it, nj, r, 0};
+            if (world > 1 && wgs_comm_bcast_tagged(comm, d_out, (int64_t)sizeof(float) * nj, r, &tag)) return 1;
+        }
         HIP_TRY(hipMemcpyAsync(carry.data(), d_out, sizeof(float) * nj, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (wgs_comm_check(comm)) return 1;               // (a receiver's view of the senders' rows)
         for (int q = 0; q < nj; ++q) {
             const int j = list[q];
-            const float res = carry[q] / (float)zk->total[fit_slot[j]];       // emMAF_cy.pyx:32 with n = the kept sites
-            if (sqrt((double)res) < tole) {                                   // emMAF_cy.pyx:33, emMAF.py:23
+            const float res = carry[q] / (float)kept_total[fit_slot[j]];      // emMAF_cy.pyx:32 with n = the kept sites of ALL shards
+            if (sqrt((double)res) < tole) {                                   // emMAF_cy.pyx:33, emMAF.py:23: the same value on every rank
                 iters_out[j] = it;
                 em->active[j] = 0;
             }
         }
     }
     return 0;
+}
+
+int wgs_em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_t max_iter, double tole, int32_t *iters_out)
+{
+    return em_fit_masked(em, zk, fit_slot, max_iter, tole, nullptr, nullptr, iters_out);
+}
+
+int wgs_em_fit_masked_sharded(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_t max_iter, double tole, const int64_t *kept_total,
+                              wgs_comm *comm, int32_t *iters_out)
+{
+    WGS_REQUIRE(kept_total, "null argument");
+    return em_fit_masked(em, zk, fit_slot, max_iter, tole, kept_total, comm, iters_out);
 }
 
 }   // extern "C"

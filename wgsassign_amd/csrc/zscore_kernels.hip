@@ -72,6 +72,10 @@ __device__ __forceinline__ ZSite zs_load(const ZInd &I, const uchar2 *__restrict
 // loaded lane <-> SNP (the next tile's loads are issued before this tile is walked), then the sites whose class this wavefront
 // owns are taken in order -- class and triple broadcast from the owning lane, the one thread of that class adds.  Every sum is
 // the literal serial chain, so its bits are the reference's by construction.
+// CARRY: the SNP shard is not the first one -- `sums` holds, per (individual, class), the three running values the shard before
+// ended with, and the chains go on from them (a class without a site in this shard hands them on as they are).  cnt, first and
+// over speak of this shard alone.  Without CARRY the chains start at 0: the kernel of one shard.
+template <bool CARRY>
 __global__ __launch_bounds__(256) void zclass_kernel(const ZInd *__restrict__ inds, const uchar2 *__restrict__ depth, int64_t m, int64_t mpad,
                                                      int32_t *__restrict__ cnt, float *__restrict__ sums, int32_t *__restrict__ first,
                                                      int32_t *__restrict__ over)
@@ -79,8 +83,14 @@ __global__ __launch_bounds__(256) void zclass_kernel(const ZInd *__restrict__ in
     const ZInd I = inds[blockIdx.x];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int64_t ntiles = (m + 63) >> 6;
+    const size_t o = (size_t)blockIdx.x * 256 + tid;
     int c = 0, f = -1, nover = 0;
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    if (CARRY) {
+        s0 = sums[o * 3 + 0];
+        s1 = sums[o * 3 + 1];
+        s2 = sums[o * 3 + 2];
+    }
     ZSite cur = zs_load(I, depth, mpad, 0, lane);
     for (int64_t t = 0; t < ntiles; ++t) {
         ZSite nxt = cur;
@@ -107,7 +117,6 @@ __global__ __launch_bounds__(256) void zclass_kernel(const ZInd *__restrict__ in
         }
         cur = nxt;
     }
-    const size_t o = (size_t)blockIdx.x * 256 + tid;
     cnt[o] = c;
     first[o] = f;
     sums[o * 3 + 0] = s0;
@@ -377,9 +386,12 @@ static int zs_ensure_log_table(wgs_ctx *ctx)
 static unsigned zs_blocks(int64_t m) { return (unsigned)((wgs_ntiles(m) + ZS_TILES_PER_BLOCK - 1) / ZS_TILES_PER_BLOCK); }
 
 int launch_zclass(wgs_ctx *ctx, const ZInd *d_inds, int count, const uchar2 *depth, int64_t m, int64_t mpad, int32_t *cnt, float *sums,
-                  int32_t *first, int32_t *over)
+                  int32_t *first, int32_t *over, bool carry)
 {
-    hipLaunchKernelGGL(zclass_kernel, dim3(count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, cnt, sums, first, over);
+    if (carry)
+        hipLaunchKernelGGL(zclass_kernel<true>, dim3(count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, cnt, sums, first, over);
+    else
+        hipLaunchKernelGGL(zclass_kernel<false>, dim3(count), dim3(256), 0, ctx->stream, d_inds, depth, m, mpad, cnt, sums, first, over);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -13,6 +13,13 @@ dictionary entries are formed here, and both tiers merge into one dictionary in 
 the key filter only with all its d + 1 classes; then its rows travel to the device in a table of their own (deep_tables) and the
 mask and statistic sweeps read them there.  Data without deep sites launches nothing of this.  The host part is a loop over the
 deep classes of an individual: fine for a few per thousand sites, slow where deep sites are the majority.
+
+Several GPUs (comm with world > 1): every rank holds a contiguous SNP shard -- matrix, depth table, frequencies -- and calls the
+drivers together.  What is defined over all sites of an individual crosses the ranks: the class sums as running values handed from
+shard to shard (wgs_zscore_classes_sharded), the deep sites as lists put together in rank order, the masked fit's convergence chain
+as a carry (wgs_em_fit_masked_sharded), and the per-site arrays themselves, which rank 0 receives and concatenates in rank order --
+site order -- so that np.sum forms its pairwise sums over the same arrays as one process would.  Rank 0 prints and returns the
+z-scores; the other ranks return None.
 """
 import ctypes
 import math
@@ -56,10 +63,12 @@ def read_majmin(path):
     return np.ascontiguousarray(sel, dtype=np.uint8)
 
 
-def stream_table(handle, m, path, counts=False, majmin=None, chunk_bytes=None, threads=None, row0=0, limit_rows=-1):
+def stream_table(handle, m, path, counts=False, majmin=None, chunk_bytes=None, threads=None, row0=0, limit_rows=-1, first_row=None,
+                 m_total=None):
     """The file `path` into the rows row0 .. of the wgs_depth `handle` on the device (wgs_depth_ingest_*).  Returns the stats of
     the ingest.  ValueError names the file's line for anything np.loadtxt would refuse or the table cannot hold, and both numbers
-    when the file does not have exactly m - row0 (or limit_rows) data lines."""
+    when the file does not have exactly m - row0 (or limit_rows) data lines.  first_row (not None): the table's m rows are the
+    file's data rows [first_row, first_row + m) -- a SNP shard; the whole file is still read and must have m_total data lines."""
     from .reader_cy import host_threads
     lib = _lib.load()
     r, g = ctypes.c_void_p(), ctypes.c_void_p()
@@ -72,6 +81,8 @@ def stream_table(handle, m, path, counts=False, majmin=None, chunk_bytes=None, t
                 raise ValueError("the allele selectors have shape %s, the table %d sites" % (sel.shape, m))
         check(lib.wgs_depth_ingest_create(handle, r, 1 if counts else 0, sel.ctypes.data if counts else None, int(limit_rows),
                                           int(chunk_bytes or 0), ctypes.byref(g)))
+        if first_row is not None:
+            check(lib.wgs_depth_ingest_set_first_row(g, int(first_row)))
         lines, row = 0, int(row0)
         got, wrote = ctypes.c_int64(), ctypes.c_int64()
         while True:
@@ -81,6 +92,8 @@ def stream_table(handle, m, path, counts=False, majmin=None, chunk_bytes=None, t
             lines += got.value
             row += wrote.value
         want = (m - int(row0)) if limit_rows < 0 else int(limit_rows)
+        if first_row is not None:
+            want = int(m_total)
         if lines != want:
             raise ValueError("%s has %d data lines, %d sites were expected" % (path, lines, want))
         stats = np.zeros(8, dtype=np.float64)
@@ -157,16 +170,29 @@ class DepthTable:
                 self.upload_rows(AD[r:r + step], r)
 
     @classmethod
-    def from_file(cls, beagle, path, counts=False, majmin=None, chunk_bytes=None):
+    def from_file(cls, beagle, path, counts=False, majmin=None, chunk_bytes=None, first_row=0, m_total=None):
         """A fresh table streamed from `path` on the device: allele depths as --ind_ad_file holds them (text, gzip or BGZF), or with
         counts=True ANGSD's counts with the (m, 2) selectors `majmin` (read_majmin).  Nothing of size m x 2n exists on the host;
         .ingest_stats tells what did.  .npy goes through the upload path.  ValueError (and no table) unless the file has exactly
-        beagle.m data lines of at least 2n (4n) integers in 0..255."""
+        beagle.m data lines of at least 2n (4n) integers in 0..255.
+        A SNP shard (m_total: the sites of all shards; beagle.m of them from first_row on are this one's): the table takes the
+        file's data rows [first_row, first_row + beagle.m), `majmin` holds the selectors of those rows, and the file must have
+        m_total data lines; every line before the range is still read, and a token np.loadtxt refuses there is still reported."""
+        ranged = m_total is not None or first_row != 0
+        m_total = beagle.m if m_total is None else int(m_total)
+        if ranged and not (0 <= first_row and first_row + beagle.m <= m_total):
+            raise ValueError("rows [%d, %d) of the depth file lie outside its %d sites" % (first_row, first_row + beagle.m, m_total))
         if str(path).endswith(".npy") and not counts:
-            return cls(beagle, read_depths(path))
+            AD = read_depths(path)
+            if ranged:
+                if AD.ndim != 2 or AD.shape[0] != m_total:
+                    raise ValueError("allele depths have shape %s, the Beagle file has %d sites" % (AD.shape, m_total))
+                AD = AD[first_row:first_row + beagle.m]
+            return cls(beagle, AD)
         t = cls(beagle)
         try:
-            t.ingest_stats = stream_table(t._h, beagle.m, path, counts, majmin, chunk_bytes)
+            t.ingest_stats = stream_table(t._h, beagle.m, path, counts, majmin, chunk_bytes, first_row=first_row if ranged else None,
+                                          m_total=m_total)
         except Exception:
             t.close()
             raise
@@ -276,28 +302,38 @@ def merge_tiers(dense, deep):
     return keys, counts, means
 
 
-def AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep=False):
-    """zscore.AD_summary (zscore.py:11-40) for individuals [i0, i0 + count): list of dict(keys, counts, means, AD_array) -- the
-    dictionary in order of first appearance and the filtered classes.  One launch (wgs_zscore_classes); with deep=True one more
-    group of launches (wgs_zscore_deep_sites) if an individual of the batch has sites deeper than 21 reads, whose classes then
-    enter the dictionary like any other.  deep=False: such data is refused, except under single_read_threshold."""
-    lib = _lib.load()
-    cnt = np.empty((count, N_CLASSES), dtype=np.int32)
-    first = np.empty((count, N_CLASSES), dtype=np.int32)
-    sums = np.empty((count, N_CLASSES, 3), dtype=np.float32)
-    over = np.empty(count, dtype=np.int32)
-    check(lib.wgs_zscore_classes(depth.handle, int(i0), int(count), i32p(cnt), f32p(sums), i32p(first), i32p(over)))
-    maxd = lib.wgs_zscore_max_depth()
+def sharded(comm):
+    return comm is not None and comm.world > 1
+
+
+def comm_handle(comm):
+    """The wgs_comm of a communicator of several ranks: the class sweep and the masked fit hand their running values from shard to
+    shard inside the library (RCCL, or the socket transport attached to it)."""
+    h = getattr(comm, "handle", None)
+    if h is None:
+        raise ValueError("the z-scores over SNP shards need a communicator the library can use (WGSASSIGN_COMM=rccl or socket), not %s"
+                         % type(comm).__name__)
+    return h
+
+
+def concat_deep(parts):
+    """The deep-site lists of one individual from every shard, in rank order -- which is site order: (sites as GLOBAL numbers, (Ar, Aa),
+    (g0, g1)), as deep_classes takes them.  parts: per rank (site, ad, g), whatever each rank's lists were serialised to."""
+    site = np.concatenate([np.asarray(p[0], dtype=np.int64).reshape(-1) for p in parts])
+    ad = np.concatenate([np.asarray(p[1], dtype=np.int32).reshape(-1, 2) for p in parts])
+    g = np.concatenate([np.asarray(p[2], dtype=np.float32).reshape(-1, 2) for p in parts])
+    return site, ad, g
+
+
+def dictionaries(i0, cnt, first, sums, over, listed, n_threshold, single_read_threshold, deep):
+    """The tail of AD_summary, the same for one shard and for many: per individual the dense tier's classes (cnt, first, sums as the
+    class sweep reports them -- over ALL shards: counts added, first sites the smallest global number, sums after the last shard),
+    merged with the dictionary entries of its deep sites (listed[j] = (site, ad, g) in site order; over[j] = how many there are)."""
+    maxd = MAX_DENSE
     d_of = np.repeat(np.arange(maxd + 1), np.arange(maxd + 1) + 1)
     a_of = np.arange(N_CLASSES) - d_of * (d_of + 1) // 2
-    if deep and over.any():
-        total = int(over.sum())
-        site, ad, g = np.empty(total, dtype=np.int32), np.empty((total, 2), dtype=np.int32), np.empty((total, 2), dtype=np.float32)
-        check(lib.wgs_zscore_deep_sites(depth.handle, int(i0), int(count), i32p(over), i32p(site), i32p(ad), f32p(g)))
-        cuts = np.cumsum(over)[:-1]
-        listed = list(zip(np.split(site, cuts), np.split(ad, cuts), np.split(g, cuts)))
     out = []
-    for j in range(count):
+    for j in range(cnt.shape[0]):
         if over[j] and not deep and not single_read_threshold:
             raise ValueError("individual %d has %d sites deeper than %d reads: the depth classes of this build end there "
                              "(--single_read_threshold needs depth 1 only and accepts such data)" % (i0 + j, int(over[j]), maxd))
@@ -308,9 +344,52 @@ def AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep=False)
             keys, counts, means = merge_tiers(dense, deep_classes(*listed[j]))
         else:
             keys, counts, means = merge_tiers(dense, (np.empty((0, 2), dtype=np.int64), np.empty(0, dtype=np.int64),
-                                                     np.empty(0, dtype=np.int32), np.empty((0, 3), dtype=np.float32)))
+                                                     np.empty(0, dtype=first.dtype), np.empty((0, 3), dtype=np.float32)))
         out.append(dict(keys=keys, counts=counts, means=means, AD_array=key_filter(keys, counts, n_threshold, single_read_threshold)))
     return out
+
+
+def list_deep_sites(depth, i0, count, over):
+    """wgs_zscore_deep_sites: per individual (site, ad, g) of this table's sites deeper than 21 reads, in site order."""
+    total = int(over.sum())
+    site, ad, g = np.empty(total, dtype=np.int32), np.empty((total, 2), dtype=np.int32), np.empty((total, 2), dtype=np.float32)
+    over = np.ascontiguousarray(over, dtype=np.int32)
+    check(_lib.load().wgs_zscore_deep_sites(depth.handle, int(i0), int(count), i32p(over), i32p(site), i32p(ad), f32p(g)))
+    cuts = np.cumsum(over)[:-1]
+    return list(zip(np.split(site, cuts), np.split(ad, cuts), np.split(g, cuts)))
+
+
+def AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep=False, comm=None):
+    """zscore.AD_summary (zscore.py:11-40) for individuals [i0, i0 + count): list of dict(keys, counts, means, AD_array) -- the
+    dictionary in order of first appearance and the filtered classes.  One launch (wgs_zscore_classes); with deep=True one more
+    group of launches (wgs_zscore_deep_sites) if an individual of the batch has sites deeper than 21 reads, whose classes then
+    enter the dictionary like any other.  deep=False: such data is refused, except under single_read_threshold.
+    comm with several ranks (collective): the table is a SNP shard; the class sweep goes from shard to shard
+    (wgs_zscore_classes_sharded), every rank lists its own deep sites and receives everybody's, and every rank returns the same
+    dictionaries, first sites in global numbers."""
+    lib = _lib.load()
+    cnt = np.empty((count, N_CLASSES), dtype=np.int32)
+    sums = np.empty((count, N_CLASSES, 3), dtype=np.float32)
+    if sharded(comm):
+        first = np.empty((count, N_CLASSES), dtype=np.int64)
+        over_by_rank = np.empty((comm.world, count), dtype=np.int32)
+        check(lib.wgs_zscore_classes_sharded(depth.handle, int(i0), int(count), comm_handle(comm), i32p(cnt), f32p(sums),
+                                             first.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), i32p(over_by_rank)))
+        over = over_by_rank.sum(axis=0)
+        listed = None
+        if deep and over.any():                               # (every rank sees every rank's counts: all of them come here, or none)
+            mine = over_by_rank[comm.rank]
+            own = list_deep_sites(depth, i0, count, mine) if mine.any() else [(np.empty(0, dtype=np.int32),) * 3] * count
+            wire = [[(site.astype(np.int64) + depth.b.site0).tolist(), ad.reshape(-1).tolist(), g.reshape(-1).astype(np.float64).tolist()]
+                    for site, ad, g in own]
+            everybody = comm.allgather_object(wire)           # [rank][individual]
+            listed = [concat_deep([everybody[r][j] for r in range(comm.world)]) for j in range(count)]
+        return dictionaries(i0, cnt, first, sums, over, listed, n_threshold, single_read_threshold, deep)
+    first = np.empty((count, N_CLASSES), dtype=np.int32)
+    over = np.empty(count, dtype=np.int32)
+    check(lib.wgs_zscore_classes(depth.handle, int(i0), int(count), i32p(cnt), f32p(sums), i32p(first), i32p(over)))
+    listed = list_deep_sites(depth, i0, count, over) if deep and over.any() else None
+    return dictionaries(i0, cnt, first, sums, over, listed, n_threshold, single_read_threshold, deep)
 
 
 def deep_tables(summaries):
@@ -399,41 +478,102 @@ def _batches(lo, hi, batch):
         yield i0, min(batch, hi - i0)
 
 
-def assignment_z_scores(beagle, depth, IDs, pops, afset, n_threshold=0, single_read_threshold=False, ind_start=0, ind_end=None,
-                        batch=64, say=print, details=None, deep=True):
-    """--get_assignment_z_score (WGSassign.py:395-446): z of individuals [ind_start, ind_end) against column k of `afset`, k = the
-    position of the individual's population in `pops`.  float32 (n_sub, 1).  details (a list) receives per individual the
-    intermediate arrays (tests).  deep: as for AD_summary -- sites deeper than 21 reads are computed with, as the reference does."""
-    ind_end = beagle.n if ind_end is None else ind_end
-    z_out = np.empty((ind_end - ind_start, 1), dtype=np.float32)
-    for i0, count in _batches(ind_start, ind_end, batch):
-        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep)
-        keep = get_L_keep(depth, i0, summ)
-        tabs, parts = stat_tables(summ)
-        cols = [int(np.argwhere(pops == IDs[i0 + j, 1])[0][0]) for j in range(count)]
-        wobs, wl, var = keep.stats(tabs, [afset.col_dev(k) for k in cols])
+class _ShardGather:
+    """What crosses the ranks behind a batch's mask and statistic sweeps (collective).  kept[r][j]: sites rank r kept of individual
+    j, from one tagged all-reduce; rows(...): rank 0 receives every rank's compacted arrays and cuts them per individual, rank order
+    -- site order -- inside each; the other ranks get None."""
+
+    def __init__(self, comm, keep, i0):
+        self.comm, self.count = comm, keep.count
+        mine = np.zeros((comm.world, keep.count))
+        mine[comm.rank] = keep.kept
+        self.kept = np.asarray(comm.allreduce_sum(mine, tag=(0, int(i0), keep.count, 0))).reshape(comm.world, keep.count).astype(np.int64)
+        self.total = self.kept.sum(axis=0)
+
+    def rows(self, per_individual):
+        """per_individual: list (count) of this rank's arrays (kept[rank][j], columns...) -> on rank 0 the list of the whole arrays."""
+        flat = np.concatenate(per_individual) if len(per_individual) else np.empty(0)
+        got = self.comm.gather_rows(np.ascontiguousarray(flat))
+        if got is None:
+            return None
+        starts = np.concatenate(([0], np.cumsum(self.kept.sum(axis=1))))      # where each rank's rows begin
+        inside = np.cumsum(self.kept, axis=1) - self.kept                      # ... and each individual's inside them
+        return [np.concatenate([got[starts[r] + inside[r, j]:starts[r] + inside[r, j] + self.kept[r, j]] for r in range(self.comm.world)])
+                for j in range(self.count)]
+
+
+def _finish_batch(comm, g, keep, i0, summ, parts, wobs, wl, var, say, z_out, ind_start, details, extra=None):
+    """The three sums, z and the printed lines of a batch -- on rank 0 over the arrays of all shards (several ranks), which also
+    fills z_out and `details` there.  extra(j, sites) -> more entries of an individual's `details` from this rank's shard, per-site
+    arrays among them (these are gathered like the statistics).  g: the batch's _ShardGather (None: one shard)."""
+    count = keep.count
+    if not sharded(comm):
         for j in range(count):
             r = _finish(i0 + j, keep.kept[j], wobs[j], wl[j], var[j], say)
             z_out[i0 + j - ind_start, 0] = r["z"]
             if details is not None:
-                details.append(dict(summ[j], keep=keep.sites(j), fac=parts[j][0], like=parts[j][1], index=parts[j][2], wobs=wobs[j],
-                                    wl=wl[j], var=var[j], **r))
+                sites = keep.sites(j)
+                details.append(dict(summ[j], keep=sites, fac=parts[j][0], like=parts[j][1], index=parts[j][2], wobs=wobs[j], wl=wl[j],
+                                    var=var[j], **(extra(j, sites) if extra else {}), **r))
+        return
+    stats = g.rows([np.stack((wobs[j], wl[j], var[j]), axis=1) for j in range(count)])
+    more = None
+    if details is not None:                                   # (every rank was asked for them, or none)
+        local = [keep.sites(j) for j in range(count)]
+        ext = [extra(j, local[j]) if extra else {} for j in range(count)]
+        per_site = sorted(k for k, v in ext[0].items() if isinstance(v, np.ndarray))
+        sites = g.rows([local[j].astype(np.int64) + keep.depth.b.site0 for j in range(count)])
+        more = {k: g.rows([ext[j][k] for j in range(count)]) for k in per_site}
+    if comm.rank != 0:
+        return
+    for j in range(count):
+        w, l, v = (np.ascontiguousarray(stats[j][:, c]) for c in range(3))
+        r = _finish(i0 + j, g.total[j], w, l, v, say)
+        z_out[i0 + j - ind_start, 0] = r["z"]
+        if details is not None:
+            d = dict(summ[j], keep=sites[j], fac=parts[j][0], like=parts[j][1], index=parts[j][2], wobs=w, wl=l, var=v, **r)
+            d.update({k: x for k, x in ext[j].items() if k not in per_site})
+            d.update({k: more[k][j] for k in per_site})
+            details.append(d)
+
+
+def assignment_z_scores(beagle, depth, IDs, pops, afset, n_threshold=0, single_read_threshold=False, ind_start=0, ind_end=None,
+                        batch=64, say=print, details=None, deep=True, comm=None):
+    """--get_assignment_z_score (WGSassign.py:395-446): z of individuals [ind_start, ind_end) against column k of `afset`, k = the
+    position of the individual's population in `pops`.  float32 (n_sub, 1).  details (a list) receives per individual the
+    intermediate arrays (tests).  deep: as for AD_summary -- sites deeper than 21 reads are computed with, as the reference does.
+    comm with several ranks (collective): beagle, depth and afset hold this rank's SNP shard.  Rank 0 prints (`say`), fills
+    `details` -- kept sites in global numbers, the per-site arrays of all shards -- and returns the z-scores; the other ranks return
+    None."""
+    ind_end = beagle.n if ind_end is None else ind_end
+    z_out = np.empty((ind_end - ind_start, 1), dtype=np.float32)
+    for i0, count in _batches(ind_start, ind_end, batch):
+        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep, comm)
+        keep = get_L_keep(depth, i0, summ)
+        g = _ShardGather(comm, keep, i0) if sharded(comm) else None
+        tabs, parts = stat_tables(summ)
+        cols = [int(np.argwhere(pops == IDs[i0 + j, 1])[0][0]) for j in range(count)]
+        wobs, wl, var = keep.stats(tabs, [afset.col_dev(k) for k in cols])
+        _finish_batch(comm, g, keep, i0, summ, parts, wobs, wl, var, say, z_out, ind_start, details)
         keep.close()
-    return z_out
+    return z_out if not sharded(comm) or comm.rank == 0 else None
 
 
 def reference_z_scores(beagle, depth, IDs, group_of, maf_iter=200, maf_tole=1e-4, n_threshold=0, single_read_threshold=False,
-                       ind_start=0, ind_end=None, batch=64, say=print, details=None, deep=True):
+                       ind_start=0, ind_end=None, batch=64, say=print, details=None, deep=True, comm=None):
     """--get_reference_z_score (WGSassign.py:311-393): per individual the leave-one-out EM fit of its population on ITS kept sites
     (wgs_em_fit_masked: the existing sweeps, the convergence chain over the kept sites), the clamp, then as above.  `beagle` must
-    hold one slab per population (group_of as --get_reference_af builds it)."""
+    hold one slab per population (group_of as --get_reference_af builds it).
+    comm with several ranks (collective): one EM batch per rank over its shard, the chain crossing the ranks
+    (wgs_em_fit_masked_sharded); every rank reports the fits' iterations through `say`; otherwise as assignment_z_scores."""
     from .device import EMBatch
     ind_end = beagle.n if ind_end is None else ind_end
     sizes = np.bincount(group_of, minlength=int(np.max(group_of)) + 1)
     z_out = np.empty((ind_end - ind_start, 1), dtype=np.float32)
     for i0, count in _batches(ind_start, ind_end, batch):
-        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep)
+        summ = AD_summary(depth, i0, count, n_threshold, single_read_threshold, deep, comm)
         keep = get_L_keep(depth, i0, summ)
+        g = _ShardGather(comm, keep, i0) if sharded(comm) else None
         tabs, parts = stat_tables(summ)
         ids = np.arange(i0, i0 + count)
         if np.any(sizes[group_of[ids]] < 2):
@@ -441,19 +581,20 @@ def reference_z_scores(beagle, depth, IDs, group_of, maf_iter=200, maf_tole=1e-4
         em = EMBatch(beagle, group_of[ids], ids)
         iters = np.zeros(count, dtype=np.int32)
         slots = np.arange(count, dtype=np.int32)
-        check(_lib.load().wgs_em_fit_masked(em.handle, keep.handle, i32p(slots), int(maf_iter), float(maf_tole), i32p(iters)))
+        if sharded(comm):
+            kept_total = np.ascontiguousarray(g.total, dtype=np.int64)
+            check(_lib.load().wgs_em_fit_masked_sharded(em.handle, keep.handle, i32p(slots), int(maf_iter), float(maf_tole),
+                                                        kept_total.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), comm_handle(comm),
+                                                        i32p(iters)))
+        else:
+            check(_lib.load().wgs_em_fit_masked(em.handle, keep.handle, i32p(slots), int(maf_iter), float(maf_tole), i32p(iters)))
         for j in range(count):
             if iters[j]:
                 say("EM (MAF) converged at iteration: " + str(int(iters[j])))
             em.clamp(j, int(sizes[group_of[i0 + j]]) - 1)
         wobs, wl, var = keep.stats(tabs, [em.f_dev(j) for j in range(count)])
-        for j in range(count):
-            r = _finish(i0 + j, keep.kept[j], wobs[j], wl[j], var[j], say)
-            z_out[i0 + j - ind_start, 0] = r["z"]
-            if details is not None:
-                sites = keep.sites(j)
-                details.append(dict(summ[j], keep=sites, fac=parts[j][0], like=parts[j][1], index=parts[j][2], wobs=wobs[j], wl=wl[j],
-                                    var=var[j], A=em.get_f(j)[sites], it=int(iters[j]), **r))
+        _finish_batch(comm, g, keep, i0, summ, parts, wobs, wl, var, say, z_out, ind_start, details,
+                      extra=lambda j, sites: dict(A=em.get_f(j)[sites], it=int(iters[j])))
         em.close()
         keep.close()
-    return z_out
+    return z_out if not sharded(comm) or comm.rank == 0 else None
