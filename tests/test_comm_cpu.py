@@ -369,3 +369,75 @@ except CollectiveMismatch as e:
     for r, (p, o) in enumerate(zip(procs, outs)):
         assert p.returncode == 76 and "went through" not in o, "rank %d: status %s\n%s" % (r, p.returncode, o[-2000:])
         assert "rank 0 issued collective #4" in o and "rank 1 issued collective #4" in o, o[-2000:]
+
+
+_RELAY_WORKER = r'''
+import os, sys
+import numpy as np
+sys.path.insert(0, {root!r})
+from wgsassign_amd.comm import SocketComm, CollectiveMismatch, COMM_DIVERGED, relay
+rank, world = int(sys.argv[1]), int(sys.argv[2])
+comm = SocketComm(rank, world, "127.0.0.1", {port})
+rng = np.random.default_rng(11)
+f32 = rng.standard_normal((world, 2, 3)).astype(np.float32)
+f32[:, 0, 0] = [np.finfo(np.float32).max, -np.float32(2.0) ** -149, np.float32(1.0) + np.finfo(np.float32).eps]   # the format's corners
+f64 = rng.standard_normal((world, 5)) * 1e-300
+assert np.isfinite(f32).all() and (f32 != 0).all() and np.isfinite(f64).all() and (f64 != 0).all()
+ok = True
+for vals in (f32, f64):
+    seen = []
+    def step(carry):
+        seen.append(carry)
+        return vals[rank]
+    before = comm._seq
+    out = relay(comm, step, vals.shape[1:], vals.dtype)
+    ok &= comm._seq - before == world                       # one all-reduce per rank, nothing else
+    ok &= len(seen) == 1                                    # this rank's turn came once
+    if rank == 0:
+        ok &= seen[0] is None
+    else:                                                   # exactly what the rank before returned
+        ok &= seen[0].dtype == vals.dtype and seen[0].shape == vals.shape[1:] and seen[0].tobytes() == vals[rank - 1].tobytes()
+    ok &= out.dtype == vals.dtype and out.shape == vals.shape[1:] and out.tobytes() == vals[world - 1].tobytes()
+print("RANK", rank, "RELAYS", "OK" if ok else "FAIL", flush=True)
+def relay_a(): return relay(comm, lambda c: np.ones(2), (2,), np.float64)
+def relay_b(): return relay(comm, lambda c: np.ones(2), (2,), np.float64)
+print("LINES", relay_a.__code__.co_firstlineno, relay_b.__code__.co_firstlineno, flush=True)
+try:
+    (relay_b if rank == 1 else relay_a)()                   # the same relay by its payload, but not by its caller
+    print("RANK", rank, "went through", flush=True)
+    sys.exit(0)
+except CollectiveMismatch as e:
+    print("RANK", rank, "MISMATCH:", e, flush=True)
+    os._exit(COMM_DIVERGED)
+'''
+
+
+def test_relay_hands_the_value_from_rank_to_rank(tmp_path, monkeypatch):
+    """comm.relay over three SocketComm ranks: rank r's step gets None (r = 0) or exactly the array rank r - 1 returned -- float32
+    values including the format's corners, and a float64 case --, every rank returns the last rank's value in the requested dtype,
+    and the communicator has issued exactly `world` all-reduces per relay.  Two ranks that call relay from different lines stop with
+    CollectiveMismatch, and the message names the CALLERS' lines, not a line of comm.py.  One rank or no communicator: the step
+    runs once with None and no collective is issued."""
+    import re
+    from wgsassign_amd import comm
+    port = free_port()
+    script = tmp_path / "worker.py"
+    script.write_text(_RELAY_WORKER.format(root=ROOT, port=port))
+    procs = [subprocess.Popen([sys.executable, str(script), str(r), "3"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+             for r in range(3)]
+    outs = [p.communicate(timeout=120)[0] for p in procs]
+    for r, (p, o) in enumerate(zip(procs, outs)):
+        assert "RANK %d RELAYS OK" % r in o, "rank %d:\n%s" % (r, o[-3000:])
+        assert "went through" not in o and p.returncode == comm.COMM_DIVERGED, "rank %d: status %s\n%s" % (r, p.returncode, o[-3000:])
+        line_a, line_b = re.search(r"LINES (\d+) (\d+)", o).groups()
+        msg = o[o.index("MISMATCH:"):]
+        assert "collective mismatch" in msg and "comm.py" not in msg, msg
+        assert set(re.findall(r"host all-reduce at (?:worker\.py|<other file>):(\d+)", msg)) == {line_a, line_b}, msg
+
+    def no_collective(self, arr, tag=None):
+        raise AssertionError("a relay over one rank issued an all-reduce")
+    monkeypatch.setattr(comm.LocalComm, "allreduce_sum", no_collective)
+    for c in (comm.LocalComm(), None):
+        seen = []
+        out = comm.relay(c, lambda carry: seen.append(carry) or np.float32([1.5, -2.5]), (2,), np.float32)
+        assert seen == [None] and out.dtype == np.float32 and out.tolist() == [1.5, -2.5]

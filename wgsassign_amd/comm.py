@@ -53,7 +53,7 @@ def _call_site(depth=1):
     import sys
     f = sys._getframe(1)
     while f is not None and os.path.basename(f.f_code.co_filename) == "comm.py" and f.f_back is not None and \
-            f.f_code.co_name in ("allreduce_sum", "barrier", "_tagged_allreduce", "fn", "allreduce_device"):
+            f.f_code.co_name in ("allreduce_sum", "barrier", "_tagged_allreduce", "fn", "allreduce_device", "relay"):
         f = f.f_back
     name = os.path.basename(f.f_code.co_filename)
     idx = _SITE_FILES.index(name) if name in _SITE_FILES else len(_SITE_FILES)
@@ -76,6 +76,24 @@ def decode_sites(msg):
     import re
     return re.sub(r"\(op 8\), generation (-?\d+), iteration (-?\d+), shape (\d+) /",
                   lambda mt: "(op 8), generation %s, iteration %s, shape %s [%s] /" % (mt.group(1), mt.group(2), mt.group(3), site_name(mt.group(3))), msg)
+
+
+def relay(comm, step, shape, dtype):
+    """A running value handed from SNP shard to SNP shard in rank order, for communicators without a library handle (the library's
+    own relay: csrc/common.h, wgs_relay).  The ranks take turns: rank r calls step(carry) -- carry is None on the first turn, else
+    the array rank r - 1 returned -- and returns its value (`shape`, `dtype`); the others contribute zeros to a sum all-reduce, which
+    makes it a broadcast.  The value crosses as float64 (float32 values are exact in float64) and comes back in `dtype`; every
+    rank returns the value after the last shard.  One rank, or comm None: step(None), no all-reduce.  The all-reduces' tags
+    carry the file and line of relay's CALLER (_call_site), so two relays are told apart like any two host all-reduces."""
+    if comm is None or comm.world == 1:
+        return np.asarray(step(None), dtype=dtype).reshape(shape)
+    carry = None
+    for r in range(comm.world):
+        mine = np.zeros(shape, dtype=np.float64)
+        if r == comm.rank:
+            mine[...] = step(carry)
+        carry = np.ascontiguousarray(comm.allreduce_sum(mine), dtype=dtype).reshape(shape)
+    return carry
 
 
 class _Tagged:

@@ -262,6 +262,27 @@ constexpr size_t wgs_comm_tail_bytes() { return wgs_comm_tail_doubles() * sizeof
 extern "C" int wgs_comm_allreduce_tagged(wgs_comm *c, double *dev_buf, int64_t n, const wgs_coll_tag *tag);
 extern "C" int wgs_comm_bcast_tagged(wgs_comm *c, void *dev_buf, int64_t bytes, int root, const wgs_coll_tag *tag);
 
+// ---- the relay: a running value handed from SNP shard to SNP shard in rank order.  On its turn rank r runs
+// step(continued) -- continued = r > 0: dev_buf then holds what rank r - 1 left -- which enqueues on the context's stream whatever
+// leaves this rank's value in dev_buf; the value is then broadcast from r under tag_of(r).  One broadcast per rank; afterwards
+// dev_buf holds the last shard's value on every rank.  comm == nullptr or one rank: step(false) alone, no collective.  Nothing here
+// waits for the device: the caller enqueues its read-backs, synchronises the stream and THEN calls wgs_comm_check.
+// dev_buf must have wgs_relay_bytes(bytes): the payload rounded up to whole float64, and the root's tag row behind it.
+constexpr size_t wgs_relay_bytes(size_t payload) { return ((payload + 7) & ~(size_t)7) + wgs_comm_tail_bytes(); }
+template <class TagOf, class Step>
+int wgs_relay(wgs_comm *comm, void *dev_buf, size_t bytes, TagOf tag_of, Step step)
+{
+    int world = 1, rank = 0;
+    if (comm) wgs_comm_rank(comm, &rank, &world);
+    for (int r = 0; r < world; ++r) {
+        if (r == rank && step(r > 0)) return 1;
+        if (world == 1) break;
+        const wgs_coll_tag tag = tag_of(r);
+        if (wgs_comm_bcast_tagged(comm, dev_buf, (int64_t)bytes, r, &tag)) return 1;
+    }
+    return 0;
+}
+
 // ---- objects of the C ABI that point at a parent (an EM batch at its matrix, a score at its matrix and frequency set).  Destroying a
 // parent destroys them first, and destroying something that is no longer alive returns at once: a caller's garbage collector may
 // release its handles in any order (Python finalises the objects of a reference cycle in arbitrary order; before round 5 an EM batch

@@ -488,9 +488,8 @@ int wgs_em_rmse_chain(wgs_em *em, int32_t fit, float carry_in, float *carry_out)
  *     in one batched launch; across SNP shards the float32 carries travel in rank order) and either
  *     finishes them or re-activates them -- such a fit simply runs its next sweep one iteration later.
  * Decisions use only all-reduced sums, so every rank takes the same path. */
-// d_chain_out: [n_fits] float32 carries (broadcast from shard to shard, the root's tag row behind them) | room for that row |
-// [n_fits] serial-block counts
-static size_t em_chain_serial_off(size_t n) { return (n + 1) / 2 * 2 + 2 * wgs_comm_tail_doubles(); }
+// d_chain_out: a relay buffer of [n_fits] float32 carries | [n_fits] serial-block counts
+static size_t em_chain_serial_off(size_t n) { return wgs_relay_bytes(sizeof(float) * n) / sizeof(float); }
 static size_t em_chain_out_floats(size_t n) { return em_chain_serial_off(n) + n; }
 
 static int em_fit_alloc(wgs_em *em)
@@ -526,28 +525,14 @@ static int em_resolve_chains(wgs_em *em, const std::vector<int32_t> &fits, doubl
     const int nj = (int)fits.size();
     converged.assign(nj, 0);
     if (nj == 0) return 0;
-    int world = 1, rank = 0;
-    if (comm) wgs_comm_rank(comm, &rank, &world);
-    // The serial float32 chain crosses the SNP shards in rank order ON THE STREAM: rank r walks its blocks from the
-    // running values it received and broadcasts the result (`world` broadcasts of nj float32, one readback at the end).
     for (int i = 0; i < nj; ++i) {
         const int j = fits[i];
         em->h_jobs[i] = ChainJob{em_f(em, j, em->cur[j]), em_f(em, j, em->prev[j]), 0.0f};
     }
     HIP_TRY(hipMemcpyAsync(em->d_jobs, em->h_jobs, sizeof(ChainJob) * nj, hipMemcpyHostToDevice, ctx->stream));
-    for (int r = 0; r < world; ++r) {
-        if (r == rank) {
-            if (r > 0 && launch_chain_set_carry(ctx, em->d_jobs, em->d_chain_out, nj)) return 1;
-            if (launch_rmse_chain_batch(ctx, em->d_jobs, nj, em->b->m, em->d_chain_out, em->d_chain_batch,
-                                        reinterpret_cast<int *>(em->d_chain_out + em_chain_serial_off(em->n_fits))))
-                return 1;
-        }
-        const wgs_coll_tag tag = {WGS_OP_EM_CHAIN, generation, iteration, nj, r, 0};
-        if (world > 1 && wgs_comm_bcast_tagged(comm, em->d_chain_out, (int64_t)sizeof(float) * nj, r, &tag)) return 1;
-    }
-    HIP_TRY(hipMemcpyAsync(em->h_chain_out, em->d_chain_out, sizeof(float) * nj, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));       // also: h_jobs has been consumed
-    if (wgs_comm_check(comm)) return 1;               // (a receiver's view of the senders' rows)
+    if (em_relay_chains(ctx, comm, WGS_OP_EM_CHAIN, generation, iteration, em->d_jobs, nj, em->b->m, em->d_chain_out, em->d_chain_batch,
+                        reinterpret_cast<int *>(em->d_chain_out + em_chain_serial_off(em->n_fits)), em->h_chain_out))
+        return 1;
     const float *carry = em->h_chain_out;
     ++em->fit_chain_batches;
     for (int i = 0; i < nj; ++i) {

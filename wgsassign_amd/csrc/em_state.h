@@ -51,3 +51,21 @@ struct wgs_em {
 bool codes_switched_off();              // WGSASSIGN_CODES=0: no class codes at all (codes.hip)
 
 static inline float *em_f(wgs_em *em, int fit, int which) { return em->fbuf[which] + (size_t)fit * em->b->m; }
+
+/* The exact chains of d_jobs[0 .. nj) (on the device, carry_in 0) over `len` elements of this shard, relayed across the SNP shards
+ * (common.h: wgs_relay): rank r walks on from the carries rank r - 1 left in d_out.  h_carry[i] = chain i after the last shard, on
+ * every rank; returns after the stream has drained and the communicator has been checked. */
+inline int em_relay_chains(wgs_ctx *ctx, wgs_comm *comm, int32_t op, int32_t generation, int32_t iteration, ChainJob *d_jobs, int nj,
+                           int64_t len, float *d_out, void *work, int *d_serial, float *h_carry)
+{
+    if (wgs_relay(
+            comm, d_out, sizeof(float) * nj, [&](int r) { return wgs_coll_tag{op, generation, iteration, nj, r, 0}; },
+            [&](bool continued) {
+                if (continued && launch_chain_set_carry(ctx, d_jobs, d_out, nj)) return 1;
+                return launch_rmse_chain_batch(ctx, d_jobs, nj, len, d_out, work, d_serial);
+            }))
+        return 1;
+    HIP_TRY(hipMemcpyAsync(h_carry, d_out, sizeof(float) * nj, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));       // also: the caller's host copy of the jobs has been consumed
+    return wgs_comm_check(comm);                      // (a receiver's view of the senders' rows)
+}

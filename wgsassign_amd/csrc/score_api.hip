@@ -267,9 +267,8 @@ int wgs_score_total_from(wgs_score *sc, const double *carry_in, double *out)
     return 0;
 }
 
-/* The n x K totals over ALL SNP shards in NumPy's order, one call: np.sum's running float64 total is handed from shard to
- * shard in SNP order ON THE STREAM -- rank r continues it over its chunk sums (chunk_total_kernel) and broadcasts the
- * result, rank r + 1 picks it up as its carry -- `world` broadcasts of n*K float64 enqueued back to back, ONE readback.
+/* The n x K totals over ALL SNP shards in NumPy's order, one call: np.sum's running float64 total is relayed from shard to shard
+ * (common.h: wgs_relay) -- rank r continues it over its chunk sums (chunk_total_kernel) from what rank r - 1 left.
  * totals_out (host, n*K) receives the totals on every rank; before_out (host, n*K, may be NULL) the total over the shards
  * BEFORE this one (what wgs_score_chains_prepare wants as `start`).  comm == NULL or one rank: the local sums.
  * Needs wgs_score_sums first. */
@@ -279,21 +278,19 @@ int wgs_score_totals_all(wgs_score *sc, wgs_comm *comm, double *totals_out, doub
     WGS_REQUIRE(sc->d_chunks, "wgs_score_totals_all needs wgs_score_sums first");
     wgs_ctx *ctx = sc->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    int world = 1, rank = 0;
-    if (comm) wgs_comm_rank(comm, &rank, &world);
     const size_t bytes = sizeof(double) * sc->cells;
     if (!sc->d_start) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_start, bytes));
-    if (!sc->d_run) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_run, bytes + wgs_comm_tail_bytes()));      // (+ the sender's tag row behind the totals)
+    if (!sc->d_run) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_run, wgs_relay_bytes(bytes)));
     HIP_TRY(hipMemsetAsync(sc->d_start, 0, bytes, ctx->stream));
     const int32_t generation = comm ? wgs_comm_next_generation(comm) : 0;
-    for (int r = 0; r < world; ++r) {
-        if (r == rank) {
-            if (r > 0) HIP_TRY(hipMemcpyAsync(sc->d_start, sc->d_run, bytes, hipMemcpyDeviceToDevice, ctx->stream));   // what precedes this shard
-            if (launch_chunk_total(ctx, sc->d_chunks, (sc->nblocks + 1) / 2, sc->cells, r > 0 ? sc->d_start : nullptr, sc->d_run)) return 1;
-        }
-        const wgs_coll_tag tag = {WGS_OP_SCORE_TOTALS, generation, r, (int32_t)(sc->row_hi - sc->row_lo), r, 0};
-        if (world > 1 && wgs_comm_bcast_tagged(comm, sc->d_run, (int64_t)bytes, r, &tag)) return 1;
-    }
+    if (wgs_relay(
+            comm, sc->d_run, bytes,
+            [&](int r) { return wgs_coll_tag{WGS_OP_SCORE_TOTALS, generation, r, (int32_t)(sc->row_hi - sc->row_lo), r, 0}; },
+            [&](bool continued) -> int {
+                if (continued) HIP_TRY(hipMemcpyAsync(sc->d_start, sc->d_run, bytes, hipMemcpyDeviceToDevice, ctx->stream));   // what precedes this shard
+                return launch_chunk_total(ctx, sc->d_chunks, (sc->nblocks + 1) / 2, sc->cells, continued ? sc->d_start : nullptr, sc->d_run);
+            }))
+        return 1;
     HIP_TRY(hipMemcpyAsync(totals_out, sc->d_run, bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (before_out) HIP_TRY(hipMemcpyAsync(before_out, sc->d_start, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -326,7 +323,7 @@ int wgs_score_chains_prepare(wgs_score *sc, int32_t P, const double *start)
             return 1;
         }
         HIP_TRY(wgs_pool_malloc(ctx, &sc->d_carry, sizeof(float) * chains));
-        HIP_TRY(wgs_pool_malloc(ctx, &sc->d_parts, sizeof(float) * chains + wgs_comm_tail_bytes()));   // (+ the sender's tag row behind the carries)
+        HIP_TRY(wgs_pool_malloc(ctx, &sc->d_parts, wgs_relay_bytes(sizeof(float) * chains)));
         if (!sc->d_nserial) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_nserial, sizeof(int32_t)));
         if (!sc->d_start) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_start, sizeof(double) * sc->cells));
         sc->P = P;
@@ -402,28 +399,26 @@ int wgs_score_chains_walk(wgs_score *sc, const float *carry_in, float *parts_out
     return 0;
 }
 
-/* The chains of ALL SNP shards, one call: rank 0 walks its blocks from zero, broadcasts its float32 values, rank 1 walks on
- * from them, ... -- `world` broadcasts of n*P*K float32 on the stream, ONE readback; parts_out (host) receives the
- * values after the last shard on every rank.  Every rank has prepared its block functions before (in parallel). */
+/* The chains of ALL SNP shards, one call: the float32 values are relayed from shard to shard (common.h: wgs_relay), rank r walking
+ * its blocks on from them; parts_out (host) receives the values after the last shard on every rank.  Every rank has prepared its
+ * block functions before (in parallel). */
 int wgs_score_chains_walk_all(wgs_score *sc, wgs_comm *comm, float *parts_out)
 {
     WGS_REQUIRE(sc && parts_out, "null argument");
     WGS_REQUIRE(sc->P >= 1 && sc->d_cand, "wgs_score_chains_walk_all needs wgs_score_chains_prepare first");
     wgs_ctx *ctx = sc->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    int world = 1, rank = 0;
-    if (comm) wgs_comm_rank(comm, &rank, &world);
     const size_t bytes = sizeof(float) * (size_t)sc->cells * sc->P;
     const int32_t generation = comm ? wgs_comm_next_generation(comm) : 0;
-    for (int r = 0; r < world; ++r) {
-        if (r == rank) {
-            if (r > 0) HIP_TRY(hipMemcpyAsync(sc->d_carry, sc->d_parts, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-            if (chains_walk_enqueue(sc, r > 0)) return 1;
-            HIP_TRY(hipMemcpyAsync(&sc->last_serial_blocks, sc->d_nserial, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        const wgs_coll_tag tag = {WGS_OP_PART_CHAINS, generation, r, sc->P, r, 0};
-        if (world > 1 && wgs_comm_bcast_tagged(comm, sc->d_parts, (int64_t)bytes, r, &tag)) return 1;
-    }
+    if (wgs_relay(
+            comm, sc->d_parts, bytes, [&](int r) { return wgs_coll_tag{WGS_OP_PART_CHAINS, generation, r, sc->P, r, 0}; },
+            [&](bool continued) -> int {
+                if (continued) HIP_TRY(hipMemcpyAsync(sc->d_carry, sc->d_parts, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+                if (chains_walk_enqueue(sc, continued)) return 1;
+                HIP_TRY(hipMemcpyAsync(&sc->last_serial_blocks, sc->d_nserial, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+                return 0;
+            }))
+        return 1;
     HIP_TRY(hipMemcpyAsync(parts_out, sc->d_parts, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->assign_ms_pending = true;

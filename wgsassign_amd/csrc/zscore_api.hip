@@ -128,19 +128,6 @@ int wgs_depth_download_rows(wgs_depth *d, int32_t *AD_rows, int64_t row0, int64_
     return 0;
 }
 
-// One (batch, rank) step of the sharded class sweep: hop r of the batch.  Rank r walks its shard -- from 0 on the first hop, else from
-// the running sums the hop before left in `sums` -- and its sums are broadcast into every rank's `sums`.  Nothing here waits for the
-// host; a caller may issue the hops of different batches in any order that keeps a batch's own hops in rank order.
-static int zclass_hop(wgs_ctx *ctx, wgs_comm *comm, int r, int rank, int world, int32_t generation, const ZInd *d_inds, int32_t i0, int count,
-                      const wgs_depth *d, int32_t *cnt, float *sums, int32_t *first, int32_t *over)
-{
-    if (r == rank && launch_zclass(ctx, d_inds, count, d->table, d->b->m, d->mpad, cnt, sums, first, over, r > 0)) return 1;
-    if (world == 1) return 0;
-    // (the broadcast's own row says who sends -- shape_b -- and how many bytes: count x 256 x 3 float32)
-    const wgs_coll_tag tag = {WGS_OP_Z_CLASS, generation, r, i0, 0, 0};       // (shape_b: wgs_comm_bcast_tagged writes the root there)
-    return wgs_comm_bcast_tagged(comm, sums, (int64_t)sizeof(float) * 3 * 256 * count, r, &tag);
-}
-
 int wgs_zscore_classes_sharded(wgs_depth *d, int32_t i0, int32_t count, wgs_comm *comm, int32_t *counts_out, float *sums_out,
                                int64_t *first_out, int32_t *over_out)
 {
@@ -162,11 +149,14 @@ int wgs_zscore_classes_sharded(wgs_depth *d, int32_t i0, int32_t count, wgs_comm
     HIP_TRY(bufs.get(&d_inds, sizeof(ZInd) * count));
     HIP_TRY(bufs.get(&cnt, sizeof(int32_t) * cells));
     HIP_TRY(bufs.get(&first, sizeof(int32_t) * cells));
-    HIP_TRY(bufs.get(&sums, ((sizeof(float) * 3 * cells + 7) & ~(size_t)7) + wgs_comm_tail_bytes()));     // (+ the root's tag row)
+    HIP_TRY(bufs.get(&sums, wgs_relay_bytes(sizeof(float) * 3 * cells)));
     HIP_TRY(bufs.get(&over, sizeof(int32_t) * count));
     HIP_TRY(hipMemcpyAsync(d_inds, inds.data(), sizeof(ZInd) * count, hipMemcpyHostToDevice, ctx->stream));
-    for (int r = 0; r < world; ++r)
-        if (zclass_hop(ctx, comm, r, rank, world, generation, d_inds, i0, count, d, cnt, sums, first, over)) return 1;
+    // the running class sums cross the shards (common.h: wgs_relay); a class that a shard does not have is handed on untouched
+    if (wgs_relay(
+            comm, sums, sizeof(float) * 3 * cells, [&](int r) { return wgs_coll_tag{WGS_OP_Z_CLASS, generation, r, i0, 0, 0}; },
+            [&](bool continued) { return launch_zclass(ctx, d_inds, count, d->table, b->m, d->mpad, cnt, sums, first, over, continued); }))
+        return 1;
     std::vector<int32_t> h_cnt(cells), h_first(cells), h_over(count);
     std::vector<float> h_sums(3 * cells);
     HIP_TRY(hipMemcpyAsync(h_cnt.data(), cnt, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
@@ -421,8 +411,6 @@ static int em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int
     wgs_beagle *b = em->b;
     wgs_ctx *ctx = b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    int world = 1, rank = 0;
-    if (comm) wgs_comm_rank(comm, &rank, &world);
     const int32_t generation = comm ? wgs_comm_next_generation(comm) : 0;
     const int nf = em->n_fits;
     int64_t stride = 1;                      // (an individual may have kept nothing in THIS shard: its chain hands the carry on)
@@ -443,7 +431,7 @@ static int em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int
         wgs_set_error("hipMalloc of 2 x %zu bytes for the compacted frequencies failed", vec_bytes);
         return 1;
     }
-    HIP_TRY(bufs.get(&d_out, ((sizeof(float) * nf + 7) & ~(size_t)7) + wgs_comm_tail_bytes()));           // (+ the root's tag row)
+    HIP_TRY(bufs.get(&d_out, wgs_relay_bytes(sizeof(float) * nf)));
     HIP_TRY(bufs.get(&d_cj, sizeof(ZCompactJob) * nf));
     HIP_TRY(bufs.get(&d_jobs, sizeof(ChainJob) * nf));
     HIP_TRY(bufs.get(&work, rmse_chain_workspace_bytes(stride) * nf));
@@ -469,18 +457,8 @@ static int em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int
         HIP_TRY(hipMemcpyAsync(d_cj, cj.data(), sizeof(ZCompactJob) * nj, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(ChainJob) * nj, hipMemcpyHostToDevice, ctx->stream));
         if (launch_zcompact(ctx, d_cj, nj, b->m, zk->mask, zk->off)) return 1;
-        // the chain over the kept sites crosses the shards in rank order on the stream, as em_resolve_chains hands its carries on
-        for (int r = 0; r < world; ++r) {
-            if (r == rank) {
-                if (r > 0 && launch_chain_set_carry(ctx, d_jobs, d_out, nj)) return 1;
-                if (launch_rmse_chain_batch(ctx, d_jobs, nj, stride, d_out, work, nullptr)) return 1;
-            }
-            const wgs_coll_tag tag = {WGS_OP_Z_CHAIN, generation, it, nj, r, 0};
-            if (world > 1 && wgs_comm_bcast_tagged(comm, d_out, (int64_t)sizeof(float) * nj, r, &tag)) return 1;
-        }
-        HIP_TRY(hipMemcpyAsync(carry.data(), d_out, sizeof(float) * nj, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (wgs_comm_check(comm)) return 1;               // (a receiver's view of the senders' rows)
+        // the chain over the kept sites crosses the shards as wgs_em_fit's chains do
+        if (em_relay_chains(ctx, comm, WGS_OP_Z_CHAIN, generation, it, d_jobs, nj, stride, d_out, work, nullptr, carry.data())) return 1;
         for (int q = 0; q < nj; ++q) {
             const int j = list[q];
             const float res = carry[q] / (float)kept_total[fit_slot[j]];      // emMAF_cy.pyx:32 with n = the kept sites of ALL shards

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import MODE_EXACT, MODE_FAST, check, f32p, f64p, i32p
+from .comm import LocalComm, relay
 
 _default_ctx = None
 _live = weakref.WeakSet()       # device objects that still own library handles
@@ -476,7 +477,6 @@ def run_em(em, max_iter, tole, comm=None, m_total=None):
     set_active(fit, bool), GUARD.  (tests drive this loop with a CPU stand-in to cover the
     multi-rank protocol without a GPU.)
     """
-    from .comm import LocalComm
     comm = comm or LocalComm()
     if m_total is None:
         m_total = int(comm.allreduce_sum(np.array([float(em.b.m)]))[0]) if comm.world > 1 else em.b.m
@@ -499,16 +499,8 @@ def run_em(em, max_iter, tole, comm=None, m_total=None):
             elif d == 0:
                 undecided.append(int(j))
         for j in undecided:
-            # the reference's float32 running sum walks all SNPs in index order: rank r continues
-            # from the carry of rank r-1 (contiguous SNP shards in rank order)
-            carry = np.float32(0.0)
-            for r in range(comm.world):
-                mine = np.zeros(1, dtype=np.float64)
-                if r == comm.rank:
-                    mine[0] = float(em.rmse_chain(j, carry))
-                if comm.world > 1:
-                    mine = comm.allreduce_sum(mine)
-                carry = np.float32(mine[0])
+            # the reference's float32 running sum walks all SNPs in index order (comm.relay)
+            carry = relay(comm, lambda c: em.rmse_chain(j, np.float32(0.0) if c is None else c[0]), (1,), np.float32)[0]
             if chain_diff(carry, m_total) < tole:
                 iters[j] = it
                 em.set_active(j, False)
@@ -619,13 +611,12 @@ class Score:
             slots[comm.rank] = out
             by_rank = comm.allreduce_sum(slots)
             self.before = np.ascontiguousarray(by_rank[:comm.rank].sum(axis=0)) if comm.rank > 0 else None
-            run = None
-            for r in range(comm.world):
+
+            def step(run):
                 mine = np.zeros_like(out)
-                if r == comm.rank:
-                    check(_lib.load().wgs_score_total_from(self._h, f64p(run) if run is not None else None, f64p(mine)))
-                run = np.ascontiguousarray(comm.allreduce_sum(mine))      # only rank r contributes: a broadcast
-            return run
+                check(_lib.load().wgs_score_total_from(self._h, f64p(run) if run is not None else None, f64p(mine)))
+                return mine
+            return relay(comm, step, out.shape, np.float64)
         self.before = None
         return out
 
@@ -637,7 +628,6 @@ class Score:
             self.sums(MODE_EXACT, comm)
         lib = _lib.load()
         world = comm.world if comm is not None else 1
-        rank = comm.rank if comm is not None else 0
         start = self.before
         check(lib.wgs_score_chains_prepare(self._h, int(P), f64p(start) if start is not None else None))
         self.ms["chains"] = last_assign_ms(self.b.ctx)
@@ -648,16 +638,12 @@ class Score:
             check(lib.wgs_score_chains_walk_all(self._h, handle, f32p(parts)))
             self.ms["walk"] = last_assign_ms(self.b.ctx)
             return parts
-        carry = None
-        for r in range(world):
-            mine = np.zeros((self.n * P, self.K), dtype=np.float64)
-            if r == rank:
-                check(lib.wgs_score_chains_walk(self._h, f32p(carry) if carry is not None else None, f32p(parts)))
-                self.ms["walk"] = last_assign_ms(self.b.ctx)
-                mine = parts.astype(np.float64)
-            mine = comm.allreduce_sum(mine)      # only rank r contributes: a broadcast of its float32 values
-            carry = np.ascontiguousarray(mine.astype(np.float32))
-        return carry
+
+        def step(carry):
+            check(lib.wgs_score_chains_walk(self._h, f32p(carry) if carry is not None else None, f32p(parts)))
+            self.ms["walk"] = last_assign_ms(self.b.ctx)
+            return parts
+        return relay(comm, step, parts.shape, np.float32)
 
     def chunk_sums(self):
         """Test hook: the last sums() per chunk of 8192 sites, (chunks, n, K) float64 (wgs_debug_score_chunks)."""
@@ -699,17 +685,10 @@ def partition_sums_exact(beagle, afset, colptr=None, P=1, comm=None, literal=Fal
             sc.close()
     _keep, cp = _colptr_arg(colptr, n, K)
     lib = _lib.load()
-    world = comm.world if comm is not None else 1
-    rank = comm.rank if comm is not None else 0
-    carry = None
     parts = np.zeros((n * P, K), dtype=np.float32)
-    for r in range(world):
-        mine = np.zeros((n * P, K), dtype=np.float64)
-        if r == rank:
-            check(lib.wgs_debug_parts_exact_literal(beagle.handle, afset.handle, cp, int(P),
-                                                    f32p(carry) if carry is not None else None, f32p(parts)))
-            mine = parts.astype(np.float64)
-        if world > 1:
-            mine = comm.allreduce_sum(mine)      # only rank r contributes: a broadcast of its float32 values
-        carry = np.ascontiguousarray(mine.astype(np.float32))
-    return carry if world > 1 else parts
+
+    def step(carry):
+        check(lib.wgs_debug_parts_exact_literal(beagle.handle, afset.handle, cp, int(P),
+                                                f32p(carry) if carry is not None else None, f32p(parts)))
+        return parts
+    return relay(comm, step, parts.shape, np.float32)

@@ -47,7 +47,7 @@ def fisher_obs_ind(L, af, IDs, t=1, beagle=None, comm=None, m_total=None, exact_
     if comm is not None and comm.world > 1:
         # np.mean's running float32 total handed from shard to shard in SNP order (shards start at multiples of NumPy's
         # 8192-element chunks: comm.shard_range); the batches must be the same on every rank
-        from .comm import SHARD_ALIGN, shard_range
+        from .comm import SHARD_ALIGN, relay, shard_range
         out = np.zeros(beagle.n, dtype=np.float32)
         group_of = beagle.group_of
         aligned = m_total // comm.world >= SHARD_ALIGN          # else the shards cut through NumPy's summation tree
@@ -72,14 +72,13 @@ def fisher_obs_ind(L, af, IDs, t=1, beagle=None, comm=None, m_total=None, exact_
                     out[i + r] = out[i + r] + np.mean(full[r])                  # fisher.py:59
                 i = j
                 continue
-            run = None
-            for r in range(comm.world):
+
+            def step(run):
                 mine = np.zeros(j - i, dtype=np.float32)
-                if r == comm.rank:
-                    _lib.check(lib.wgs_fisher_ind_sums(beagle.handle, afs.handle, i, j - i, _lib.f32p(run) if run is not None else None,
-                                                       _lib.f32p(mine)))
-                # only rank r contributes: a broadcast of float32 values (exact in float64)
-                run = np.ascontiguousarray(comm.allreduce_sum(mine.astype(np.float64)).astype(np.float32))
+                _lib.check(lib.wgs_fisher_ind_sums(beagle.handle, afs.handle, i, j - i, _lib.f32p(run) if run is not None else None,
+                                                   _lib.f32p(mine)))
+                return mine
+            run = relay(comm, step, (j - i,), np.float32)
             out[i:j] = (run.astype(np.float64) / m_total).astype(np.float32)      # np.mean: float64 division, float32 result
             i = j
     else:
