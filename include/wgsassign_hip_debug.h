@@ -79,6 +79,13 @@ int wgs_debug_log_values(wgs_ctx *ctx, const float *x, float *out, int64_t n, in
  * *nchunks is set) receives ceil(blocks / 2) x n*K float64, out[c * n*K + i * K + k]. */
 int wgs_debug_score_chunks(wgs_score *sc, double *out, int64_t *nchunks);
 
+/* What the last wgs_score_sums of this object decided before it enqueued anything (csrc/score_api.hip: score_plan_sums):
+ * info[0] 0 = the sweep over the float32 slabs, 1 = through the class codes; [1] populations per register batch and [2] pairs of
+ * individuals per wavefront of the sweep; [3], [4] the same of the chain kernel of wgs_score_chains_prepare (both known from
+ * wgs_score_create on); and of the coded sweep (0, 0, 1 otherwise): [5] SNPs per table, [6] bytes per table element, [7] workgroups
+ * that share a block. */
+int wgs_debug_score_plan(wgs_score *sc, int32_t info[8]);
+
 /* The two device kernels around a tagged RCCL collective (csrc/rccl_comm.hip: the row every rank writes behind the payload, the
  * comparison of all ranks' rows with one's own behind the all-reduce) on rows made up by the caller: what the ranks of a world-rank
  * job would run -- RCCL refuses two ranks on one GPU, so no test reaches them otherwise.  rows: world x 8 float64 {sequence number,

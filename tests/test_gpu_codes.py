@@ -66,6 +66,15 @@ def fit_and_score(dev, b, K, counts, mode=None):
     return [int(x) for x in iters], np.stack(cols, axis=1), out
 
 
+def scored_path(dev, b, afs):
+    """0: a scoring sweep of these frequencies runs over the float32 slabs, 1: through the class codes (Score.plan)"""
+    sc = dev.Score(b, afs)
+    sc.sums()
+    path = sc.plan()["path"]
+    sc.close()
+    return path
+
+
 @pytest.mark.parametrize("m,n,K,slots", [(1, 3, 1, 64), (63, 9, 2, 128), (4097, 37, 4, 256), (20_011, 61, 5, 64), (70_003, 103, 7, 128), (300_017, 64, 10, 64),
                                          (40_000, 130, 13, 256), (9_000, 257, 20, 64), (20_000, 230, 3, 128), (6_000, 499, 4, 256), (6_000, 499, 4, 0)])
 def test_coded_kernels_equal_direct_kernels_and_oracle(dev, oracle, m, n, K, slots, monkeypatch):
@@ -88,11 +97,15 @@ def test_coded_kernels_equal_direct_kernels_and_oracle(dev, oracle, m, n, K, slo
     b = dev.DeviceBeagle.from_host(L, group_of, K)
     with codes(False):
         it0, af0, out0 = fit_and_score(dev, b, K, counts)
+        afs = dev.AFSet.from_host(af0)
+        assert scored_path(dev, b, afs) == 0
     with codes(True):
         info = b.codes_info()
         assert info["available"] and 1 <= info["max_classes"] <= 64 and info["mean_classes"] <= info["max_classes"]
         assert info["rich_snp_share"] == 0 and info["hash_slots"] == (slots or 64) and info["em_table_rows"] > 0
         it1, af1, out1 = fit_and_score(dev, b, K, counts)
+        assert scored_path(dev, b, afs) == 1
+        afs.close()
         from wgsassign_amd._lib import MODE_FAST
         _, _, fast1 = fit_and_score(dev, b, K, counts, mode=MODE_FAST)
     with codes(False):
@@ -126,9 +139,11 @@ def test_special_values_through_the_class_table(dev, oracle):
     afs = dev.AFSet.from_host(A)
     with codes(False):
         out0, _ = dev.assign(b, afs)
+        assert scored_path(dev, b, afs) == 0
     with codes(True):
         assert b.codes_info()["available"]
         out1, _ = dev.assign(b, afs)
+        assert scored_path(dev, b, afs) == 1
     assert same_nan(out1, out0) and (np.isinf(out1).any() or np.isnan(out1).any())
     with np.errstate(all="ignore"):
         assert same_nan(out1.astype(np.float32), oracle.assignLL(L, A.copy(), 4))

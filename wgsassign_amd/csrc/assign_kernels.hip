@@ -258,10 +258,6 @@ constexpr int sweep_waves_per_simd(int KB, int NP, int MODE, bool PER_IND)
     if (MODE == WGS_MODE_EXACT) return (KB * NP <= 8 && KB != 8) ? 3 : 2;
     return (KB * NP > 10 || KB > 8) ? 2 : 3;
 }
-// Pairs of slab columns per wave: two halve the per-tile frequency loads and conversions per term (measured
-// 174 -> 150 ms at K = 10 as two passes of 5) while the accumulators leave room for it.
-constexpr int sweep_pairs(int KB, bool PER_IND) { return KB <= (PER_IND ? 4 : 6) ? 2 : 1; }
-constexpr int chain_pairs(int KB, bool PER_IND) { return !PER_IND && KB <= 4 ? 2 : 1; }
 
 template <int KB, int NP, int MODE, bool PER_IND>
 __global__ __launch_bounds__(256, sweep_waves_per_simd(KB, NP, MODE, PER_IND)) void score_sweep_kernel(ScoreArgs A)
@@ -408,12 +404,6 @@ __global__ __launch_bounds__(256, sweep_waves_per_simd(KB, NP, MODE, PER_IND)) v
 // order, so S[block][cell] -- and everything built on it: NumPy-order totals, chain predictions -- is unchanged.
 // Cost per (SNP, individual, population): a quarter of an LDS read, one conversion, one add (41.6 instructions in the
 // direct sweep) plus classes/individuals of the table work.
-struct CodedSlab {
-    const uint32_t *codes;
-    const int32_t *members;
-    const float4 *slab;            // the float32 slab, for the SNPs the encoder left uncoded (ncls = 0: too many classes)
-    int32_t nquads, ncols, quad0, col_lo, col_hi, npairs;
-};
 struct CodedScoreArgs {
     const float2 *dict;
     const uint8_t *ncls;
@@ -1267,15 +1257,30 @@ __global__ void log_values_kernel(const float *x, float *out, int64_t n, int use
     for (; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = use_libm ? (float)log((double)x[i]) : logf_of_f32(x[i], tab);
 }
 
-template <int KB>
-int launch_assign_kb(wgs_ctx *ctx, const AssignArgs &a, int mode, dim3 grid)
+// One compile-time dispatcher for every kernel family of this file: the launchers receive what the plan decided (common.h: ScorePlan)
+// as run-time values and these turn each into a constant -- f(std::integral_constant<int, KB>{}) for kb in LO .. HI, and the same for
+// the booleans, the mode and the coded sweep's table.  A value no instantiation exists for is an error, not another kernel.
+template <int LO, int HI, class F>
+int with_kb(int kb, F f)
 {
-    if (mode == WGS_MODE_EXACT)
-        hipLaunchKernelGGL((assign_kernel<KB, WGS_MODE_EXACT>), grid, dim3(256), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((assign_kernel<KB, WGS_MODE_FAST>), grid, dim3(256), 0, ctx->stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    if constexpr (LO < HI)
+        if (kb != LO) return with_kb<LO + 1, HI>(kb, f);
+    WGS_REQUIRE(kb == LO, "no kernel for a register batch of %d populations", kb);
+    return f(std::integral_constant<int, LO>{});
+}
+template <class F>
+int with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F>
+int with_mode(int mode, F f)
+{
+    return mode == WGS_MODE_EXACT ? f(std::integral_constant<int, WGS_MODE_EXACT>{}) : f(std::integral_constant<int, WGS_MODE_FAST>{});
+}
+template <class F>
+int with_table(int batch, int elem_bytes, F f)
+{
+    if (batch == 8) return f(double{}, std::integral_constant<int, 8>{});
+    if (batch == 4) return f(double{}, std::integral_constant<int, 4>{});
+    return elem_bytes == 8 ? f(double{}, std::integral_constant<int, 16>{}) : f(float{}, std::integral_constant<int, 16>{});
 }
 
 }  // namespace
@@ -1305,31 +1310,8 @@ int launch_log_values(wgs_ctx *ctx, const float *d_x, float *d_out, int64_t n, i
     return 0;
 }
 
-// KB = populations per register batch: the batch size with the fewest passes over K, then the least padding.
-// Every pass re-reads the block's GLs, so K <= 10 is ONE pass (HBM traffic = algorithmic bytes) and K = 20 two;
-// KB = 9, 10 run one pair per wave at 2 waves/SIMD (measured equal to two passes of 5 in exact mode -- the kernel is
-// bound by FP64 issue either way -- and 11 % faster in float32 mode).
-static int pick_kb(int K, int kb_max = 10)
-{
-    int best = 4, best_cost = 1 << 30;
-    for (int kb = 4; kb <= kb_max; ++kb) {
-        const int passes = (K + kb - 1) / kb;
-        const int cost = passes * 1000 + passes * kb - K;
-        if (cost < best_cost) best_cost = cost, best = kb;
-    }
-    return best;
-}
-
-int score_pairs_per_wave(int K, bool per_ind) { return sweep_pairs(pick_kb(K), per_ind); }
-int score_kb(int K) { return pick_kb(K); }
-// The chain kernel keeps three float32 per (cell, lane) instead of one float64; with per-individual columns
-// its pointer and frequency tables leave room for one pair only.
-// It stays with batches of at most 8 populations (9 and 10 would spill).
-static int pick_kb_chain(int K) { return pick_kb(K, 8); }
-int chain_pairs_per_wave(int K, bool per_ind) { return chain_pairs(pick_kb_chain(K), per_ind); }
-
 // The float64 partition sums of WGSASSIGN_PARTS=fast (P > 1): lane <-> individual pair, one slab per launch.
-int launch_assign(wgs_ctx *ctx, const AssignArgs &a_in, int mode)
+int launch_assign(wgs_ctx *ctx, const AssignArgs &a_in, int kb, int mode)
 {
     if (ensure_log_table(ctx)) return 1;
     AssignArgs a = a_in;
@@ -1345,48 +1327,33 @@ int launch_assign(wgs_ctx *ctx, const AssignArgs &a_in, int mode)
     a.tiles_per_wave = (int32_t)(tpw > 0x7fffffff ? 0x7fffffff : tpw);
     const int64_t waves = (ntiles + a.tiles_per_wave - 1) / a.tiles_per_wave;
     dim3 grid((unsigned)((waves + 3) / 4), (unsigned)pairblocks);
-    switch (pick_kb(a.K, 8)) {
-        case 4: return launch_assign_kb<4>(ctx, a, mode, grid);
-        case 5: return launch_assign_kb<5>(ctx, a, mode, grid);
-        case 6: return launch_assign_kb<6>(ctx, a, mode, grid);
-        case 7: return launch_assign_kb<7>(ctx, a, mode, grid);
-        default: return launch_assign_kb<8>(ctx, a, mode, grid);
-    }
+    return with_kb<4, 8>(kb, [&](auto KB) {
+        return with_mode(mode, [&](auto MODE) {
+            hipLaunchKernelGGL((assign_kernel<KB.value, MODE.value>), grid, dim3(256), 0, ctx->stream, a);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        });
+    });
 }
 
-#define WGS_FOR_KB(X, K)                \
-    switch (pick_kb(K)) {               \
-        case 4: X(4); break;            \
-        case 5: X(5); break;            \
-        case 6: X(6); break;            \
-        case 7: X(7); break;            \
-        case 8: X(8); break;            \
-        case 9: X(9); break;            \
-        default: X(10); break;          \
-    }
-
-int launch_score_sweep(wgs_ctx *ctx, const ScoreArgs &a, int mode)
+int launch_score_sweep(wgs_ctx *ctx, const ScoreArgs &a, int kb, int np, int mode)
 {
     if (a.m <= 0 || a.total_pg <= 0 || a.K <= 0 || a.nblocks <= 0) return 0;
     if (ensure_log_table(ctx)) return 1;
     const int64_t waves = (int64_t)a.total_pg * a.nblocks;
     WGS_REQUIRE(waves < (1ll << 32), "scoring sweep: too many work units for one launch");
     dim3 grid((unsigned)((waves + 3) / 4));
-    const bool per_ind = a.colptr != nullptr;
-#define WGS_SWEEP(KB)                                                                                                                          \
-    do {                                                                                                                                       \
-        if (mode == WGS_MODE_EXACT) {                                                                                                          \
-            if (per_ind) hipLaunchKernelGGL((score_sweep_kernel<KB, sweep_pairs(KB, true), WGS_MODE_EXACT, true>), grid, dim3(256), 0, ctx->stream, a);   \
-            else hipLaunchKernelGGL((score_sweep_kernel<KB, sweep_pairs(KB, false), WGS_MODE_EXACT, false>), grid, dim3(256), 0, ctx->stream, a);         \
-        } else {                                                                                                                               \
-            if (per_ind) hipLaunchKernelGGL((score_sweep_kernel<KB, sweep_pairs(KB, true), WGS_MODE_FAST, true>), grid, dim3(256), 0, ctx->stream, a);    \
-            else hipLaunchKernelGGL((score_sweep_kernel<KB, sweep_pairs(KB, false), WGS_MODE_FAST, false>), grid, dim3(256), 0, ctx->stream, a);          \
-        }                                                                                                                                      \
-    } while (0)
-    WGS_FOR_KB(WGS_SWEEP, a.K)
-#undef WGS_SWEEP
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return with_kb<4, 10>(kb, [&](auto KB) {
+        return with_bool(a.colptr != nullptr, [&](auto PER_IND) {
+            return with_mode(mode, [&](auto MODE) {
+                constexpr int NP = sweep_pairs(KB.value, PER_IND.value);
+                WGS_REQUIRE(np == NP, "scoring sweep: planned for %d pairs per wave, the kernel takes %d", np, NP);
+                hipLaunchKernelGGL((score_sweep_kernel<KB.value, NP, MODE.value, PER_IND.value>), grid, dim3(256), 0, ctx->stream, a);
+                HIP_TRY(hipGetLastError());
+                return 0;
+            });
+        });
+    });
 }
 
 // S[block][cell] = ((Sp[0] + Sp[1]) + Sp[2]) + ... over the parts of a block: a fixed order (and exact anyway while the
@@ -1400,34 +1367,35 @@ __global__ __launch_bounds__(256) void combine_parts_kernel(const double *__rest
     S[e] = acc;
 }
 
-// float table rows where they need (almost) no padding to 16 bytes, float64 rows (no conversion in phase 2) elsewhere
-static bool score_coded_wide(int kb)
+int launch_combine_parts(wgs_ctx *ctx, const double *Sp, double *S, int64_t total, int parts)
 {
-    const char *e = getenv("WGS_SCORE_CODED_TABLE");
-    if (e && e[0] == 'f') return false;
-    if (e && e[0] == 'd') return true;
-    return ((kb + 3) & ~3) - kb > 1;
+    if (total <= 0) return 0;
+    hipLaunchKernelGGL(combine_parts_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, Sp, S, total, parts);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
-size_t score_coded_lds_bytes(int rows, int kb, int batch)
+
+size_t score_coded_lds_bytes(int rows, int kb, int elem_bytes)
 {
-    const size_t row = (batch < 16 || score_coded_wide(kb)) ? sizeof(double) * (kb | 1) : sizeof(float) * ((kb + 3) & ~3);
+    const size_t row = elem_bytes == 8 ? sizeof(double) * (kb | 1) : sizeof(float) * ((kb + 3) & ~3);
     return sizeof(double2) * WGS_LOG_N * CODED_LOG_REP + ((2 * sizeof(CodedPrep) + 15) & ~(size_t)15) + sizeof(float2) * (size_t)((rows + 1) & ~1) +
            row * (size_t)(rows + 1);                      // (+ the row of zeros that absent and uncoded SNPs read)
 }
 
 // The scoring sweep through the class codes (shared columns only).  d_slabs: n_slabs CodedSlab records in device memory.
-int launch_score_coded(wgs_ctx *ctx, const wgs_codes *c, const void *d_slabs, int n_slabs, int total_quads, const float *const *d_acol,
-                       int64_t m, int64_t cells, int K, int nblocks, double *S, int mode)
+int launch_score_coded(wgs_ctx *ctx, const ScorePlan &p, const CodedSlab *d_slabs, int n_slabs, const float *const *d_acol, int64_t m,
+                       int64_t cells, int K, int nblocks, double *S, int mode)
 {
-    if (m <= 0 || total_quads <= 0 || K <= 0 || nblocks <= 0) return 0;
+    if (m <= 0 || p.total_quads <= 0 || K <= 0 || nblocks <= 0) return 0;
     if (ensure_log_table(ctx)) return 1;
+    const wgs_codes *c = p.codes;
     CodedScoreArgs A;
     A.dict = c->dict;
     A.ncls = c->ncls;
-    A.slabs = reinterpret_cast<const CodedSlab *>(d_slabs);
+    A.slabs = d_slabs;
     A.n_slabs = n_slabs;
     A.drows = c->drows;
-    A.total_quads = total_quads;
+    A.total_quads = p.total_quads;
     A.acol = d_acol;
     A.m = m;
     A.cells = cells;
@@ -1435,69 +1403,22 @@ int launch_score_coded(wgs_ctx *ctx, const wgs_codes *c, const void *d_slabs, in
     A.nblocks = nblocks;
     A.S = S;
     A.table_rows = c->rows_batch;
+    A.parts = p.parts;
     void *sym = nullptr;
     HIP_TRY(hipGetSymbolAddress(&sym, HIP_SYMBOL(wgs_log_table_dev)));
     A.logtab = reinterpret_cast<const double2 *>(sym);
-    const int kb = pick_kb(K);
-    const int batch = c->score_batch;
-    const bool wide = batch < 16 || score_coded_wide(kb);          // (the 8- and 4-SNP tables exist with float64 rows only)
-    const size_t lds = score_coded_lds_bytes(c->rows_batch, kb, batch);
-    WGS_REQUIRE(lds <= 64 * 1024, "class table too large for LDS");
-    const unsigned ygroups = (unsigned)((total_quads + 255) / 256);
-    // A block's 64 tiles go to `parts` workgroups: enough of them to fill the chip (short matrices), and -- the workgroups all take
-    // the same time -- a count that does not leave the last round of workgroups mostly empty: 2442 blocks on 768 places (3 per CU by
-    // registers, fewer when the table is large) are 3.18 rounds, i.e. a fifth of the chip-time idle; in halves 6.36 of 7, in quarters
-    // 12.7 of 13.
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / std::max<size_t>(lds, 1)));
-    const double places = (double)std::max(1, ctx->cus) * per_cu;
-    // Any count from 1 to 16 whose runs of ceil(64 / parts) tiles are all non-empty (round 5, late: the powers of two alone left a
-    // shard of 1.25M SNPs -- 306 blocks -- at 6.4 rounds of 7 with 16 parts; 5 parts are 1.99 rounds of 2).  The workgroups all take
-    // about the same time, a run's tiles plus what a workgroup costs before its first one (the log table, the first batch's trips to
-    // memory: about a tile's worth), so the split with the fewest rounds x (tiles per run + 1) wins -- tools/probe_score_parts.py
-    // times every split: 5 at 1.25M SNPs (1.44 ms; 16: 1.59), 10 at 300 k (0.45 ms; 16: 0.46, 4: 0.73), 3-5 or 12 at 10M (within 2 %).
-    auto usable = [](int p) { return (p - 1) * ((WGS_BLOCK_TILES + p - 1) / p) < WGS_BLOCK_TILES; };
-    int parts = 1;
-    {
-        double best_cost = 0.0;
-        for (int p = 1; p <= 16; ++p) {
-            if (!usable(p)) continue;
-            const double rounds = ceil((double)nblocks * ygroups * p / places);
-            const double cost = rounds * (double)((WGS_BLOCK_TILES + p - 1) / p + 1);
-            if (p == 1 || cost < best_cost - 1e-9) parts = p, best_cost = cost;
-        }
-    }
-    if (const char *pe = getenv("WGS_SCORE_CODED_PARTS")) {        // experiments: 1 .. 16
-        const int v = atoi(pe);
-        if (v >= 1 && v <= 16 && usable(v)) parts = v;
-    }
-    A.parts = parts;
-    const int64_t total = (int64_t)nblocks * cells;
-    if (parts > 1) {
-        void *ws = nullptr;
-        if (wgs_ctx_workspace(ctx, sizeof(double) * (size_t)total * parts, &ws)) return 1;
-        HIP_TRY(hipMemsetAsync(ws, 0, sizeof(double) * (size_t)total * parts, ctx->stream));   // rows outside the scored range stay 0
-        A.S = reinterpret_cast<double *>(ws);
-    }
-    dim3 grid((unsigned)nblocks, ygroups, (unsigned)parts);
-#define WGS_CODED(KB)                                                                                                     \
-    do {                                                                                                                  \
-        if (batch == 8) {                                                                                                 \
-            if (mode == WGS_MODE_EXACT) hipLaunchKernelGGL((score_coded_kernel<KB, WGS_MODE_EXACT, double, 8>), grid, dim3(256), lds, ctx->stream, A); \
-            else hipLaunchKernelGGL((score_coded_kernel<KB, WGS_MODE_FAST, double, 8>), grid, dim3(256), lds, ctx->stream, A); \
-        } else if (batch == 4) {                                                                                          \
-            if (mode == WGS_MODE_EXACT) hipLaunchKernelGGL((score_coded_kernel<KB, WGS_MODE_EXACT, double, 4>), grid, dim3(256), lds, ctx->stream, A); \
-            else hipLaunchKernelGGL((score_coded_kernel<KB, WGS_MODE_FAST, double, 4>), grid, dim3(256), lds, ctx->stream, A); \
-        } else if (wide) {                                                                                                \
-            if (mode == WGS_MODE_EXACT) hipLaunchKernelGGL((score_coded_kernel<KB, WGS_MODE_EXACT, double, 16>), grid, dim3(256), lds, ctx->stream, A); \
-            else hipLaunchKernelGGL((score_coded_kernel<KB, WGS_MODE_FAST, double, 16>), grid, dim3(256), lds, ctx->stream, A); \
-        } else {                                                                                                          \
-            if (mode == WGS_MODE_EXACT) hipLaunchKernelGGL((score_coded_kernel<KB, WGS_MODE_EXACT, float, 16>), grid, dim3(256), lds, ctx->stream, A); \
-            else hipLaunchKernelGGL((score_coded_kernel<KB, WGS_MODE_FAST, float, 16>), grid, dim3(256), lds, ctx->stream, A); \
-        }                                                                                                                 \
-    } while (0)
-    WGS_FOR_KB(WGS_CODED, K)
-#undef WGS_CODED
-    HIP_TRY(hipGetLastError());
+    dim3 grid((unsigned)nblocks, (unsigned)((p.total_quads + 255) / 256), (unsigned)p.parts);
+    const int rc = with_kb<4, 10>(p.kb, [&](auto KB) {
+        return with_mode(mode, [&](auto MODE) {
+            return with_table(p.score_batch, p.elem_bytes, [&](auto tv, auto BATCH) {
+                hipLaunchKernelGGL((score_coded_kernel<KB.value, MODE.value, decltype(tv), BATCH.value>), grid, dim3(256), p.lds,
+                                   ctx->stream, A);
+                HIP_TRY(hipGetLastError());
+                return 0;
+            });
+        });
+    });
+    if (rc) return rc;
 #ifdef WGS_SCORE_STATS
     {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1509,10 +1430,6 @@ int launch_score_coded(wgs_ctx *ctx, const wgs_codes *c, const void *d_slabs, in
                 "barrier %.0f\n", st[6], nb / w, st[0] / nb, st[1] / nb, st[2] / nb, st[3] / nb, st[4] / nb);
     }
 #endif
-    if (parts > 1) {
-        hipLaunchKernelGGL(combine_parts_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, A.S, S, total, parts);
-        HIP_TRY(hipGetLastError());
-    }
     return 0;
 }
 
@@ -1533,37 +1450,25 @@ int launch_chunk_total(wgs_ctx *ctx, const double *chunks, int nchunks, int64_t 
     return 0;
 }
 
-size_t chain_cand_lds_bytes(int K, int P, bool per_ind)
-{
-    const int kb = pick_kb_chain(K), np = chain_pairs_per_wave(K, per_ind);
-    return (size_t)4 * 2 * (np * 2 * kb) * P * sizeof(unsigned);
-}
+size_t chain_cand_lds_bytes(int kb, int np, int P) { return (size_t)4 * 2 * (np * 2 * kb) * P * sizeof(unsigned); }
 
-int launch_chain_cand(wgs_ctx *ctx, const ScoreArgs &a)
+int launch_chain_cand(wgs_ctx *ctx, const ScoreArgs &a, int kb, int np)
 {
     if (a.m <= 0 || a.total_pg <= 0 || a.K <= 0 || a.nblocks <= 0) return 0;
     if (ensure_log_table(ctx)) return 1;
     const int64_t waves = (int64_t)a.total_pg * a.nblocks;
     WGS_REQUIRE(waves < (1ll << 32), "partition chains: too many work units for one launch");
     dim3 grid((unsigned)((waves + 3) / 4));
-    const bool per_ind = a.colptr != nullptr;
-    const size_t lds = chain_cand_lds_bytes(a.K, a.P, per_ind);
-    WGS_REQUIRE(lds <= 96 * 1024, "partition chains: too many partitions for the block-parallel kernel");
-#define WGS_CAND(KB)                                                                                                                  \
-    do {                                                                                                                              \
-        if (per_ind) hipLaunchKernelGGL((chain_cand_kernel<KB, chain_pairs(KB, true), true>), grid, dim3(256), lds, ctx->stream, a);  \
-        else hipLaunchKernelGGL((chain_cand_kernel<KB, chain_pairs(KB, false), false>), grid, dim3(256), lds, ctx->stream, a);        \
-    } while (0)
-    switch (pick_kb_chain(a.K)) {
-        case 4: WGS_CAND(4); break;
-        case 5: WGS_CAND(5); break;
-        case 6: WGS_CAND(6); break;
-        case 7: WGS_CAND(7); break;
-        default: WGS_CAND(8); break;
-    }
-#undef WGS_CAND
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return with_kb<4, 8>(kb, [&](auto KB) {
+        return with_bool(a.colptr != nullptr, [&](auto PER_IND) {
+            constexpr int NP = chain_pairs(KB.value, PER_IND.value);
+            WGS_REQUIRE(np == NP, "partition chains: planned for %d pairs per wave, the kernel takes %d", np, NP);
+            hipLaunchKernelGGL((chain_cand_kernel<KB.value, NP, PER_IND.value>), grid, dim3(256), chain_cand_lds_bytes(KB.value, NP, a.P),
+                               ctx->stream, a);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        });
+    });
 }
 
 int launch_chain_walk(wgs_ctx *ctx, const WalkArgs &w)

@@ -379,7 +379,7 @@ struct AssignArgs {
     int32_t npairs, ncols, K, P;
     int32_t tiles_per_wave;
 };
-int launch_assign(wgs_ctx *ctx, const AssignArgs &a, int mode);
+int launch_assign(wgs_ctx *ctx, const AssignArgs &a, int kb, int mode);      // kb: ScorePlan::chain_kb (4 .. 8)
 struct PartsSlab {     // one population slab inside the single exact-partition launch
     const float4 *slab;
     const int32_t *members;
@@ -429,23 +429,42 @@ struct WalkArgs {
     int32_t n, K, P, nblocks, row_lo, row_hi;
     int32_t *n_serial;             // device counter: blocks that took the literal serial loop (or nullptr)
 };
-int score_pairs_per_wave(int K, bool per_ind); // NP of the sweep for K populations (depends on the register batch KB)
-int chain_pairs_per_wave(int K, bool per_ind); // NP of the chain kernel (the slab table must be built for it)
-int launch_score_sweep(wgs_ctx *ctx, const ScoreArgs &a, int mode);
-struct CodedSlabHost {             // = CodedSlab of assign_kernels.hip
+struct CodedSlab {                 // one population slab of the sweep through the class codes (score_coded_kernel)
     const uint32_t *codes;
     const int32_t *members;
-    const float4 *slab;            // the float32 slab: SNPs the encoder left uncoded (ncls = 0) are scored from it
+    const float4 *slab;            // the float32 slab, for the SNPs the encoder left uncoded (ncls = 0: too many classes)
     int32_t nquads, ncols, quad0, col_lo, col_hi, npairs;
 };
-int score_kb(int K);                                   // populations per pass of the scoring sweeps
-size_t score_coded_lds_bytes(int rows, int kb, int batch);   // LDS of the coded sweep for a matrix whose richest batch of SNPs has `rows` classes
-int launch_score_coded(wgs_ctx *ctx, const wgs_codes *c, const void *d_slabs, int n_slabs, int total_quads, const float *const *d_acol,
-                       int64_t m, int64_t cells, int K, int nblocks, double *S, int mode);
+// Pairs of slab columns per wave: two halve the per-tile frequency loads and conversions per term (measured
+// 174 -> 150 ms at K = 10 as two passes of 5) while the accumulators leave room for it.
+// The chain kernel keeps three float32 per (cell, lane) instead of one float64; with per-individual columns
+// its pointer and frequency tables leave room for one pair only.
+constexpr int sweep_pairs(int KB, bool PER_IND) { return KB <= (PER_IND ? 4 : 6) ? 2 : 1; }
+constexpr int chain_pairs(int KB, bool PER_IND) { return !PER_IND && KB <= 4 ? 2 : 1; }
+// What one scoring call does, decided before anything of it is enqueued (score_api.hip: score_plan_shape at wgs_score_create,
+// score_plan_sums per sweep); the launchers below select the instantiation it names and decide nothing.
+struct ScorePlan {
+    wgs_codes *codes = nullptr;        // the sweep goes through these class codes; nullptr: over the float32 slabs
+    int kb = 0, np = 0;                // populations per register batch and pairs per wave of the sweep (the slab tables are built for np)
+    int chain_kb = 0, chain_np = 0;    // ... of the chain kernel
+    // of the coded sweep (codes != nullptr):
+    int score_batch = 0;               // SNPs per LDS table: 16, 8 or 4
+    int elem_bytes = 0;                // of a table element: 4 (float rows) or 8 (float64 rows)
+    size_t lds = 0;                    // bytes of LDS per workgroup
+    int total_quads = 0;               // quads of individuals over the slabs that hold scored ones
+    int parts = 1;                     // workgroups that share a block's 64 tiles; > 1: they write to the context workspace
+    bool combine() const { return parts > 1; }     //   and combine_parts_kernel adds the parts up in a fixed order
+};
+int launch_score_sweep(wgs_ctx *ctx, const ScoreArgs &a, int kb, int np, int mode);     // np must be sweep_pairs(kb, per-individual)
+size_t score_coded_lds_bytes(int rows, int kb, int elem_bytes);   // LDS of the coded sweep for a matrix whose richest batch of SNPs has `rows` classes
+// S: [nblocks][cells] block sums, or with p.combine() [parts][nblocks][cells] (zeroed by the caller)
+int launch_score_coded(wgs_ctx *ctx, const ScorePlan &p, const CodedSlab *d_slabs, int n_slabs, const float *const *d_acol, int64_t m,
+                       int64_t cells, int K, int nblocks, double *S, int mode);
+int launch_combine_parts(wgs_ctx *ctx, const double *Sp, double *S, int64_t total, int parts);
 int launch_block_prefix(wgs_ctx *ctx, double *S, int nblocks, int64_t cells, double *out, int keep_prefix, double *chunks);
 int launch_chunk_total(wgs_ctx *ctx, const double *chunks, int nchunks, int64_t cells, const double *carry, double *out);
-size_t chain_cand_lds_bytes(int K, int P, bool per_ind);
-int launch_chain_cand(wgs_ctx *ctx, const ScoreArgs &a);
+size_t chain_cand_lds_bytes(int kb, int np, int P);
+int launch_chain_cand(wgs_ctx *ctx, const ScoreArgs &a, int kb, int np);                // np must be chain_pairs(kb, per-individual)
 int launch_chain_walk(wgs_ctx *ctx, const WalkArgs &w);
 int launch_log_mismatch(wgs_ctx *ctx, unsigned int b0, unsigned int b1, unsigned long long *d_count, unsigned int *d_first);
 int launch_log_values(wgs_ctx *ctx, const float *d_x, float *d_out, int64_t n, int use_libm);

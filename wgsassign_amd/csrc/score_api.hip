@@ -9,6 +9,186 @@
 
 #include "common.h"
 
+struct wgs_score {
+    wgs_beagle *b = nullptr;
+    wgs_afset *a = nullptr;
+    int32_t K = 0, row_lo = 0, row_hi = 0, nblocks = 0, P = 0;
+    int64_t n = 0, cells = 0;
+    bool per_ind = false, have_prefix = false;
+    const float **d_acol = nullptr, **d_colptr = nullptr;
+    ScoreSlab *d_slabs[2] = {nullptr, nullptr};      // [0] table of the sweep, [1] table of the chain kernel
+    int n_slabs[2] = {0, 0}, total_pg[2] = {0, 0};
+    double *d_S = nullptr, *d_out = nullptr, *d_start = nullptr, *d_run = nullptr, *d_chunks = nullptr;     // d_chunks: [ceil(nblocks/2)][cells]
+    uint32_t *d_cand = nullptr;
+    float *d_carry = nullptr, *d_parts = nullptr;
+    int32_t *d_nserial = nullptr;
+    int32_t last_serial_blocks = 0;
+    CodedSlab *d_coded = nullptr;         // slab table of the sweep through the class codes (shared columns)
+    int n_coded = 0, coded_quads = 0;     // its records and the quads of individuals they cover
+    int64_t coded_generation = -1;        // wgs_codes::generation of the build d_coded was made from
+    ScorePlan plan;                       // the shape since wgs_score_create, all of it of the last wgs_score_sums (wgs_debug_score_plan)
+};
+
+/* f(g, slab, col_lo, col_hi) for every population slab that holds individuals of [row_lo, row_hi): the members of a slab are in
+ * file order, so those are a contiguous column range. */
+template <class F>
+static void for_scored_slabs(const wgs_beagle *b, int64_t row_lo, int64_t row_hi, F f)
+{
+    for (int g = 0; g < b->n_groups; ++g) {
+        const Slab &s = b->slabs[g];
+        const int lo = (int)(std::lower_bound(s.members.begin(), s.members.end(), row_lo) - s.members.begin());
+        const int hi = (int)(std::lower_bound(s.members.begin(), s.members.end(), row_hi) - s.members.begin());
+        if (hi > lo) f(g, s, lo, hi);          // (an empty slab has no members)
+    }
+}
+
+// A slab table in pooled device memory (*d: what it replaces, or nullptr; stays nullptr for an empty table)
+template <class T>
+static int upload_table(wgs_ctx *ctx, const std::vector<T> &tab, T **d)
+{
+    if (*d) wgs_pool_free(ctx, *d);
+    *d = nullptr;
+    if (tab.empty()) return 0;
+    HIP_TRY(wgs_pool_malloc(ctx, d, sizeof(T) * tab.size()));
+    HIP_TRY(hipMemcpy(*d, tab.data(), sizeof(T) * tab.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// d_acol[k] = column k of the frequency set; `host` holds the pointers until the caller has synchronised `stream` (nullptr: a blocking copy)
+static hipError_t upload_columns(const wgs_afset *a, std::vector<const float *> &host, const float **d_acol, hipStream_t stream)
+{
+    host.resize(a->K);
+    for (int k = 0; k < a->K; ++k) host[k] = a->buf + (size_t)k * a->m;
+    if (!stream) return hipMemcpy(d_acol, host.data(), sizeof(float *) * a->K, hipMemcpyHostToDevice);
+    return hipMemcpyAsync(d_acol, host.data(), sizeof(float *) * a->K, hipMemcpyHostToDevice, stream);
+}
+
+// The buffers a wgs_score allocates when first needed and keeps
+template <class T>
+static hipError_t grow_once(wgs_score *sc, T **p, size_t bytes) { return *p ? hipSuccess : wgs_pool_malloc(sc->b->ctx, p, bytes); }
+
+// KB = populations per register batch: the batch size with the fewest passes over K, then the least padding.
+// Every pass re-reads the block's GLs, so K <= 10 is ONE pass (HBM traffic = algorithmic bytes) and K = 20 two;
+// KB = 9, 10 run one pair per wave at 2 waves/SIMD (measured equal to two passes of 5 in exact mode -- the kernel is
+// bound by FP64 issue either way -- and 11 % faster in float32 mode).
+static int pick_kb(int K, int kb_max = 10)
+{
+    int best = 4, best_cost = 1 << 30;
+    for (int kb = 4; kb <= kb_max; ++kb) {
+        const int passes = (K + kb - 1) / kb;
+        const int cost = passes * 1000 + passes * kb - K;
+        if (cost < best_cost) best_cost = cost, best = kb;
+    }
+    return best;
+}
+
+/* The shape of the plan -- register batches and pairs per wave, which the slab tables are built for: wgs_score_create and every
+ * launch take it from here.  The chain kernel (and the WGSASSIGN_PARTS=fast cross-check kernel) stays with batches of at most 8
+ * populations (9 and 10 would spill). */
+static ScorePlan score_plan_shape(int K, bool per_ind)
+{
+    ScorePlan p;
+    p.kb = pick_kb(K);
+    p.np = sweep_pairs(p.kb, per_ind);
+    p.chain_kb = pick_kb(K, 8);
+    p.chain_np = chain_pairs(p.chain_kb, per_ind);
+    return p;
+}
+
+// The block-parallel chains take P partitions while their tables fit 64 KiB of LDS and a chain's index 31 bits; else the literal chains
+static bool chains_block_parallel(const ScorePlan &p, int64_t cells, int32_t P)
+{
+    return chain_cand_lds_bytes(p.chain_kb, p.chain_np, P) <= 64 * 1024 && cells * P < (1ll << 31);
+}
+
+// The environment switches of scoring, read once per wgs_score_sums (tests and tools/probe_score_parts.py change them between calls)
+struct ScoreSwitches {
+    const char *env_table = getenv("WGS_SCORE_CODED_TABLE"), *env_parts = getenv("WGS_SCORE_CODED_PARTS");
+    char coded_table = env_table ? env_table[0] : 0;        // = f | d: float / float64 rows of the 16-SNP table whatever KB (experiments)
+    int coded_parts = env_parts ? atoi(env_parts) : 0;      // = 1 .. 16: workgroups per block of the coded sweep (experiments)
+};
+
+/* Slab table for NP pairs per wave, restricted to the individuals [row_lo, row_hi). */
+static int build_slab_table(wgs_score *sc, int np, int which)
+{
+    std::vector<ScoreSlab> tab;
+    int pg = 0;
+    for_scored_slabs(sc->b, sc->row_lo, sc->row_hi, [&](int, const Slab &s, int lo, int hi) {
+        const int pair0 = lo / 2, npg = ((hi - 1) / 2 - pair0 + 1 + np - 1) / np;
+        tab.push_back({s.base, s.d_members, s.npairs, s.ncols, pair0, npg, pg, lo, hi});
+        pg += npg;
+    });
+    sc->n_slabs[which] = (int)tab.size();
+    sc->total_pg[which] = pg;
+    return upload_table(sc->b->ctx, tab, &sc->d_slabs[which]);
+}
+
+/* The same for the sweep through the class codes. */
+static int build_coded_table(wgs_score *sc, const wgs_codes *codes)
+{
+    std::vector<CodedSlab> tab;
+    int quad0 = 0;
+    for_scored_slabs(sc->b, sc->row_lo, sc->row_hi, [&](int g, const Slab &s, int lo, int hi) {
+        const SlabCodes &c = codes->slabs[g];
+        tab.push_back({c.codes, s.d_members, s.base, c.nquads, s.ncols, quad0, lo, hi, s.npairs});
+        quad0 += c.nquads;
+    });
+    sc->n_coded = (int)tab.size();
+    sc->coded_quads = quad0;
+    if (upload_table(sc->b->ctx, tab, &sc->d_coded)) return 1;
+    sc->coded_generation = codes->generation;
+    return 0;
+}
+
+/* The plan of one wgs_score_sums: through the class codes or over the float32 slabs and, for the coded sweep, its table and how many
+ * workgroups share a block.  May build the codes and, for a new build of them, their slab table (its quads size the grid);
+ * enqueues no sweep. */
+static int score_plan_sums(wgs_score *sc, const ScoreSwitches &sw, ScorePlan *plan)
+{
+    wgs_ctx *ctx = sc->b->ctx;
+    ScorePlan &p = *plan = score_plan_shape(sc->K, sc->per_ind);
+    // shared columns + a codable matrix: the sweep through the class codes (same S, bit for bit)
+    // (built for this sweep only when what it saves exceeds the encode pass: codes.hip: wgs_codes_pay_for_scoring)
+    wgs_codes *codes = sc->per_ind ? nullptr : wgs_beagle_codes(sc->b, false);
+    if (!codes && !sc->per_ind && wgs_codes_pay_for_scoring(sc->b, sc->K)) codes = wgs_beagle_codes(sc->b, true, false, true);
+    if (!codes) return 0;
+    // float table rows where they need (almost) no padding to 16 bytes, float64 rows (no conversion in phase 2) elsewhere
+    // (the 8- and 4-SNP tables exist with float64 rows only)
+    const bool wide = codes->score_batch < 16 || sw.coded_table == 'd' || (sw.coded_table != 'f' && ((p.kb + 3) & ~3) - p.kb > 1);
+    const size_t lds = score_coded_lds_bytes(codes->rows_batch, p.kb, wide ? 8 : 4);
+    if (lds > 64 * 1024) return 0;             // class table too large for LDS
+    // (keyed on the build, not on the object's address: a rebuilt wgs_codes may reuse it)
+    if (sc->coded_generation != codes->generation && build_coded_table(sc, codes)) return 1;
+    p.codes = codes;
+    p.score_batch = codes->score_batch;
+    p.elem_bytes = wide ? 8 : 4;
+    p.lds = lds;
+    p.total_quads = sc->coded_quads;
+    if (sc->b->m <= 0 || p.total_quads <= 0 || sc->K <= 0 || sc->nblocks <= 0) return 0;     // (nothing to sweep)
+    const unsigned ygroups = (unsigned)((p.total_quads + 255) / 256);
+    // A block's 64 tiles go to `parts` workgroups: enough of them to fill the chip (short matrices), and -- the workgroups all take
+    // the same time -- a count that does not leave the last round of workgroups mostly empty: 2442 blocks on 768 places (3 per CU by
+    // registers, fewer when the table is large) are 3.18 rounds, i.e. a fifth of the chip-time idle; in halves 6.36 of 7, in quarters
+    // 12.7 of 13.
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / std::max<size_t>(lds, 1)));
+    const double places = (double)std::max(1, ctx->cus) * per_cu;
+    // Any count from 1 to 16 whose runs of ceil(64 / parts) tiles are all non-empty (round 5, late: the powers of two alone left a
+    // shard of 1.25M SNPs -- 306 blocks -- at 6.4 rounds of 7 with 16 parts; 5 parts are 1.99 rounds of 2).  The workgroups all take
+    // about the same time, a run's tiles plus what a workgroup costs before its first one (the log table, the first batch's trips to
+    // memory: about a tile's worth), so the split with the fewest rounds x (tiles per run + 1) wins -- tools/probe_score_parts.py
+    // times every split: 5 at 1.25M SNPs (1.44 ms; 16: 1.59), 10 at 300 k (0.45 ms; 16: 0.46, 4: 0.73), 3-5 or 12 at 10M (within 2 %).
+    auto usable = [](int q) { return (q - 1) * ((WGS_BLOCK_TILES + q - 1) / q) < WGS_BLOCK_TILES; };
+    double best_cost = 0.0;
+    for (int q = 1; q <= 16; ++q) {
+        if (!usable(q)) continue;
+        const double rounds = ceil((double)sc->nblocks * ygroups * q / places);
+        const double cost = rounds * (double)((WGS_BLOCK_TILES + q - 1) / q + 1);
+        if (q == 1 || cost < best_cost - 1e-9) p.parts = q, best_cost = cost;
+    }
+    if (sw.coded_parts >= 1 && sw.coded_parts <= 16 && usable(sw.coded_parts)) p.parts = sw.coded_parts;
+    return 0;
+}
+
 extern "C" {
 
 /* ------------------------------------------------------------------ assignment / scoring */
@@ -30,26 +210,6 @@ int wgs_assign_last_ms(wgs_ctx *ctx, float *ms)
     return 0;
 }
 
-struct wgs_score {
-    wgs_beagle *b = nullptr;
-    wgs_afset *a = nullptr;
-    int32_t K = 0, row_lo = 0, row_hi = 0, nblocks = 0, P = 0;
-    int64_t n = 0, cells = 0;
-    bool per_ind = false, have_prefix = false;
-    const float **d_acol = nullptr, **d_colptr = nullptr;
-    ScoreSlab *d_slabs[2] = {nullptr, nullptr};      // [0] table of the sweep, [1] table of the chain kernel
-    int n_slabs[2] = {0, 0}, total_pg[2] = {0, 0};
-    double *d_S = nullptr, *d_out = nullptr, *d_start = nullptr, *d_run = nullptr, *d_chunks = nullptr;     // d_chunks: [ceil(nblocks/2)][cells]
-    uint32_t *d_cand = nullptr;
-    float *d_carry = nullptr, *d_parts = nullptr;
-    int32_t *d_nserial = nullptr;
-    int32_t last_serial_blocks = 0;
-    CodedSlabHost *d_coded = nullptr;     // slab table of the sweep through the class codes (shared columns)
-    int n_coded = 0, coded_quads = 0;
-    int64_t coded_generation = -1;        // wgs_codes::generation of the build d_coded was made from
-    int last_path = 0;                    // 1: the last wgs_score_sums went through the class codes
-};
-
 void wgs_score_destroy(wgs_score *sc)
 {
     if (!sc || !wgs_live_remove(sc)) return;          // (destroyed already, e.g. together with its matrix or frequency set)
@@ -60,39 +220,6 @@ void wgs_score_destroy(wgs_score *sc)
     for (void *p : bufs)
         if (p) wgs_pool_free(sc->b->ctx, p);
     delete sc;
-}
-
-/* Slab table for NP pairs per wave, restricted to the individuals [row_lo, row_hi): the members of a slab
- * are in file order, so the scored ones are a contiguous column range. */
-static int build_slab_table(wgs_score *sc, int np, int which)
-{
-    std::vector<ScoreSlab> tab;
-    int pg = 0;
-    for (int g = 0; g < sc->b->n_groups; ++g) {
-        const Slab &s = sc->b->slabs[g];
-        if (s.ncols == 0) continue;
-        const int lo = (int)(std::lower_bound(s.members.begin(), s.members.end(), sc->row_lo) - s.members.begin());
-        const int hi = (int)(std::lower_bound(s.members.begin(), s.members.end(), sc->row_hi) - s.members.begin());
-        if (hi <= lo) continue;
-        ScoreSlab e;
-        e.slab = s.base;
-        e.members = s.d_members;
-        e.npairs = s.npairs;
-        e.ncols = s.ncols;
-        e.pair0 = lo / 2;
-        e.npg = ((hi - 1) / 2 - e.pair0 + 1 + np - 1) / np;
-        e.pg0 = pg;
-        e.col_lo = lo;
-        e.col_hi = hi;
-        pg += e.npg;
-        tab.push_back(e);
-    }
-    sc->n_slabs[which] = (int)tab.size();
-    sc->total_pg[which] = pg;
-    if (tab.empty()) return 0;
-    HIP_TRY(wgs_pool_malloc(sc->b->ctx, &sc->d_slabs[which], sizeof(ScoreSlab) * tab.size()));
-    HIP_TRY(hipMemcpy(sc->d_slabs[which], tab.data(), sizeof(ScoreSlab) * tab.size(), hipMemcpyHostToDevice));
-    return 0;
 }
 
 int wgs_score_create(wgs_beagle *b, wgs_afset *a, const float *const *colptr, int32_t row_lo, int32_t row_hi, wgs_score **out)
@@ -115,21 +242,20 @@ int wgs_score_create(wgs_beagle *b, wgs_afset *a, const float *const *colptr, in
     sc->row_hi = row_hi;
     sc->per_ind = colptr != nullptr;
     sc->nblocks = (int32_t)((wgs_ntiles(b->m) + WGS_BLOCK_TILES - 1) / WGS_BLOCK_TILES);
-    std::vector<const float *> acol(a->K);
-    for (int k = 0; k < a->K; ++k) acol[k] = a->buf + (size_t)k * a->m;
     HIP_TRY(wgs_pool_malloc(ctx, &sc->d_acol, sizeof(float *) * a->K));
-    HIP_TRY(hipMemcpy(sc->d_acol, acol.data(), sizeof(float *) * a->K, hipMemcpyHostToDevice));
+    std::vector<const float *> acol;
+    HIP_TRY(upload_columns(a, acol, sc->d_acol, nullptr));
     if (colptr) {
         HIP_TRY(wgs_pool_malloc(ctx, &sc->d_colptr, sizeof(float *) * sc->cells));
         HIP_TRY(hipMemcpy(sc->d_colptr, colptr, sizeof(float *) * sc->cells, hipMemcpyHostToDevice));
     }
-    const int np_sweep = score_pairs_per_wave(a->K, sc->per_ind), np_chain = chain_pairs_per_wave(a->K, sc->per_ind);
-    if (build_slab_table(sc, np_sweep, 0)) return 1;
-    if (np_chain == np_sweep) {
+    sc->plan = score_plan_shape(a->K, sc->per_ind);
+    if (build_slab_table(sc, sc->plan.np, 0)) return 1;
+    if (sc->plan.chain_np == sc->plan.np) {
         sc->d_slabs[1] = sc->d_slabs[0];
         sc->n_slabs[1] = sc->n_slabs[0];
         sc->total_pg[1] = sc->total_pg[0];
-    } else if (build_slab_table(sc, np_chain, 1)) {
+    } else if (build_slab_table(sc, sc->plan.chain_np, 1)) {
         return 1;
     }
     if (wgs_pool_malloc(ctx, &sc->d_S, sizeof(double) * (size_t)sc->nblocks * sc->cells) != hipSuccess) {
@@ -144,7 +270,7 @@ int wgs_score_create(wgs_beagle *b, wgs_afset *a, const float *const *colptr, in
 
 static ScoreArgs score_args(const wgs_score *sc, int which)
 {
-    ScoreArgs A;
+    ScoreArgs A = {};              // (no start, no cand: wgs_score_chains_prepare sets them)
     A.slabs = sc->d_slabs[which];
     A.n_slabs = sc->n_slabs[which];
     A.total_pg = sc->total_pg[which];
@@ -158,9 +284,24 @@ static ScoreArgs score_args(const wgs_score *sc, int which)
     A.period = 1;
     A.nblocks = sc->nblocks;
     A.S = sc->d_S;
-    A.start = nullptr;
-    A.cand = nullptr;
     return A;
+}
+
+// The sweep of the plan into sc->d_S (zeroed): one kernel, or the coded kernel in parts and their sum
+static int score_enqueue_sweep(wgs_score *sc, const ScorePlan &p, int mode)
+{
+    wgs_ctx *ctx = sc->b->ctx;
+    if (!p.codes) return launch_score_sweep(ctx, score_args(sc, 0), p.kb, p.np, mode);
+    const int64_t total = (int64_t)sc->nblocks * sc->cells;
+    double *S = sc->d_S;
+    if (p.combine()) {
+        void *ws = nullptr;
+        if (wgs_ctx_workspace(ctx, sizeof(double) * (size_t)total * p.parts, &ws)) return 1;
+        HIP_TRY(hipMemsetAsync(ws, 0, sizeof(double) * (size_t)total * p.parts, ctx->stream));   // rows outside the scored range stay 0
+        S = reinterpret_cast<double *>(ws);
+    }
+    if (launch_score_coded(ctx, p, sc->d_coded, sc->n_coded, sc->d_acol, sc->b->m, sc->cells, sc->K, sc->nblocks, S, mode)) return 1;
+    return p.combine() ? launch_combine_parts(ctx, S, sc->d_S, total, p.parts) : 0;
 }
 
 /* All n x K sums of glassy.py:31-42 / 92-105 for the scored individuals: out[i*K + k] (host, overwritten;
@@ -173,63 +314,27 @@ int wgs_score_sums(wgs_score *sc, int mode, double *out)
     WGS_REQUIRE(mode == WGS_MODE_EXACT || mode == WGS_MODE_FAST, "unknown mode %d", mode);
     wgs_ctx *ctx = sc->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    // shared columns + a codable matrix: the sweep through the class codes (same S, bit for bit)
-    // (built for this sweep only when what it saves exceeds the encode pass: codes.hip: wgs_codes_pay_for_scoring)
-    wgs_codes *codes = sc->per_ind ? nullptr : wgs_beagle_codes(sc->b, false);
-    if (!codes && !sc->per_ind && wgs_codes_pay_for_scoring(sc->b, sc->K)) codes = wgs_beagle_codes(sc->b, true, false, true);
-    if (codes && score_coded_lds_bytes(codes->rows_batch, score_kb(sc->K), codes->score_batch) > 64 * 1024) codes = nullptr;
-    if (codes && sc->coded_generation != codes->generation) {     // (keyed on the build, not on the object's address: a rebuilt wgs_codes may reuse it)
-        std::vector<CodedSlabHost> tab;
-        int quad0 = 0;
-        for (int g = 0; g < sc->b->n_groups; ++g) {
-            const Slab &s = sc->b->slabs[g];
-            if (s.ncols == 0) continue;
-            const int lo = (int)(std::lower_bound(s.members.begin(), s.members.end(), sc->row_lo) - s.members.begin());
-            const int hi = (int)(std::lower_bound(s.members.begin(), s.members.end(), sc->row_hi) - s.members.begin());
-            if (hi <= lo) continue;
-            CodedSlabHost e;
-            e.codes = codes->slabs[g].codes;
-            e.members = s.d_members;
-            e.slab = s.base;
-            e.npairs = s.npairs;
-            e.nquads = codes->slabs[g].nquads;
-            e.ncols = s.ncols;
-            e.quad0 = quad0;
-            e.col_lo = lo;
-            e.col_hi = hi;
-            quad0 += e.nquads;
-            tab.push_back(e);
-        }
-        if (sc->d_coded) wgs_pool_free(ctx, sc->d_coded);
-        sc->d_coded = nullptr;
-        sc->n_coded = (int)tab.size();
-        sc->coded_quads = quad0;
-        if (!tab.empty()) {
-            HIP_TRY(wgs_pool_malloc(ctx, &sc->d_coded, sizeof(CodedSlabHost) * tab.size()));
-            HIP_TRY(hipMemcpy(sc->d_coded, tab.data(), sizeof(CodedSlabHost) * tab.size(), hipMemcpyHostToDevice));
-        }
-        sc->coded_generation = codes->generation;
-    }
+    if (score_plan_sums(sc, ScoreSwitches(), &sc->plan)) return 1;
     HIP_TRY(hipMemsetAsync(sc->d_S, 0, sizeof(double) * (size_t)sc->nblocks * sc->cells, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    sc->last_path = codes ? 1 : 0;
-    if (codes) {
-        if (launch_score_coded(ctx, codes, sc->d_coded, sc->n_coded, sc->coded_quads, sc->d_acol, sc->b->m, sc->cells, sc->K, sc->nblocks,
-                               sc->d_S, mode))
-            return 1;
-    } else if (launch_score_sweep(ctx, score_args(sc, 0), mode)) {
-        return 1;
-    }
-    if (!sc->d_chunks && wgs_pool_malloc(ctx, &sc->d_chunks, sizeof(double) * (size_t)((sc->nblocks + 1) / 2) * sc->cells) != hipSuccess) {
-        wgs_set_error("hipMalloc of the chunk sums failed");
-        return 1;
-    }
+    if (score_enqueue_sweep(sc, sc->plan, mode)) return 1;
+    HIP_TRY(grow_once(sc, &sc->d_chunks, sizeof(double) * (size_t)((sc->nblocks + 1) / 2) * sc->cells));
     if (launch_block_prefix(ctx, sc->d_S, sc->nblocks, sc->cells, sc->d_out, 1, sc->d_chunks)) return 1;
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(hipMemcpyAsync(out, sc->d_out, sizeof(double) * sc->cells, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->assign_ms_pending = true;
     sc->have_prefix = (mode == WGS_MODE_EXACT);
+    return 0;
+}
+
+/* Test hook (include/wgsassign_hip_debug.h): the plan of the last wgs_score_sums, as eight numbers. */
+int wgs_debug_score_plan(wgs_score *sc, int32_t info[8])
+{
+    WGS_REQUIRE(sc && info, "null argument");
+    const ScorePlan &p = sc->plan;
+    const int32_t v[8] = {p.codes ? 1 : 0, p.kb, p.np, p.chain_kb, p.chain_np, p.score_batch, p.elem_bytes, p.parts};
+    std::copy(v, v + 8, info);
     return 0;
 }
 
@@ -259,7 +364,7 @@ int wgs_score_total_from(wgs_score *sc, const double *carry_in, double *out)
     WGS_REQUIRE(sc->d_chunks, "wgs_score_total_from needs wgs_score_sums first");
     wgs_ctx *ctx = sc->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!sc->d_start) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_start, sizeof(double) * sc->cells));
+    HIP_TRY(grow_once(sc, &sc->d_start, sizeof(double) * sc->cells));
     if (carry_in) HIP_TRY(hipMemcpyAsync(sc->d_start, carry_in, sizeof(double) * sc->cells, hipMemcpyHostToDevice, ctx->stream));
     if (launch_chunk_total(ctx, sc->d_chunks, (sc->nblocks + 1) / 2, sc->cells, carry_in ? sc->d_start : nullptr, sc->d_out)) return 1;
     HIP_TRY(hipMemcpyAsync(out, sc->d_out, sizeof(double) * sc->cells, hipMemcpyDeviceToHost, ctx->stream));
@@ -279,8 +384,8 @@ int wgs_score_totals_all(wgs_score *sc, wgs_comm *comm, double *totals_out, doub
     wgs_ctx *ctx = sc->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t bytes = sizeof(double) * sc->cells;
-    if (!sc->d_start) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_start, bytes));
-    if (!sc->d_run) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_run, wgs_relay_bytes(bytes)));
+    HIP_TRY(grow_once(sc, &sc->d_start, bytes));
+    HIP_TRY(grow_once(sc, &sc->d_run, wgs_relay_bytes(bytes)));
     HIP_TRY(hipMemsetAsync(sc->d_start, 0, bytes, ctx->stream));
     const int32_t generation = comm ? wgs_comm_next_generation(comm) : 0;
     if (wgs_relay(
@@ -306,8 +411,7 @@ int wgs_score_chains_prepare(wgs_score *sc, int32_t P, const double *start)
     WGS_REQUIRE(sc, "null argument");
     WGS_REQUIRE(P >= 1, "partition count must be >= 1");
     WGS_REQUIRE(sc->have_prefix, "wgs_score_chains_prepare needs wgs_score_sums(WGS_MODE_EXACT) first");
-    WGS_REQUIRE(chain_cand_lds_bytes(sc->K, P, sc->per_ind) <= 64 * 1024 && (int64_t)sc->cells * P < (1ll << 31),
-                "too many partitions (%d) for the block-parallel chains", P);
+    WGS_REQUIRE(chains_block_parallel(sc->plan, sc->cells, P), "too many partitions (%d) for the block-parallel chains", P);
     wgs_ctx *ctx = sc->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t chains = (size_t)sc->cells * P;
@@ -324,8 +428,8 @@ int wgs_score_chains_prepare(wgs_score *sc, int32_t P, const double *start)
         }
         HIP_TRY(wgs_pool_malloc(ctx, &sc->d_carry, sizeof(float) * chains));
         HIP_TRY(wgs_pool_malloc(ctx, &sc->d_parts, wgs_relay_bytes(sizeof(float) * chains)));
-        if (!sc->d_nserial) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_nserial, sizeof(int32_t)));
-        if (!sc->d_start) HIP_TRY(wgs_pool_malloc(ctx, &sc->d_start, sizeof(double) * sc->cells));
+        HIP_TRY(grow_once(sc, &sc->d_nserial, sizeof(int32_t)));
+        HIP_TRY(grow_once(sc, &sc->d_start, sizeof(double) * sc->cells));
         sc->P = P;
     }
     HIP_TRY(hipMemsetAsync(sc->d_cand, 0, sizeof(uint32_t) * chains * sc->nblocks, ctx->stream));
@@ -342,7 +446,7 @@ int wgs_score_chains_prepare(wgs_score *sc, int32_t P, const double *start)
     A.start = start ? sc->d_start : nullptr;
     A.cand = sc->d_cand;
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    if (launch_chain_cand(ctx, A)) return 1;
+    if (launch_chain_cand(ctx, A, sc->plan.chain_kb, sc->plan.chain_np)) return 1;
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));       // `start` (host) has been consumed
     ctx->assign_ms_pending = true;
@@ -480,31 +584,19 @@ int wgs_debug_assign_parts_f64(wgs_beagle *b, wgs_afset *a, const float *const *
     double *d_out = reinterpret_cast<double *>(ws);
     const float **d_acol = reinterpret_cast<const float **>(reinterpret_cast<char *>(ws) + off_acol);
     const float **d_colptr = colptr ? reinterpret_cast<const float **>(reinterpret_cast<char *>(ws) + off_colptr) : nullptr;
-    std::vector<const float *> acol(K);
-    for (int k = 0; k < K; ++k) acol[k] = a->buf + (size_t)k * a->m;
+    std::vector<const float *> acol;
     HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(double) * cells, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_acol, acol.data(), sizeof(float *) * K, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(upload_columns(a, acol, d_acol, ctx->stream));
     if (colptr) HIP_TRY(hipMemcpyAsync(d_colptr, colptr, sizeof(float *) * n * K, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));      // acol (a local vector) has been consumed
+    HIP_TRY(hipStreamSynchronize(ctx->stream));      // acol has been consumed
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    for (int g = 0; g < b->n_groups; ++g) {
-        const Slab &s = b->slabs[g];
-        if (s.ncols == 0) continue;
-        AssignArgs args;
-        args.slab = s.base;
-        args.members = s.d_members;
-        args.colptr = d_colptr;
-        args.acol = d_acol;
-        args.out = d_out;
-        args.m = b->m;
-        args.site0 = b->site0;
-        args.npairs = s.npairs;
-        args.ncols = s.ncols;
-        args.K = K;
-        args.P = P;
-        args.tiles_per_wave = 0;
-        if (launch_assign(ctx, args, mode)) return 1;
-    }
+    const int kb = score_plan_shape(K, colptr != nullptr).chain_kb;
+    int rc = 0;
+    for_scored_slabs(b, 0, n, [&](int, const Slab &s, int, int) {
+        const AssignArgs args = {s.base, s.d_members, d_colptr, d_acol, d_out, b->m, b->site0, s.npairs, s.ncols, K, P, 0};
+        if (!rc) rc = launch_assign(ctx, args, kb, mode);
+    });
+    if (rc) return 1;
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(hipMemcpyAsync(h.data(), d_out, sizeof(double) * cells, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -664,7 +756,7 @@ int wgs_assign_parts_exact(wgs_beagle *b, wgs_afset *a, const float *const *colp
     WGS_REQUIRE(b && a && parts_out, "null argument");
     WGS_REQUIRE(a->m == b->m, "allele frequencies cover %lld SNPs, the Beagle shard %lld", (long long)a->m, (long long)b->m);
     WGS_REQUIRE(P >= 1, "partition count must be >= 1");
-    if (chain_cand_lds_bytes(a->K, P, colptr != nullptr) > 64 * 1024 || b->n * (int64_t)a->K * P >= (1ll << 31))
+    if (!chains_block_parallel(score_plan_shape(a->K, colptr != nullptr), b->n * (int64_t)a->K, P))
         return parts_exact_literal(b, a, colptr, P, carry_in, parts_out);
     const size_t cells = (size_t)b->n * a->K;
     std::vector<double> sums(cells), start;
@@ -713,38 +805,27 @@ static int parts_exact_literal(wgs_beagle *b, wgs_afset *a, const float *const *
     PartsSlab *d_slabs = reinterpret_cast<PartsSlab *>(base + off_slabs);
     const float **d_acol = reinterpret_cast<const float **>(base + off_acol);
     const float **d_colptr = colptr ? reinterpret_cast<const float **>(base + off_colptr) : nullptr;
-    std::vector<const float *> acol(K);
-    for (int k = 0; k < K; ++k) acol[k] = a->buf + (size_t)k * a->m;
     HIP_TRY(hipMemsetAsync(d_parts, 0, sizeof(float) * cells, ctx->stream));
     if (carry_in) HIP_TRY(hipMemcpyAsync(d_carry, carry_in, sizeof(float) * cells, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_acol, acol.data(), sizeof(float *) * K, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<const float *> acol;
+    HIP_TRY(upload_columns(a, acol, d_acol, ctx->stream));
     if (colptr) HIP_TRY(hipMemcpyAsync(d_colptr, colptr, sizeof(float *) * n * K, hipMemcpyHostToDevice, ctx->stream));
     std::vector<PartsSlab> slabs;
     int blocks = 0;
-    for (int g = 0; g < b->n_groups; ++g) {
-        const Slab &s = b->slabs[g];
-        if (s.ncols == 0) continue;
+    for_scored_slabs(b, 0, n, [&](int, const Slab &s, int, int) {
         slabs.push_back({s.base, s.d_members, s.npairs, s.ncols, blocks});
         blocks += (s.ncols + 63) / 64;
-    }
+    });
     HIP_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(PartsSlab) * slabs.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    {
-        AssignArgs args;
-        args.slab = nullptr;
-        args.members = nullptr;
-        args.colptr = d_colptr;
-        args.acol = d_acol;
-        args.out = nullptr;
-        args.m = b->m;
-        args.site0 = b->site0;
-        args.npairs = 0;
-        args.ncols = 0;
-        args.K = K;
-        args.P = P;
-        args.tiles_per_wave = 0;
-        if (launch_parts_exact(ctx, args, d_slabs, (int)slabs.size(), blocks, d_carry, d_parts)) return 1;
-    }
+    AssignArgs args = {};          // (the fields common to all slabs)
+    args.colptr = d_colptr;
+    args.acol = d_acol;
+    args.m = b->m;
+    args.site0 = b->site0;
+    args.K = K;
+    args.P = P;
+    if (launch_parts_exact(ctx, args, d_slabs, (int)slabs.size(), blocks, d_carry, d_parts)) return 1;
     HIP_TRY(hipMemcpyAsync(parts_out, d_parts, sizeof(float) * cells, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;

@@ -653,6 +653,13 @@ class Score:
         check(_lib.load().wgs_debug_score_chunks(self._h, f64p(out), ctypes.byref(nc)))
         return out
 
+    def plan(self):
+        """Test hook: what the last sums() decided (wgs_debug_score_plan): path (0 float32 slabs, 1 class codes), kb and pairs per
+        wave of the sweep, of the chain kernel, and of the coded sweep SNPs per table, bytes per table element, parts."""
+        out = (ctypes.c_int32 * 8)()
+        check(_lib.load().wgs_debug_score_plan(self._h, out))
+        return dict(zip(("path", "kb", "pairs", "chain_kb", "chain_pairs", "score_batch", "elem_bytes", "parts"), map(int, out)))
+
     def serial_blocks(self):
         """(blocks redone with the literal serial loop, (chain, block) pairs walked) of the last walk."""
         tot = ctypes.c_int64()
