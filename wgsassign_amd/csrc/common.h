@@ -10,6 +10,7 @@
 
 #include "../../include/wgsassign_hip.h"
 #include "../../include/wgsassign_hip_debug.h"
+#include "em_fit_ledger.h"
 
 void wgs_set_error(const char *fmt, ...);
 
@@ -325,8 +326,7 @@ struct FitDesc {       // one EM fit as the sweep kernel sees it
     const uint8_t *tile_rows;
     int32_t nquads, lrows;
 };
-// (_A: of the two iterations of a fused sweep the FIRST converged / is undecided; the plain values then speak of the second)
-enum { EM_ACTIVE = 0, EM_CONVERGED = 1, EM_UNDECIDED = 2, EM_CONVERGED_A = 3, EM_UNDECIDED_A = 4 };
+// (the fit states EM_ACTIVE ... EM_UNDECIDED_A: em_fit_ledger.h)
 // One exact convergence chain (emMAF_cy.pyx:30-31 over this shard): float32 running sum of (a-b)^2 from carry_in.
 struct ChainJob {
     const float *a, *b;
@@ -355,7 +355,7 @@ int em_fits_per_group(void);
 int launch_em_sweep_groups(wgs_ctx *ctx, const FitDesc *d_descs, const int32_t *d_groups, int32_t n_groups, int64_t m, int mode);
 int ssq_reduce_chunks(void);
 int launch_ssq_reduce(wgs_ctx *ctx, const FitDesc *d_descs, int32_t n_fits, int64_t m, double *part2, int second = 0);
-// state[fit] of every listed fit that swept: ssq < lo -> EM_CONVERGED, ssq >= hi (or NaN) -> EM_ACTIVE, else EM_UNDECIDED
+// state[fit] of every listed fit that swept: em_decide (em_fit_ledger.h) of its sums with the band [lo, hi)
 int launch_em_decide(wgs_ctx *ctx, const FitDesc *d_descs, int32_t n_fits, double lo, double hi);
 int launch_rcp_error(wgs_ctx *ctx, int exponent, unsigned long long *d_max_bits);
 int launch_div_check(wgs_ctx *ctx, unsigned long long seed, unsigned long long per_thread, unsigned long long *d_mismatch);

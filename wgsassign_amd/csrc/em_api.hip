@@ -362,19 +362,19 @@ static int32_t em_write_descs(wgs_em *em, const EmSweepPlan &p, int slot, double
         d.tile_rows = p.codes ? p.codes->slabs[em->group[j]].tile_rows : nullptr;
         d.nquads = p.codes ? p.codes->slabs[em->group[j]].nquads : 0;
         d.slab = s.base;
-        const int c = em->cur[j], n1 = (c + 1) % nb, n2 = (c + 2) % nb;
         const int fuse = p.fusing && (*p.may_fuse)[j] >= 2 ? 2 : 1;
-        d.f_old = em_f(em, j, c);
-        d.f_new = em_f(em, j, n1);
-        d.f_new2 = fuse == 2 ? em_f(em, j, n2) : d.f_new;
+        const EmBuffers first = em_rotate(em->cur[j], nb, 1), last = em_rotate(em->cur[j], nb, fuse);
+        d.f_old = em_f(em, j, em->cur[j]);
+        d.f_new = em_f(em, j, first.cur);
+        d.f_new2 = em_f(em, j, last.cur);                    // (= f_new when one iteration runs)
         d.fuse = fuse;
         d.ssq = ssq + j;
         d.ssq2 = ssq_b ? ssq_b + j : d.ssq;
         d.ssq_part = em->d_part + (size_t)j * ntiles;
         d.ssq_part2 = fuse == 2 ? em->d_part_b + (size_t)j * ntiles : d.ssq_part;
         em->fuse_used[j] = (uint8_t)fuse;
-        em->pend_cur[j] = (uint8_t)(fuse == 2 ? n2 : n1);
-        em->pend_prev[j] = (uint8_t)(fuse == 2 ? n1 : c);
+        em->pend_cur[j] = last.cur;
+        em->pend_prev[j] = last.prev;
         d.npairs = s.npairs;
         d.ncols = s.ncols;
         d.skip = em->skip_local[j];
@@ -476,18 +476,10 @@ int wgs_em_rmse_chain(wgs_em *em, int32_t fit, float carry_in, float *carry_out)
     return 0;
 }
 
-/* ---- emMAF.py:15-27 for every fit of the batch in ONE call ------------------------------------------
- * The host enqueues iteration t (sweep, sum reduction, [RCCL all-reduce], decision kernel, state readback)
- * BEFORE it reads the decisions of iteration t-1, so the GPU never waits for the host:
- *   - the decision kernel settles the clear cases on the device (EM_CONVERGED / EM_ACTIVE) and parks the
- *     fits whose float64 sum lies in the guard band (EM_UNDECIDED);
- *   - a sweep skips every fit that is not EM_ACTIVE, so a fit that converged at t-1 keeps the frequencies of
- *     update t-1 (emMAF.py:23-25 breaks after the update) and a parked fit keeps both vectors its exact
- *     chain needs;
- *   - the host, one iteration behind, resolves parked fits with the exact serial float32 chain (all of them
- *     in one batched launch; across SNP shards the float32 carries travel in rank order) and either
- *     finishes them or re-activates them -- such a fit simply runs its next sweep one iteration later.
- * Decisions use only all-reduced sums, so every rank takes the same path. */
+/* ---- emMAF.py:15-27 for every fit of the batch in ONE call: wgs_em_fit enqueues sweep t (sweep, sum reduction, [RCCL all-reduce],
+ * decision kernel, read-back) BEFORE it reads the decisions of sweep t-1, so the GPU never waits for the host.  What that takes in
+ * bookkeeping -- who is listed, who really ran, who is parked for the exact chain -- is EmFitLedger's (em_fit_ledger.h, where the
+ * protocol is described); here are the buffers, the chains and the loop that enqueues what the ledger says. */
 // d_chain_out: a relay buffer of [n_fits] float32 carries | [n_fits] serial-block counts
 static size_t em_chain_serial_off(size_t n) { return wgs_relay_bytes(sizeof(float) * n) / sizeof(float); }
 static size_t em_chain_out_floats(size_t n) { return em_chain_serial_off(n) + n; }
@@ -533,12 +525,8 @@ static int em_resolve_chains(wgs_em *em, const std::vector<int32_t> &fits, doubl
     if (em_relay_chains(ctx, comm, WGS_OP_EM_CHAIN, generation, iteration, em->d_jobs, nj, em->b->m, em->d_chain_out, em->d_chain_batch,
                         reinterpret_cast<int *>(em->d_chain_out + em_chain_serial_off(em->n_fits)), em->h_chain_out))
         return 1;
-    const float *carry = em->h_chain_out;
     ++em->fit_chain_batches;
-    for (int i = 0; i < nj; ++i) {
-        const float res = carry[i] / (float)m_total;         // emMAF_cy.pyx:32
-        converged[i] = sqrt((double)res) < tole;             // emMAF_cy.pyx:33, emMAF.py:23
-    }
+    for (int i = 0; i < nj; ++i) converged[i] = em_chain_converged(em->h_chain_out[i], m_total, tole);
     return 0;
 }
 
@@ -549,18 +537,11 @@ int wgs_em_fit(wgs_em *em, int32_t max_iter, double tole, int64_t m_total, wgs_c
     const EmSwitches sw;
     wgs_ctx *ctx = em->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
+    const EmBand band = em_band(tole, m_total, guard_floor);
     if (em_fit_alloc(em)) return 1;
     const int n = em->n_fits;
-    // the band of device.py: guard_band / decide_converged
-    double lo = -1.0, hi = -INFINITY;                        // tole <= 0 or NaN: `diff < tole` never holds
-    if (tole > 0) {
-        const double thresh = tole * tole * (double)m_total;
-        const double g = std::max(guard_floor, (double)m_total * 0x1p-24) + 1e-6;
-        lo = g < 1.0 ? thresh * (1.0 - g) : -1.0;
-        hi = thresh * (1.0 + g);
-    }
     // Across SNP shards every rank must run the same number of iterations per sweep (the sums of a sweep are all-reduced, and the
-    // bookkeeping below counts iterations): two per sweep only once EVERY rank can -- its codes built with the slabs' own numbering
+    // ledger counts iterations): two per sweep only once EVERY rank can -- its codes built with the slabs' own numbering
     // and the buffers at hand.  Whether a rank can is rank-local (its cost model, when its helper thread's allocation arrives, its
     // environment), so it is never acted upon directly: each sweep's all-reduce carries every rank's "I could" (the free word of its
     // tag row), the host reads the rows with the sweep's decisions -- one sweep behind, like everything else here -- and from then on
@@ -571,55 +552,26 @@ int wgs_em_fit(wgs_em *em, int32_t max_iter, double tole, int64_t m_total, wgs_c
     if (comm) wgs_comm_rank(comm, &rank, &world);
     const int32_t generation = comm ? wgs_comm_next_generation(comm) : 0;
     bool fuse_agreed = comm == nullptr;                      // one shard: nothing to agree on
-    std::vector<char> fin(n, 0), skipped(n, 0);
-    std::vector<int32_t> sweeps(n, 0), init(n), may_fuse(n, 1), ran, parked, parked_a, lists[2];
-    for (int j = 0; j < n; ++j) {
-        iters_out[j] = 0;
-        fin[j] = !em->active[j];
-        init[j] = em->active[j] ? EM_ACTIVE : EM_CONVERGED;
+    EmFitLedger ledger({em->cur, em->prev, em->pend_cur, em->pend_prev, em->fuse_used, em->active}, max_iter, iters_out);
+    std::vector<char> conv;
+    conv.reserve(n);
+    {
+        const std::vector<int32_t> init = ledger.initial_states();
+        HIP_TRY(hipMemcpyAsync(em->d_state, init.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    HIP_TRY(hipMemcpyAsync(em->d_state, init.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     em->fit_iterations = em->fit_chain_batches = 0;
     em->fit_sweep_ms = 0.0;
     em->fit_timed = 0;
     em->fit_sweep_pending = false;
     const auto t_begin = std::chrono::steady_clock::now();
-    // the reference's `diff < tole` from a float64 sum, as em_decide_kernel classifies it
-    auto classify = [&](double v) { return (v != v || v >= hi) ? EM_ACTIVE : (v < lo ? EM_CONVERGED : EM_UNDECIDED); };
-    // the fit ends with the frequencies in `cur`, `it` iterations after its start
-    auto finish = [&](int j, int it) {
-        fin[j] = 1;
-        iters_out[j] = it;
-    };
-    // stream-ordered behind the iteration in flight (whose sweep must see the fit parked throughout)
-    auto set_state = [&](int j, int32_t st) -> int {
-        em->h_setstate[j] = st;
-        HIP_TRY(hipMemcpyAsync(em->d_state + j, em->h_setstate + j, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        return 0;
-    };
-    bool launched_prev = false;
     for (int t = 1;; ++t) {
         const int slot = t & 1;
-        // Who ran at t-1 is known now: its list minus the fits found finished or parked when the decisions
-        // of t-2 were read (those sweeps returned at once).
-        ran.clear();
-        for (int j : lists[slot ^ 1]) {
-            if (skipped[j]) continue;
-            sweeps[j] += em->fuse_used[j];                   // one EM iteration, or the two of a fused sweep
-            em_commit_sweep(em, j);
-            ran.push_back(j);
-        }
-        std::fill(skipped.begin(), skipped.end(), 0);
-        // ---- enqueue iteration t (fits that turn out to have converged at t-1 return at once)
-        std::vector<int32_t> &L = lists[slot];
-        L.clear();
-        for (int j = 0; j < n; ++j) {
-            if (!fin[j] && sweeps[j] < max_iter) L.push_back(j);
-            may_fuse[j] = max_iter - sweeps[j] >= 2 ? 2 : 1;
-        }
-        if (!L.empty()) {
-            hipEvent_t sw0 = nullptr, sw1 = nullptr;         // this iteration's pair (the first EM_TIMED_SWEEPS iterations of a fit are timed)
+        const bool read_back = ledger.in_flight();           // sweep t-1 was enqueued
+        // ---- enqueue sweep t
+        const std::vector<int32_t> &L = ledger.begin(t);
+        if (ledger.in_flight()) {
+            hipEvent_t sw0 = nullptr, sw1 = nullptr;         // this sweep's pair (the first EM_TIMED_SWEEPS sweeps of a fit are timed)
             if (em->fit_timed < EM_TIMED_SWEEPS) {
                 while ((int)em->ev_sw.size() < 2 * em->fit_timed + 2) {
                     hipEvent_t e = nullptr;
@@ -631,25 +583,23 @@ int wgs_em_fit(wgs_em *em, int32_t max_iter, double tole, int64_t m_total, wgs_c
                 ++em->fit_timed;
                 em->fit_sweep_pending = true;
             }
-            const EmSweepPlan p = em_plan_sweep(em, L, max_iter - t + 1, &may_fuse, fuse_agreed, sw);
+            const EmSweepPlan p = em_plan_sweep(em, L, max_iter - t + 1, &ledger.may_fuse(), fuse_agreed, sw);
             if (em_enqueue_sweep(em, p, slot, em->d_ssq2, em->d_ssq2 + n, em->d_state, sw0, sw1)) return 1;
             // Fits that skipped this sweep have stale sums; the decision kernel ignores them, and they are stale
             // in the same way on every rank (all ranks take the same decisions).
             if (comm) {
-                int32_t iterations_run = 0;
-                for (int j : L) iterations_run += em->fuse_used[j];
-                const wgs_coll_tag tag = {WGS_OP_EM_SUMS, generation, t, (int32_t)L.size(), iterations_run, p.can_fuse ? 1 : 0};
+                const wgs_coll_tag tag = {WGS_OP_EM_SUMS, generation, t, (int32_t)L.size(), ledger.iterations_listed(), p.can_fuse ? 1 : 0};
                 if (wgs_comm_allreduce_tagged(comm, em->d_ssq2, 2 * n, &tag)) return 1;
             }
-            if (launch_em_decide(ctx, em->d_descs[slot], (int)L.size(), lo, hi)) return 1;
+            if (launch_em_decide(ctx, em->d_descs[slot], (int)L.size(), band.lo, band.hi)) return 1;
             HIP_TRY(hipMemcpyAsync(em->h_state[slot], em->d_state, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipMemcpyAsync(em->h_ssq[slot], em->d_ssq2, sizeof(double) * (2 * n + (comm ? world * WGS_TAG_WORDS : 0)), hipMemcpyDeviceToHost,
                                    ctx->stream));
             HIP_TRY(hipEventRecord(em->ev_it[slot], ctx->stream));
             ++em->fit_iterations;
         }
-        // ---- read the decisions of iteration t-1 while the GPU works on iteration t
-        if (launched_prev) {
+        // ---- read the decisions of sweep t-1 while the GPU works on sweep t
+        if (read_back) {
             const int ps = slot ^ 1;
             HIP_TRY(hipEventSynchronize(em->ev_it[ps]));     // also: the pinned descriptors of t-1 have been consumed
             if (comm) {
@@ -658,97 +608,27 @@ int wgs_em_fit(wgs_em *em, int32_t max_iter, double tole, int64_t m_total, wgs_c
                 for (int r = 0; r < world; ++r) all = all && em->h_ssq[ps][2 * n + r * WGS_TAG_WORDS + WGS_TAG_AUX] == 1.0;
                 fuse_agreed = all;                           // acted upon from sweep t+1 on, by every rank alike
             }
-            parked.clear();
-            parked_a.clear();
-            for (int j : ran) {
-                const int st = em->h_state[ps][j];
-                if (st == EM_CONVERGED) {
-                    skipped[j] = 1;                          // its sweep t (if enqueued) returned at once
-                    finish(j, sweeps[j]);
-                } else if (st == EM_CONVERGED_A) {
-                    // the FIRST of the sweep's two iterations converged: its frequencies are the result, the second is dropped
-                    skipped[j] = 1;
-                    const int third = 3 - em->cur[j] - em->prev[j];
-                    em->cur[j] = em->prev[j];
-                    em->prev[j] = (uint8_t)third;
-                    sweeps[j] -= 1;
-                    finish(j, sweeps[j]);
-                } else if (st == EM_UNDECIDED) {
-                    parked.push_back(j);
-                    skipped[j] = 1;
-                } else if (st == EM_UNDECIDED_A) {
-                    parked_a.push_back(j);
-                    skipped[j] = 1;
-                } else if (sweeps[j] >= max_iter) {
-                    fin[j] = 1;                              // exhausted: the reference prints nothing, iters stays 0
-                }
-            }
-            // parked after the first of two iterations: the exact chain speaks about (f_a, f_in) -- looked at through cur / prev
-            // for the call; when it says "not converged" the second iteration counts and its sum is classified here as the
-            // device would have (the same thresholds on the same all-reduced float64), possibly parking the fit again
-            if (!parked_a.empty()) {
-                std::vector<uint8_t> fb(parked_a.size()), fa(parked_a.size());
-                for (size_t i = 0; i < parked_a.size(); ++i) {
-                    const int j = parked_a[i];
-                    fb[i] = em->cur[j];
-                    fa[i] = em->prev[j];
-                    em->cur[j] = fa[i];
-                    em->prev[j] = (uint8_t)(3 - fa[i] - fb[i]);
-                }
-                std::vector<char> conv;
-                if (em_resolve_chains(em, parked_a, tole, m_total, comm, conv, generation, 2 * t)) return 1;
-                for (size_t i = 0; i < parked_a.size(); ++i) {
-                    const int j = parked_a[i];
-                    if (conv[i]) {
-                        sweeps[j] -= 1;
-                        finish(j, sweeps[j]);
-                        if (set_state(j, EM_CONVERGED)) return 1;
-                        continue;
-                    }
-                    em->cur[j] = fb[i];                      // the first iteration goes on: the second one's result stands
-                    em->prev[j] = fa[i];
-                    const int cls = classify(em->h_ssq[ps][n + j]);
-                    if (cls == EM_CONVERGED) {
-                        finish(j, sweeps[j]);
-                        if (set_state(j, EM_CONVERGED)) return 1;
-                    } else if (cls == EM_UNDECIDED) {
-                        parked.push_back(j);
-                    } else if (sweeps[j] >= max_iter) {
-                        fin[j] = 1;
-                        if (set_state(j, EM_CONVERGED)) return 1;
-                    } else if (set_state(j, EM_ACTIVE)) {
-                        return 1;
-                    }
-                }
-            }
-            if (!parked.empty()) {
-                std::vector<char> conv;
-                if (em_resolve_chains(em, parked, tole, m_total, comm, conv, generation, 2 * t + 1)) return 1;
-                for (size_t i = 0; i < parked.size(); ++i) {
-                    const int j = parked[i];
-                    if (conv[i]) finish(j, sweeps[j]);
-                    else if (sweeps[j] >= max_iter) fin[j] = 1;
-                    if (set_state(j, conv[i] ? EM_CONVERGED : EM_ACTIVE)) return 1;
+            ledger.read(em->h_state[ps], em->h_ssq[ps] + n, band);
+            while (!ledger.batch().empty()) {
+                if (em_resolve_chains(em, ledger.batch(), tole, m_total, comm, conv, generation, ledger.batch_iteration())) return 1;
+                // stream-ordered behind the sweep in flight (which must see these fits parked throughout)
+                for (const EmStateWrite &w : ledger.resolved(conv)) {
+                    em->h_setstate[w.fit] = w.state;
+                    HIP_TRY(hipMemcpyAsync(em->d_state + w.fit, em->h_setstate + w.fit, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
                 }
             }
         }
-        launched_prev = !L.empty();
-        if (!launched_prev) break;                           // nothing in flight: every fit finished or exhausted
+        if (!ledger.in_flight()) break;                      // nothing in flight: every fit finished or exhausted
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (comm) {
         // the ranks close the fit together: what each of them found (iteration counts, sweeps enqueued, chain resolutions) travels
         // as the tag of one last collective, so ranks that ended with different results fail here instead of returning them
-        int64_t sum = 0, mix = 0;
-        for (int j = 0; j < n; ++j) {
-            sum += iters_out[j];
-            mix = (mix * 31 + iters_out[j] + 7 * (j + 1)) % 16777213;
-        }
-        const wgs_coll_tag tag = {WGS_OP_EM_FIT_END, generation, em->fit_iterations, (int32_t)(sum % 16777213), (int32_t)mix, em->fit_chain_batches};
+        const EmClosing c = ledger.closing();
+        const wgs_coll_tag tag = {WGS_OP_EM_FIT_END, generation, em->fit_iterations, c.sum, c.mix, em->fit_chain_batches};
         if (wgs_comm_allreduce_host_tagged(comm, nullptr, 0, &tag, nullptr)) return 1;
     }
-    for (int j = 0; j < n; ++j)
-        if (iters_out[j] > 0) em->active[j] = 0;             // frozen, as wgs_em_set_active(j, 0) would
+    ledger.freeze_converged();
     em->fit_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
 }

@@ -778,10 +778,8 @@ __global__ __launch_bounds__(64) void ssq_reduce2_kernel(const FitDesc *__restri
     if (threadIdx.x == 0) *(second ? fits[blockIdx.x].ssq2 : fits[blockIdx.x].ssq) = v;
 }
 
-// emMAF.py:22-23 on the device for the clear cases: the float64 sum S decides `diff < tole` unless it lies in
-// the band [lo, hi) around tole^2 * m in which the reference's serial float32 sum may fall on either side
-// (device.py: guard_band); those fits are parked as EM_UNDECIDED for the exact chain.  Fits that did not
-// sweep (state != EM_ACTIVE) keep their state.  NaN never converges (NaN < tole is False).
+// emMAF.py:22-23 on the device for the clear cases (em_fit_ledger.h: em_decide with the band [lo, hi)); fits whose sum lies
+// in the band are parked for the exact chain.  Fits that did not sweep (state != EM_ACTIVE) keep their state.
 __global__ void em_decide_kernel(const FitDesc *__restrict__ fits, int n_fits, double lo, double hi)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -789,16 +787,7 @@ __global__ void em_decide_kernel(const FitDesc *__restrict__ fits, int n_fits, d
     const FitDesc fd = fits[j];
     int32_t *st = const_cast<int32_t *>(fd.state);
     if (!st || *st != EM_ACTIVE) return;
-    auto classify = [&](double s) { return (s != s || s >= hi) ? EM_ACTIVE : (s < lo ? EM_CONVERGED : EM_UNDECIDED); };
-    const int a = classify(*fd.ssq);
-    if (fd.fuse != 2) {
-        *st = a;
-        return;
-    }
-    // two iterations ran: the first decides first; only when it goes on does the second count
-    if (a == EM_CONVERGED) *st = EM_CONVERGED_A;
-    else if (a == EM_UNDECIDED) *st = EM_UNDECIDED_A;
-    else *st = classify(*fd.ssq2);
+    *st = em_decide(*fd.ssq, *fd.ssq2, fd.fuse, EmBand{lo, hi});      // (ssq2 = ssq when one iteration ran)
 }
 
 __global__ void fill_kernel(float *p, int64_t count, float v)

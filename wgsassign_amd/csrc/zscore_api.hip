@@ -461,8 +461,7 @@ static int em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int
         if (em_relay_chains(ctx, comm, WGS_OP_Z_CHAIN, generation, it, d_jobs, nj, stride, d_out, work, nullptr, carry.data())) return 1;
         for (int q = 0; q < nj; ++q) {
             const int j = list[q];
-            const float res = carry[q] / (float)kept_total[fit_slot[j]];      // emMAF_cy.pyx:32 with n = the kept sites of ALL shards
-            if (sqrt((double)res) < tole) {                                   // emMAF_cy.pyx:33, emMAF.py:23: the same value on every rank
+            if (em_chain_converged(carry[q], kept_total[fit_slot[j]], tole)) {    // n = the kept sites of ALL shards: the same value on every rank
                 iters_out[j] = it;
                 em->active[j] = 0;
             }

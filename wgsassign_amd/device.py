@@ -452,6 +452,8 @@ def decide_converged(ssq, m_total, tole, guard=0.0):
     `sqrt(float32_serial_sum / float32(m)) < tole` (emMAF_cy.pyx:26-33, emMAF.py:22-23):
     returns +1 converged, -1 not converged, 0 too close to call (needs the exact chain).
     NaN never converges (NaN < tole is False)."""
+    # must agree with em_band / em_classify of csrc/em_fit_ledger.h (what wgs_em_fit and em_decide_kernel run): EM_CONVERGED, EM_ACTIVE,
+    # EM_UNDECIDED for +1, -1, 0 -- tests/test_em_fit_ledger_cpu.py compares the two edge for edge
     if ssq != ssq or not tole > 0:
         return -1
     thresh = tole * tole * float(m_total)
