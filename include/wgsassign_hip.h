@@ -49,7 +49,8 @@ const char *wgs_last_error(void);
  * (wgs_depth_*, wgs_zscore_*, wgs_zkeep_*, wgs_em_fit_masked) were ADDED under 3: no existing signature changed; so were the
  * integer-table reader (wgs_reader_open_table), the depth ingest (wgs_depth_ingest_*), wgs_depth_create_shape and
  * wgs_depth_download_rows, the deep tier of the z-scores (wgs_zscore_deep_sites, wgs_zkeep_create_deep), and the z-scores over SNP
- * shards (wgs_zscore_classes_sharded, wgs_em_fit_masked_sharded, wgs_depth_ingest_set_first_row, WGS_OP_Z_CLASS, WGS_OP_Z_CHAIN). */
+ * shards (wgs_zscore_classes_sharded, wgs_em_fit_masked_sharded, wgs_depth_ingest_set_first_row, WGS_OP_Z_CLASS, WGS_OP_Z_CHAIN), and
+ * windowed scoring (wgs_score_stream_*, wgs_beagle_set_window). */
 #define WGS_ABI_VERSION 3
 int wgs_version(void);
 /* sha256[:16] over every source of the library / over the sources of the EM and scoring kernels (em_kernels.hip,
@@ -118,6 +119,14 @@ int64_t wgs_beagle_bytes(const wgs_beagle *b);
  * too large are moved into allocations of the right size.  Only before anything was made FROM the matrix (EM batches,
  * scores: rc 2 otherwise); its class codes are dropped. */
 int wgs_beagle_set_rows(wgs_beagle *b, int64_t rows);
+/* A matrix that is about to be filled again with another range of the same file (the two window matrices of windowed scoring):
+ * site0 becomes the global index of its first SNP and rows (0 < rows <= its rows now) its number of sites.  Unlike wgs_beagle_set_rows
+ * nothing is allocated, moved or cleared, however few rows remain -- the matrix is swept once more and closed.  What the last tile of
+ * 64 SNPs holds BEHIND row `rows` is therefore undefined (the values of the range before), where wgs_beagle_create and
+ * wgs_beagle_set_rows leave zeros: the scoring sweeps and the class encoder stop at `rows` and never read it, and no other consumer
+ * may rely on zeros there.  Only before anything was made FROM the matrix (rc 2 otherwise); its class codes are dropped when the
+ * rows change. */
+int wgs_beagle_set_window(wgs_beagle *b, int64_t site0, int64_t rows);
 /* Class codes of the matrix: low-depth genotype likelihoods take few distinct (g0, g1) values per SNP (29 on average in
  * the bundled 85-individual data, 27 among 1000 individuals of the 2x synthetic matrices, ~80 with binned base qualities), so
  * the kernels evaluate the EM term's quotient / the per-site log-likelihood once per CLASS and SNP and look it up per
@@ -275,6 +284,26 @@ int wgs_score_chains_walk(wgs_score *sc, const float *carry_in, float *parts_out
 /* The walks of ALL shards in one call (every rank has prepared its block functions): `world` broadcasts of n*P*K
  * float32 on the stream, one readback; parts_out receives the values after the last shard on every rank. */
 int wgs_score_chains_walk_all(wgs_score *sc, wgs_comm *comm, float *parts_out);
+/* Windowed scoring: the n x K totals of glassy.py:31-42 over a file whose matrix does not fit the device, from consecutive WINDOWS of
+ * its sites, each an ordinary device matrix with site0 = its first site.  The accumulator keeps np.sum's running float64 total on the
+ * device and continues it over every pushed window's 8192-site chunk sums -- wgs_score_total_from's hand-over from SNP shard to SNP
+ * shard, in time instead of in space -- so the totals equal those of one resident matrix bit for bit.
+ *   wgs_score_stream_create   for n individuals, K populations and m_total sites in all;
+ *   wgs_score_stream_push     scores one window (the sweep of wgs_score_sums; shared columns).  window->site0 must equal the number of
+ *                             sites pushed so far and be a multiple of WGS_WINDOW_ALIGN; every window but the last holds a multiple of
+ *                             WGS_WINDOW_ALIGN sites.  Anything else: rc 2 and a message, nothing launched.  Returns when the device is
+ *                             done with the window (its matrix and frequency set may be refilled); nothing is read back;
+ *   wgs_score_stream_finish   the totals (host, n*K float64, overwritten): the one read-back.  rc 2 before all m_total sites were pushed;
+ *   wgs_score_stream_destroy  a no-op for a stream that is gone already (as long as nothing has been created since).
+ * A stream keeps its context's address and is no child of it in the library's registry: like every object made from a wgs_ctx it
+ * must be destroyed, or at least no longer pushed to or finished, BEFORE wgs_ctx_destroy (destroying it afterwards is safe: its two
+ * buffers are plain device allocations).  The Python wrapper closes a context's streams before the context. */
+#define WGS_WINDOW_ALIGN 8192
+typedef struct wgs_score_stream wgs_score_stream;
+int wgs_score_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, wgs_score_stream **out);
+int wgs_score_stream_push(wgs_score_stream *stream, wgs_beagle *window, wgs_afset *window_af, int mode);
+int wgs_score_stream_finish(wgs_score_stream *stream, double *out_nK);
+void wgs_score_stream_destroy(wgs_score_stream *stream);
 /* glassy.loo(L, af, IDs, t, maf_iter, maf_tole, downsampled_L, num_partitions) -- glassy.py:47-112 -- in one
  * call on device-resident data: per individual (file order) the re-fit of its population without it
  * (wgs_em_fit, a batch of individuals at once), the clamp with n_pop - 1, the never-restored overwrite of

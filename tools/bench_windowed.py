@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""--get_pop_like from a BGZF file, resident against windowed: one JSON line.
+
+    python tools/bench_windowed.py [--snps 1000000 --inds 200 --pops 5] [--windows 4] [--repeats 3]
+                                   [--parent-root DIR] [--out profiles/windowed_bench.json]
+
+The file comes from tools/beagle_files.py (seeded, seconds to write).  Every end-to-end figure is the wall time of one
+`python -m wgsassign_amd.WGSassign --get_pop_like` process -- interpreter start, HIP initialisation, ingest, scoring, the text
+file -- with the index of the Beagle file cached (one run per variant warms it up and is not counted).  The variants alternate
+inside every repeat, so what else the machine does meanwhile hits them alike; median and range are reported.
+  resident_s          this tree, the matrix resident (WGSASSIGN_WINDOW_SITES not set);
+  parent_resident_s   the same command in the tree given by --parent-root (a built checkout of the parent commit), else null;
+  windowed_s          this tree, WGSASSIGN_WINDOW_SITES chosen so that --windows windows are used.
+The sweep times are device events around the scoring kernels, taken in THIS process on the same file: the resident sweep
+(device.assign) and the sum of the per-window sweeps (glassy.assignLL_windowed), median of the repeats after one warm-up.
+The outputs of all variants are compared byte for byte.
+What to expect: the device's share of an ingest (BGZF inflate, tokeniser) and the sweeps use the context's one stream and every push
+waits for it, so for a BGZF file the device work of consecutive windows is strictly serial; what overlaps a window's sweep is only
+the producer thread's reading of the next window (for plain gzip also its inflate).  The windowed run therefore costs the resident
+run plus, per window, a reader opened through the index, an ingest created, and the launches and synchronisations of one sweep."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import numpy as np  # noqa: E402
+
+
+def cli_seconds(root, beagle, af, out, env_extra):
+    env = dict(os.environ)
+    env.pop("WGSASSIGN_WINDOW_SITES", None)
+    env.update(env_extra)
+    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, "-m", "wgsassign_amd.WGSassign", "--beagle", beagle, "--pop_af_file", af, "--get_pop_like",
+                        "--out", out], cwd=os.path.dirname(out), env=env, capture_output=True, text=True)
+    dt = time.perf_counter() - t0
+    if r.returncode != 0:
+        raise RuntimeError("the command line failed in %s:\n%s" % (root, r.stderr[-2000:]))
+    return dt, r.stderr
+
+
+def spread(xs):
+    return {"median": round(statistics.median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3), "runs": len(xs)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--snps", type=int, default=1_000_000)
+    ap.add_argument("--inds", type=int, default=200)
+    ap.add_argument("--pops", type=int, default=5)
+    ap.add_argument("--windows", type=int, default=4)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--parent-root", default=None, help="a built checkout of the parent commit")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    a = ap.parse_args()
+    import beagle_files
+    from wgsassign_amd import device, glassy, reader_cy, windows
+    m, n, K = a.snps, a.inds, a.pops
+    per_window = (m + a.windows - 1) // a.windows
+    W = (per_window + windows.ALIGN - 1) // windows.ALIGN * windows.ALIGN          # rounded UP to whole chunks of 8192
+    if windows.window_count(m, W) != a.windows:
+        raise SystemExit("%d sites cannot be cut into %d windows of a multiple of %d sites" % (m, a.windows, windows.ALIGN))
+    res = {"bench": "windowed_pop_like", "snps": m, "inds": n, "pops": K, "window_sites": W, "windows": a.windows,
+           "kernels_id": None, "device": None}
+    with tempfile.TemporaryDirectory() as td:
+        os.environ["WGSASSIGN_INDEX_DIR"] = td
+        bg, af = os.path.join(td, "x.beagle.gz"), os.path.join(td, "x.pop_af.npy")
+        t0 = time.perf_counter()
+        beagle_files.write_lowdepth_bgzf(bg, n, m, seed=5)
+        A = np.random.default_rng(5).uniform(0.02, 0.98, size=(m, K)).astype(np.float32)
+        np.save(af, A)
+        res["file_mb"] = round(os.path.getsize(bg) / 1e6, 1)
+        res["write_s"] = round(time.perf_counter() - t0, 1)
+        variants = [("resident_s", ROOT, {})]
+        if a.parent_root:
+            variants.insert(0, ("parent_resident_s", os.path.abspath(a.parent_root), {}))
+        variants.append(("windowed_s", ROOT, {"WGSASSIGN_WINDOW_SITES": str(W)}))
+        times = {name: [] for name, _, _ in variants}
+        for rep in range(a.repeats + 1):                  # (the first repeat warms up: index cache, page cache, code objects)
+            for name, root, env in variants:
+                dt, err = cli_seconds(root, bg, af, os.path.join(td, name), env)
+                if rep:
+                    times[name].append(dt)
+                if name == "windowed_s" and ("scored in %d windows" % a.windows) not in err:
+                    raise RuntimeError("the windowed run did not use %d windows: %s" % (a.windows, err[-300:]))
+        texts = {name: open(os.path.join(td, name + ".pop_like.txt"), "rb").read() for name, _, _ in variants}
+        res["outputs_identical"] = len(set(texts.values())) == 1
+        for name in ("parent_resident_s", "resident_s", "windowed_s"):
+            res[name] = spread(times[name]) if name in times else None
+        # the sweeps alone, in this process
+        ctx = device.get_context()
+        res["device"] = ctx.info()["name"].strip()
+        res["kernels_id"] = (device._lib.load().wgs_kernels_id() or b"").decode()
+        resident_ms, windowed_ms, each = [], [], None
+        beagle, _, _, _ = reader_cy.stream_to_device(bg, ctx=ctx, names="ends")
+        afs = device.AFSet.from_host(A, ctx=ctx)
+        for rep in range(a.repeats + 1):
+            out_r, _ = device.assign(beagle, afs)
+            if rep and device.assign.last_ms >= 0:
+                resident_ms.append(device.assign.last_ms)
+        afs.close()
+        beagle.close()
+        for rep in range(a.repeats + 1):
+            out_w = glassy.assignLL_windowed(bg, A, W, ctx=ctx)
+            if rep:
+                each = [round(x, 3) for x in glassy.assignLL_windowed.stats["sweep_ms"]]
+                if min(each) >= 0:            # (-1: a sweep's time was not to be had while the class codes' memory was being allocated)
+                    windowed_ms.append(sum(glassy.assignLL_windowed.stats["sweep_ms"]))
+        res["totals_bit_identical"] = bool(np.array_equal(out_r, out_w))
+        res["resident_sweep_ms"] = spread(resident_ms) if resident_ms else None
+        res["windowed_sweeps_ms"] = spread(windowed_ms) if windowed_ms else None
+        res["window_sweep_ms_last_repeat"] = each
+        res["largest_matrix_bytes"] = glassy.assignLL_windowed.stats["largest_matrix_bytes"]
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -65,6 +65,68 @@ for _flag in ("--pop_like", "--pop_like_IDs", "--mixture_iter"):
     parser.add_argument(_flag, help=argparse.SUPPRESS)
 
 
+def windowed_candidate(args, world=1):
+    """Whether these options may be scored in site windows (glassy.assignLL_windowed): --get_pop_like alone, on one rank.
+    Every other option needs the whole matrix on the device (the EM fit's convergence test couples all sites; the z-scores and
+    the leave-one-out re-fits build on it), and a rank of several holds a shard, not a file."""
+    others = (args.get_reference_af, args.loo, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score,
+              args.loo_downsampled_beagle)
+    return bool(args.get_pop_like) and int(world) == 1 and not any(others)
+
+
+WINDOWS_ONLY = "windowed scoring (WGSASSIGN_WINDOW_SITES) covers --get_pop_like on one rank only"
+SLAB_ALLOC_FAILED = ("hipMalloc of", "for population slab")       # csrc/api.hip: wgs_beagle_create, when the matrix does not fit the device
+
+
+SET_WINDOW_SITES = ("the matrix was expected to fit the device and does not: set WGSASSIGN_WINDOW_SITES (a multiple of 8192 sites) to "
+                    "score the file in site windows")
+
+
+def with_windows_hint(error, candidate=False):
+    """The error of a resident run whose matrix did not fit the device, saying what windows cover -- or, when the options were
+    those windows cover (candidate: the file was only judged to fit), how to ask for them; any other error as it is."""
+    if isinstance(error, RuntimeError) and all(part in str(error) for part in SLAB_ALLOC_FAILED):
+        return RuntimeError(str(error) + ": " + (SET_WINDOW_SITES if candidate else WINDOWS_ONLY))
+    return error
+
+
+def _window_sites(args, comm, ctx):
+    """The window --get_pop_like is scored in, or None for the resident path: WGSASSIGN_WINDOW_SITES when set, else windows only
+    when the resident matrix would not fit (windows.plan).  A file whose compressed size alone says that it fits (windows.surely_fits)
+    is looked at no further; beyond that the decision costs a cold BGZF file no pass of its own: what its one-pass ingest would
+    allocate (the estimate plus a quarter) is tried first."""
+    import numpy as np
+
+    from . import reader_cy, windows
+    if not windowed_candidate(args, comm.world) or not (args.pop_af_file and os.path.isfile(args.pop_af_file)):
+        return None                     # (a missing frequency file is reported where it always was)
+    try:
+        W = windows.env_window_sites()
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if W is not None:
+        return W
+    free = ctx.mem_info()[0]
+    if windows.surely_fits(os.path.getsize(args.beagle), free):
+        return None
+    try:
+        A = np.load(args.pop_af_file, mmap_mode="r")
+    except Exception:
+        return None                     # (an unreadable frequency file, too, is reported where it always was)
+    if A.ndim != 2:
+        return None
+    with reader_cy.BeagleStream(args.beagle, threads=1) as st:
+        n = st.n
+    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
+    if est is not None and windows.fits_resident(est + est // 4 + 1024, n, A.shape[1], free):
+        return None
+    m = reader_cy.ensure_index(args.beagle)[2]
+    try:
+        return windows.plan(m, n, A.shape[1], free)
+    except MemoryError as e:
+        raise SystemExit(str(e))
+
+
 def _run(args, comm):
     """The hot-path options on device-resident data.  Under torchrun (one process per GPU) the SNPs are
     sharded over the ranks: every rank parses and holds only its contiguous SNP range; the EM convergence sums,
@@ -101,6 +163,24 @@ def _run(args, comm):
         print(f"site_names: {m_sites} sites total: " + (", ".join(shown) if m_sites <= 4 else
                                                           ", ".join(shown[:2]) + ", ..., " + ", ".join(shown[2:])))
 
+    W = _window_sites(args, comm, ctx)
+    if W is not None:
+        # --get_pop_like alone on a file that does not fit (or WGSASSIGN_WINDOW_SITES): scored window by window; the lines of the
+        # resident run in their order, and one more on stderr
+        A = np.load(args.pop_af_file, mmap_mode="r")
+        out = glassy.assignLL_windowed(args.beagle, A, W, ctx=ctx)
+        info, stats = glassy.assignLL_windowed.info, glassy.assignLL_windowed.stats
+        say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
+        summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
+        say("Parsing population allele frequency file.")
+        say("Calculating likelihood of population assignment")
+        say(str(info["n"]) + " individuals to assign to " + str(A.shape[1]) + " populations")
+        print("wgsassign_amd: scored in %d windows of %d sites" % (stats["windows"], stats["window_sites"]), file=sys.stderr, flush=True)
+        np.savetxt(args.out + ".pop_like.txt", out.astype(np.float32), fmt="%.7f")
+        say("Saved population assignment log likelihoods as " + str(args.out) + ".pop_like.txt (text)")
+        comm.barrier()
+        return
+
     scored = None
     if args.loo_downsampled_beagle:
         # WGSassign.py:172-198 with names-only passes: every rank derives the same two site masks, then
@@ -134,8 +214,14 @@ def _run(args, comm):
         scored, _, _, _ = reader_cy.stream_to_device(args.loo_downsampled_beagle, group_of, n_groups, ctx=ctx,
                                                      rank=comm.rank, world=comm.world, keep=keep_ds, comm=comm)
     else:
-        beagle, sample_names, site_names, m = reader_cy.stream_to_device(
-            args.beagle, group_of, n_groups, ctx=ctx, rank=comm.rank, world=comm.world, comm=comm, names="ends")
+        try:
+            beagle, sample_names, site_names, m = reader_cy.stream_to_device(
+                args.beagle, group_of, n_groups, ctx=ctx, rank=comm.rank, world=comm.world, comm=comm, names="ends")
+        except RuntimeError as e:
+            hinted = with_windows_hint(e, windowed_candidate(args, comm.world))
+            if hinted is e:
+                raise
+            raise hinted from e
         n = beagle.n
         say("Loaded " + str(m) + " sites and " + str(n) + " individuals.")
         ends = comm.allgather_object((site_names[:4], site_names[-4:]))

@@ -48,6 +48,7 @@ SIGNATURES = {
     "wgs_beagle_synth": (c_int, [c_vp, ctypes.c_uint64, ctypes.c_double]),
     "wgs_beagle_bytes": (c_i64, [c_vp]),
     "wgs_beagle_set_rows": (c_int, [c_vp, c_i64]),
+    "wgs_beagle_set_window": (c_int, [c_vp, c_i64, c_i64]),
     "wgs_beagle_synth_quality": (c_int, [c_vp, ctypes.c_uint64, ctypes.c_double, c_i32, c_f64p, c_f64p]),
     "wgs_beagle_codes_info": (c_int, [c_vp, c_f64p]),
     "wgs_beagle_codes_prepare": (c_int, [c_vp, c_int]),
@@ -160,6 +161,10 @@ SIGNATURES = {
     "wgs_score_total_from": (c_int, [c_vp, c_f64p, c_f64p]),
     "wgs_score_totals_all": (c_int, [c_vp, c_vp, c_f64p, c_f64p]),
     "wgs_score_chains_walk_all": (c_int, [c_vp, c_vp, c_f32p]),
+    "wgs_score_stream_create": (c_int, [c_vp, c_i64, c_i32, c_i64, ctypes.POINTER(c_vp)]),
+    "wgs_score_stream_push": (c_int, [c_vp, c_vp, c_vp, c_int]),
+    "wgs_score_stream_finish": (c_int, [c_vp, c_f64p]),
+    "wgs_score_stream_destroy": (None, [c_vp]),
     "wgs_score_chains_prepare": (c_int, [c_vp, c_i32, c_f64p]),
     "wgs_score_chains_walk": (c_int, [c_vp, c_f32p, c_f32p]),
     "wgs_loo": (c_int, [c_vp, c_vp, c_vp, c_i32, ctypes.c_double, c_i64, c_vp, c_i32, c_i32, c_int, c_int, c_f64p, c_f32p, c_i32p]),

@@ -428,6 +428,22 @@ int wgs_beagle_set_rows(wgs_beagle *b, int64_t rows)
     return 0;
 }
 
+int wgs_beagle_set_window(wgs_beagle *b, int64_t site0, int64_t rows)
+{
+    WGS_REQUIRE(b, "null argument");
+    WGS_REQUIRE(site0 >= 0, "first site %lld is negative", (long long)site0);
+    WGS_REQUIRE(rows > 0 && rows <= b->m, "a matrix of %lld rows cannot be set to %lld", (long long)b->m, (long long)rows);
+    WGS_REQUIRE(!wgs_live_has_children(b), "the matrix is in use (EM batches or scores were made from it)");
+    b->site0 = site0;
+    if (rows == b->m) return 0;
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    wgs_beagle_drop_codes(b);
+    b->m = rows;                                            // (the slabs stay as they are: nothing is moved, unlike wgs_beagle_set_rows)
+    b->bytes = 0;
+    for (const Slab &s : b->slabs) b->bytes += (int64_t)((size_t)wgs_ntiles(rows) * s.npairs * 64 * sizeof(float4));
+    return 0;
+}
+
 static int64_t staging_rows(const wgs_beagle *b, int64_t nrows)
 {
     const int64_t row_bytes = b->n * 2 * (int64_t)sizeof(float);

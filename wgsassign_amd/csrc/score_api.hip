@@ -304,6 +304,28 @@ static int score_enqueue_sweep(wgs_score *sc, const ScorePlan &p, int mode)
     return p.combine() ? launch_combine_parts(ctx, S, sc->d_S, total, p.parts) : 0;
 }
 
+// Plans and enqueues one sweep of the scored individuals and the per-chunk sums behind it (sc->d_out: the sums of this matrix alone,
+// sc->d_chunks: what a running total continues over); nothing is read back and nothing waits.
+static int score_sums_enqueue(wgs_score *sc, int mode)
+{
+    wgs_ctx *ctx = sc->b->ctx;
+    if (score_plan_sums(sc, ScoreSwitches(), &sc->plan)) return 1;
+    HIP_TRY(hipMemsetAsync(sc->d_S, 0, sizeof(double) * (size_t)sc->nblocks * sc->cells, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    if (score_enqueue_sweep(sc, sc->plan, mode)) return 1;
+    HIP_TRY(grow_once(sc, &sc->d_chunks, sizeof(double) * (size_t)((sc->nblocks + 1) / 2) * sc->cells));
+    if (launch_block_prefix(ctx, sc->d_S, sc->nblocks, sc->cells, sc->d_out, 1, sc->d_chunks)) return 1;
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    return 0;
+}
+
+// np.sum's running total continued over the chunk sums of the last sweep: d_out = ((d_carry + C0) + C1) + ... (d_carry == nullptr:
+// from zero).  What wgs_score_total_from hands from SNP shard to SNP shard and wgs_score_stream_push from window to window.
+static int score_total_enqueue(wgs_score *sc, const double *d_carry, double *d_out)
+{
+    return launch_chunk_total(sc->b->ctx, sc->d_chunks, (sc->nblocks + 1) / 2, sc->cells, d_carry, d_out);
+}
+
 /* All n x K sums of glassy.py:31-42 / 92-105 for the scored individuals: out[i*K + k] (host, overwritten;
  * rows outside the scored range are 0) = the float64 sum over this shard's SNPs of the float32 per-site
  * values, formed in a fixed order (per lane over the tiles of a block, a fixed shuffle tree over lanes,
@@ -314,13 +336,7 @@ int wgs_score_sums(wgs_score *sc, int mode, double *out)
     WGS_REQUIRE(mode == WGS_MODE_EXACT || mode == WGS_MODE_FAST, "unknown mode %d", mode);
     wgs_ctx *ctx = sc->b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (score_plan_sums(sc, ScoreSwitches(), &sc->plan)) return 1;
-    HIP_TRY(hipMemsetAsync(sc->d_S, 0, sizeof(double) * (size_t)sc->nblocks * sc->cells, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    if (score_enqueue_sweep(sc, sc->plan, mode)) return 1;
-    HIP_TRY(grow_once(sc, &sc->d_chunks, sizeof(double) * (size_t)((sc->nblocks + 1) / 2) * sc->cells));
-    if (launch_block_prefix(ctx, sc->d_S, sc->nblocks, sc->cells, sc->d_out, 1, sc->d_chunks)) return 1;
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    if (score_sums_enqueue(sc, mode)) return 1;
     HIP_TRY(hipMemcpyAsync(out, sc->d_out, sizeof(double) * sc->cells, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->assign_ms_pending = true;
@@ -366,7 +382,7 @@ int wgs_score_total_from(wgs_score *sc, const double *carry_in, double *out)
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(grow_once(sc, &sc->d_start, sizeof(double) * sc->cells));
     if (carry_in) HIP_TRY(hipMemcpyAsync(sc->d_start, carry_in, sizeof(double) * sc->cells, hipMemcpyHostToDevice, ctx->stream));
-    if (launch_chunk_total(ctx, sc->d_chunks, (sc->nblocks + 1) / 2, sc->cells, carry_in ? sc->d_start : nullptr, sc->d_out)) return 1;
+    if (score_total_enqueue(sc, carry_in ? sc->d_start : nullptr, sc->d_out)) return 1;
     HIP_TRY(hipMemcpyAsync(out, sc->d_out, sizeof(double) * sc->cells, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -400,6 +416,98 @@ int wgs_score_totals_all(wgs_score *sc, wgs_comm *comm, double *totals_out, doub
     if (before_out) HIP_TRY(hipMemcpyAsync(before_out, sc->d_start, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return wgs_comm_check(comm);
+}
+
+/* ---- windowed scoring: one GPU walks the sites of a file window by window.  What the relay above does
+ * across ranks -- np.sum's running float64 total continued from one site range to the next over the range's 8192-site chunk sums --
+ * happens here in time: the total stays in device memory between the pushes (two buffers in alternation: the kernel reads one and
+ * writes the other) and crosses to the host once, in wgs_score_stream_finish. */
+constexpr int WGS_LIVE_STREAM = 5;      // kind in the live-object registry (common.h: 1, 2; zscore.h: 3, 4): a stream has no parent, only its liveness is kept
+struct wgs_score_stream {
+    wgs_ctx *ctx = nullptr;
+    int device = 0;
+    int64_t n = 0, m_total = 0, pushed = 0, cells = 0;
+    int32_t K = 0;
+    double *d_run[2] = {nullptr, nullptr};
+    int cur = 0;                      // d_run[cur]: the totals over the sites pushed so far (pushed > 0)
+};
+
+void wgs_score_stream_destroy(wgs_score_stream *st)
+{
+    if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
+    (void)hipSetDevice(st->device);
+    for (double *p : st->d_run)
+        if (p) (void)hipFree(p);                      // (plain allocations, not the context's pool: the handle may outlive its context)
+    delete st;
+}
+
+int wgs_score_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, wgs_score_stream **out)
+{
+    WGS_REQUIRE(ctx && out, "null argument");
+    WGS_REQUIRE(n > 0 && K > 0 && m_total > 0, "a score stream needs individuals, populations and sites (%lld x %d over %lld sites)",
+                (long long)n, K, (long long)m_total);
+    HIP_TRY(hipSetDevice(ctx->device));
+    wgs_score_stream *st = new wgs_score_stream();
+    wgs_live_add(st, WGS_LIVE_STREAM, nullptr);
+    auto guard = on_failure([&] { wgs_score_stream_destroy(st); });
+    st->ctx = ctx;
+    st->device = ctx->device;
+    st->n = n;
+    st->K = K;
+    st->m_total = m_total;
+    st->cells = n * (int64_t)K;
+    for (double *&p : st->d_run) HIP_TRY(wgs_malloc(&p, sizeof(double) * (size_t)st->cells));
+    guard.dismiss();
+    *out = st;
+    return 0;
+}
+
+/* One window: its first site must be the number of sites pushed so far and a multiple of WGS_WINDOW_ALIGN (8192, the sites of one
+ * addend of NumPy's running total: a window that began elsewhere would regroup them), and every window but the last must hold a
+ * multiple of 8192 sites.  Anything else is refused before a kernel is launched.  The window is swept by the path wgs_score_sums
+ * takes; its chunk sums are folded onto the running total by the code behind wgs_score_total_from.  Returns when the device is done with the
+ * window -- its matrix and frequencies may be refilled -- but reads nothing back.  wgs_assign_last_ms: this window's sweep. */
+int wgs_score_stream_push(wgs_score_stream *st, wgs_beagle *window, wgs_afset *window_af, int mode)
+{
+    WGS_REQUIRE(st && window && window_af, "null argument");
+    WGS_REQUIRE(mode == WGS_MODE_EXACT || mode == WGS_MODE_FAST, "unknown mode %d", mode);
+    WGS_REQUIRE(window->ctx == st->ctx && window_af->ctx == st->ctx, "the window belongs to another context than the score stream");
+    WGS_REQUIRE(window->n == st->n && window_af->K == st->K, "the window is %lld individuals x %d populations, the score stream %lld x %d",
+                (long long)window->n, window_af->K, (long long)st->n, st->K);
+    WGS_REQUIRE(window->m > 0, "an empty window");
+    WGS_REQUIRE(window_af->m == window->m, "allele frequencies cover %lld SNPs, the window %lld", (long long)window_af->m, (long long)window->m);
+    WGS_REQUIRE(window->site0 % WGS_WINDOW_ALIGN == 0, "the window starts at site %lld, which is not a multiple of %d", (long long)window->site0,
+                WGS_WINDOW_ALIGN);
+    WGS_REQUIRE(window->site0 == st->pushed, "the window starts at site %lld, but %lld sites were pushed so far", (long long)window->site0,
+                (long long)st->pushed);
+    WGS_REQUIRE(st->pushed + window->m <= st->m_total, "the window's %lld sites after %lld pushed exceed the %lld sites of the score stream",
+                (long long)window->m, (long long)st->pushed, (long long)st->m_total);
+    WGS_REQUIRE(st->pushed + window->m == st->m_total || window->m % WGS_WINDOW_ALIGN == 0,
+                "a window of %lld sites that is not the last one (not a multiple of %d)", (long long)window->m, WGS_WINDOW_ALIGN);
+    wgs_ctx *ctx = st->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    wgs_score *sc = nullptr;
+    auto guard = on_failure([&] { wgs_score_destroy(sc); });
+    if (int rc = wgs_score_create(window, window_af, nullptr, 0, (int32_t)window->n, &sc)) return rc;
+    if (score_sums_enqueue(sc, mode)) return 1;
+    if (score_total_enqueue(sc, st->pushed ? st->d_run[st->cur] : nullptr, st->d_run[st->cur ^ 1])) return 1;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    guard.dismiss();
+    wgs_score_destroy(sc);
+    ctx->assign_ms_pending = true;
+    st->cur ^= 1;
+    st->pushed += window->m;
+    return 0;
+}
+
+int wgs_score_stream_finish(wgs_score_stream *st, double *out_nK)
+{
+    WGS_REQUIRE(st && out_nK, "null argument");
+    WGS_REQUIRE(st->pushed == st->m_total, "only %lld of the %lld sites were pushed", (long long)st->pushed, (long long)st->m_total);
+    HIP_TRY(hipSetDevice(st->ctx->device));
+    HIP_TRY(hipMemcpyAsync(out_nK, st->d_run[st->cur], sizeof(double) * (size_t)st->cells, hipMemcpyDeviceToHost, st->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(st->ctx->stream));
+    return 0;
 }
 
 /* Block functions of the exact partition chains (utils.py:147-149) for P partitions; needs the block

@@ -24,7 +24,7 @@ _live = weakref.WeakSet()       # device objects that still own library handles
 def _close_all():
     """Release every device object before the interpreter tears modules down: children (scores, EM batches)
     before the matrices they refer to, so no destructor runs against a freed parent or an unloaded library."""
-    order = {"Score": 0, "EMBatch": 1, "AFSet": 2, "DeviceBeagle": 3}
+    order = {"Score": 0, "ScoreStream": 0, "EMBatch": 1, "AFSet": 2, "DeviceBeagle": 3}
     for obj in sorted(list(_live), key=lambda o: order.get(type(o).__name__, 9)):
         try:
             obj.close()
@@ -90,6 +90,7 @@ class Context:
         check(lib.wgs_ctx_create(int(device), ctypes.byref(h)))
         self._h = h
         self.device = int(device)
+        self._children = weakref.WeakSet()      # score streams of this context: closed before it
 
     @property
     def handle(self):
@@ -117,6 +118,8 @@ class Context:
 
     def close(self):
         if self._h:
+            for child in list(self._children):
+                child.close()
             _lib.load().wgs_ctx_destroy(self._h)
             self._h = None
 
@@ -198,6 +201,14 @@ class DeviceBeagle:
         (include/wgsassign_hip.h: wgs_beagle_set_rows) -- before any EM batch or score is made from it."""
         check(_lib.load().wgs_beagle_set_rows(self._h, int(m)))
         self.m = int(m)
+
+    def set_window(self, site0, m=None):
+        """The matrix is about to be filled with another range of its file (reader_cy.stream_windows): `site0` becomes the global
+        index of its first site and m (at most its rows now; None: as they are) its number of sites, without moving anything
+        (wgs_beagle_set_window) -- before any EM batch or score is made from it."""
+        m = self.m if m is None else int(m)
+        check(_lib.load().wgs_beagle_set_window(self._h, int(site0), m))
+        self.site0, self.m = int(site0), m
 
     def prepare_codes(self, em=True):
         """Build the class codes now (em: and the slabs' own numbering for the coded EM sweep) instead of at first use."""
@@ -671,6 +682,50 @@ class Score:
     def close(self):
         if self._h:
             _lib.load().wgs_score_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ScoreStream:
+    """The accumulator of windowed scoring (wgs_score_stream): the n x K float64 totals over m_total sites from consecutive
+    windows, np.sum's running total staying on the device from push to push -- bit for bit what one resident matrix gives."""
+
+    def __init__(self, n, K, m_total, ctx=None):
+        self.ctx = ctx or get_context()
+        self.n, self.K, self.m_total = int(n), int(K), int(m_total)
+        self.windows = 0
+        self.sweep_ms = []                      # kernel time of every window's sweep
+        h = ctypes.c_void_p()
+        check(_lib.load().wgs_score_stream_create(self.ctx.handle, self.n, self.K, self.m_total, ctypes.byref(h)))
+        self._h = h
+        self.ctx._children.add(self)
+        _live.add(self)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def push(self, beagle, afset, mode=None):
+        """Scores one window: beagle.site0 must be the number of sites pushed so far (a multiple of 8192)."""
+        mode = default_mode() if mode is None else mode
+        check(_lib.load().wgs_score_stream_push(self._h, beagle.handle, afset.handle, mode))
+        self.windows += 1
+        self.sweep_ms.append(last_assign_ms(self.ctx))
+
+    def finish(self):
+        """(n, K) float64 totals; refused before all m_total sites were pushed."""
+        out = np.zeros((self.n, self.K), dtype=np.float64)
+        check(_lib.load().wgs_score_stream_finish(self._h, f64p(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            _lib.load().wgs_score_stream_destroy(self._h)
             self._h = None
 
     def __del__(self):

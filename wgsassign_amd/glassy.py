@@ -29,6 +29,62 @@ def assignLL(L, af, t=1):
         return out.astype(np.float32)
 
 
+def assignLL_windowed(path, A, window_sites=None, ctx=None, mode=None):
+    """The (n, K) float64 sums of assignLL for a Beagle FILE whose matrix need not fit the device: its sites are scored in
+    consecutive windows of `window_sites` sites (a multiple of 8192, rounded down; None: WGSASSIGN_WINDOW_SITES, else what
+    windows.plan derives from the free device memory -- one window when everything fits).  A: the (m, K) frequencies, an array
+    or an np.load(..., mmap_mode="r") view; rows [lo, hi) are uploaded per window.  Two window matrices exist at most
+    (reader_cy.stream_windows), np.sum's running total stays on the device between the windows (device.ScoreStream): the result
+    equals device.assign on the resident matrix bit for bit.
+    assignLL_windowed.stats: windows, window_sites, largest_matrix_bytes, matrices (created), seconds, sweep_ms (per window);
+    assignLL_windowed.info: n, m, sample_names, site_names (the first and last four)."""
+    import time
+
+    from . import reader_cy, windows
+    from .device import ScoreStream, get_context
+    ctx = ctx or get_context()
+    t0 = time.perf_counter()
+    if A.ndim != 2:
+        raise ValueError("the allele frequencies must be an (m, K) matrix")
+    K = A.shape[1]
+    if window_sites is None:
+        W = windows.env_window_sites()
+        if W is None:
+            index, _, m = reader_cy.ensure_index(path)
+            with reader_cy.BeagleStream(path, threads=1, index=index, first_row=0) as st:
+                n = st.n
+            W = windows.plan(m, n, K, ctx.mem_info()[0]) or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN
+    else:
+        if int(window_sites) < windows.ALIGN:
+            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
+        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+    info, stream = {}, None
+    gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info)
+    try:
+        for b in gen:
+            if stream is None:
+                if A.shape[0] != info["m"]:
+                    raise ValueError("the allele frequency file has %d sites, the Beagle file %d" % (A.shape[0], info["m"]))
+                stream = ScoreStream(b.n, K, info["m"], ctx)
+            afs = AFSet.from_host(np.ascontiguousarray(A[b.site0:b.site0 + b.m], dtype=np.float32), ctx=ctx)
+            try:
+                stream.push(b, afs, mode)
+            finally:
+                afs.close()
+        if stream is None:
+            raise ValueError("%s holds no sites" % path)
+        out = stream.finish()
+        sweep_ms = list(stream.sweep_ms)
+    finally:
+        gen.close()
+        if stream is not None:
+            stream.close()
+    assignLL_windowed.stats = {"windows": info["windows"], "window_sites": W, "largest_matrix_bytes": info["largest_matrix_bytes"],
+                               "matrices": info["matrices"], "seconds": time.perf_counter() - t0, "sweep_ms": sweep_ms}
+    assignLL_windowed.info = {k: info[k] for k in ("n", "m", "sample_names", "site_names")}
+    return out
+
+
 def loo(L, af, IDs, t, maf_iter, maf_tole, downsampled_L=None, num_partitions=1, need_parts=True):
     """glassy.py:47-112: leave-one-out assignment log-likelihoods.
 

@@ -108,13 +108,22 @@ class BeagleStream:
         GPU, which tokenises it straight into the slabs of `beagle` from row `row0` on.  keep: bool array over those
         sites (False = the site takes no row).  Yields (rows_written, site_names of the chunk's kept sites); names="ends" (and
         no keep mask): only the first and the last four names of a chunk of more than eight sites."""
-        lib = _lib.load()
+        yield from self.ingest_begin(beagle, row0, limit, keep, chunk_bytes, names)
+
+    def ingest_begin(self, beagle, row0=0, limit=None, keep=None, chunk_bytes=None, names="all"):
+        """ingest() in two steps: the ingest is created NOW -- its producer thread starts to read and inflate the file -- and the
+        generator of ingest() is returned; the device's share of the work happens as that is iterated.  (stream_windows opens
+        the next window this way before it hands out the current one.)"""
         if chunk_bytes is None:
             chunk_bytes = int(os.environ.get("WGSASSIGN_TEXT_CHUNK_BYTES", 0))
         g = ctypes.c_void_p()
-        _lib.check(lib.wgs_ingest_create(beagle.handle, self._h, -1 if limit is None else int(limit), int(chunk_bytes),
-                                         ctypes.byref(g)))
+        _lib.check(_lib.load().wgs_ingest_create(beagle.handle, self._h, -1 if limit is None else int(limit), int(chunk_bytes),
+                                                 ctypes.byref(g)))
         self._ingest = g
+        return self._ingest_chunks(g, row0, keep, names)
+
+    def _ingest_chunks(self, g, row0, keep, names):
+        lib = _lib.load()
         if keep is not None:
             keep = np.ascontiguousarray(keep, dtype=np.uint8)
         consumed = 0
@@ -493,3 +502,70 @@ def stream_to_device(path, group_of=None, n_groups=1, ctx=None, threads=None, ra
         if row0 != hi - lo:
             raise RuntimeError("Beagle file changed while reading: expected %d sites, parsed %d" % (hi - lo, row0))
         return beagle, list(st.sample_names), site_names, m_total
+
+
+def stream_windows(path, window_sites, ctx=None, threads=None, info=None):
+    """The sites of a Beagle file as consecutive device windows of `window_sites` sites (a multiple of 8192; the last window
+    may be shorter): a generator of DeviceBeagle objects (one group, as --get_pop_like scores) with site0 = the window's first
+    site.  TWO device matrices of window_sites rows exist at most and are filled in alternation (DeviceBeagle.set_window moves a
+    matrix to its next range and cuts the last, shorter window; nothing is allocated or copied for that).  A window is the
+    caller's only until it asks for the next one: by then the matrix of the window before has been moved to the range after
+    (site0, rows) and its ingest created, and its data are overwritten when that window is asked for.  The caller closes what
+    it made from a window (scores) before it asks for the next.  Every window has a reader of its own, positioned through the
+    index (wgs_reader_open_indexed) and limited to the window's rows; the reader of window w + 1 is opened and its ingest
+    created BEFORE window w is handed out, so its producer thread reads the file (and, for plain gzip, inflates it) while the
+    caller scores window w.  The device's share of an ingest -- BGZF inflate, tokeniser -- runs on the context's one stream, from
+    the caller's thread, when the next window is asked for: the device work of consecutive windows is strictly serial.
+    info (a dict, optional) receives n, m, sample_names, site_names (the first and last four of the file, as names="ends"),
+    windows, matrices (created) and largest_matrix_bytes."""
+    from .device import DeviceBeagle
+    W = int(window_sites)
+    if W < 8192 or W % 8192:
+        raise ValueError("a window holds a multiple of 8192 sites, not %d" % W)
+    info = {} if info is None else info
+    index, _, m = ensure_index(path)
+    nwin = (m + W - 1) // W
+    info.update(m=m, windows=nwin, matrices=0, largest_matrix_bytes=0, site_names=[])
+    bufs = [None, None]
+    opened = []
+
+    def open_window(w):
+        lo = w * W
+        rows = min(W, m - lo)
+        st = BeagleStream(path, threads, index=index, first_row=lo)
+        opened.append(st)
+        if "n" not in info:
+            info.update(n=st.n, sample_names=list(st.sample_names))
+        b = bufs[w & 1]
+        if b is None:
+            b = bufs[w & 1] = DeviceBeagle(rows, st.n, site0=lo, ctx=ctx)      # (the second matrix of a two-window file is the short one)
+            info["matrices"] += 1
+            info["largest_matrix_bytes"] = max(info["largest_matrix_bytes"], b.nbytes())
+        else:
+            b.set_window(lo, rows)
+        return st, b, rows, st.ingest_begin(b, 0, rows, None, names="ends")
+
+    try:
+        head, tail = [], []
+        nxt = open_window(0) if nwin else None
+        for w in range(nwin):
+            st, b, rows, chunks = nxt
+            got = 0
+            for nrows, names in chunks:
+                got += nrows
+                if len(head) < 4:
+                    head = (head + names)[:4]
+                tail = (tail + names)[-4:]
+            st.close()
+            opened.remove(st)
+            if got != rows:
+                raise RuntimeError("Beagle file changed while reading: expected %d sites in window %d, parsed %d" % (rows, w, got))
+            info["site_names"] = head + tail if m > 4 else head
+            nxt = open_window(w + 1) if w + 1 < nwin else None
+            yield b
+    finally:
+        for st in opened:
+            st.close()
+        for b in bufs:
+            if b is not None:
+                b.close()

@@ -1,0 +1,89 @@
+"""Windowed scoring: how many sites one window holds.  Pure arithmetic, no GPU.
+
+A file whose m x 2n float32 matrix does not fit the device is scored in consecutive windows of W sites; W is a multiple of
+8192 (comm.SHARD_ALIGN: one addend of NumPy's running total), so the running total goes from window to window exactly as
+it goes from SNP shard to SNP shard.
+
+Device bytes per site of a matrix of n individuals scored against K populations (one group: the --get_pop_like layout):
+
+    matrix       16 * ceil(n / 2)             one float4 per pair of individuals (csrc/common.h: Slab)
+    frequencies  4 * K                        K float32 columns (wgs_afset)
+    class codes  4 * ceil(n / 4) + 8 * 254    one byte per individual, padded to whole quads, and a dictionary of at most 254
+                 + 1 + 8                      (g0, g1) rows (the bound: csrc/common.h: wgs_codes), the class count, and the
+                                              encoder's per-wavefront records (csrc/codes.hip: wgs_beagle_codes, the build a
+                                              scoring sweep asks for -- without the slabs' own numbering)
+
+The class codes are counted whether or not the cost model will build them for a window: it decides per matrix, after the
+window is there.  What may be used is FRACTION (0.8, the share wgs_loo gives its batches) of the free device memory less
+RESERVE (4 GiB, at most a quarter of the free memory: the ingest's text and line arrays -- up to 3 GiB of text per chunk
+when the device inflates -- the block sums of a sweep, the context's workspace).  A resident matrix needs m sites of it;
+windowed scoring holds TWO windows (the one being scored and the one being filled), each with its frequencies and codes.
+"""
+import os
+
+ALIGN = 8192                    # = comm.SHARD_ALIGN = WGS_WINDOW_ALIGN of include/wgsassign_hip.h
+FRACTION = 0.8
+RESERVE = 4 << 30
+ENV = "WGSASSIGN_WINDOW_SITES"
+SURELY_FITS = 64                # see surely_fits
+
+
+def site_bytes(n, K):
+    """Device bytes one site takes: matrix, frequency columns and the class codes a scoring sweep may build."""
+    n, K = int(n), int(K)
+    return 16 * ((n + 1) // 2) + 4 * K + 4 * ((n + 3) // 4) + 8 * 254 + 1 + 8
+
+
+def budget(free_bytes):
+    """Device bytes the matrices, frequencies and codes may take of `free_bytes` of free memory."""
+    return int(FRACTION * int(free_bytes)) - min(RESERVE, int(free_bytes) // 4)
+
+
+def env_window_sites(environ=None):
+    """WGSASSIGN_WINDOW_SITES rounded down to a multiple of 8192, or None when it is not set (or empty).  A value below
+    8192, or not an integer, is an error that names the variable."""
+    value = (os.environ if environ is None else environ).get(ENV)
+    if value is None or not str(value).strip():
+        return None
+    try:
+        sites = int(str(value).strip())
+    except ValueError:
+        raise ValueError("%s must be a number of sites (an integer >= %d), got %r" % (ENV, ALIGN, value))
+    if sites < ALIGN:
+        raise ValueError("%s=%d is below %d sites, the smallest window (windows are multiples of %d sites)" % (ENV, sites, ALIGN, ALIGN))
+    return sites // ALIGN * ALIGN
+
+
+def surely_fits(compressed_bytes, free_bytes):
+    """The first, free look at a file: its matrix fits when SURELY_FITS (64) times its COMPRESSED size fits the budget, and then the
+    command line looks no further (no reader opened, no index asked for: the resident run costs what it always did).  A likelihood is
+    at least two characters of text and a third of them is dropped, so the matrix is at most 8 / 6 = 1.34 times the text; Beagle text
+    deflates about 10 : 1, and 64 holds up to 48 : 1.  (The class codes are left out here: their allocation is asked for on its own
+    and a sweep does without them when it fails.)"""
+    return SURELY_FITS * int(compressed_bytes) <= budget(free_bytes)
+
+
+def fits_resident(m, n, K, free_bytes):
+    """Whether one matrix of m sites, its frequencies and its codes fit the budget."""
+    return int(m) * site_bytes(n, K) <= budget(free_bytes)
+
+
+def window_count(m, W):
+    return (int(m) + int(W) - 1) // int(W)
+
+
+def plan(m, n, K, free_bytes, environ=None):
+    """The window for scoring m sites x n individuals against K populations with `free_bytes` of device memory free:
+    None when the resident matrix fits and WGSASSIGN_WINDOW_SITES does not ask for windows, else W (a multiple of 8192;
+    the last window may be shorter).  Too little memory for two windows of 8192 sites is an error."""
+    forced = env_window_sites(environ)
+    if forced is not None:
+        return forced
+    if fits_resident(m, n, K, free_bytes):
+        return None
+    W = budget(free_bytes) // (2 * site_bytes(n, K)) // ALIGN * ALIGN
+    if W < ALIGN:
+        raise MemoryError("windowed scoring needs two windows of %d sites x %d individuals on the device (%d bytes with their "
+                          "frequencies and class codes); %d of the %d free bytes can be used" %
+                          (ALIGN, n, 2 * ALIGN * site_bytes(n, K), max(0, budget(free_bytes)), free_bytes))
+    return W
