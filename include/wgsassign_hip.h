@@ -304,6 +304,34 @@ int wgs_score_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total,
 int wgs_score_stream_push(wgs_score_stream *stream, wgs_beagle *window, wgs_afset *window_af, int mode);
 int wgs_score_stream_finish(wgs_score_stream *stream, double *out_nK);
 void wgs_score_stream_destroy(wgs_score_stream *stream);
+
+/* Windowed fits: --get_reference_af for a file whose matrix does not fit the device.  The EM update is per
+ * site; only the stopping test couples the sites, through one sum per iteration over all of them.  A ROUND pushes every window of
+ * the file once, in file order; the stream keeps, on the device and across pushes, S[t][fit] (float64: the sum of squared
+ * differences of iteration t) and C[t][fit] (float32: the running value of the reference's serial sum, handed from window to window).
+ *   wgs_em_stream_create        for n_fits fits of at most max_iter iterations over m_total sites;
+ *   wgs_em_stream_push          one window through the EM batch `window_em` made from its matrix: every fit starts at 0.25 and runs
+ *                               run_iters[fit] iterations; with add_sums the window's sum of iteration t joins S[t][fit]; the chains
+ *                               (chain_fit[i], chain_iter[i]), sorted by iteration, go on from C[t][fit]; a fit with final[fit] != 0
+ *                               (final may be NULL) ends at run_iters[fit], is clamped to [clamp_lo[fit], clamp_hi[fit]] and its window
+ *                               rows are copied to f_out[fit * f_stride ...] (host).  All of it is enqueued at once; nothing is read
+ *                               back but f_out.  The matrix's site0 must equal the sites pushed so far in this round and be a multiple
+ *                               of WGS_WINDOW_ALIGN; every window but the last holds a multiple of WGS_WINDOW_ALIGN sites; the batch
+ *                               has n_fits fits.  Anything else: rc 2 and a message, nothing launched.  Returns when the device is
+ *                               done with the window;
+ *   wgs_em_stream_read          the round's one read-back: S and C (host, max_iter * n_fits each, either may be NULL).  rc 2 before
+ *                               all m_total sites were pushed; the next push starts the next round at site 0, its chains from zero;
+ *   wgs_em_stream_move_window   wgs_beagle_set_window for the matrix under `window_em`, which stays: rows may be anything up to the
+ *                               rows the batch was made for.  The batch must be the only object made from the matrix;
+ *   wgs_em_stream_destroy       a no-op for a stream that is gone already. */
+typedef struct wgs_em_stream wgs_em_stream;
+int wgs_em_stream_create(wgs_ctx *ctx, int32_t n_fits, int32_t max_iter, int64_t m_total, wgs_em_stream **out);
+int wgs_em_stream_push(wgs_em_stream *stream, wgs_em *window_em, const int32_t *run_iters, const int32_t *final, const float *clamp_lo,
+                       const float *clamp_hi, const int32_t *chain_fit, const int32_t *chain_iter, int32_t n_chain, int add_sums,
+                       float *f_out, int64_t f_stride);
+int wgs_em_stream_read(wgs_em_stream *stream, double *S_host, float *C_host);
+int wgs_em_stream_move_window(wgs_em *window_em, int64_t site0, int64_t rows);
+void wgs_em_stream_destroy(wgs_em_stream *stream);
 /* glassy.loo(L, af, IDs, t, maf_iter, maf_tole, downsampled_L, num_partitions) -- glassy.py:47-112 -- in one
  * call on device-resident data: per individual (file order) the re-fit of its population without it
  * (wgs_em_fit, a batch of individuals at once), the clamp with n_pop - 1, the never-restored overwrite of

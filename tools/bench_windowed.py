@@ -3,6 +3,7 @@
 
     python tools/bench_windowed.py [--snps 1000000 --inds 200 --pops 5] [--windows 4] [--repeats 3]
                                    [--parent-root DIR] [--out profiles/windowed_bench.json]
+    python tools/bench_windowed.py --fit [...] [--out profiles/windowed_fit_bench.json]      # the same for --get_reference_af
 
 The file comes from tools/beagle_files.py (seeded, seconds to write).  Every end-to-end figure is the wall time of one
 `python -m wgsassign_amd.WGSassign --get_pop_like` process -- interpreter start, HIP initialisation, ingest, scoring, the text
@@ -14,6 +15,9 @@ inside every repeat, so what else the machine does meanwhile hits them alike; me
 The sweep times are device events around the scoring kernels, taken in THIS process on the same file: the resident sweep
 (device.assign) and the sum of the per-window sweeps (glassy.assignLL_windowed), median of the repeats after one warm-up.
 The outputs of all variants are compared byte for byte.
+--fit measures --get_reference_af instead (the fit in windows, in rounds over the file): the same three whole-process figures, and from
+one emMAF.emMAF_windowed in this process the rounds, the seconds of every round and the EM iterations round 1 ran against the
+iterations the fits needed.  What to expect there: rounds x the windowed scoring run's cost, plus round 1's extra sweeps.
 What to expect: the device's share of an ingest (BGZF inflate, tokeniser) and the sweeps use the context's one stream and every push
 waits for it, so for a BGZF file the device work of consecutive windows is strictly serial; what overlaps a window's sweep is only
 the producer thread's reading of the next window (for plain gzip also its inflate).  The windowed run therefore costs the resident
@@ -33,14 +37,16 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 
 
-def cli_seconds(root, beagle, af, out, env_extra):
+def cli_seconds(root, beagle, af, out, env_extra, fit=False):
+    """af: the frequency file of --get_pop_like, or with fit the ID file of --get_reference_af."""
     env = dict(os.environ)
     env.pop("WGSASSIGN_WINDOW_SITES", None)
     env.update(env_extra)
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
+    what = ["--pop_af_IDs", af, "--get_reference_af"] if fit else ["--pop_af_file", af, "--get_pop_like"]
     t0 = time.perf_counter()
-    r = subprocess.run([sys.executable, "-m", "wgsassign_amd.WGSassign", "--beagle", beagle, "--pop_af_file", af, "--get_pop_like",
-                        "--out", out], cwd=os.path.dirname(out), env=env, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, "-m", "wgsassign_amd.WGSassign", "--beagle", beagle] + what + ["--out", out],
+                       cwd=os.path.dirname(out), env=env, capture_output=True, text=True)
     dt = time.perf_counter() - t0
     if r.returncode != 0:
         raise RuntimeError("the command line failed in %s:\n%s" % (root, r.stderr[-2000:]))
@@ -51,8 +57,48 @@ def spread(xs):
     return {"median": round(statistics.median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3), "runs": len(xs)}
 
 
+def fit_leg(a, m, n, K, W):
+    """--get_reference_af resident against windowed; one JSON-able dict."""
+    import beagle_files
+    from wgsassign_amd import device, emMAF
+    res = {"bench": "windowed_reference_af", "snps": m, "inds": n, "pops": K, "window_sites": W, "windows": a.windows}
+    with tempfile.TemporaryDirectory() as td:
+        os.environ["WGSASSIGN_INDEX_DIR"] = td
+        bg, ids = os.path.join(td, "x.beagle.gz"), os.path.join(td, "ids.txt")
+        beagle_files.write_lowdepth_bgzf(bg, n, m, seed=5)
+        IDs = np.array([["Ind%d" % i, "pop%d" % (i * K // n)] for i in range(n)])
+        np.savetxt(ids, IDs, fmt="%s", delimiter="\t")
+        res["file_mb"] = round(os.path.getsize(bg) / 1e6, 1)
+        variants = [("resident_s", ROOT, {})]
+        if a.parent_root:
+            variants.insert(0, ("parent_resident_s", os.path.abspath(a.parent_root), {}))
+        variants.append(("windowed_s", ROOT, {"WGSASSIGN_WINDOW_SITES": str(W)}))
+        times = {name: [] for name, _, _ in variants}
+        for rep in range(a.repeats + 1):
+            for name, root, env in variants:
+                dt, err = cli_seconds(root, bg, ids, os.path.join(td, name), env, fit=True)
+                if rep:
+                    times[name].append(dt)
+                if name == "windowed_s" and ("rounds of %d windows" % a.windows) not in err:
+                    raise RuntimeError("the windowed run did not use %d windows: %s" % (a.windows, err[-300:]))
+        files = {name: open(os.path.join(td, name + ".pop_af.npy"), "rb").read() for name, _, _ in variants}
+        res["outputs_identical"] = len(set(files.values())) == 1
+        for name in ("parent_resident_s", "resident_s", "windowed_s"):
+            res[name] = spread(times[name]) if name in times else None
+        ctx = device.get_context()
+        res["device"] = ctx.info()["name"].strip()
+        for rep in range(2):
+            _, iters = emMAF.emMAF_windowed(bg, IDs, 200, 1e-4, W, ctx=ctx)
+        st = emMAF.emMAF_windowed.stats
+        res.update(rounds=st["rounds"], round_seconds=[round(x, 3) for x in st["round_seconds"]], iterations=[int(i) for i in iters],
+                   iterations_round1=st["iterations_round1"], iterations_needed=st["iterations_needed"],
+                   chain_iterations=st["chain_iterations"], largest_matrix_bytes=st["largest_matrix_bytes"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fit", action="store_true", help="measure --get_reference_af (the fit in windows) instead of --get_pop_like")
     ap.add_argument("--snps", type=int, default=1_000_000)
     ap.add_argument("--inds", type=int, default=200)
     ap.add_argument("--pops", type=int, default=5)
@@ -68,6 +114,13 @@ def main():
     W = (per_window + windows.ALIGN - 1) // windows.ALIGN * windows.ALIGN          # rounded UP to whole chunks of 8192
     if windows.window_count(m, W) != a.windows:
         raise SystemExit("%d sites cannot be cut into %d windows of a multiple of %d sites" % (m, a.windows, windows.ALIGN))
+    if a.fit:
+        line = json.dumps(fit_leg(a, m, n, K, W))
+        print(line)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     res = {"bench": "windowed_pop_like", "snps": m, "inds": n, "pops": K, "window_sites": W, "windows": a.windows,
            "kernels_id": None, "device": None}
     with tempfile.TemporaryDirectory() as td:

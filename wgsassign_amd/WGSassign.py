@@ -127,6 +127,51 @@ def _window_sites(args, comm, ctx):
         raise SystemExit(str(e))
 
 
+def windowed_fit_candidate(args, world=1):
+    """Whether these options may be fitted in site windows (emMAF.emMAF_windowed): --get_reference_af alone, on one rank.  The
+    leave-one-out re-fits, --ne_obs and the z-scores still need the whole matrix on the device."""
+    others = (args.get_pop_like, args.loo, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score,
+              args.loo_downsampled_beagle)
+    return bool(args.get_reference_af) and int(world) == 1 and not any(others)
+
+
+SET_WINDOW_SITES_FIT = ("the matrix was expected to fit the device and does not: set WGSASSIGN_WINDOW_SITES (a multiple of 8192 sites) to "
+                        "fit the file in site windows")
+
+
+def _fit_window_sites(args, comm, ctx):
+    """The window --get_reference_af is fitted in, or None for the resident path: WGSASSIGN_WINDOW_SITES when set, else windows
+    only when the resident matrix would not fit (windows.plan_fit), after the same first look as _window_sites takes."""
+    import numpy as np
+
+    from . import reader_cy, windows
+    if not windowed_fit_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
+        return None                     # (a missing ID file is reported where it always was)
+    try:
+        W = windows.env_window_sites()
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if W is not None:
+        return W
+    free = ctx.mem_info()[0]
+    if windows.surely_fits(os.path.getsize(args.beagle), free):
+        return None
+    try:
+        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
+        counts = np.unique(IDs[:, 1], return_counts=True)[1]
+    except Exception:
+        return None                     # (an unreadable ID file, too, is reported where it always was)
+    n, K = int(counts.sum()), len(counts)
+    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
+    if est is not None and windows.fits_resident_fit(est + est // 4 + 1024, n, K, free, counts):
+        return None
+    m = reader_cy.ensure_index(args.beagle)[2]
+    try:
+        return windows.plan_fit(m, n, K, free, counts=counts)
+    except MemoryError as e:
+        raise SystemExit(str(e))
+
+
 def _run(args, comm):
     """The hot-path options on device-resident data.  Under torchrun (one process per GPU) the SNPs are
     sharded over the ranks: every rank parses and holds only its contiguous SNP range; the EM convergence sums,
@@ -178,6 +223,29 @@ def _run(args, comm):
         print("wgsassign_amd: scored in %d windows of %d sites" % (stats["windows"], stats["window_sites"]), file=sys.stderr, flush=True)
         np.savetxt(args.out + ".pop_like.txt", out.astype(np.float32), fmt="%.7f")
         say("Saved population assignment log likelihoods as " + str(args.out) + ".pop_like.txt (text)")
+        comm.barrier()
+        return
+
+    W = _fit_window_sites(args, comm, ctx)
+    if W is not None:
+        # --get_reference_af alone on a file that does not fit (or WGSASSIGN_WINDOW_SITES): fitted window by window in rounds; the
+        # lines and files of the resident run, and one more line on stderr
+        af, iters = emMAF.emMAF_windowed(args.beagle, IDs, args.maf_iter, args.maf_tole, W, out=args.out + ".pop_af.npy", ctx=ctx)
+        info, stats = emMAF.emMAF_windowed.info, emMAF.emMAF_windowed.stats
+        say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
+        summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
+        say("Parsing reference population ID file.")
+        for it in iters:
+            if it > 0:
+                say("EM (MAF) converged at iteration: " + str(int(it)))
+        print("wgsassign_amd: fitted in %d rounds of %d windows of %d sites" % (stats["rounds"], stats["windows"], stats["window_sites"]),
+              file=sys.stderr, flush=True)
+        del af
+        say("Saved reference population allele frequencies as " + str(args.out) + ".pop_af.npy (Binary - np.float32)\n")
+        say("Column order of populations is: " + str(pops))
+        np.savetxt(args.out + ".pop_names.txt", pops, fmt="%s")
+        say("Saved reference population names as " + str(args.out) +
+            ".pop_names.txt (String: Order of pops for .pop_af.npy, .ne_obs.npy, and fisher_obs.npy files)\n")
         comm.barrier()
         return
 

@@ -444,6 +444,31 @@ int wgs_beagle_set_window(wgs_beagle *b, int64_t site0, int64_t rows)
     return 0;
 }
 
+/* wgs_beagle_set_window for the matrix under an EM batch that a fit stream pushes window after window (em_api.hip: wgs_em_stream):
+ * the batch stays -- its buffers hold the rows it was made for, and the matrix may take any number of rows up to that again (the
+ * next round starts over with a whole window where the last one was cut short).  The batch must be the only thing made from the
+ * matrix. */
+int wgs_em_stream_move_window(wgs_em *em, int64_t site0, int64_t rows)
+{
+    WGS_REQUIRE(em, "null argument");
+    wgs_beagle *b = em->b;
+    WGS_REQUIRE(site0 >= 0, "first site %lld is negative", (long long)site0);
+    WGS_REQUIRE(rows > 0 && rows <= em->cap_m, "a batch made for %lld rows cannot be moved to a window of %lld", (long long)em->cap_m, (long long)rows);
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        for (const LiveEntry &x : g_live)
+            WGS_REQUIRE((x.parent != b && x.parent2 != b) || x.obj == em, "the matrix is in use (other EM batches or scores were made from it)");
+    }
+    b->site0 = site0;
+    if (rows == b->m) return 0;
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    wgs_beagle_drop_codes(b);
+    b->m = rows;
+    b->bytes = 0;
+    for (const Slab &s : b->slabs) b->bytes += (int64_t)((size_t)wgs_ntiles(rows) * s.npairs * 64 * sizeof(float4));
+    return 0;
+}
+
 static int64_t staging_rows(const wgs_beagle *b, int64_t nrows)
 {
     const int64_t row_bytes = b->n * 2 * (int64_t)sizeof(float);

@@ -368,6 +368,11 @@ int launch_rmse_chain(wgs_ctx *ctx, const float *a, const float *b, int64_t m, f
 // n_jobs chains at once (device array of jobs): d_out[j] / d_serial[j]; work: n_jobs * rmse_chain_workspace_bytes(m)
 int launch_chain_set_carry(wgs_ctx *ctx, ChainJob *d_jobs, const float *d_carry, int n_jobs);
 int launch_rmse_chain_batch(wgs_ctx *ctx, const ChainJob *d_jobs, int n_jobs, int64_t m, float *d_out, void *work, int *d_serial);
+// windowed fits (wgs_em_stream): total[j] += window[j] for j < n; the chains' running values taken from / put back into the table of
+// carries at cell[i] (jobs[i].carry_in = table[cell[i]]; table[cell[i]] = out[i])
+int launch_em_stream_add_sums(wgs_ctx *ctx, const double *d_window, double *d_total, int n);
+int launch_em_stream_chain_load(wgs_ctx *ctx, ChainJob *d_jobs, const int32_t *d_cell, const float *d_table, int n_jobs);
+int launch_em_stream_chain_store(wgs_ctx *ctx, const float *d_out, const int32_t *d_cell, float *d_table, int n_jobs);
 
 struct AssignArgs {
     const float4 *slab;

@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "em_state.h"
+#include "em_stream_checks.h"
 
 // Enqueues `units` fits or fit groups as launch(first, count) over slices of at most `per_launch` of them.
 template <class Launch> static int em_launch_sliced(size_t units, size_t per_launch, Launch launch)
@@ -68,6 +69,7 @@ int wgs_em_create(wgs_beagle *b, int32_t n_fits, const int32_t *fit_group, const
     auto guard = on_failure([&] { wgs_em_destroy(em); });
     em->b = b;
     em->n_fits = n_fits;
+    em->cap_m = b->m;
     em->mode = mode;
     em->group.resize(n_fits);
     em->skip_local.resize(n_fits);
@@ -345,17 +347,25 @@ static EmSweepPlan em_plan_sweep(wgs_em *em, const std::vector<int32_t> &list, i
     return p;
 }
 
-// Slot `slot` of the pinned rings from the plan: the fits' descriptors and the group table (returns its number of pairs); fuse_used,
+// Where one sweep's descriptors and (first, count) group pairs are written (pinned host memory) and where they go on the device:
+// a slot of the batch's own two-slot rings, or one of a longer ring whose owner enqueues many sweeps without waiting (wgs_em_stream).
+struct EmDescSlot {
+    FitDesc *h, *d;
+    int32_t *hg, *dg;
+};
+static EmDescSlot em_ring_slot(wgs_em *em, int slot) { return EmDescSlot{em->h_descs[slot], em->d_descs[slot], em->h_groups[slot], em->d_groups[slot]}; }
+
+// The slot's pinned memory from the plan: the fits' descriptors and the group table (returns its number of pairs); fuse_used,
 // pend_cur / pend_prev.  ssq[j] receives fit j's sum, ssq_b[j] (NULL: ssq[j]) that of its second iteration; state (device, may be
 // NULL) holds the fit states a sweep honours.
-static int32_t em_write_descs(wgs_em *em, const EmSweepPlan &p, int slot, double *ssq, double *ssq_b, int32_t *state)
+static int32_t em_write_descs(wgs_em *em, const EmSweepPlan &p, const EmDescSlot &slot, double *ssq, double *ssq_b, int32_t *state)
 {
     const int64_t ntiles = wgs_ntiles(em->b->m);
     const int nb = em->fbuf[2] ? 3 : 2;
     for (size_t i = 0; i < p.order.size(); ++i) {
         const int j = p.order[i];
         const Slab &s = em->b->slabs[em->group[j]];
-        FitDesc &d = em->h_descs[slot][i];
+        FitDesc &d = slot.h[i];
         d.lcodes = p.codes ? p.codes->slabs[em->group[j]].lcodes : nullptr;
         d.ldict = p.codes ? p.codes->slabs[em->group[j]].ldict : nullptr;
         d.lrows = p.codes ? p.codes->lrows : 0;
@@ -381,7 +391,7 @@ static int32_t em_write_descs(wgs_em *em, const EmSweepPlan &p, int slot, double
         d.n_eff = em->n_eff[j];
         d.state = state ? state + j : nullptr;
     }
-    int32_t n_groups = 0, *Hg = em->h_groups[slot];
+    int32_t n_groups = 0, *Hg = slot.hg;
     for (size_t i = 0; p.shared && i < p.order.size();) {
         size_t k = i + 1;
         while (k < p.order.size() && (int)(k - i) < p.fits_per_group && em->group[p.order[k]] == em->group[p.order[i]]) ++k;
@@ -393,20 +403,20 @@ static int32_t em_write_descs(wgs_em *em, const EmSweepPlan &p, int slot, double
     return n_groups;
 }
 
-/* Enqueue the planned sweep (+ the fixed-order reduction of its sums): descriptors into slot `slot` of the pinned rings and from
+/* Enqueue the planned sweep (+ the fixed-order reduction of its sums): descriptors into the slot's pinned memory and from
  * there to the device, then the plan's kernel in slices of fits or groups.  ev0 / ev1 (may be NULL) bracket the sweep kernel(s). */
-static int em_enqueue_sweep(wgs_em *em, const EmSweepPlan &p, int slot, double *ssq, double *ssq_b, int32_t *state, hipEvent_t ev0,
-                            hipEvent_t ev1)
+static int em_enqueue_sweep(wgs_em *em, const EmSweepPlan &p, const EmDescSlot &slot, double *ssq, double *ssq_b, int32_t *state,
+                            hipEvent_t ev0, hipEvent_t ev1)
 {
     WGS_STALL_SCOPE("the sweep's launches");
     wgs_ctx *ctx = em->b->ctx;
     const int64_t m = em->b->m, ntiles = wgs_ntiles(m);
     const int32_t n_groups = em_write_descs(em, p, slot, ssq, ssq_b, state);
-    FitDesc *D = em->d_descs[slot];
-    int32_t *Dg = em->d_groups[slot];
+    FitDesc *D = slot.d;
+    int32_t *Dg = slot.dg;
     // the slot's pinned memory stays untouched until the caller has waited for this sweep
-    HIP_TRY(hipMemcpyAsync(D, em->h_descs[slot], sizeof(FitDesc) * p.order.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (p.shared) HIP_TRY(hipMemcpyAsync(Dg, em->h_groups[slot], sizeof(int32_t) * 2 * n_groups, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(D, slot.h, sizeof(FitDesc) * p.order.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (p.shared) HIP_TRY(hipMemcpyAsync(Dg, slot.hg, sizeof(int32_t) * 2 * n_groups, hipMemcpyHostToDevice, ctx->stream));
     ++em->sweep_paths[(p.codes ? 2 : 0) + (p.shared ? 1 : 0)];
     if (ev0) HIP_TRY(hipEventRecord(ev0, ctx->stream));
     // workgroups per fit / per group (at least one tile per workgroup for the coded kernels): slices stay below 2^31
@@ -442,7 +452,7 @@ int wgs_em_step_dev(wgs_em *em, double *ssq_dev)
     if (em->last.empty()) return 0;
     em->step_slot ^= 1;         // (the slots alternate; the caller only starts the next step after consuming this step's sums)
     const EmSweepPlan p = em_plan_sweep(em, em->last, 0, nullptr, true, sw);
-    if (em_enqueue_sweep(em, p, em->step_slot, ssq_dev, nullptr, nullptr, em->ev0, em->ev1)) return 1;
+    if (em_enqueue_sweep(em, p, em_ring_slot(em, em->step_slot), ssq_dev, nullptr, nullptr, em->ev0, em->ev1)) return 1;
     for (int j : em->last) em_commit_sweep(em, j);
     return 0;
 }
@@ -584,7 +594,7 @@ int wgs_em_fit(wgs_em *em, int32_t max_iter, double tole, int64_t m_total, wgs_c
                 em->fit_sweep_pending = true;
             }
             const EmSweepPlan p = em_plan_sweep(em, L, max_iter - t + 1, &ledger.may_fuse(), fuse_agreed, sw);
-            if (em_enqueue_sweep(em, p, slot, em->d_ssq2, em->d_ssq2 + n, em->d_state, sw0, sw1)) return 1;
+            if (em_enqueue_sweep(em, p, em_ring_slot(em, slot), em->d_ssq2, em->d_ssq2 + n, em->d_state, sw0, sw1)) return 1;
             // Fits that skipped this sweep have stale sums; the decision kernel ignores them, and they are stale
             // in the same way on every rank (all ranks take the same decisions).
             if (comm) {
@@ -736,6 +746,213 @@ const float *wgs_em_f_dev(wgs_em *em, int32_t fit)
 {
     if (!em || fit < 0 || fit >= em->n_fits) return nullptr;
     return em_f(em, fit, em->cur[fit]);
+}
+
+/* ---- windowed fits: one GPU fits the sites of a file window by window ("the fit in windows").  The EM update
+ * is per site; only the stopping test couples the sites, through one sum per iteration over ALL of them.  So a round pushes every
+ * window of the file once, in file order, and each push runs the window's fits from 0.25 for as many iterations as the host asks:
+ * the window's float64 sum of iteration t joins S[t][fit], the exact float32 chain of the (fit, iteration) pairs the host names goes
+ * on from C[t][fit] -- the carry the window before left there, as a SNP shard's carry reaches the next shard (em_relay_chains) --
+ * and fits whose stopping iteration is known stop there, are clamped and handed out.  S and C stay on the device from push to push;
+ * the host reads them once per round (wgs_em_stream_read) and decides with the rule of wgs_em_fit (em_band / em_classify /
+ * em_chain_converged; wgsassign_amd/windowed_fit.py keeps the rounds).  Nothing is read back while a window is fitted. */
+constexpr int WGS_LIVE_EM_STREAM = 6;   // kind in the live-object registry (score_api.hip: 5): no parent, only its liveness is kept
+constexpr int EM_STREAM_SLOTS = 256;    // sweeps a push enqueues before it waits for the device once (their descriptors stay pinned until then)
+struct wgs_em_stream {
+    wgs_ctx *ctx = nullptr;
+    int device = 0;
+    int32_t n_fits = 0, max_iter = 0;
+    int64_t m_total = 0, pushed = 0;
+    int32_t rounds = 0;                 // rounds read so far
+    double *d_S = nullptr;              // [max_iter][n_fits] sums of squared differences over the sites pushed in the accumulating round(s)
+    float *d_C = nullptr;               // [max_iter][n_fits] float32 carries of the chains of this round
+    double *d_win = nullptr;            // [n_fits] the sums of the sweep in flight
+    int slots = 0;
+    FitDesc *h_descs = nullptr, *d_descs = nullptr;        // [slots][n_fits]
+    int32_t *h_groups = nullptr, *d_groups = nullptr;      // [slots][2 n_fits]
+    size_t job_cap = 0;                 // chain jobs of one push
+    ChainJob *h_jobs = nullptr, *d_jobs = nullptr;
+    int32_t *h_cell = nullptr, *d_cell = nullptr;
+    float *d_chain_out = nullptr;       // [n_fits]
+    void *d_chain_work = nullptr;
+    size_t chain_work_bytes = 0;
+};
+
+void wgs_em_stream_destroy(wgs_em_stream *st)
+{
+    if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
+    (void)hipSetDevice(st->device);
+    for (void *p : {(void *)st->d_S, (void *)st->d_C, (void *)st->d_win, (void *)st->d_descs, (void *)st->d_groups, (void *)st->d_jobs,
+                    (void *)st->d_cell, (void *)st->d_chain_out, st->d_chain_work})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)st->h_descs, (void *)st->h_groups, (void *)st->h_jobs, (void *)st->h_cell})
+        if (p) (void)hipHostFree(p);
+    delete st;
+}
+
+int wgs_em_stream_create(wgs_ctx *ctx, int32_t n_fits, int32_t max_iter, int64_t m_total, wgs_em_stream **out)
+{
+    WGS_REQUIRE(ctx && out, "null argument");
+    WGS_REQUIRE(n_fits > 0 && max_iter >= 0 && m_total > 0, "a fit stream needs fits and sites (%d fits, %d iterations, %lld sites)", n_fits,
+                max_iter, (long long)m_total);
+    WGS_REQUIRE((int64_t)n_fits * std::max(1, max_iter) < (1ll << 30), "%d fits x %d iterations are too many for one fit stream", n_fits, max_iter);
+    HIP_TRY(hipSetDevice(ctx->device));
+    wgs_em_stream *st = new wgs_em_stream();
+    wgs_live_add(st, WGS_LIVE_EM_STREAM, nullptr);
+    auto guard = on_failure([&] { wgs_em_stream_destroy(st); });
+    st->ctx = ctx;
+    st->device = ctx->device;
+    st->n_fits = n_fits;
+    st->max_iter = max_iter;
+    st->m_total = m_total;
+    const size_t n = (size_t)n_fits, cells = n * (size_t)std::max(1, max_iter);
+    st->slots = std::max(1, std::min(max_iter, EM_STREAM_SLOTS));
+    HIP_TRY(wgs_malloc(&st->d_S, sizeof(double) * cells));
+    HIP_TRY(wgs_malloc(&st->d_C, sizeof(float) * cells));
+    HIP_TRY(wgs_malloc(&st->d_win, sizeof(double) * n));
+    HIP_TRY(wgs_malloc(&st->d_chain_out, sizeof(float) * n));
+    HIP_TRY(wgs_malloc(&st->d_descs, sizeof(FitDesc) * n * st->slots));
+    HIP_TRY(wgs_malloc(&st->d_groups, sizeof(int32_t) * 2 * n * st->slots));
+    HIP_TRY(hipHostMalloc(&st->h_descs, sizeof(FitDesc) * n * st->slots, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&st->h_groups, sizeof(int32_t) * 2 * n * st->slots, hipHostMallocDefault));
+    HIP_TRY(hipMemsetAsync(st->d_S, 0, sizeof(double) * cells, ctx->stream));
+    HIP_TRY(hipMemsetAsync(st->d_C, 0, sizeof(float) * cells, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    guard.dismiss();
+    *out = st;
+    return 0;
+}
+
+// Room for the chain jobs of one push and for the workspace of the chains of one iteration (one per fit at most) over `m` sites.
+static int em_stream_chain_room(wgs_em_stream *st, size_t jobs, int64_t m)
+{
+    wgs_ctx *ctx = st->ctx;
+    if (jobs > st->job_cap) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (void *p : {(void *)st->d_jobs, (void *)st->d_cell})
+            if (p) HIP_TRY(hipFree(p));
+        for (void *p : {(void *)st->h_jobs, (void *)st->h_cell})
+            if (p) HIP_TRY(hipHostFree(p));
+        st->d_jobs = st->h_jobs = nullptr;
+        st->d_cell = st->h_cell = nullptr;
+        st->job_cap = 0;
+        const size_t cap = std::max(jobs, (size_t)st->n_fits * 8);
+        HIP_TRY(wgs_malloc(&st->d_jobs, sizeof(ChainJob) * cap));
+        HIP_TRY(wgs_malloc(&st->d_cell, sizeof(int32_t) * cap));
+        HIP_TRY(hipHostMalloc(&st->h_jobs, sizeof(ChainJob) * cap, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(&st->h_cell, sizeof(int32_t) * cap, hipHostMallocDefault));
+        st->job_cap = cap;
+    }
+    const size_t work = rmse_chain_workspace_bytes(m) * (size_t)st->n_fits;
+    if (jobs && work > st->chain_work_bytes) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (st->d_chain_work) HIP_TRY(hipFree(st->d_chain_work));
+        st->d_chain_work = nullptr;
+        st->chain_work_bytes = 0;
+        HIP_TRY(wgs_malloc(&st->d_chain_work, work));
+        st->chain_work_bytes = work;
+    }
+    return 0;
+}
+
+/* One window, through its EM batch `em` (made from the window matrix; one fit per fit of the stream).  The matrix's first site must
+ * be the number of sites pushed in this round and a multiple of WGS_WINDOW_ALIGN, every window but the last holds a multiple of
+ * WGS_WINDOW_ALIGN sites, and the batch has the stream's number of fits: anything else is refused before a kernel is launched.
+ *   run_iters[fit]   iterations fit runs here from f = 0.25 (0 .. max_iter; 0: the fit is left alone unless it is final);
+ *   final[fit]       (may be NULL) != 0: run_iters[fit] is the fit's stopping iteration -- afterwards its frequencies are clamped to
+ *                    [clamp_lo[fit], clamp_hi[fit]] (WGSassign.py:236-240) and copied to f_out[fit * f_stride .. + window rows);
+ *   chain_fit / chain_iter [n_chain]   the exact chain over (f_t, f_t-1) of this window for fit chain_fit[i], t = chain_iter[i]
+ *                    (1 <= t <= run_iters[fit]; sorted by t), from C[t][fit] to C[t][fit];
+ *   add_sums         != 0: the window's sum of every iteration t a fit runs is added to S[t][fit].
+ * Returns when the device is done with the window: its matrix may be refilled, f_out holds the final fits' rows. */
+int wgs_em_stream_push(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, const int32_t *final, const float *clamp_lo,
+                       const float *clamp_hi, const int32_t *chain_fit, const int32_t *chain_iter, int32_t n_chain, int add_sums,
+                       float *f_out, int64_t f_stride)
+{
+    WGS_REQUIRE(st && em && run_iters, "null argument");
+    wgs_beagle *window = em->b;
+    WGS_REQUIRE(window->ctx == st->ctx, "the window belongs to another context than the fit stream");
+    WGS_REQUIRE(em->n_fits == st->n_fits, "the window's batch has %d fits, the fit stream %d", em->n_fits, st->n_fits);
+    WGS_REQUIRE(em->mode == WGS_MODE_EXACT, "windowed fits are exact fits");
+    const int n = st->n_fits;
+    const int64_t m = window->m;
+    int32_t T = 0;
+    bool any_final = false;
+    char why[256];
+    if (em_stream_window_refusal(window->site0, m, em->cap_m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why) ||
+        em_stream_plan_refusal(n, st->max_iter, run_iters, final, clamp_lo && clamp_hi, f_out != nullptr, f_stride, m, chain_fit, chain_iter, n_chain,
+                               &T, &any_final, why, sizeof why)) {
+        wgs_set_error("%s", why);
+        return 2;
+    }
+    const EmSwitches sw;
+    wgs_ctx *ctx = st->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (em_stream_chain_room(st, (size_t)n_chain, m)) return 1;
+    if (st->pushed == 0)                                     // a round begins: its chains start from zero
+        HIP_TRY(hipMemsetAsync(st->d_C, 0, sizeof(float) * (size_t)n * std::max(1, st->max_iter), ctx->stream));
+    if (launch_fill(ctx, em->fbuf[0], (int64_t)n * m, 0.25f)) return 1;       // emMAF.py:17-18
+    em->cur.assign(n, 0);
+    em->prev.assign(n, 1);
+    std::vector<int32_t> list;
+    list.reserve(n);
+    int next_chain = 0;
+    for (int t = 1; t <= T; ++t) {
+        const int s = (t - 1) % st->slots;
+        if (t > 1 && s == 0) HIP_TRY(hipStreamSynchronize(ctx->stream));      // the ring of pinned descriptors goes round
+        list.clear();
+        for (int j = 0; j < n; ++j)
+            if (t <= run_iters[j]) list.push_back(j);        // (a fit past its last iteration keeps the frequencies of that iteration)
+        em->fit_iterations = t - 1;
+        const EmSweepPlan p = em_plan_sweep(em, list, T - t + 1, nullptr, true, sw);
+        const EmDescSlot slot = {st->h_descs + (size_t)s * n, st->d_descs + (size_t)s * n, st->h_groups + (size_t)s * 2 * n,
+                                 st->d_groups + (size_t)s * 2 * n};
+        HIP_TRY(hipMemsetAsync(st->d_win, 0, sizeof(double) * n, ctx->stream));
+        if (em_enqueue_sweep(em, p, slot, st->d_win, nullptr, nullptr, nullptr, nullptr)) return 1;
+        for (int j : list) em_commit_sweep(em, j);
+        if (add_sums && launch_em_stream_add_sums(ctx, st->d_win, st->d_S + (size_t)(t - 1) * n, n)) return 1;
+        // the chains of iteration t, over what this sweep wrote and what it read
+        const int first = next_chain;
+        while (next_chain < n_chain && chain_iter[next_chain] == t) {
+            const int j = chain_fit[next_chain];
+            st->h_jobs[next_chain] = ChainJob{em_f(em, j, em->cur[j]), em_f(em, j, em->prev[j]), 0.0f};
+            st->h_cell[next_chain] = (int32_t)((size_t)(t - 1) * n + j);
+            ++next_chain;
+        }
+        for (int i = first; i < next_chain; i += n) {        // (at most one chain per fit shares the workspace)
+            const int cnt = std::min(n, next_chain - i);
+            HIP_TRY(hipMemcpyAsync(st->d_jobs + i, st->h_jobs + i, sizeof(ChainJob) * cnt, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(st->d_cell + i, st->h_cell + i, sizeof(int32_t) * cnt, hipMemcpyHostToDevice, ctx->stream));
+            if (launch_em_stream_chain_load(ctx, st->d_jobs + i, st->d_cell + i, st->d_C, cnt)) return 1;
+            if (launch_rmse_chain_batch(ctx, st->d_jobs + i, cnt, m, st->d_chain_out, st->d_chain_work, nullptr)) return 1;
+            if (launch_em_stream_chain_store(ctx, st->d_chain_out, st->d_cell + i, st->d_C, cnt)) return 1;
+        }
+    }
+    for (int j = 0; j < n && any_final; ++j) {
+        if (!final[j]) continue;
+        float *f = em_f(em, j, em->cur[j]);
+        if (launch_clamp(ctx, f, m, clamp_lo[j], clamp_hi[j])) return 1;
+        HIP_TRY(hipMemcpyAsync(f_out + (size_t)j * f_stride, f, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st->pushed += m;
+    return 0;
+}
+
+/* The round's one read-back: S (max_iter x n_fits float64) and C (max_iter x n_fits float32), either may be NULL.  rc 2 before all
+ * m_total sites were pushed; afterwards the next round begins at site 0. */
+int wgs_em_stream_read(wgs_em_stream *st, double *S_host, float *C_host)
+{
+    WGS_REQUIRE(st, "null argument");
+    WGS_REQUIRE(st->pushed == st->m_total, "only %lld of the %lld sites were pushed", (long long)st->pushed, (long long)st->m_total);
+    HIP_TRY(hipSetDevice(st->ctx->device));
+    const size_t cells = (size_t)st->n_fits * st->max_iter;
+    if (S_host && cells) HIP_TRY(hipMemcpyAsync(S_host, st->d_S, sizeof(double) * cells, hipMemcpyDeviceToHost, st->ctx->stream));
+    if (C_host && cells) HIP_TRY(hipMemcpyAsync(C_host, st->d_C, sizeof(float) * cells, hipMemcpyDeviceToHost, st->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(st->ctx->stream));
+    st->pushed = 0;
+    ++st->rounds;
+    return 0;
 }
 
 }   // extern "C"

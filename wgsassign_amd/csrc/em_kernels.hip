@@ -1590,3 +1590,48 @@ int launch_rmse_chain(wgs_ctx *ctx, const float *a, const float *b, int64_t m, f
     HIP_TRY(hipStreamSynchronize(ctx->stream));        // `job` is a local
     return launch_rmse_chain_batch(ctx, d_job, 1, m, d_out, work, d_serial);
 }
+
+/* ---- windowed fits (em_api.hip: wgs_em_stream): a window's sums of one iteration join that iteration's running float64 total, and
+ * the exact chain of one (fit, iteration) goes on from the value the window before left in the table of carries -- all of it
+ * stream-ordered between the sweeps, so no value crosses to the host while a window is fitted. */
+__global__ void em_stream_add_sums_kernel(const double *__restrict__ window, double *__restrict__ total, int n)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) total[j] += window[j];                  // (one addition per window, in file order: the same total run to run)
+}
+
+__global__ void em_stream_chain_load_kernel(ChainJob *__restrict__ jobs, const int32_t *__restrict__ cell, const float *__restrict__ table, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) jobs[i].carry_in = table[cell[i]];
+}
+
+__global__ void em_stream_chain_store_kernel(const float *__restrict__ out, const int32_t *__restrict__ cell, float *__restrict__ table, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) table[cell[i]] = out[i];
+}
+
+int launch_em_stream_add_sums(wgs_ctx *ctx, const double *d_window, double *d_total, int n)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(em_stream_add_sums_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_window, d_total, n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_em_stream_chain_load(wgs_ctx *ctx, ChainJob *d_jobs, const int32_t *d_cell, const float *d_table, int n_jobs)
+{
+    if (n_jobs <= 0) return 0;
+    hipLaunchKernelGGL(em_stream_chain_load_kernel, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, ctx->stream, d_jobs, d_cell, d_table, n_jobs);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_em_stream_chain_store(wgs_ctx *ctx, const float *d_out, const int32_t *d_cell, float *d_table, int n_jobs)
+{
+    if (n_jobs <= 0) return 0;
+    hipLaunchKernelGGL(em_stream_chain_store_kernel, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, ctx->stream, d_out, d_cell, d_table, n_jobs);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

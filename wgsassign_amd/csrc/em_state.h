@@ -8,6 +8,7 @@ constexpr int EM_TIMED_SWEEPS = 4096;     // iterations of one wgs_em_fit whose 
 struct wgs_em {
     wgs_beagle *b = nullptr;
     int32_t n_fits = 0;
+    int64_t cap_m = 0;                    // the matrix's rows when the batch was made: what its buffers hold (wgs_em_stream_move_window)
     int mode = WGS_MODE_EXACT;
     std::vector<int32_t> group, skip_local, n_eff;
     std::vector<uint8_t> cur, prev, active;   // per fit: the buffer holding the current / the previous frequencies

@@ -24,7 +24,7 @@ _live = weakref.WeakSet()       # device objects that still own library handles
 def _close_all():
     """Release every device object before the interpreter tears modules down: children (scores, EM batches)
     before the matrices they refer to, so no destructor runs against a freed parent or an unloaded library."""
-    order = {"Score": 0, "ScoreStream": 0, "EMBatch": 1, "AFSet": 2, "DeviceBeagle": 3}
+    order = {"Score": 0, "ScoreStream": 0, "EMStream": 0, "EMBatch": 1, "AFSet": 2, "DeviceBeagle": 3}
     for obj in sorted(list(_live), key=lambda o: order.get(type(o).__name__, 9)):
         try:
             obj.close()
@@ -207,7 +207,12 @@ class DeviceBeagle:
         index of its first site and m (at most its rows now; None: as they are) its number of sites, without moving anything
         (wgs_beagle_set_window) -- before any EM batch or score is made from it."""
         m = self.m if m is None else int(m)
-        check(_lib.load().wgs_beagle_set_window(self._h, int(site0), m))
+        em = getattr(self, "window_em", None)
+        if em is not None and em.handle:
+            # the matrix under the EM batch of a windowed fit: the batch stays, and the rows may grow back to what it was made for
+            check(_lib.load().wgs_em_stream_move_window(em.handle, int(site0), m))
+        else:
+            check(_lib.load().wgs_beagle_set_window(self._h, int(site0), m))
         self.site0, self.m = int(site0), m
 
     def prepare_codes(self, em=True):
@@ -726,6 +731,69 @@ class ScoreStream:
     def close(self):
         if self._h:
             _lib.load().wgs_score_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EMStream:
+    """The tables of a windowed fit (wgs_em_stream): S (maf_iter x n_fits float64 sums) and C (float32 chain carries) stay on the
+    device from window to window; a round pushes every window once and reads them back once (windowed_fit.py keeps the rounds)."""
+
+    def __init__(self, n_fits, maf_iter, m_total, ctx=None):
+        self.ctx = ctx or get_context()
+        self.n_fits, self.maf_iter, self.m_total = int(n_fits), int(maf_iter), int(m_total)
+        self.windows = 0
+        h = ctypes.c_void_p()
+        check(_lib.load().wgs_em_stream_create(self.ctx.handle, self.n_fits, self.maf_iter, self.m_total, ctypes.byref(h)))
+        self._h = h
+        self.ctx._children.add(self)
+        _live.add(self)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def push(self, em, run_iters, final=None, clamp_lo=None, clamp_hi=None, chains=(), add_sums=False, f_out=None):
+        """One window through its EMBatch: em.b.site0 must be the number of sites pushed so far in this round.  chains: (fit,
+        iteration) pairs sorted by iteration; f_out: (n_fits, >= window rows) float32 that receives the final fits' rows."""
+        run = np.ascontiguousarray(run_iters, dtype=np.int32)
+        if run.shape != (self.n_fits,):
+            raise ValueError("run_iters must have one entry per fit")
+        fin = None if final is None else np.ascontiguousarray(final, dtype=np.int32)
+        lo = None if clamp_lo is None else np.ascontiguousarray(clamp_lo, dtype=np.float32)
+        hi = None if clamp_hi is None else np.ascontiguousarray(clamp_hi, dtype=np.float32)
+        for a in (fin, lo, hi):
+            if a is not None and a.shape != (self.n_fits,):
+                raise ValueError("final and the clamps must have one entry per fit")
+        cf = np.ascontiguousarray([c[0] for c in chains], dtype=np.int32)
+        ci = np.ascontiguousarray([c[1] for c in chains], dtype=np.int32)
+        stride = 0
+        if f_out is not None:
+            f_out = _as_f32c(f_out, "f_out")
+            if f_out.ndim != 2 or f_out.shape[0] != self.n_fits:
+                raise ValueError("f_out must be (n_fits, rows)")
+            stride = f_out.shape[1]
+        check(_lib.load().wgs_em_stream_push(self._h, em.handle, i32p(run), None if fin is None else i32p(fin),
+                                             None if lo is None else f32p(lo), None if hi is None else f32p(hi),
+                                             i32p(cf) if len(cf) else None, i32p(ci) if len(ci) else None, len(cf), int(bool(add_sums)),
+                                             None if f_out is None else f32p(f_out), int(stride)))
+        self.windows += 1
+
+    def read(self):
+        """(S, C) of the round just pushed, (maf_iter, n_fits) float64 / float32; the next push begins the next round."""
+        S = np.zeros((self.maf_iter, self.n_fits), dtype=np.float64)
+        C = np.zeros((self.maf_iter, self.n_fits), dtype=np.float32)
+        check(_lib.load().wgs_em_stream_read(self._h, f64p(S) if S.size else None, f32p(C) if C.size else None))
+        return S, C
+
+    def close(self):
+        if self._h:
+            _lib.load().wgs_em_stream_destroy(self._h)
             self._h = None
 
     def __del__(self):

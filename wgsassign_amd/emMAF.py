@@ -62,3 +62,107 @@ def emMAF_populations(L, IDs, iter, tole, beagle=None, comm=None):
     if own:
         beagle.close()
     return pops, af, iters
+
+
+class _DeviceRounds:
+    """windowed_fit's backend on the device: a round is one pass of reader_cy.stream_windows, every window pushed through the
+    EMBatch of its matrix into one device.EMStream."""
+
+    def __init__(self, windows, stream, counts, af, stats):
+        self.windows, self.stream, self.af, self.stats = windows, stream, af, stats
+        lo = 1 / (2 * (np.asarray(counts, dtype=np.float64) + 1))          # WGSassign.py:236-240, as EMBatch.clamp forms them
+        self.lo, self.hi = lo.astype(np.float32), (1 - lo).astype(np.float32)
+        self.batches = {}
+        self.stage = None
+        self.want_more = False
+
+    def again(self):
+        return self.want_more
+
+    def run_round(self, plan):
+        import time
+        t0 = time.perf_counter()
+        K = self.stream.n_fits
+        final = np.flatnonzero(plan.final)
+        pushed = 0
+        for b in self.windows:
+            em = self.batches.get(id(b))
+            if em is None:          # one EMBatch per window matrix, made once and kept for every window and round
+                em = self.batches[id(b)] = EMBatch(b, np.arange(K, dtype=np.int32))
+                b.window_em = em
+            if len(final) and (self.stage is None or self.stage.shape[1] < b.m):
+                self.stage = np.empty((K, b.m), dtype=np.float32)
+            self.stream.push(em, plan.run_iters, plan.final, self.lo, self.hi, plan.chains, plan.add_sums,
+                             self.stage if len(final) else None)
+            for k in final:
+                self.af[b.site0:b.site0 + b.m, k] = self.stage[k, :b.m]
+            pushed += b.m
+            if pushed >= self.stream.m_total:
+                break
+        S, C = self.stream.read()
+        self.stats["round_seconds"].append(time.perf_counter() - t0)
+        self.want_more = True       # asked by stream_windows when the next round takes its first window
+        return S, C
+
+
+def emMAF_windowed(path, IDs, maf_iter, tole, window_sites=None, out=None, ctx=None):
+    """emMAF_populations for a Beagle FILE whose matrix need not fit the device: the sites are fitted in consecutive windows of
+    `window_sites` sites (a multiple of 8192, rounded down; None: WGSASSIGN_WINDOW_SITES, else what windows.plan_fit derives from
+    the free device memory), in rounds over the file (windowed_fit.py: the stopping iteration of every fit from sums and chains
+    gathered over all windows, then every window run to exactly that iteration).  Returns (af, iters): af the (m, K) float32
+    frequencies clamped per WGSassign.py:236-240 -- an np.lib.format.open_memmap at `out` when given, so the host holds one
+    window of them -- and iters (K,), bit for bit what emMAF_populations gives on the resident matrix.  Prints nothing.
+    emMAF_windowed.stats: rounds, windows, window_sites, chain_iterations, largest_matrix_bytes, matrices, seconds,
+    round_seconds, iterations_round1 (EM iterations round 1 ran per site, all fits) against iterations_needed (the sum of the
+    fits' stopping iterations);
+    emMAF_windowed.info: n, m, sample_names, site_names (the first and last four), pops."""
+    import time
+
+    from . import reader_cy, windowed_fit, windows
+    from .device import EMStream, get_context
+    ctx = ctx or get_context()
+    t0 = time.perf_counter()
+    IDs = np.asarray(IDs)
+    pops = np.unique(IDs[:, 1])
+    group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
+    counts = np.bincount(group_of, minlength=len(pops))
+    K = len(pops)
+    index, _, m = reader_cy.ensure_index(path)
+    if m <= 0:
+        raise ValueError("%s holds no sites" % path)
+    if window_sites is None:
+        W = windows.env_window_sites()
+        if W is None:
+            W = windows.plan_fit(m, len(group_of), K, ctx.mem_info()[0]) or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN
+    else:
+        if int(window_sites) < windows.ALIGN:
+            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
+        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+
+    def groups(sample_names):
+        if len(sample_names) != len(group_of):
+            raise AssertionError("Number of individuals in beagle and reference ID file do not match!")
+        return group_of, K
+
+    af = np.empty((m, K), dtype=np.float32) if out is None else np.lib.format.open_memmap(out, mode="w+", dtype=np.float32, shape=(m, K))
+    info, stats = {}, {"round_seconds": []}
+    stream = EMStream(K, maf_iter, m, ctx)
+    rounds = _DeviceRounds(None, stream, counts, af, stats)
+    gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info, group_of=groups, n_groups=K, again=rounds.again)
+    rounds.windows = gen
+    try:
+        iters, scheme = windowed_fit.fit(rounds, K, maf_iter, tole, m, EMBatch.GUARD)
+    finally:
+        rounds.want_more = False
+        gen.close()
+        for em in rounds.batches.values():
+            em.close()
+        stream.close()
+    if out is not None:
+        af.flush()
+    stats.update(rounds=scheme.rounds, windows=info["windows"], window_sites=W, chain_iterations=scheme.chain_iterations,
+                 largest_matrix_bytes=info["largest_matrix_bytes"], matrices=info["matrices"], seconds=time.perf_counter() - t0,
+                 iterations_round1=int(max(0, maf_iter)) * K, iterations_needed=int(sum(scheme.stop)))
+    emMAF_windowed.stats = stats
+    emMAF_windowed.info = dict({k: info[k] for k in ("n", "m", "sample_names", "site_names")}, pops=pops)
+    return af, iters

@@ -504,7 +504,7 @@ def stream_to_device(path, group_of=None, n_groups=1, ctx=None, threads=None, ra
         return beagle, list(st.sample_names), site_names, m_total
 
 
-def stream_windows(path, window_sites, ctx=None, threads=None, info=None):
+def stream_windows(path, window_sites, ctx=None, threads=None, info=None, group_of=None, n_groups=1, again=None):
     """The sites of a Beagle file as consecutive device windows of `window_sites` sites (a multiple of 8192; the last window
     may be shorter): a generator of DeviceBeagle objects (one group, as --get_pop_like scores) with site0 = the window's first
     site.  TWO device matrices of window_sites rows exist at most and are filled in alternation (DeviceBeagle.set_window moves a
@@ -517,7 +517,11 @@ def stream_windows(path, window_sites, ctx=None, threads=None, info=None):
     caller scores window w.  The device's share of an ingest -- BGZF inflate, tokeniser -- runs on the context's one stream, from
     the caller's thread, when the next window is asked for: the device work of consecutive windows is strictly serial.
     info (a dict, optional) receives n, m, sample_names, site_names (the first and last four of the file, as names="ends"),
-    windows, matrices (created) and largest_matrix_bytes."""
+    windows, matrices (created) and largest_matrix_bytes.
+    group_of / n_groups (optional; group_of may be a callable(sample_names) -> (group_of, n_groups)): the windows carry the
+    population slabs a fit needs instead of the one-group layout.  again (optional, a callable): asked once the caller is done
+    with the file's last window; while it answers True the windows start over at site 0 ON THE SAME MATRICES (a pass more of a
+    windowed fit: an EM batch attached to a matrix as its `window_em` stays with it, DeviceBeagle.set_window)."""
     from .device import DeviceBeagle
     W = int(window_sites)
     if W < 8192 or W % 8192:
@@ -528,6 +532,7 @@ def stream_windows(path, window_sites, ctx=None, threads=None, info=None):
     info.update(m=m, windows=nwin, matrices=0, largest_matrix_bytes=0, site_names=[])
     bufs = [None, None]
     opened = []
+    groups = {"of": group_of, "n": n_groups}
 
     def open_window(w):
         lo = w * W
@@ -538,7 +543,9 @@ def stream_windows(path, window_sites, ctx=None, threads=None, info=None):
             info.update(n=st.n, sample_names=list(st.sample_names))
         b = bufs[w & 1]
         if b is None:
-            b = bufs[w & 1] = DeviceBeagle(rows, st.n, site0=lo, ctx=ctx)      # (the second matrix of a two-window file is the short one)
+            if callable(groups["of"]):
+                groups["of"], groups["n"] = groups["of"](list(st.sample_names))
+            b = bufs[w & 1] = DeviceBeagle(rows, st.n, groups["of"], groups["n"], site0=lo, ctx=ctx)      # (the second matrix of a two-window file is the short one)
             info["matrices"] += 1
             info["largest_matrix_bytes"] = max(info["largest_matrix_bytes"], b.nbytes())
         else:
@@ -547,22 +554,29 @@ def stream_windows(path, window_sites, ctx=None, threads=None, info=None):
 
     try:
         head, tail = [], []
-        nxt = open_window(0) if nwin else None
-        for w in range(nwin):
-            st, b, rows, chunks = nxt
-            got = 0
-            for nrows, names in chunks:
-                got += nrows
-                if len(head) < 4:
-                    head = (head + names)[:4]
-                tail = (tail + names)[-4:]
-            st.close()
-            opened.remove(st)
-            if got != rows:
-                raise RuntimeError("Beagle file changed while reading: expected %d sites in window %d, parsed %d" % (rows, w, got))
-            info["site_names"] = head + tail if m > 4 else head
-            nxt = open_window(w + 1) if w + 1 < nwin else None
-            yield b
+        first_pass = True
+        while first_pass or (again is not None and again()):
+            nxt = open_window(0) if nwin else None
+            for w in range(nwin):
+                st, b, rows, chunks = nxt
+                got = 0
+                for nrows, names in chunks:
+                    got += nrows
+                    if first_pass:
+                        if len(head) < 4:
+                            head = (head + names)[:4]
+                        tail = (tail + names)[-4:]
+                st.close()
+                opened.remove(st)
+                if got != rows:
+                    raise RuntimeError("Beagle file changed while reading: expected %d sites in window %d, parsed %d" % (rows, w, got))
+                if first_pass:
+                    info["site_names"] = head + tail if m > 4 else head
+                nxt = open_window(w + 1) if w + 1 < nwin else None
+                yield b
+            first_pass = False
+            if not nwin:
+                break
     finally:
         for st in opened:
             st.close()

@@ -1,0 +1,152 @@
+"""The EM fit in site windows: which iteration each fit stops at, found in rounds over the file.
+Host-only and free of the GPU: pure decision logic over the sums and carries a round brings back, so a CPU stand-in drives
+it in the tests as tests/cpu_standin.py drives device.run_em.
+
+The EM update is per site (emMAF_cy.pyx:10-23): site s of fit k follows f_0 = 0.25, f_1, f_2, ... whatever the other sites
+do.  Only the stopping test couples the sites: the reference's result is f_t* with t* the first t <= maf_iter at which its
+serial float32 rmse1d(f_t, f_t-1) < tole, or f_maf_iter (iteration count 0, nothing printed) when there is none.  So t* is
+found from per-iteration sums gathered over ALL windows, and every window is then run for exactly t* iterations.
+
+A ROUND is one pass over the file in windows.  Every window resets every fit to 0.25 and runs it for as long as the round's
+plan says.  Round 1 runs maf_iter iterations and adds each window's float64 sum of squared differences of iteration t to
+S[t][k]; the order of that addition does not matter, because the sum only decides outside the band of
+device.guard_band / decide_converged (= em_band / em_classify of csrc/em_fit_ledger.h), where any float64 rounding is
+far inside the band's margin, and inside the band the exact chain decides: the reference's own serial float32 sum, walked
+over the windows in file order with a float32 carry C[t][k], as it is walked over SNP shards.  A chain needs another round,
+because which iterations need one is known only once all windows have added to S.  A fit whose stopping iteration was known
+when a round began is run to it, clamped and written out in that round.
+
+Per fit k:  ruled_out[k]  iterations known not to stop the fit
+            stop[k]       None, or the iteration its frequencies are taken from
+            iters[k]      what the reference would report: stop[k], or 0 when maf_iter was exhausted
+            chain[k]      iterations whose exact chain the next round walks
+Two rounds when the sums decide every fit, three when a chain is needed and its first batch of candidates settles it.
+"""
+import numpy as np
+
+from .device import chain_diff, decide_converged
+
+CHAIN_LOOKAHEAD = 8         # iterations of one fit a round walks the exact chain for, at most
+
+ACTIVE, CONVERGED, UNDECIDED = 0, 1, 2      # = EM_ACTIVE, EM_CONVERGED, EM_UNDECIDED of csrc/em_fit_ledger.h
+
+
+def classify(ssq, m_total, tole, guard=0.0):
+    """em_classify(ssq, em_band(tole, m_total, guard)) through device.decide_converged, which tests hold to it edge for edge."""
+    d = decide_converged(float(ssq), m_total, tole, guard)
+    return CONVERGED if d > 0 else ACTIVE if d < 0 else UNDECIDED
+
+
+class RoundPlan:
+    """What one round does in every window: run_iters[k] iterations of fit k from 0.25; final[k]: that is its stopping
+    iteration, clamp and write it; chains: (fit, iteration) pairs sorted by iteration; add_sums: the sums join S."""
+
+    def __init__(self, number, run_iters, final, chains, add_sums):
+        self.number = int(number)
+        self.run_iters = np.ascontiguousarray(run_iters, dtype=np.int32)
+        self.final = np.ascontiguousarray(final, dtype=np.int32)
+        self.chains = sorted(((int(k), int(t)) for k, t in chains), key=lambda c: (c[1], c[0]))
+        self.add_sums = bool(add_sums)
+
+    @property
+    def T(self):
+        return int(self.run_iters.max()) if len(self.run_iters) else 0
+
+
+class RoundScheme:
+    def __init__(self, n_fits, maf_iter, tole, m_total, guard=0.0, lookahead=None):
+        self.n_fits, self.maf_iter, self.tole, self.m_total, self.guard = int(n_fits), max(0, int(maf_iter)), float(tole), int(m_total), float(guard)
+        self.lookahead = max(1, int(CHAIN_LOOKAHEAD if lookahead is None else lookahead))
+        self.ruled_out = [0] * self.n_fits
+        self.stop = [None] * self.n_fits
+        self.iters = np.zeros(self.n_fits, dtype=np.int32)
+        self.chain = [[] for _ in range(self.n_fits)]
+        self.written = [False] * self.n_fits
+        self.rounds = 0
+        self.chain_iterations = 0           # (fit, iteration) chains walked over the file so far
+        self.have_sums = False
+        if self.maf_iter == 0:              # emMAF.py:20 never enters its loop: f = 0.25, nothing to decide
+            self.stop = [0] * self.n_fits
+            self.have_sums = True
+
+    def done(self):
+        return all(self.written)
+
+    def plan(self):
+        """The next round."""
+        if not self.have_sums:
+            return RoundPlan(self.rounds + 1, [self.maf_iter] * self.n_fits, [0] * self.n_fits, [], True)
+        run, final, chains = [], [], []
+        for k in range(self.n_fits):
+            if self.written[k]:
+                run.append(0), final.append(0)
+            elif self.stop[k] is not None:
+                run.append(self.stop[k]), final.append(1)
+            else:
+                run.append(max(self.chain[k])), final.append(0)
+                chains.extend((k, t) for t in self.chain[k])
+        return RoundPlan(self.rounds + 1, run, final, chains, False)
+
+    def _class(self, S, t, k):
+        return classify(S[t - 1][k], self.m_total, self.tole, self.guard)
+
+    def after_round(self, plan, S, C):
+        """The decisions a round allows.  S[t-1][k]: the float64 sum of iteration t over all sites; C[t-1][k]: the float32
+        carry after the last window of the chains this round walked (other cells are not looked at)."""
+        self.rounds += 1
+        self.have_sums = True
+        self.chain_iterations += len(plan.chains)
+        for k in range(self.n_fits):
+            if plan.final[k]:
+                self.written[k] = True
+        chained = [set() for _ in range(self.n_fits)]
+        for k, t in plan.chains:
+            chained[k].add(t)
+        for k in range(self.n_fits):
+            if self.stop[k] is not None:
+                continue
+            self.chain[k] = []
+            t = self.ruled_out[k] + 1
+            while True:
+                if t > self.maf_iter:                   # exhausted: f_maf_iter, the reference prints nothing
+                    self.stop[k], self.iters[k] = self.maf_iter, 0
+                    break
+                c = self._class(S, t, k)
+                if c == UNDECIDED and t in chained[k]:
+                    c = CONVERGED if chain_diff(C[t - 1][k], self.m_total) < self.tole else ACTIVE
+                if c == ACTIVE:
+                    self.ruled_out[k] = t
+                    t += 1
+                elif c == CONVERGED:
+                    self.stop[k], self.iters[k] = t, t
+                    break
+                else:                                   # the sum cannot say, and no chain of this iteration was walked: next round
+                    self.chain[k] = self._candidates(S, t, k)
+                    break
+
+    def _candidates(self, S, t, k):
+        """t and the following iterations that are not ruled out by their sums, lookahead of them at most, ending with the
+        first one whose sum says converged (the fit stops there at the latest)."""
+        out = [t]
+        u = t + 1
+        while len(out) < self.lookahead and u <= self.maf_iter and self._class(S, out[-1], k) != CONVERGED:
+            c = self._class(S, u, k)
+            if c != ACTIVE:
+                out.append(u)
+            if c == CONVERGED:
+                break
+            u += 1
+        return out
+
+
+def fit(backend, n_fits, maf_iter, tole, m_total, guard=0.0, lookahead=None):
+    """Rounds until every fit is written.  backend.run_round(plan) -> (S, C) runs the plan in every window of the file, in
+    file order, and writes the final fits.  Returns (iters (n_fits,) int32, the scheme -- rounds, chain_iterations, stop)."""
+    scheme = RoundScheme(n_fits, maf_iter, tole, m_total, guard, lookahead)
+    while not scheme.done():
+        plan = scheme.plan()
+        S, C = backend.run_round(plan)
+        scheme.after_round(plan, S, C)
+        if scheme.rounds > scheme.maf_iter + 2:
+            raise RuntimeError("the windowed fit did not settle in %d rounds" % scheme.rounds)
+    return scheme.iters.copy(), scheme

@@ -87,3 +87,50 @@ def plan(m, n, K, free_bytes, environ=None):
                           "frequencies and class codes); %d of the %d free bytes can be used" %
                           (ALIGN, n, 2 * ALIGN * site_bytes(n, K), max(0, budget(free_bytes)), free_bytes))
     return W
+
+
+def fit_site_bytes(n, K, counts=None):
+    """Device bytes one site takes in a windowed --get_reference_af of n individuals in K populations (counts: the individuals
+    of every population when known, else the worst split is assumed), from what the library really allocates per site:
+
+        matrix       16 * sum_g ceil(n_g / 2)       one slab per population (csrc/api.hip: wgs_beagle_create), at most
+                                                    16 * ((n + K) // 2)
+        frequencies  2 * 4 * K                      wgs_em_create's two float32 buffers per fit (csrc/em_api.hip; the third buffer
+                                                    of fused sweeps is never asked for by a windowed fit)
+        sums         8 * K / 64, rounded up         wgs_em_create's per-tile float64 partial sums: one per fit and 64 sites
+        class codes  1 + 8 * 254 + 8                class counts, the dictionary of at most 254 (g0, g1) rows, the encoder's records
+                     + sum_g (8 * ceil(n_g / 4)     per slab the codes AND the slab's own numbering of them (one byte per
+                              + 1 + 8 * 254)        individual each, whole quads), the per-tile row counts and the slab's own
+                                                    dictionary (csrc/codes.hip: wgs_beagle_codes, the build an EM sweep asks for)
+
+    The stopping test's tables (wgs_em_stream: maf_iter x K float64 and float32) and the chains' workspace (60 bytes per fit and
+    4096 sites) do not grow with the window worth mentioning and come out of RESERVE."""
+    n, K = int(n), int(K)
+    if counts is not None:
+        pairs = sum((int(c) + 1) // 2 for c in counts)
+        quads = sum((int(c) + 3) // 4 for c in counts)
+    else:
+        pairs, quads = (n + K) // 2, (n + 3 * K) // 4
+    return 16 * pairs + 8 * K + (8 * K + 63) // 64 + (1 + 8 * 254 + 8) + 8 * quads + K * (1 + 8 * 254)
+
+
+def fits_resident_fit(m, n, K, free_bytes, counts=None):
+    """Whether one matrix of m sites with its EM batch and codes fits the budget."""
+    return int(m) * fit_site_bytes(n, K, counts) <= budget(free_bytes)
+
+
+def plan_fit(m, n, K, free_bytes, environ=None, counts=None):
+    """plan() for --get_reference_af: None when the resident fit fits and WGSASSIGN_WINDOW_SITES does not ask for windows, else W (a
+    multiple of 8192).  Two windows are held, each with its EM batch and codes."""
+    forced = env_window_sites(environ)
+    if forced is not None:
+        return forced
+    if fits_resident_fit(m, n, K, free_bytes, counts):
+        return None
+    per_site = fit_site_bytes(n, K, counts)
+    W = budget(free_bytes) // (2 * per_site) // ALIGN * ALIGN
+    if W < ALIGN:
+        raise MemoryError("a windowed fit needs two windows of %d sites x %d individuals on the device (%d bytes with their "
+                          "frequency buffers and class codes); %d of the %d free bytes can be used" %
+                          (ALIGN, n, 2 * ALIGN * per_site, max(0, budget(free_bytes)), free_bytes))
+    return W
