@@ -1,38 +1,13 @@
 """BGZF inflate on the device (csrc/inflate.hip, RFC 1951 from the specification) against zlib: every block type (stored,
 fixed, dynamic), every compression level, text and binary data, empty and maximal blocks, long codes, corrupt streams."""
-import ctypes
 import zlib
 
 import numpy as np
 import pytest
 
+from inflate_dev import deflate, device_inflate
+
 pytestmark = pytest.mark.gpu
-
-
-def deflate(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, wbits=-15):
-    co = zlib.compressobj(level, zlib.DEFLATED, wbits, 9, strategy)
-    return co.compress(data) + co.flush()
-
-
-def device_inflate(streams, sizes):
-    from wgsassign_amd import _lib, device
-    ctx = device.get_context()
-    comp = b"".join(streams)
-    n = len(streams)
-    in_len = np.array([len(s) for s in streams], dtype=np.uint32)
-    in_off = np.concatenate([[0], np.cumsum(in_len[:-1], dtype=np.uint64)]).astype(np.uint64) if n else np.zeros(0, np.uint64)
-    isize = np.array(sizes, dtype=np.uint32)
-    out_off = np.concatenate([[0], np.cumsum(isize[:-1], dtype=np.uint64)]).astype(np.uint64) if n else np.zeros(0, np.uint64)
-    total = int(isize.sum())
-    out = np.zeros(max(total, 1), dtype=np.uint8)
-    status = np.full(max(n, 1), 9, dtype=np.uint8)
-    cbuf = np.frombuffer(comp + b"\0", dtype=np.uint8).copy()
-    ms = ctypes.c_float()
-    _lib.check(_lib.load().wgs_debug_inflate(ctx.handle, cbuf.ctypes.data, len(comp), in_off.ctypes.data, in_len.ctypes.data,
-                                             out_off.ctypes.data, isize.ctypes.data, n, out.ctypes.data, total, status.ctypes.data,
-                                             ctypes.byref(ms)))
-    outs = [out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off, isize)]
-    return outs, status[:n], ms.value
 
 
 def test_every_block_type_level_and_kind_of_data():
