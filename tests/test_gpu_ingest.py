@@ -67,8 +67,12 @@ def test_awkward_tokens_flag_lines_for_the_host(tmp_path, monkeypatch, container
     rng = np.random.default_rng(2)
     n = 24
 
+    from token_cases import device_takes
+    left_to_host = []                                           # per line: a KEPT token (two of every three) is outside the device's grammar
+
     def line(name, pool, sep="\t"):
         t = [pool[int(k)] for k in rng.integers(0, len(pool), size=3 * n)]
+        left_to_host.append(any(not device_takes(x.encode()) for i, x in enumerate(t) if i % 3 < 2))
         return name + sep + "A" + sep + "C" + sep + sep.join(t)
     head = "marker allele1 allele2 " + " ".join("S%d S%d S%d" % (i, i, i) for i in range(n))
     lines = [head]
@@ -92,7 +96,8 @@ def test_awkward_tokens_flag_lines_for_the_host(tmp_path, monkeypatch, container
     want, samples_h, sites_h = reader_cy.readBeagle(p)
     rows, samples, sites, stats = device_rows(p)
     assert same_bits(rows, want) and samples == samples_h and sites == sites_h == ["s%d" % s for s in range(400)]
-    assert 0 < stats["host_lines"] <= sum(kinds)                # only lines that hold a hard token went to the host
+    assert 0 < sum(left_to_host) <= sum(kinds)
+    assert stats["host_lines"] == sum(left_to_host)             # exactly the lines that hold a hard token in a kept column went to the host
     # a short line is reported like the host reader reports it
     write(head + "\n" + line("s0", plain) + "\ns1\tA\tC\t0.1\t0.2\n")
     with pytest.raises(ValueError, match="Beagle data line 3 has fewer than %d" % (3 * n)):
