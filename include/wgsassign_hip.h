@@ -332,6 +332,37 @@ int wgs_em_stream_push(wgs_em_stream *stream, wgs_em *window_em, const int32_t *
 int wgs_em_stream_read(wgs_em_stream *stream, double *S_host, float *C_host);
 int wgs_em_stream_move_window(wgs_em *window_em, int64_t site0, int64_t rows);
 void wgs_em_stream_destroy(wgs_em_stream *stream);
+/*   wgs_em_stream_push_keep     wgs_em_stream_push for fits the host does not want (leave-one-out re-fits): a final fit is clamped and
+ *                               STAYS in the batch -- wgs_em_f_dev finds it until the batch is pushed again -- and nothing of the window's
+ *                               size is copied.  sums_from (may be NULL: no sums are added): the window's sum of iteration t joins
+ *                               S[t][fit] for t > sums_from[fit] only (0 <= sums_from[fit] <= run_iters[fit]), so a round that runs a
+ *                               fit further than an earlier round did adds what is new and nothing twice: S is zeroed when the stream is
+ *                               made and never again.  Refuses what wgs_em_stream_push refuses. */
+int wgs_em_stream_push_keep(wgs_em_stream *stream, wgs_em *window_em, const int32_t *run_iters, const int32_t *final, const float *clamp_lo,
+                            const float *clamp_hi, const int32_t *chain_fit, const int32_t *chain_iter, int32_t n_chain,
+                            const int32_t *sums_from);
+
+/* The leave-one-out run in site windows: what wgs_loo does after its re-fits, window by window.  The stream
+ * keeps, on the device and across pushes, np.sum's running float64 totals (n x K) and -- for P > 0 -- the serial float32 partition sums
+ * so far (n x P x K); a window continues both as the SNP shard of a rank > 0 does in wgs_loo, so they equal those of one resident matrix
+ * bit for bit.
+ *   wgs_loo_stream_create    for n individuals, K populations, m_total sites and P partitions (0: no partition sums);
+ *   wgs_loo_stream_push      one window: `window_em` is the batch of n re-fits over the window's matrix (fit i: the population of
+ *                            individual i without i) at their stopping iterations and clamped (wgs_em_stream_push_keep), window_af the
+ *                            window's rows of the full-population frequencies.  Builds the column table of glassy.py:87-105, runs the
+ *                            per-individual sweep (exact whenever P > 0, else `mode`), folds the window's 8192-site chunk sums onto the
+ *                            totals and walks the partition chains on from the carries (labels (site0 + s) % P; the literal chains beyond
+ *                            WGS_MAX_BLOCK_PARALLEL_PARTS partitions).  The window rules of wgs_score_stream_push hold, the window has
+ *                            the stream's n and K and the batch is the n re-fits; anything else: rc 2 and a message, nothing launched;
+ *   wgs_loo_stream_finish    the one read-back: ll_out (host, n*K float64), parts_out (host, n*P*K float32, index (i*P + p)*K + k; NULL
+ *                            when P == 0).  rc 2 before all m_total sites were pushed;
+ *   wgs_loo_stream_destroy   a no-op for a stream that is gone already.  Like the other streams, to be destroyed before its context. */
+#define WGS_MAX_BLOCK_PARALLEL_PARTS 64
+typedef struct wgs_loo_stream wgs_loo_stream;
+int wgs_loo_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, int32_t P, wgs_loo_stream **out);
+int wgs_loo_stream_push(wgs_loo_stream *stream, wgs_em *window_em, wgs_afset *window_af, int mode);
+int wgs_loo_stream_finish(wgs_loo_stream *stream, double *ll_out, float *parts_out);
+void wgs_loo_stream_destroy(wgs_loo_stream *stream);
 /* glassy.loo(L, af, IDs, t, maf_iter, maf_tole, downsampled_L, num_partitions) -- glassy.py:47-112 -- in one
  * call on device-resident data: per individual (file order) the re-fit of its population without it
  * (wgs_em_fit, a batch of individuals at once), the clamp with n_pop - 1, the never-restored overwrite of

@@ -4,6 +4,7 @@
     python tools/bench_windowed.py [--snps 1000000 --inds 200 --pops 5] [--windows 4] [--repeats 3]
                                    [--parent-root DIR] [--out profiles/windowed_bench.json]
     python tools/bench_windowed.py --fit [...] [--out profiles/windowed_fit_bench.json]      # the same for --get_reference_af
+    python tools/bench_windowed.py --loo [...] [--out profiles/windowed_loo_bench.json]      # the same for --get_reference_af --loo
 
 The file comes from tools/beagle_files.py (seeded, seconds to write).  Every end-to-end figure is the wall time of one
 `python -m wgsassign_amd.WGSassign --get_pop_like` process -- interpreter start, HIP initialisation, ingest, scoring, the text
@@ -18,6 +19,11 @@ The outputs of all variants are compared byte for byte.
 --fit measures --get_reference_af instead (the fit in windows, in rounds over the file): the same three whole-process figures, and from
 one emMAF.emMAF_windowed in this process the rounds, the seconds of every round and the EM iterations round 1 ran against the
 iterations the fits needed.  What to expect there: rounds x the windowed scoring run's cost, plus round 1's extra sweeps.
+--loo measures --get_reference_af --loo (the windowed fit, then the leave-one-out run in the same windows;
+WGSASSIGN_LOO_WINDOW_SITES): the three whole-process figures, and from one emMAF.emMAF_windowed + glassy.loo_windowed in this process
+the rounds, the seconds of every round, the first horizons' iterations against the iterations the re-fits needed, and the resident
+re-fit and scoring seconds of glassy.loo_device on the same file.  What to expect there: rounds x the windowed pass, plus the resident
+re-fit time x (iterations run / iterations needed), plus the per-window launches.
 What to expect: the device's share of an ingest (BGZF inflate, tokeniser) and the sweeps use the context's one stream and every push
 waits for it, so for a BGZF file the device work of consecutive windows is strictly serial; what overlaps a window's sweep is only
 the producer thread's reading of the next window (for plain gzip also its inflate).  The windowed run therefore costs the resident
@@ -37,13 +43,14 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 
 
-def cli_seconds(root, beagle, af, out, env_extra, fit=False):
-    """af: the frequency file of --get_pop_like, or with fit the ID file of --get_reference_af."""
+def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False):
+    """af: the frequency file of --get_pop_like, or with fit (or loo) the ID file of --get_reference_af."""
     env = dict(os.environ)
     env.pop("WGSASSIGN_WINDOW_SITES", None)
+    env.pop("WGSASSIGN_LOO_WINDOW_SITES", None)
     env.update(env_extra)
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
-    what = ["--pop_af_IDs", af, "--get_reference_af"] if fit else ["--pop_af_file", af, "--get_pop_like"]
+    what = ["--pop_af_IDs", af, "--get_reference_af"] + (["--loo"] if loo else []) if fit or loo else ["--pop_af_file", af, "--get_pop_like"]
     t0 = time.perf_counter()
     r = subprocess.run([sys.executable, "-m", "wgsassign_amd.WGSassign", "--beagle", beagle] + what + ["--out", out],
                        cwd=os.path.dirname(out), env=env, capture_output=True, text=True)
@@ -96,8 +103,61 @@ def fit_leg(a, m, n, K, W):
     return res
 
 
+def loo_leg(a, m, n, K, W):
+    """--get_reference_af --loo resident against windowed; one JSON-able dict."""
+    import beagle_files
+    from wgsassign_amd import device, emMAF, glassy, reader_cy
+    res = {"bench": "windowed_loo", "snps": m, "inds": n, "pops": K, "window_sites": W, "windows": a.windows}
+    with tempfile.TemporaryDirectory() as td:
+        os.environ["WGSASSIGN_INDEX_DIR"] = td
+        bg, ids = os.path.join(td, "x.beagle.gz"), os.path.join(td, "ids.txt")
+        beagle_files.write_lowdepth_bgzf(bg, n, m, seed=5)
+        IDs = np.array([["Ind%d" % i, "pop%d" % (i * K // n)] for i in range(n)])
+        np.savetxt(ids, IDs, fmt="%s", delimiter="\t")
+        res["file_mb"] = round(os.path.getsize(bg) / 1e6, 1)
+        variants = [("resident_s", ROOT, {})]
+        if a.parent_root:
+            variants.insert(0, ("parent_resident_s", os.path.abspath(a.parent_root), {}))
+        variants.append(("windowed_s", ROOT, {"WGSASSIGN_LOO_WINDOW_SITES": str(W)}))
+        times = {name: [] for name, _, _ in variants}
+        for rep in range(a.repeats + 1):
+            for name, root, env in variants:
+                dt, err = cli_seconds(root, bg, ids, os.path.join(td, name), env, loo=True)
+                if rep:
+                    times[name].append(dt)
+                if name == "windowed_s" and ("leave-one-out in" not in err or ("rounds of %d windows" % a.windows) not in err):
+                    raise RuntimeError("the windowed run did not use %d windows: %s" % (a.windows, err[-300:]))
+        files = {name: open(os.path.join(td, name + ".pop_af.npy"), "rb").read() + open(os.path.join(td, name + ".pop_like_LOO.tsv"), "rb").read()
+                 for name, _, _ in variants}
+        res["outputs_identical"] = len(set(files.values())) == 1
+        for name in ("parent_resident_s", "resident_s", "windowed_s"):
+            res[name] = spread(times[name]) if name in times else None
+        ctx = device.get_context()
+        res["device"] = ctx.info()["name"].strip()
+        pops = np.unique(IDs[:, 1])
+        group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
+        for rep in range(2):
+            af, pop_iters = emMAF.emMAF_windowed(bg, IDs, 200, 1e-4, W, ctx=ctx)
+            ll, _, iters = glassy.loo_windowed(bg, af, IDs, 200, 1e-4, W, 1, need_parts=False, pop_iters=pop_iters, ctx=ctx)
+        st = glassy.loo_windowed.stats
+        res.update(fit_rounds=emMAF.emMAF_windowed.stats["rounds"], fit_round_seconds=[round(x, 3) for x in emMAF.emMAF_windowed.stats["round_seconds"]],
+                   rounds=st["rounds"], round_seconds=[round(x, 3) for x in st["round_seconds"]], extension_rounds=st["extension_rounds"],
+                   population_iterations=[int(i) for i in pop_iters], iterations_min_max=[int(iters.min()), int(iters.max())],
+                   iterations_round1=st["iterations_round1"], iterations_needed=st["iterations_needed"],
+                   chain_iterations=st["chain_iterations"], largest_matrix_bytes=st["largest_matrix_bytes"], margin=glassy.LOO_MARGIN)
+        beagle, _, _, _ = reader_cy.stream_to_device(bg, group_of, K, ctx=ctx, names="ends")
+        for rep in range(2):
+            tm = {}
+            ll_r, _ = glassy.loo_device(beagle, beagle, np.array(af), group_of, 200, 1e-4, 1, verbose=False, timings=tm, need_parts=False)
+        beagle.close()
+        res.update(resident_refit_seconds=round(tm.get("em_seconds", 0.0), 4), resident_score_seconds=round(tm.get("score_seconds", 0.0), 4),
+                   resident_iterations_enqueued=tm.get("em_iterations_enqueued"), totals_bit_identical=bool(ll.tobytes() == ll_r.tobytes()))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--loo", action="store_true", help="measure --get_reference_af --loo (the leave-one-out run in windows)")
     ap.add_argument("--fit", action="store_true", help="measure --get_reference_af (the fit in windows) instead of --get_pop_like")
     ap.add_argument("--snps", type=int, default=1_000_000)
     ap.add_argument("--inds", type=int, default=200)
@@ -114,8 +174,8 @@ def main():
     W = (per_window + windows.ALIGN - 1) // windows.ALIGN * windows.ALIGN          # rounded UP to whole chunks of 8192
     if windows.window_count(m, W) != a.windows:
         raise SystemExit("%d sites cannot be cut into %d windows of a multiple of %d sites" % (m, a.windows, windows.ALIGN))
-    if a.fit:
-        line = json.dumps(fit_leg(a, m, n, K, W))
+    if a.fit or a.loo:
+        line = json.dumps(loo_leg(a, m, n, K, W) if a.loo else fit_leg(a, m, n, K, W))
         print(line)
         if a.out:
             with open(a.out, "w") as fh:

@@ -172,6 +172,48 @@ def _fit_window_sites(args, comm, ctx):
         raise SystemExit(str(e))
 
 
+def windowed_loo_candidate(args, world=1):
+    """Whether these options may run in site windows end to end (emMAF.emMAF_windowed, then glassy.loo_windowed):
+    --get_reference_af --loo alone, with any --partition_sites, on one rank.  --ne_obs, the z-scores, --get_pop_like beside them
+    and --loo_downsampled_beagle (two files in lockstep under a site filter) still need the whole matrix on the device."""
+    others = (args.get_pop_like, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score, args.loo_downsampled_beagle)
+    return bool(args.get_reference_af) and bool(args.loo) and int(world) == 1 and not any(others)
+
+
+def _loo_window_sites(args, comm, ctx):
+    """The window --get_reference_af --loo runs in, or None for the resident path: WGSASSIGN_LOO_WINDOW_SITES when set
+    (WGSASSIGN_WINDOW_SITES alone sends no leave-one-out run to windows), else windows only when the resident matrix would not
+    fit (windows.plan_loo), after the same first look as _fit_window_sites takes."""
+    import numpy as np
+
+    from . import reader_cy, windows
+    if not windowed_loo_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
+        return None                     # (a missing ID file is reported where it always was)
+    try:
+        W = windows.env_window_sites(name=windows.ENV_LOO)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if W is not None:
+        return W
+    free = ctx.mem_info()[0]
+    if windows.surely_fits(os.path.getsize(args.beagle), free):
+        return None
+    try:
+        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
+        counts = np.unique(IDs[:, 1], return_counts=True)[1]
+    except Exception:
+        return None                     # (an unreadable ID file, too, is reported where it always was)
+    n, K = int(counts.sum()), len(counts)
+    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
+    if est is not None and windows.fits_resident_fit(est + est // 4 + 1024, n, K, free, counts):
+        return None
+    m = reader_cy.ensure_index(args.beagle)[2]
+    try:
+        return windows.plan_loo(m, n, K, free, counts=counts, P=args.partition_sites)
+    except MemoryError as e:
+        raise SystemExit(str(e))
+
+
 def _run(args, comm):
     """The hot-path options on device-resident data.  Under torchrun (one process per GPU) the SNPs are
     sharded over the ranks: every rank parses and holds only its contiguous SNP range; the EM convergence sums,
@@ -227,9 +269,12 @@ def _run(args, comm):
         return
 
     W = _fit_window_sites(args, comm, ctx)
-    if W is not None:
+    W_loo = _loo_window_sites(args, comm, ctx) if W is None else None
+    if W is not None or W_loo is not None:
         # --get_reference_af alone on a file that does not fit (or WGSASSIGN_WINDOW_SITES): fitted window by window in rounds; the
-        # lines and files of the resident run, and one more line on stderr
+        # lines and files of the resident run, and one more line on stderr.  With --loo beside it (a file that does not fit, or
+        # WGSASSIGN_LOO_WINDOW_SITES) the leave-one-out run follows in the same windows, on the frequencies just written.
+        W = W if W is not None else W_loo
         af, iters = emMAF.emMAF_windowed(args.beagle, IDs, args.maf_iter, args.maf_tole, W, out=args.out + ".pop_af.npy", ctx=ctx)
         info, stats = emMAF.emMAF_windowed.info, emMAF.emMAF_windowed.stats
         say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
@@ -246,6 +291,29 @@ def _run(args, comm):
         np.savetxt(args.out + ".pop_names.txt", pops, fmt="%s")
         say("Saved reference population names as " + str(args.out) +
             ".pop_names.txt (String: Order of pops for .pop_af.npy, .ne_obs.npy, and fisher_obs.npy files)\n")
+        if W_loo is not None:
+            P = args.partition_sites
+            say("Performing leave-one-out cross validation.")
+            say(str(info["n"]) + " individuals to assign to " + str(len(pops)) + " populations")
+            A = np.load(args.out + ".pop_af.npy", mmap_mode="r")
+            ll, parts, loo_iters = glassy.loo_windowed(args.beagle, A, IDs, args.maf_iter, args.maf_tole, W, P, need_parts=P > 1,
+                                                       pop_iters=iters, ctx=ctx)
+            del A
+            stats = glassy.loo_windowed.stats
+            for it in loo_iters:
+                if it > 0:
+                    say("EM (MAF) converged at iteration: " + str(int(it)))
+            print("wgsassign_amd: leave-one-out in %d rounds of %d windows of %d sites" % (stats["rounds"], stats["windows"], stats["window_sites"]),
+                  file=sys.stderr, flush=True)
+            outfile = f"{args.out}.pop_like_LOO.tsv"
+            partfile = f"{args.out}.pop_like_LOO_partitions_{P}.tsv.gz"
+            utils.write_ass_mats(outfile, ll, info["sample_names"], pops, print_part_column=False, sample_locations=IDs[:, 1], doing_LOO=True)
+            say(f"Saved leave-one-out cross validation log likelihoods as {outfile}")
+            if P > 1:
+                utils.write_ass_mats(partfile, parts, info["sample_names"], pops, partition_count=P, print_part_column=True,
+                                     sample_locations=IDs[:, 1], doing_LOO=True)
+                say(f"Saved leave-one-out cross validation log likelihoods from partitioned sites as {partfile}")
+            say(f"Column order of populations is: {pops}")
         comm.barrier()
         return
 

@@ -170,6 +170,11 @@ SIGNATURES = {
     "wgs_em_stream_read": (c_int, [c_vp, c_f64p, c_f32p]),
     "wgs_em_stream_move_window": (c_int, [c_vp, c_i64, c_i64]),
     "wgs_em_stream_destroy": (None, [c_vp]),
+    "wgs_em_stream_push_keep": (c_int, [c_vp, c_vp, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32, c_i32p]),
+    "wgs_loo_stream_create": (c_int, [c_vp, c_i64, c_i32, c_i64, c_i32, ctypes.POINTER(c_vp)]),
+    "wgs_loo_stream_push": (c_int, [c_vp, c_vp, c_vp, c_int]),
+    "wgs_loo_stream_finish": (c_int, [c_vp, c_f64p, c_f32p]),
+    "wgs_loo_stream_destroy": (None, [c_vp]),
     "wgs_score_chains_prepare": (c_int, [c_vp, c_i32, c_f64p]),
     "wgs_score_chains_walk": (c_int, [c_vp, c_f32p, c_f32p]),
     "wgs_loo": (c_int, [c_vp, c_vp, c_vp, c_i32, ctypes.c_double, c_i64, c_vp, c_i32, c_i32, c_int, c_int, c_f64p, c_f32p, c_i32p]),

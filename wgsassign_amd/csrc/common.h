@@ -371,6 +371,7 @@ int launch_rmse_chain_batch(wgs_ctx *ctx, const ChainJob *d_jobs, int n_jobs, in
 // windowed fits (wgs_em_stream): total[j] += window[j] for j < n; the chains' running values taken from / put back into the table of
 // carries at cell[i] (jobs[i].carry_in = table[cell[i]]; table[cell[i]] = out[i])
 int launch_em_stream_add_sums(wgs_ctx *ctx, const double *d_window, double *d_total, int n);
+int launch_em_stream_add_sums_above(wgs_ctx *ctx, const double *d_window, double *d_total, const int32_t *d_from, int t, int n);
 int launch_em_stream_chain_load(wgs_ctx *ctx, ChainJob *d_jobs, const int32_t *d_cell, const float *d_table, int n_jobs);
 int launch_em_stream_chain_store(wgs_ctx *ctx, const float *d_out, const int32_t *d_cell, float *d_table, int n_jobs);
 

@@ -776,6 +776,7 @@ struct wgs_em_stream {
     float *d_chain_out = nullptr;       // [n_fits]
     void *d_chain_work = nullptr;
     size_t chain_work_bytes = 0;
+    int32_t *d_from = nullptr;          // [n_fits] wgs_em_stream_push_keep: the iterations of every fit whose sums S holds already
 };
 
 void wgs_em_stream_destroy(wgs_em_stream *st)
@@ -783,7 +784,7 @@ void wgs_em_stream_destroy(wgs_em_stream *st)
     if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
     (void)hipSetDevice(st->device);
     for (void *p : {(void *)st->d_S, (void *)st->d_C, (void *)st->d_win, (void *)st->d_descs, (void *)st->d_groups, (void *)st->d_jobs,
-                    (void *)st->d_cell, (void *)st->d_chain_out, st->d_chain_work})
+                    (void *)st->d_cell, (void *)st->d_chain_out, st->d_chain_work, (void *)st->d_from})
         if (p) (void)hipFree(p);
     for (void *p : {(void *)st->h_descs, (void *)st->h_groups, (void *)st->h_jobs, (void *)st->h_cell})
         if (p) (void)hipHostFree(p);
@@ -865,9 +866,11 @@ static int em_stream_chain_room(wgs_em_stream *st, size_t jobs, int64_t m)
  *                    (1 <= t <= run_iters[fit]; sorted by t), from C[t][fit] to C[t][fit];
  *   add_sums         != 0: the window's sum of every iteration t a fit runs is added to S[t][fit].
  * Returns when the device is done with the window: its matrix may be refilled, f_out holds the final fits' rows. */
-int wgs_em_stream_push(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, const int32_t *final, const float *clamp_lo,
-                       const float *clamp_hi, const int32_t *chain_fit, const int32_t *chain_iter, int32_t n_chain, int add_sums,
-                       float *f_out, int64_t f_stride)
+// Both pushes.  keep: final fits are clamped and stay in the batch (no f_out); sums_from (keep only; may be NULL: no sums): the sum of
+// iteration t of a fit joins S only for t > sums_from[fit].
+static int em_stream_push_window(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, const int32_t *final, const float *clamp_lo,
+                                 const float *clamp_hi, const int32_t *chain_fit, const int32_t *chain_iter, int32_t n_chain, int add_sums,
+                                 float *f_out, int64_t f_stride, bool keep, const int32_t *sums_from)
 {
     WGS_REQUIRE(st && em && run_iters, "null argument");
     wgs_beagle *window = em->b;
@@ -880,8 +883,9 @@ int wgs_em_stream_push(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, 
     bool any_final = false;
     char why[256];
     if (em_stream_window_refusal(window->site0, m, em->cap_m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why) ||
-        em_stream_plan_refusal(n, st->max_iter, run_iters, final, clamp_lo && clamp_hi, f_out != nullptr, f_stride, m, chain_fit, chain_iter, n_chain,
-                               &T, &any_final, why, sizeof why)) {
+        em_stream_plan_refusal(n, st->max_iter, run_iters, final, clamp_lo && clamp_hi, keep || f_out != nullptr, keep ? m : f_stride, m, chain_fit,
+                               chain_iter, n_chain, &T, &any_final, why, sizeof why) ||
+        (sums_from && em_stream_sums_from_refusal(n, run_iters, sums_from, why, sizeof why))) {
         wgs_set_error("%s", why);
         return 2;
     }
@@ -889,6 +893,11 @@ int wgs_em_stream_push(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, 
     wgs_ctx *ctx = st->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     if (em_stream_chain_room(st, (size_t)n_chain, m)) return 1;
+    if (sums_from) {
+        if (!st->d_from) HIP_TRY(wgs_malloc(&st->d_from, sizeof(int32_t) * (size_t)n));
+        HIP_TRY(hipMemcpyAsync(st->d_from, sums_from, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));          // (sums_from is the caller's)
+    }
     if (st->pushed == 0)                                     // a round begins: its chains start from zero
         HIP_TRY(hipMemsetAsync(st->d_C, 0, sizeof(float) * (size_t)n * std::max(1, st->max_iter), ctx->stream));
     if (launch_fill(ctx, em->fbuf[0], (int64_t)n * m, 0.25f)) return 1;       // emMAF.py:17-18
@@ -910,7 +919,8 @@ int wgs_em_stream_push(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, 
         HIP_TRY(hipMemsetAsync(st->d_win, 0, sizeof(double) * n, ctx->stream));
         if (em_enqueue_sweep(em, p, slot, st->d_win, nullptr, nullptr, nullptr, nullptr)) return 1;
         for (int j : list) em_commit_sweep(em, j);
-        if (add_sums && launch_em_stream_add_sums(ctx, st->d_win, st->d_S + (size_t)(t - 1) * n, n)) return 1;
+        if (add_sums && !sums_from && launch_em_stream_add_sums(ctx, st->d_win, st->d_S + (size_t)(t - 1) * n, n)) return 1;
+        if (sums_from && launch_em_stream_add_sums_above(ctx, st->d_win, st->d_S + (size_t)(t - 1) * n, st->d_from, t, n)) return 1;
         // the chains of iteration t, over what this sweep wrote and what it read
         const int first = next_chain;
         while (next_chain < n_chain && chain_iter[next_chain] == t) {
@@ -932,11 +942,32 @@ int wgs_em_stream_push(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, 
         if (!final[j]) continue;
         float *f = em_f(em, j, em->cur[j]);
         if (launch_clamp(ctx, f, m, clamp_lo[j], clamp_hi[j])) return 1;
-        HIP_TRY(hipMemcpyAsync(f_out + (size_t)j * f_stride, f, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
+        if (!keep) HIP_TRY(hipMemcpyAsync(f_out + (size_t)j * f_stride, f, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     st->pushed += m;
     return 0;
+}
+
+int wgs_em_stream_push(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, const int32_t *final, const float *clamp_lo,
+                       const float *clamp_hi, const int32_t *chain_fit, const int32_t *chain_iter, int32_t n_chain, int add_sums,
+                       float *f_out, int64_t f_stride)
+{
+    return em_stream_push_window(st, em, run_iters, final, clamp_lo, clamp_hi, chain_fit, chain_iter, n_chain, add_sums, f_out, f_stride, false,
+                                 nullptr);
+}
+
+/* wgs_em_stream_push for fits nobody on the host wants (the leave-one-out re-fits, wgs_loo_stream_push): a final fit is clamped and
+ * STAYS in the batch, where wgs_em_f_dev finds it until the batch is pushed again -- nothing of the window's size is copied anywhere.
+ * sums_from (may be NULL: this push adds no sums): the window's sum of iteration t of a fit joins S[t][fit] for t > sums_from[fit]
+ * only, 0 <= sums_from[fit] <= run_iters[fit] -- a round that runs a fit further than an earlier one did adds what is new and nothing
+ * twice (S is zeroed when the stream is made and never again). */
+int wgs_em_stream_push_keep(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, const int32_t *final, const float *clamp_lo,
+                            const float *clamp_hi, const int32_t *chain_fit, const int32_t *chain_iter, int32_t n_chain,
+                            const int32_t *sums_from)
+{
+    return em_stream_push_window(st, em, run_iters, final, clamp_lo, clamp_hi, chain_fit, chain_iter, n_chain, sums_from != nullptr, nullptr, 0,
+                                 true, sums_from);
 }
 
 /* The round's one read-back: S (max_iter x n_fits float64) and C (max_iter x n_fits float32), either may be NULL.  rc 2 before all

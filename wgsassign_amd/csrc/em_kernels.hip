@@ -1600,6 +1600,14 @@ __global__ void em_stream_add_sums_kernel(const double *__restrict__ window, dou
     if (j < n) total[j] += window[j];                  // (one addition per window, in file order: the same total run to run)
 }
 
+// total[j] += window[j] for the fits whose sum of iteration t is not in the table yet (t > from[j])
+__global__ void em_stream_add_sums_above_kernel(const double *__restrict__ window, double *__restrict__ total, const int32_t *__restrict__ from,
+                                                int t, int n)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n && t > from[j]) total[j] += window[j];
+}
+
 __global__ void em_stream_chain_load_kernel(ChainJob *__restrict__ jobs, const int32_t *__restrict__ cell, const float *__restrict__ table, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1616,6 +1624,14 @@ int launch_em_stream_add_sums(wgs_ctx *ctx, const double *d_window, double *d_to
 {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(em_stream_add_sums_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_window, d_total, n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_em_stream_add_sums_above(wgs_ctx *ctx, const double *d_window, double *d_total, const int32_t *d_from, int t, int n)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(em_stream_add_sums_above_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_window, d_total, d_from, t, n);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -53,3 +53,12 @@ inline int em_stream_plan_refusal(int32_t n_fits, int32_t max_iter, const int32_
     *any_final_out = any_final;
     return 0;
 }
+
+// wgs_em_stream_push_keep: the iterations of every fit whose sums the table holds already lie inside what the fit runs.
+inline int em_stream_sums_from_refusal(int32_t n_fits, const int32_t *run_iters, const int32_t *sums_from, char *msg, size_t msg_len)
+{
+    for (int32_t j = 0; j < n_fits; ++j)
+        EM_STREAM_REFUSE(sums_from[j] >= 0 && sums_from[j] <= run_iters[j], "fit %d: sums above iteration %d, but it runs %d", j, sums_from[j],
+                         run_iters[j]);
+    return 0;
+}

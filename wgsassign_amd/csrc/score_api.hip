@@ -8,6 +8,8 @@
 #include <string>
 
 #include "common.h"
+#include "em_state.h"
+#include "loo_stream_checks.h"
 
 struct wgs_score {
     wgs_beagle *b = nullptr;
@@ -514,14 +516,11 @@ int wgs_score_stream_finish(wgs_score_stream *st, double *out_nK)
  * sums of wgs_score_sums(WGS_MODE_EXACT).  start (host, n*K doubles, may be NULL) = the float64 sums over
  * the SNP shards that precede this one (its partitions are predicted to hold equal shares).  rc 2 when P is
  * too large for the block-parallel kernel (use wgs_assign_parts_exact's literal chains then). */
-int wgs_score_chains_prepare(wgs_score *sc, int32_t P, const double *start)
+// The block functions of wgs_score_chains_prepare, enqueued: `start` (n*K float64, may be NULL) is copied from the host or from the device
+// (start_on_device: a running total that never left it, wgs_loo_stream_push).  The caller waits for the stream before `start` changes.
+static int chains_prepare_enqueue(wgs_score *sc, int32_t P, const double *start, bool start_on_device)
 {
-    WGS_REQUIRE(sc, "null argument");
-    WGS_REQUIRE(P >= 1, "partition count must be >= 1");
-    WGS_REQUIRE(sc->have_prefix, "wgs_score_chains_prepare needs wgs_score_sums(WGS_MODE_EXACT) first");
-    WGS_REQUIRE(chains_block_parallel(sc->plan, sc->cells, P), "too many partitions (%d) for the block-parallel chains", P);
     wgs_ctx *ctx = sc->b->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
     const size_t chains = (size_t)sc->cells * P;
     if (sc->P != P) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -541,7 +540,9 @@ int wgs_score_chains_prepare(wgs_score *sc, int32_t P, const double *start)
         sc->P = P;
     }
     HIP_TRY(hipMemsetAsync(sc->d_cand, 0, sizeof(uint32_t) * chains * sc->nblocks, ctx->stream));
-    if (start) HIP_TRY(hipMemcpyAsync(sc->d_start, start, sizeof(double) * sc->cells, hipMemcpyHostToDevice, ctx->stream));
+    if (start)
+        HIP_TRY(hipMemcpyAsync(sc->d_start, start, sizeof(double) * sc->cells, start_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                               ctx->stream));
     ScoreArgs A = score_args(sc, 1);
     A.P = P;
     int g = 64, r = P;                       // gcd(64, P)
@@ -556,6 +557,18 @@ int wgs_score_chains_prepare(wgs_score *sc, int32_t P, const double *start)
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     if (launch_chain_cand(ctx, A, sc->plan.chain_kb, sc->plan.chain_np)) return 1;
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    return 0;
+}
+
+int wgs_score_chains_prepare(wgs_score *sc, int32_t P, const double *start)
+{
+    WGS_REQUIRE(sc, "null argument");
+    WGS_REQUIRE(P >= 1, "partition count must be >= 1");
+    WGS_REQUIRE(sc->have_prefix, "wgs_score_chains_prepare needs wgs_score_sums(WGS_MODE_EXACT) first");
+    WGS_REQUIRE(chains_block_parallel(sc->plan, sc->cells, P), "too many partitions (%d) for the block-parallel chains", P);
+    wgs_ctx *ctx = sc->b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (chains_prepare_enqueue(sc, P, start, false)) return 1;
     HIP_TRY(hipStreamSynchronize(ctx->stream));       // `start` (host) has been consumed
     ctx->assign_ms_pending = true;
     return 0;
@@ -936,6 +949,140 @@ static int parts_exact_literal(wgs_beagle *b, wgs_afset *a, const float *const *
     if (launch_parts_exact(ctx, args, d_slabs, (int)slabs.size(), blocks, d_carry, d_parts)) return 1;
     HIP_TRY(hipMemcpyAsync(parts_out, d_parts, sizeof(float) * cells, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+/* ---- the leave-one-out run in site windows ("leave-one-out in windows").  What wgs_loo does on one resident
+ * matrix after its re-fits -- the column table of glassy.py:87-105, the per-individual sweep, np.sum's float64 totals, the serial float32
+ * partition sums -- happens here window by window, on the window's batch of n re-fits that the last round of a windowed fit left
+ * clamped on the device (wgs_em_stream_push_keep).  Between the pushes the stream keeps the n x K running totals (two buffers in
+ * alternation, as wgs_score_stream) and the n x P x K float32 partition carries on the device; a window continues both exactly as the
+ * SNP shard of a rank > 0 continues them in wgs_loo: the totals over its 8192-site chunk sums, the chains from the carries with the
+ * totals before the window as `start`.  wgs_loo_stream_finish is the one read-back. */
+constexpr int WGS_LIVE_LOO_STREAM = 7;  // kind in the live-object registry (5: score stream, 6: fit stream): only its liveness is kept
+struct wgs_loo_stream {
+    wgs_ctx *ctx = nullptr;
+    int device = 0;
+    int64_t n = 0, m_total = 0, pushed = 0, cells = 0;
+    int32_t K = 0, P = 0;               // P == 0: no partition sums
+    double *d_run[2] = {nullptr, nullptr};
+    int cur = 0;                        // d_run[cur]: the totals over the sites pushed so far (pushed > 0)
+    float *d_carry = nullptr;           // [n * P * K] the partition sums over the sites pushed so far
+    std::vector<float> h_carry, h_parts;    // the literal chains (P too large for the block-parallel ones) take and give host arrays
+};
+
+void wgs_loo_stream_destroy(wgs_loo_stream *st)
+{
+    if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
+    (void)hipSetDevice(st->device);
+    for (void *p : {(void *)st->d_run[0], (void *)st->d_run[1], (void *)st->d_carry})
+        if (p) (void)hipFree(p);
+    delete st;
+}
+
+int wgs_loo_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, int32_t P, wgs_loo_stream **out)
+{
+    WGS_REQUIRE(ctx && out, "null argument");
+    WGS_REQUIRE(n > 0 && K > 0 && m_total > 0, "a leave-one-out stream needs individuals, populations and sites (%lld x %d over %lld sites)",
+                (long long)n, K, (long long)m_total);
+    WGS_REQUIRE(P >= 0, "partition count must be >= 0 (0: no partition sums)");
+    WGS_REQUIRE(n * (int64_t)K * std::max(1, P) < (1ll << 31), "%lld individuals x %d populations x %d partitions are too many for one stream",
+                (long long)n, K, P);
+    HIP_TRY(hipSetDevice(ctx->device));
+    wgs_loo_stream *st = new wgs_loo_stream();
+    wgs_live_add(st, WGS_LIVE_LOO_STREAM, nullptr);
+    auto guard = on_failure([&] { wgs_loo_stream_destroy(st); });
+    st->ctx = ctx;
+    st->device = ctx->device;
+    st->n = n;
+    st->K = K;
+    st->P = P;
+    st->m_total = m_total;
+    st->cells = n * (int64_t)K;
+    for (double *&p : st->d_run) HIP_TRY(wgs_malloc(&p, sizeof(double) * (size_t)st->cells));
+    if (P > 0) HIP_TRY(wgs_malloc(&st->d_carry, sizeof(float) * (size_t)st->cells * P));
+    guard.dismiss();
+    *out = st;
+    return 0;
+}
+
+/* One window: `window_em` is the batch of n re-fits made from the window's matrix (fit i: the population of individual i without i),
+ * every fit at its stopping iteration and clamped; window_af the window's rows of the full-population frequencies.  Individual i is
+ * scored against its own re-fit and, for every other population, the re-fit of the most recent earlier individual of that population,
+ * else the column of window_af (glassy.py:87-105).  mode: the arithmetic of the sweep when no partition sums are kept (with them it is
+ * exact).  A wrong first site, a misaligned or ragged middle window, an overrun, another n or K, a batch that is not the n re-fits:
+ * rc 2 and a message, nothing launched.  Returns when the device is done with the window; nothing is read back. */
+int wgs_loo_stream_push(wgs_loo_stream *st, wgs_em *window_em, wgs_afset *window_af, int mode)
+{
+    WGS_REQUIRE(st && window_em && window_af, "null argument");
+    WGS_REQUIRE(mode == WGS_MODE_EXACT || mode == WGS_MODE_FAST, "unknown mode %d", mode);
+    wgs_beagle *window = window_em->b;
+    WGS_REQUIRE(window->ctx == st->ctx && window_af->ctx == st->ctx, "the window belongs to another context than the leave-one-out stream");
+    char why[256];
+    if (loo_stream_shape_refusal(window->n, window->n_groups, window_em->n_fits, window_af->K, window_af->m, window->m, st->n, st->K, why,
+                                 sizeof why) ||
+        loo_stream_fits_refusal(st->n, window_em->group.data(), window_em->skip_local.data(), window->group_of.data(), why, sizeof why) ||
+        loo_stream_window_refusal(window->site0, window->m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why)) {
+        wgs_set_error("%s", why);
+        return 2;
+    }
+    wgs_ctx *ctx = st->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int64_t n = st->n;
+    const int K = st->K, P = st->P;
+    const size_t cells = (size_t)st->cells;
+    // glassy.py:87-105: individual i's own re-fit, else the most recent earlier re-fit, else the column of window_af
+    std::vector<const float *> colptr(cells), cur(K);
+    for (int k = 0; k < K; ++k) cur[k] = window_af->buf + (size_t)k * window_af->m;
+    for (int64_t i = 0; i < n; ++i) {
+        cur[window->group_of[i]] = wgs_em_f_dev(window_em, (int32_t)i);
+        for (int k = 0; k < K; ++k) colptr[(size_t)i * K + k] = cur[k];
+    }
+    wgs_score *sc = nullptr;
+    auto guard = on_failure([&] { wgs_score_destroy(sc); });
+    if (int rc = wgs_score_create(window, window_af, colptr.data(), 0, (int32_t)n, &sc)) return rc;
+    if (score_sums_enqueue(sc, P > 0 ? WGS_MODE_EXACT : mode)) return 1;
+    sc->have_prefix = P > 0;
+    const double *before = st->pushed ? st->d_run[st->cur] : nullptr;      // the totals over the windows before this one
+    if (score_total_enqueue(sc, before, st->d_run[st->cur ^ 1])) return 1;
+    const size_t chains = cells * (size_t)std::max(1, P);
+    if (P > 0 && P <= WGS_MAX_BLOCK_PARALLEL_PARTS && chains_block_parallel(sc->plan, sc->cells, P)) {
+        if (chains_prepare_enqueue(sc, P, before, true)) return 1;
+        if (before) HIP_TRY(hipMemcpyAsync(sc->d_carry, st->d_carry, sizeof(float) * chains, hipMemcpyDeviceToDevice, ctx->stream));
+        if (chains_walk_enqueue(sc, before != nullptr)) return 1;
+        HIP_TRY(hipMemcpyAsync(st->d_carry, sc->d_parts, sizeof(float) * chains, hipMemcpyDeviceToDevice, ctx->stream));
+    } else if (P > 0) {
+        // many short chains: the literal one-lane chains, which take the carry and give the sums as host arrays (n * P * K floats)
+        st->h_parts.assign(chains, 0.0f);
+        if (before) {
+            st->h_carry.resize(chains);
+            HIP_TRY(hipMemcpyAsync(st->h_carry.data(), st->d_carry, sizeof(float) * chains, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (int rc = parts_exact_literal(window, window_af, colptr.data(), P, before ? st->h_carry.data() : nullptr, st->h_parts.data())) return rc;
+        HIP_TRY(hipMemcpyAsync(st->d_carry, st->h_parts.data(), sizeof(float) * chains, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    guard.dismiss();
+    wgs_score_destroy(sc);
+    ctx->assign_ms_pending = true;
+    st->cur ^= 1;
+    st->pushed += window->m;
+    return 0;
+}
+
+/* The one read-back: ll_out (host, n*K float64, overwritten) the totals, parts_out (host, n*P*K float32, index (i*P + p)*K + k; NULL
+ * when the stream keeps no partition sums) the partition sums.  rc 2 before all m_total sites were pushed. */
+int wgs_loo_stream_finish(wgs_loo_stream *st, double *ll_out, float *parts_out)
+{
+    WGS_REQUIRE(st && ll_out, "null argument");
+    WGS_REQUIRE(st->pushed == st->m_total, "only %lld of the %lld sites were pushed", (long long)st->pushed, (long long)st->m_total);
+    WGS_REQUIRE(!parts_out || st->P > 0, "the leave-one-out stream keeps no partition sums");
+    HIP_TRY(hipSetDevice(st->ctx->device));
+    HIP_TRY(hipMemcpyAsync(ll_out, st->d_run[st->cur], sizeof(double) * (size_t)st->cells, hipMemcpyDeviceToHost, st->ctx->stream));
+    if (parts_out)
+        HIP_TRY(hipMemcpyAsync(parts_out, st->d_carry, sizeof(float) * (size_t)st->cells * st->P, hipMemcpyDeviceToHost, st->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(st->ctx->stream));
     return 0;
 }
 

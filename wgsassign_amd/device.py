@@ -24,7 +24,7 @@ _live = weakref.WeakSet()       # device objects that still own library handles
 def _close_all():
     """Release every device object before the interpreter tears modules down: children (scores, EM batches)
     before the matrices they refer to, so no destructor runs against a freed parent or an unloaded library."""
-    order = {"Score": 0, "ScoreStream": 0, "EMStream": 0, "EMBatch": 1, "AFSet": 2, "DeviceBeagle": 3}
+    order = {"Score": 0, "ScoreStream": 0, "EMStream": 0, "LooStream": 0, "EMBatch": 1, "AFSet": 2, "DeviceBeagle": 3}
     for obj in sorted(list(_live), key=lambda o: order.get(type(o).__name__, 9)):
         try:
             obj.close()
@@ -784,6 +784,28 @@ class EMStream:
                                              None if f_out is None else f32p(f_out), int(stride)))
         self.windows += 1
 
+    def push_keep(self, em, run_iters, final=None, clamp_lo=None, clamp_hi=None, chains=(), sums_from=None):
+        """push() for fits the host does not want (wgs_em_stream_push_keep): a final fit is clamped and stays in `em` (em.f_dev),
+        no frequencies are copied.  sums_from (n_fits,) or None (no sums): the sum of iteration t of fit k joins S for
+        t > sums_from[k] only."""
+        run = np.ascontiguousarray(run_iters, dtype=np.int32)
+        if run.shape != (self.n_fits,):
+            raise ValueError("run_iters must have one entry per fit")
+        fin = None if final is None else np.ascontiguousarray(final, dtype=np.int32)
+        lo = None if clamp_lo is None else np.ascontiguousarray(clamp_lo, dtype=np.float32)
+        hi = None if clamp_hi is None else np.ascontiguousarray(clamp_hi, dtype=np.float32)
+        frm = None if sums_from is None else np.ascontiguousarray(sums_from, dtype=np.int32)
+        for a in (fin, lo, hi, frm):
+            if a is not None and a.shape != (self.n_fits,):
+                raise ValueError("final, the clamps and sums_from must have one entry per fit")
+        cf = np.ascontiguousarray([c[0] for c in chains], dtype=np.int32)
+        ci = np.ascontiguousarray([c[1] for c in chains], dtype=np.int32)
+        check(_lib.load().wgs_em_stream_push_keep(self._h, em.handle, i32p(run), None if fin is None else i32p(fin),
+                                                  None if lo is None else f32p(lo), None if hi is None else f32p(hi),
+                                                  i32p(cf) if len(cf) else None, i32p(ci) if len(ci) else None, len(cf),
+                                                  None if frm is None else i32p(frm)))
+        self.windows += 1
+
     def read(self):
         """(S, C) of the round just pushed, (maf_iter, n_fits) float64 / float32; the next push begins the next round."""
         S = np.zeros((self.maf_iter, self.n_fits), dtype=np.float64)
@@ -794,6 +816,51 @@ class EMStream:
     def close(self):
         if self._h:
             _lib.load().wgs_em_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LooStream:
+    """The accumulator of the leave-one-out run in site windows (wgs_loo_stream): np.sum's n x K float64 totals and, for P > 0,
+    the n x P x K serial float32 partition sums stay on the device from push to push -- bit for bit what glassy.loo_device gives
+    on one resident matrix."""
+
+    def __init__(self, n, K, m_total, P=0, ctx=None):
+        self.ctx = ctx or get_context()
+        self.n, self.K, self.m_total, self.P = int(n), int(K), int(m_total), int(P)
+        self.windows = 0
+        h = ctypes.c_void_p()
+        check(_lib.load().wgs_loo_stream_create(self.ctx.handle, self.n, self.K, self.m_total, self.P, ctypes.byref(h)))
+        self._h = h
+        self.ctx._children.add(self)
+        _live.add(self)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def push(self, em, afset, mode=None):
+        """Scores one window: `em` holds its n re-fits at their stopping iterations, clamped (EMStream.push_keep); afset the
+        window's rows of the full-population frequencies.  em.b.site0 must be the number of sites pushed so far."""
+        mode = default_mode() if mode is None else mode
+        check(_lib.load().wgs_loo_stream_push(self._h, em.handle, afset.handle, mode))
+        self.windows += 1
+
+    def finish(self):
+        """((n, K) float64 totals, (n*P, K) float32 partition sums or None); refused before all m_total sites were pushed."""
+        out = np.zeros((self.n, self.K), dtype=np.float64)
+        parts = np.zeros((self.n * self.P, self.K), dtype=np.float32) if self.P > 0 else None
+        check(_lib.load().wgs_loo_stream_finish(self._h, f64p(out), f32p(parts) if parts is not None else None))
+        return out, parts
+
+    def close(self):
+        if self._h:
+            _lib.load().wgs_loo_stream_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -259,6 +259,149 @@ def loo_device(beagle, scored, af, group_of, maf_iter, maf_tole, P=1, comm=None,
     return logl, logl_parts
 
 
+# Iterations a re-fit's first horizon lies beyond the stopping iteration of its population's full fit: the largest t*_i - t*_pop(i)
+# tools/measure_loo_margin.py found on the resident --loo at 2M x 500 x K=8 and 5M x 180 x K=5 (0 for every
+# re-fit at depth 2 and 8, +1 for 36 of 180 at depth 0.5).  A re-fit that stops later than that costs one extension round.
+LOO_MARGIN = 1
+
+
+def loo_first_iters(group_of, pop_iters, maf_iter, margin=None):
+    """The first horizon of every leave-one-out re-fit (windowed_fit.RoundScheme): the stopping iteration of its population's
+    full fit plus LOO_MARGIN, maf_iter where that fit was exhausted (pop_iters[k] == 0).  Only the number of rounds depends on
+    it, never the result."""
+    margin = LOO_MARGIN if margin is None else int(margin)
+    pop_iters = np.asarray(pop_iters)
+    return [int(maf_iter) if pop_iters[g] <= 0 else min(int(maf_iter), int(pop_iters[g]) + margin) for g in group_of]
+
+
+class _LooRounds:
+    """windowed_fit's backend for the leave-one-out re-fits: a round is one pass of reader_cy.stream_windows, every window pushed
+    through the EMBatch of its matrix (n re-fits, kept for every window and round) into one device.EMStream; in the last round --
+    every fit final -- the batch stays on the device and the window is scored into one device.LooStream."""
+
+    def __init__(self, windows, stream, loo, group_of, counts, af, stats, mode):
+        self.windows, self.stream, self.loo, self.group_of, self.af, self.stats, self.mode = windows, stream, loo, group_of, af, stats, mode
+        lo = 1 / (2 * (np.asarray(counts, dtype=np.float64)[group_of] - 1 + 1))        # glassy.py:80-85 with n_pop = |pop| - 1, as EMBatch.clamp forms them
+        self.lo, self.hi = lo.astype(np.float32), (1 - lo).astype(np.float32)
+        self.batches = {}
+        self.want_more = False
+
+    def again(self):
+        return self.want_more
+
+    def run_round(self, plan):
+        import time
+        t0 = time.perf_counter()
+        n = self.stream.n_fits
+        final = bool(plan.final.any())
+        if final and not plan.final.all():
+            raise RuntimeError("a leave-one-out window is scored with every re-fit final, or not at all")
+        pushed = 0
+        for b in self.windows:
+            em = self.batches.get(id(b))
+            if em is None:          # one EMBatch per window matrix, made once and kept for every window and round
+                em = self.batches[id(b)] = EMBatch(b, self.group_of, np.arange(n, dtype=np.int32))
+                b.window_em = em
+            self.stream.push_keep(em, plan.run_iters, plan.final if final else None, self.lo, self.hi, plan.chains,
+                                  plan.sums_from if plan.add_sums else None)
+            if final:
+                afs = AFSet.from_host(np.ascontiguousarray(self.af[b.site0:b.site0 + b.m], dtype=np.float32), ctx=self.stream.ctx)
+                try:
+                    self.loo.push(em, afs, self.mode)
+                finally:
+                    afs.close()
+            pushed += b.m
+            if pushed >= self.stream.m_total:
+                break
+        S, C = self.stream.read()
+        self.stats["round_seconds"].append(time.perf_counter() - t0)
+        self.want_more = True       # asked by stream_windows when the next round takes its first window
+        return S, C
+
+
+def loo_windowed(path, af, IDs, maf_iter, maf_tole, window_sites=None, num_partitions=1, need_parts=True, pop_iters=None,
+                 first_iters=None, ctx=None):
+    """loo_device for a Beagle FILE whose matrix need not fit the device: (logl (n, K) float32, parts (n*P, K) float32, iters (n,)),
+    bit for bit what loo_device returns on the resident matrix of the same file.  The sites are taken in consecutive windows of
+    `window_sites` sites (a multiple of 8192, rounded down; None: WGSASSIGN_LOO_WINDOW_SITES, else what windows.plan_loo derives
+    from the free device memory), in rounds over the file (windowed_fit.py): the n re-fits of a window are ONE EM batch
+    (WGSASSIGN_LOO_BATCH does not apply), their stopping iterations are found from sums and chains gathered over all windows, and
+    one last round runs every re-fit to its stop, clamps it with n_pop - 1 and scores the window (device.LooStream) -- the re-fits
+    never leave the device.
+    af: the (m, K) full-population estimates, an array or an np.load(..., mmap_mode="r") view; rows [lo, hi) are uploaded per
+    window.  Unlike loo(), af is NOT mutated.  pop_iters (K,): the iteration counts of the full fits, from which the re-fits' first
+    horizons are taken (loo_first_iters); first_iters (n,) gives them outright; neither: round 1 runs maf_iter iterations.
+    Prints nothing.
+    loo_windowed.stats: rounds, windows, window_sites, chain_iterations, largest_matrix_bytes, matrices, seconds, round_seconds,
+    iterations_round1 (the sum of the first horizons) against iterations_needed (the sum of the stopping iterations),
+    extension_rounds, refit_bytes_to_host (0: no re-fit frequencies cross to the host);
+    loo_windowed.info: n, m, sample_names, site_names (the first and last four), pops."""
+    import time
+
+    from . import reader_cy, windowed_fit, windows
+    from .device import EMStream, LooStream, default_mode, get_context
+    ctx = ctx or get_context()
+    t0 = time.perf_counter()
+    IDs = np.asarray(IDs)
+    pops = np.unique(IDs[:, 1])
+    group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
+    counts = np.bincount(group_of, minlength=len(pops))
+    n, K, P = len(group_of), len(pops), int(num_partitions)
+    if af.ndim != 2 or af.shape[1] != K:
+        raise ValueError("the allele frequencies must be an (m, %d) matrix" % K)
+    if P < 1:
+        raise ValueError("partition count must be >= 1")
+    exact_parts = os.environ.get("WGSASSIGN_PARTS", "exact") != "fast" and (need_parts or P > 1)
+    if P > 1 and not exact_parts:
+        raise ValueError("WGSASSIGN_PARTS=fast (float64 partition sums) is not provided in site windows")
+    index, _, m = reader_cy.ensure_index(path)
+    if m <= 0:
+        raise ValueError("%s holds no sites" % path)
+    if af.shape[0] != m:
+        raise ValueError("the allele frequency file has %d sites, the Beagle file %d" % (af.shape[0], m))
+    if window_sites is None:
+        W = windows.env_window_sites(name=windows.ENV_LOO)
+        if W is None:
+            W = windows.plan_loo(m, n, K, ctx.mem_info()[0], counts=counts, P=P) or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN
+    else:
+        if int(window_sites) < windows.ALIGN:
+            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
+        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+    if first_iters is None and pop_iters is not None:
+        first_iters = loo_first_iters(group_of, pop_iters, maf_iter)
+
+    def groups(sample_names):
+        if len(sample_names) != n:
+            raise AssertionError("Number of individuals in beagle and reference ID file do not match!")
+        return group_of, K
+
+    info, stats = {}, {"round_seconds": []}
+    stream = EMStream(n, maf_iter, m, ctx)
+    loo_stream = LooStream(n, K, m, P if exact_parts else 0, ctx)
+    rounds = _LooRounds(None, stream, loo_stream, group_of, counts, af, stats, default_mode())
+    gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info, group_of=groups, n_groups=K, again=rounds.again)
+    rounds.windows = gen
+    try:
+        iters, scheme = windowed_fit.fit(rounds, n, maf_iter, maf_tole, m, EMBatch.GUARD, first_iters=first_iters, hold_final=True)
+        out, parts = loo_stream.finish()
+    finally:
+        rounds.want_more = False
+        gen.close()
+        for em in rounds.batches.values():
+            em.close()
+        loo_stream.close()
+        stream.close()
+    stats.update(rounds=scheme.rounds, windows=info["windows"], window_sites=W, chain_iterations=scheme.chain_iterations,
+                 largest_matrix_bytes=info["largest_matrix_bytes"], matrices=info["matrices"], seconds=time.perf_counter() - t0,
+                 iterations_round1=scheme.iterations_round1, iterations_needed=int(sum(scheme.stop)),
+                 extension_rounds=scheme.extension_rounds, refit_bytes_to_host=0)
+    loo_windowed.stats = stats
+    loo_windowed.info = dict({k: info[k] for k in ("n", "m", "sample_names", "site_names")}, pops=pops)
+    with np.errstate(over="ignore"):
+        logl = out.astype(np.float32)
+    return logl, (parts if parts is not None else logl.copy()), iters
+
+
 def loo_batch_size(beagle, n, comm=None):
     """Number of leave-one-out re-fits per EM batch: what fits the free device memory (or
     WGSASSIGN_LOO_BATCH), agreed across SNP-shard ranks -- every rank must build batches of the same

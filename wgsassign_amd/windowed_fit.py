@@ -21,6 +21,15 @@ Per fit k:  ruled_out[k]  iterations known not to stop the fit
             iters[k]      what the reference would report: stop[k], or 0 when maf_iter was exhausted
             chain[k]      iterations whose exact chain the next round walks
 Two rounds when the sums decide every fit, three when a chain is needed and its first batch of candidates settles it.
+
+Leave-one-out re-fits (glassy.loo_windowed) are n fits of the same kind, with two differences, both optional here:
+  first_iters   a per-fit HORIZON: round 1 runs fit k for first_iters[k] iterations instead of maf_iter and gathers sums only for
+                those; the decision walk stops at the horizon (summed[k]: the iterations of fit k whose sums S holds).  A fit
+                neither stopped nor exhausted there gets a further sums round with a doubled horizon, capped at maf_iter, whose
+                plan says through sums_from[k] = summed[k] that only the iterations above the old horizon are added: S is zeroed
+                once, when the stream is made, and every (window, iteration, fit) sum enters it exactly once;
+  hold_final    no fit is final before every stop is known: scoring individual i needs its own re-fit and other individuals'
+                re-fits in the same window at the same time, so one last round runs every fit to its stop.
 """
 import numpy as np
 
@@ -39,14 +48,16 @@ def classify(ssq, m_total, tole, guard=0.0):
 
 class RoundPlan:
     """What one round does in every window: run_iters[k] iterations of fit k from 0.25; final[k]: that is its stopping
-    iteration, clamp and write it; chains: (fit, iteration) pairs sorted by iteration; add_sums: the sums join S."""
+    iteration, clamp and write it; chains: (fit, iteration) pairs sorted by iteration; add_sums: the sums join S -- those of
+    iteration t of fit k for t > sums_from[k] (zeros unless the round extends a horizon)."""
 
-    def __init__(self, number, run_iters, final, chains, add_sums):
+    def __init__(self, number, run_iters, final, chains, add_sums, sums_from=None):
         self.number = int(number)
         self.run_iters = np.ascontiguousarray(run_iters, dtype=np.int32)
         self.final = np.ascontiguousarray(final, dtype=np.int32)
         self.chains = sorted(((int(k), int(t)) for k, t in chains), key=lambda c: (c[1], c[0]))
         self.add_sums = bool(add_sums)
+        self.sums_from = np.zeros(len(self.run_iters), dtype=np.int32) if sums_from is None else np.ascontiguousarray(sums_from, dtype=np.int32)
 
     @property
     def T(self):
@@ -54,7 +65,7 @@ class RoundPlan:
 
 
 class RoundScheme:
-    def __init__(self, n_fits, maf_iter, tole, m_total, guard=0.0, lookahead=None):
+    def __init__(self, n_fits, maf_iter, tole, m_total, guard=0.0, lookahead=None, first_iters=None, hold_final=False):
         self.n_fits, self.maf_iter, self.tole, self.m_total, self.guard = int(n_fits), max(0, int(maf_iter)), float(tole), int(m_total), float(guard)
         self.lookahead = max(1, int(CHAIN_LOOKAHEAD if lookahead is None else lookahead))
         self.ruled_out = [0] * self.n_fits
@@ -65,6 +76,17 @@ class RoundScheme:
         self.rounds = 0
         self.chain_iterations = 0           # (fit, iteration) chains walked over the file so far
         self.have_sums = False
+        self.hold_final = bool(hold_final)
+        if first_iters is None:
+            self.horizon = [self.maf_iter] * self.n_fits
+        else:
+            if len(first_iters) != self.n_fits:
+                raise ValueError("first_iters must have one entry per fit")
+            self.horizon = [min(self.maf_iter, max(1, int(h))) for h in first_iters]
+        self.iterations_round1 = int(sum(self.horizon))
+        self.summed = [0] * self.n_fits         # iterations of every fit whose sums S holds
+        self.extend = [False] * self.n_fits     # the walk reached the horizon: the next round runs the fit to its doubled horizon
+        self.extension_rounds = 0
         if self.maf_iter == 0:              # emMAF.py:20 never enters its loop: f = 0.25, nothing to decide
             self.stop = [0] * self.n_fits
             self.have_sums = True
@@ -75,17 +97,22 @@ class RoundScheme:
     def plan(self):
         """The next round."""
         if not self.have_sums:
-            return RoundPlan(self.rounds + 1, [self.maf_iter] * self.n_fits, [0] * self.n_fits, [], True)
-        run, final, chains = [], [], []
+            return RoundPlan(self.rounds + 1, list(self.horizon), [0] * self.n_fits, [], True)
+        hold = self.hold_final and any(s is None for s in self.stop)
+        run, final, chains, sums_from = [], [], [], []
         for k in range(self.n_fits):
             if self.written[k]:
                 run.append(0), final.append(0)
             elif self.stop[k] is not None:
-                run.append(self.stop[k]), final.append(1)
+                run.append(0 if hold else self.stop[k]), final.append(0 if hold else 1)
+            elif self.extend[k]:
+                run.append(self.horizon[k]), final.append(0)
             else:
                 run.append(max(self.chain[k])), final.append(0)
                 chains.extend((k, t) for t in self.chain[k])
-        return RoundPlan(self.rounds + 1, run, final, chains, False)
+            sums_from.append(self.summed[k] if self.extend[k] else run[-1])
+        add = any(self.extend)
+        return RoundPlan(self.rounds + 1, run, final, chains, add, sums_from if add else None)
 
     def _class(self, S, t, k):
         return classify(S[t - 1][k], self.m_total, self.tole, self.guard)
@@ -96,6 +123,11 @@ class RoundScheme:
         self.rounds += 1
         self.have_sums = True
         self.chain_iterations += len(plan.chains)
+        if plan.add_sums:
+            self.extension_rounds += 1 if plan.number > 1 else 0
+            for k in range(self.n_fits):
+                if plan.sums_from[k] < plan.run_iters[k]:
+                    self.summed[k] = max(self.summed[k], int(plan.run_iters[k]))
         for k in range(self.n_fits):
             if plan.final[k]:
                 self.written[k] = True
@@ -106,10 +138,15 @@ class RoundScheme:
             if self.stop[k] is not None:
                 continue
             self.chain[k] = []
+            self.extend[k] = False
             t = self.ruled_out[k] + 1
             while True:
                 if t > self.maf_iter:                   # exhausted: f_maf_iter, the reference prints nothing
                     self.stop[k], self.iters[k] = self.maf_iter, 0
+                    break
+                if t > self.summed[k]:                  # the horizon: nothing is known of iteration t yet -- a further sums round
+                    self.horizon[k] = min(self.maf_iter, max(2 * self.horizon[k], t))
+                    self.extend[k] = True
                     break
                 c = self._class(S, t, k)
                 if c == UNDECIDED and t in chained[k]:
@@ -126,10 +163,10 @@ class RoundScheme:
 
     def _candidates(self, S, t, k):
         """t and the following iterations that are not ruled out by their sums, lookahead of them at most, ending with the
-        first one whose sum says converged (the fit stops there at the latest)."""
+        first one whose sum says converged (the fit stops there at the latest); none past the fit's horizon."""
         out = [t]
         u = t + 1
-        while len(out) < self.lookahead and u <= self.maf_iter and self._class(S, out[-1], k) != CONVERGED:
+        while len(out) < self.lookahead and u <= self.summed[k] and self._class(S, out[-1], k) != CONVERGED:
             c = self._class(S, u, k)
             if c != ACTIVE:
                 out.append(u)
@@ -139,14 +176,17 @@ class RoundScheme:
         return out
 
 
-def fit(backend, n_fits, maf_iter, tole, m_total, guard=0.0, lookahead=None):
+def fit(backend, n_fits, maf_iter, tole, m_total, guard=0.0, lookahead=None, first_iters=None, hold_final=False):
     """Rounds until every fit is written.  backend.run_round(plan) -> (S, C) runs the plan in every window of the file, in
-    file order, and writes the final fits.  Returns (iters (n_fits,) int32, the scheme -- rounds, chain_iterations, stop)."""
-    scheme = RoundScheme(n_fits, maf_iter, tole, m_total, guard, lookahead)
+    file order, and writes the final fits.  Returns (iters (n_fits,) int32, the scheme -- rounds, chain_iterations, stop).
+    first_iters, hold_final: the horizons and the one last round of the leave-one-out re-fits (see above)."""
+    scheme = RoundScheme(n_fits, maf_iter, tole, m_total, guard, lookahead, first_iters, hold_final)
+    # (a horizon doubles: at most log2(maf_iter) + 1 extension rounds between the chain rounds)
+    limit = scheme.maf_iter + 2 + (0 if first_iters is None else 2 * (scheme.maf_iter.bit_length() + 1))
     while not scheme.done():
         plan = scheme.plan()
         S, C = backend.run_round(plan)
         scheme.after_round(plan, S, C)
-        if scheme.rounds > scheme.maf_iter + 2:
+        if scheme.rounds > limit:
             raise RuntimeError("the windowed fit did not settle in %d rounds" % scheme.rounds)
     return scheme.iters.copy(), scheme

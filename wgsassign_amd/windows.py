@@ -25,6 +25,7 @@ ALIGN = 8192                    # = comm.SHARD_ALIGN = WGS_WINDOW_ALIGN of inclu
 FRACTION = 0.8
 RESERVE = 4 << 30
 ENV = "WGSASSIGN_WINDOW_SITES"
+ENV_LOO = "WGSASSIGN_LOO_WINDOW_SITES"      # the leave-one-out run is sent to windows by a variable of its own (see plan_loo)
 SURELY_FITS = 64                # see surely_fits
 
 
@@ -39,18 +40,18 @@ def budget(free_bytes):
     return int(FRACTION * int(free_bytes)) - min(RESERVE, int(free_bytes) // 4)
 
 
-def env_window_sites(environ=None):
-    """WGSASSIGN_WINDOW_SITES rounded down to a multiple of 8192, or None when it is not set (or empty).  A value below
-    8192, or not an integer, is an error that names the variable."""
-    value = (os.environ if environ is None else environ).get(ENV)
+def env_window_sites(environ=None, name=ENV):
+    """WGSASSIGN_WINDOW_SITES (or the variable named) rounded down to a multiple of 8192, or None when it is not set (or empty).
+    A value below 8192, or not an integer, is an error that names the variable."""
+    value = (os.environ if environ is None else environ).get(name)
     if value is None or not str(value).strip():
         return None
     try:
         sites = int(str(value).strip())
     except ValueError:
-        raise ValueError("%s must be a number of sites (an integer >= %d), got %r" % (ENV, ALIGN, value))
+        raise ValueError("%s must be a number of sites (an integer >= %d), got %r" % (name, ALIGN, value))
     if sites < ALIGN:
-        raise ValueError("%s=%d is below %d sites, the smallest window (windows are multiples of %d sites)" % (ENV, sites, ALIGN, ALIGN))
+        raise ValueError("%s=%d is below %d sites, the smallest window (windows are multiples of %d sites)" % (name, sites, ALIGN, ALIGN))
     return sites // ALIGN * ALIGN
 
 
@@ -133,4 +134,44 @@ def plan_fit(m, n, K, free_bytes, environ=None, counts=None):
         raise MemoryError("a windowed fit needs two windows of %d sites x %d individuals on the device (%d bytes with their "
                           "frequency buffers and class codes); %d of the %d free bytes can be used" %
                           (ALIGN, n, 2 * ALIGN * per_site, max(0, budget(free_bytes)), free_bytes))
+    return W
+
+
+def loo_site_bytes(n, K, counts=None, P=1):
+    """Device bytes one site takes in a windowed --get_reference_af --loo of n individuals in K populations with P partition
+    chains: fit_site_bytes with the frequency buffers and per-tile sums counted for the n re-fits of a window instead of K fits
+    (all n are ONE EM batch: WGSASSIGN_LOO_BATCH does not apply in windows), plus what the leave-one-out scoring of the window
+    allocates per site, read from the library as fit_site_bytes was:
+
+        frequencies  2 * 4 * n                      wgs_em_create's two float32 buffers per re-fit
+        sums         8 * n / 64, rounded up         its per-tile float64 partial sums
+        columns      4 * K                          the window's rows of the full-population frequencies (wgs_afset)
+        block sums   8 * n * K / 4096, rounded up   wgs_score_create: one float64 per (individual, population) and block of 4096
+                                                    sites,
+        chunk sums   8 * n * K / 8192, rounded up   and one per chunk of 8192 (score_sums_enqueue)
+        chains       4 * n * K * P / 4096, r. up    wgs_score_chains_prepare: one block function per chain and block
+
+    The column table (8 n K bytes), the chains' carries and results (12 n K P) and the stream's totals do not grow with the
+    window and come out of RESERVE."""
+    n, K, P = int(n), int(K), max(1, int(P))
+    cells = n * K
+    return (fit_site_bytes(n, K, counts) - 8 * K - (8 * K + 63) // 64 + 8 * n + (8 * n + 63) // 64 + 4 * K
+            + (8 * cells + 4095) // 4096 + (8 * cells + 8191) // 8192 + (4 * cells * P + 4095) // 4096)
+
+
+def plan_loo(m, n, K, free_bytes, environ=None, counts=None, P=1):
+    """plan() for --get_reference_af --loo: None when the resident matrix fits (the resident run batches its re-fits by what is
+    left and needs only the matrix: fits_resident_fit) and WGSASSIGN_LOO_WINDOW_SITES does not ask for windows, else W (a
+    multiple of 8192) for two windows, each with its batch of n re-fits."""
+    forced = env_window_sites(environ, ENV_LOO)
+    if forced is not None:
+        return forced
+    if fits_resident_fit(m, n, K, free_bytes, counts):
+        return None
+    per_site = loo_site_bytes(n, K, counts, P)
+    W = budget(free_bytes) // (2 * per_site) // ALIGN * ALIGN
+    if W < ALIGN:
+        raise MemoryError("a windowed leave-one-out run needs two windows of %d sites x %d individuals on the device (%d bytes with "
+                          "their %d re-fits, class codes and scoring tables); %d of the %d free bytes can be used" %
+                          (ALIGN, n, 2 * ALIGN * per_site, n, max(0, budget(free_bytes)), free_bytes))
     return W
