@@ -61,6 +61,20 @@ int wgs_debug_rmse1d(wgs_ctx *ctx, const float *v1, const float *v2, int64_t m, 
  * however many launches it takes and however many iterations it runs. */
 int wgs_debug_em_sweep_paths(wgs_em *em, int64_t counts[4]);
 
+/* What the last build of the class codes left for this matrix (csrc/common.h: wgs_codes), copied to the host and de-interleaved;
+ * waits for the codes' memory (wgs_beagle_codes_wait), builds nothing, and fails (rc 2) when no codes are built.  Every array but
+ * geom may be NULL (a first call learns the sizes).  tiles = ceil(m / 64); slabs follow each other in population order.
+ *   geom[0] hash slots per SNP, [1] drows, [2] lrows, [3] score_batch, [4] 1 when the slabs' own numbering was built, [5] slabs,
+ *        [6] tile_rows bytes per tile, [7] classes an aligned group of score_batch SNPs may sum to
+ *   ncls       [m]
+ *   dict       [m][drows][2]             the (g0, g1) bit patterns of class 0 .. drows - 1 of the SNP (rows beyond ncls: whatever was there)
+ *   codes      [m][n]                    class byte of every individual, the individuals of slab 0 first (slab order within a slab)
+ *   lcodes     [m][n]                    the same in the slab's own numbering            (untouched unless geom[4])
+ *   ldict      [slabs][m][lrows][2]      the slab's own dictionary                        (untouched unless geom[4])
+ *   tile_rows  [slabs][tiles][geom[6]] */
+int wgs_debug_codes_download(wgs_beagle *b, int32_t geom[8], uint8_t *ncls, uint32_t *dict, uint8_t *codes, uint8_t *lcodes, uint32_t *ldict,
+                             uint8_t *tile_rows);
+
 /* Test hook for the EM kernel's correctly rounded divide (csrc/em_kernels.hip: div_exact): number of
  * 2^20 x per_thread pseudo-random EM-shaped operand pairs whose quotient differs bitwise from the
  * compiler's IEEE double divide. */

@@ -150,6 +150,7 @@ SIGNATURES = {
     "wgs_debug_rmse1d": (c_int, [c_vp, c_f32p, c_f32p, c_i64, c_f64p, c_int, ctypes.POINTER(c_int)]),
     "wgs_em_last_chain_serial_blocks": (c_int, [c_vp]),
     "wgs_debug_em_sweep_paths": (c_int, [c_vp, ctypes.POINTER(c_i64)]),
+    "wgs_debug_codes_download": (c_int, [c_vp, c_i32p, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wgs_debug_rcp_error": (c_int, [c_vp, c_int, c_f64p]),
     "wgs_debug_div_mismatch": (c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "wgs_debug_log_mismatch": (c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),

@@ -440,4 +440,69 @@ int wgs_beagle_codes_prepare(wgs_beagle *b, int em)
     return 0;
 }
 
+/* Test hook (include/wgsassign_hip_debug.h): what the last build left for this matrix, de-interleaved on the host.  Builds nothing. */
+int wgs_debug_codes_download(wgs_beagle *b, int32_t geom[8], uint8_t *ncls, uint32_t *dict, uint8_t *codes, uint8_t *lcodes, uint32_t *ldict,
+                             uint8_t *tile_rows)
+{
+    WGS_REQUIRE(b && geom, "null argument");
+    if (wgs_beagle_codes_wait(b, nullptr)) return 1;
+    const wgs_codes *c = b->codes;
+    WGS_REQUIRE(b->codes_state > 0 && c, "wgs_debug_codes_download: no class codes are built for this matrix");
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    const int64_t m = b->m, tiles = wgs_ntiles(m), n = b->n;
+    const int32_t drows = c->drows, lrows = c->lrows;
+    geom[0] = WGS_ENC_SLOTS / c->snps_per_wave;
+    geom[1] = drows;
+    geom[2] = lrows;
+    geom[3] = c->score_batch;
+    geom[4] = lrows > 0 ? 1 : 0;
+    geom[5] = b->n_groups;
+    geom[6] = WGS_TILE_ROWS_BYTES;
+    geom[7] = WGS_BATCH_ROWS_CAP;
+    if (ncls) HIP_TRY(hipMemcpy(ncls, c->ncls, (size_t)m, hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> rows;
+    // [(tile * nrows + row) * 64 + lane] of 8-byte (g0, g1) entries -> out[(snp * nrows + row) * 2 + {0, 1}]
+    auto pairs = [&](const float2 *dev, int32_t nrows, uint32_t *out) -> int {
+        rows.resize((size_t)tiles * nrows * 64);
+        HIP_TRY(hipMemcpy(rows.data(), dev, rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (int64_t snp = 0; snp < m; ++snp)
+            for (int32_t r = 0; r < nrows; ++r) {
+                const unsigned long long e = rows[(size_t)((snp / 64) * nrows + r) * 64 + (size_t)(snp % 64)];
+                out[(snp * nrows + r) * 2] = (uint32_t)e;
+                out[(snp * nrows + r) * 2 + 1] = (uint32_t)(e >> 32);
+            }
+        return 0;
+    };
+    if (dict && pairs(c->dict, drows, dict)) return 1;
+    std::vector<uint32_t> words;
+    // [(tile * nquads + quad) * 64 + lane] of four class bytes -> out[snp * n + col0 + individual of the slab]
+    auto bytes = [&](const uint32_t *dev, int32_t nquads, int32_t ncols, int64_t col0, uint8_t *out) -> int {
+        words.resize((size_t)tiles * nquads * 64);
+        HIP_TRY(hipMemcpy(words.data(), dev, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int64_t snp = 0; snp < m; ++snp)
+            for (int32_t i = 0; i < ncols; ++i)
+                out[snp * n + col0 + i] = (uint8_t)(words[(size_t)((snp / 64) * nquads + i / 4) * 64 + (size_t)(snp % 64)] >> (8 * (i % 4)));
+        return 0;
+    };
+    int64_t col0 = 0;
+    for (int g = 0; g < b->n_groups; ++g) {
+        const SlabCodes &s = c->slabs[g];
+        const int32_t ncols = b->slabs[g].ncols;
+        if (tile_rows) {
+            if (s.nquads) HIP_TRY(hipMemcpy(tile_rows + (size_t)g * tiles * WGS_TILE_ROWS_BYTES, s.tile_rows, (size_t)tiles * WGS_TILE_ROWS_BYTES, hipMemcpyDeviceToHost));
+            else memset(tile_rows + (size_t)g * tiles * WGS_TILE_ROWS_BYTES, 0, (size_t)tiles * WGS_TILE_ROWS_BYTES);
+        }
+        if (s.nquads) {
+            if (codes && bytes(s.codes, s.nquads, ncols, col0, codes)) return 1;
+            if (lrows > 0 && lcodes && bytes(s.lcodes, s.nquads, ncols, col0, lcodes)) return 1;
+            if (lrows > 0 && ldict && pairs(s.ldict, lrows, ldict + (size_t)g * m * lrows * 2)) return 1;
+        } else if (lrows > 0 && ldict) {
+            memset(ldict + (size_t)g * m * lrows * 2, 0, (size_t)m * lrows * 2 * sizeof(uint32_t));
+        }
+        col0 += ncols;
+    }
+    return 0;
+}
+
 }   // extern "C"

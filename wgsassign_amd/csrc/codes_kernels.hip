@@ -27,7 +27,10 @@
 //                rewrote every slab's code words: a sixth of the pass's traffic and instructions.)
 // A SNP whose table overflows (more than RMAX probes, i.e. too many classes for T), with more classes than the dictionary
 // has rows, or holding the one bit pattern used as EMPTY is RICH: ncls = 0 and tile_rows = 255 tell the sweeps to take that
-// SNP (scoring) / that tile of that slab (EM) from the float32 slab.  Nothing about a rich SNP affects the others.
+// SNP (scoring) / that tile, in every slab (EM), from the float32 slab.  Nothing about a rich SNP affects the others.
+// tests/codes_cases.py states this contract case by case -- probe chains of known length and wrap, class counts on both sides of
+// every limit above, classes that first appear at a slab's very end, keys that differ in one bit, the EMPTY pattern, the group rule --
+// and tests/test_gpu_encoder.py reads back what this kernel writes and holds it to them.
 #include "common.h"
 
 namespace {
@@ -309,6 +312,9 @@ __global__ __launch_bounds__(64, ENC_SLOTS >= 2048 ? 2 : 4) void class_encode_ke
 #pragma unroll
                 for (int i = 0; i < NL; ++i) {
                     if (live[i] && !pend[i] && old[i] == KEY_EMPTY) {
+                        // the one bit pattern used as EMPTY, looked up: it always "goes in", without changing its slot -- which a later key
+                        // may take, so it has to be noticed here: that SNP cannot be coded
+                        if (key[i] == KEY_EMPTY) rich = true;
                         gid_of[slot[i] * SNPS + s] = (uint8_t)min(id, 255);
                         if (id < T) slot_of[id * SNPS + s] = (uint8_t)slot[i];
                         ++id;
@@ -394,10 +400,7 @@ __global__ __launch_bounds__(64, ENC_SLOTS >= 2048 ? 2 : 4) void class_encode_ke
     ENC_CLOCK(2);
     const int ncls = nid;
     if (ncls > A.drows || ncls > 254 || ncls > T) rich = true;
-    // the one bit pattern used as EMPTY, looked up: it "went in" without changing its slot -- that SNP cannot be coded
-    for (int r0 = col; r0 < min(ncls, T); r0 += COLS)
-        if (keys[(unsigned)slot_of[r0 * SNPS + s] * SNPS + s] == KEY_EMPTY) rich = true;
-    rich = snp_or(rich);
+    rich = snp_or(rich);                                   // (the EMPTY pattern, looked up, was noticed where it "went in")
     if (SAMPLE) {
         if (col == 0) A.sample[((int64_t)blockIdx.x * (A.n_slabs + 1) + A.n_slabs) * SNPS + s] = (uint8_t)(snp < A.m ? (rich ? 255 : min(ncls, 254)) : 0);
         return;
@@ -425,6 +428,18 @@ __global__ __launch_bounds__(64, ENC_SLOTS >= 2048 ? 2 : 4) void class_encode_ke
         }
     }
     if (col == 0) ((gu8_ptr)A.ncls)[snp] = (uint8_t)eff;
+    // A SNP given up after a slab's end had written tile_rows -- in a later slab, or only here (more classes than dictionary rows, the
+    // group rule): its tile is swept directly in EVERY slab, as the contract above says.  Not a correction -- the lcodes and ldict of the
+    // slabs finished before were valid -- but one rule for a reader of tile_rows; it costs the coded EM sweep that tile's float32
+    // traffic (4 x) in all slabs, which data with many SNPs rich by the group rule alone would feel.  (Rare, wave-uniform.)
+    if (__any(rich)) {
+        if (lane < SNPS / WGS_ENC_MIN_SNPS) {
+            for (int g = 0; g < A.n_slabs; ++g) {
+                const SlabCodes sc = A.slabs[g];
+                if (sc.nquads) ((gu8_ptr)sc.tile_rows)[tile * WGS_TILE_ROWS_BYTES + sub * (SNPS / WGS_ENC_MIN_SNPS) + lane] = (uint8_t)255;
+            }
+        }
+    }
     {
         const int mb = wave_max(group_sum(eff)), mc = wave_max(eff);
         unsigned long long tot = (unsigned long long)((col == 0 && snp < A.m) ? eff : 0), nrich = (col == 0 && snp < A.m && rich) ? 1ull : 0ull;

@@ -253,6 +253,31 @@ class DeviceBeagle:
                 "sample_mean_classes": info[16], "sample_mean_classes_per_slab": info[17], "score_batch_snps": int(info[18]),
                 "alloc_wait_ms": info[19]}
 
+    def codes_download(self):
+        """Test hook (wgs_debug_codes_download): what the last build of the class codes left, on the host and de-interleaved --
+        the geometry, `ncls` (m,), `dict` (m, drows, 2) uint32 bit patterns, and per slab (population order) `codes` / `lcodes`
+        (m, individuals of the slab) bytes, `ldict` (m, lrows, 2) uint32 and `tile_rows` (tiles, bytes per tile).  Builds nothing;
+        raises ValueError when no codes are built."""
+        lib = _lib.load()
+        geom = np.zeros(8, dtype=np.int32)
+        check(lib.wgs_debug_codes_download(self._h, i32p(geom), None, None, None, None, None, None))
+        slots, drows, lrows, batch, local, n_slabs, trb, cap = (int(x) for x in geom)
+        tiles = (self.m + 63) // 64
+        ncls = np.zeros(self.m, dtype=np.uint8)
+        dic = np.zeros((self.m, drows, 2), dtype=np.uint32)
+        codes = np.zeros((self.m, self.n), dtype=np.uint8)
+        lcodes = np.zeros((self.m, self.n), dtype=np.uint8)
+        ldict = np.zeros((n_slabs, self.m, max(lrows, 1), 2), dtype=np.uint32)
+        tile_rows = np.zeros((n_slabs, tiles, trb), dtype=np.uint8)
+        check(lib.wgs_debug_codes_download(self._h, i32p(geom), ncls.ctypes.data, dic.ctypes.data, codes.ctypes.data, lcodes.ctypes.data,
+                                           ldict.ctypes.data, tile_rows.ctypes.data))
+        sizes = np.bincount(self.group_of, minlength=n_slabs)
+        ends = np.cumsum(sizes)
+        slabs = [{"codes": codes[:, e - s:e], "lcodes": lcodes[:, e - s:e] if local else None, "ldict": ldict[g, :, :lrows] if local else None,
+                  "tile_rows": tile_rows[g]} for g, (s, e) in enumerate(zip(sizes, ends))]
+        return {"hash_slots": slots, "dict_rows": drows, "em_table_rows": lrows, "score_batch_snps": batch, "slab_numbering": bool(local),
+                "tile_rows_bytes": trb, "batch_rows_cap": cap, "ncls": ncls, "dict": dic, "slabs": slabs}
+
     def close(self):
         if self._h:
             for child in list(self._children):
