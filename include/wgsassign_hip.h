@@ -50,8 +50,9 @@ const char *wgs_last_error(void);
  * integer-table reader (wgs_reader_open_table), the depth ingest (wgs_depth_ingest_*), wgs_depth_create_shape and
  * wgs_depth_download_rows, the deep tier of the z-scores (wgs_zscore_deep_sites, wgs_zkeep_create_deep), and the z-scores over SNP
  * shards (wgs_zscore_classes_sharded, wgs_em_fit_masked_sharded, wgs_depth_ingest_set_first_row, WGS_OP_Z_CLASS, WGS_OP_Z_CHAIN), and
- * windowed scoring (wgs_score_stream_*, wgs_beagle_set_window). */
-#define WGS_ABI_VERSION 3
+ * windowed scoring (wgs_score_stream_*, wgs_beagle_set_window).  4: --ne_obs in site windows (wgs_fisher_stream_*); no existing
+ * signature changed. */
+#define WGS_ABI_VERSION 4
 int wgs_version(void);
 /* sha256[:16] over every source of the library / over the sources of the EM and scoring kernels (em_kernels.hip,
  * assign_kernels.hip, beagle_kernels.hip, codes_kernels.hip, common.h, log_table.h), fixed at build time: profiles record them, bench.py quotes hardware
@@ -363,6 +364,28 @@ int wgs_loo_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, i
 int wgs_loo_stream_push(wgs_loo_stream *stream, wgs_em *window_em, wgs_afset *window_af, int mode);
 int wgs_loo_stream_finish(wgs_loo_stream *stream, double *ll_out, float *parts_out);
 void wgs_loo_stream_destroy(wgs_loo_stream *stream);
+
+/* --ne_obs in site windows: what wgs_fisher_obs and wgs_fisher_ind_means give on one resident matrix, from one
+ * pass over consecutive windows, bit for bit.  One fused sweep per window gives the window's rows of f_obs / ne_obs and, per individual,
+ * the 128-site leaf sums of NumPy's pairwise float32 sum over the window's full 8192-site chunks; np.mean's running float32 totals (n
+ * floats, by individual in file order) stay on the device across pushes.
+ *   wgs_fisher_stream_create    for n individuals, K populations and m_total sites in all;
+ *   wgs_fisher_stream_push      one window: `window` a matrix with one slab per population (none empty), window_af the window's rows of
+ *                               the fitted frequencies; f_obs_rows / ne_obs_rows (host, rows x K float32, site-major, overwritten) the
+ *                               window's rows of .fisher_obs.npy / .ne_obs.npy.  The window rules of wgs_score_stream_push hold and the
+ *                               window has the stream's n and K; anything else: rc 2 and a message, nothing launched.  Returns when the
+ *                               device is done with the window;
+ *   wgs_fisher_stream_sweep_ms  kernel time of the last push's fused sweep, between events;
+ *   wgs_fisher_stream_finish    ne_ind_out (host, n float32): float32(float64(total) / m_total) per individual, np.mean's last step.
+ *                               rc 2 before all m_total sites were pushed, and for a second call;
+ *   wgs_fisher_stream_destroy   a no-op for a stream that is gone already.  Like the other streams, to be destroyed before its context. */
+typedef struct wgs_fisher_stream wgs_fisher_stream;
+int wgs_fisher_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, wgs_fisher_stream **out);
+int wgs_fisher_stream_push(wgs_fisher_stream *stream, wgs_beagle *window, wgs_afset *window_af, float *f_obs_rows, float *ne_obs_rows);
+int wgs_fisher_stream_sweep_ms(wgs_fisher_stream *stream, float *ms);
+int wgs_fisher_stream_finish(wgs_fisher_stream *stream, float *ne_ind_out);
+void wgs_fisher_stream_destroy(wgs_fisher_stream *stream);
+
 /* glassy.loo(L, af, IDs, t, maf_iter, maf_tole, downsampled_L, num_partitions) -- glassy.py:47-112 -- in one
  * call on device-resident data: per individual (file order) the re-fit of its population without it
  * (wgs_em_fit, a batch of individuals at once), the clamp with n_pop - 1, the never-restored overwrite of

@@ -5,6 +5,7 @@
                                    [--parent-root DIR] [--out profiles/windowed_bench.json]
     python tools/bench_windowed.py --fit [...] [--out profiles/windowed_fit_bench.json]      # the same for --get_reference_af
     python tools/bench_windowed.py --loo [...] [--out profiles/windowed_loo_bench.json]      # the same for --get_reference_af --loo
+    python tools/bench_windowed.py --ne [...] [--out profiles/windowed_ne_obs_bench.json]    # the same for --get_reference_af --ne_obs
 
 The file comes from tools/beagle_files.py (seeded, seconds to write).  Every end-to-end figure is the wall time of one
 `python -m wgsassign_amd.WGSassign --get_pop_like` process -- interpreter start, HIP initialisation, ingest, scoring, the text
@@ -24,6 +25,12 @@ WGSASSIGN_LOO_WINDOW_SITES): the three whole-process figures, and from one emMAF
 the rounds, the seconds of every round, the first horizons' iterations against the iterations the re-fits needed, and the resident
 re-fit and scoring seconds of glassy.loo_device on the same file.  What to expect there: rounds x the windowed pass, plus the resident
 re-fit time x (iterations run / iterations needed), plus the per-window launches.
+--ne measures --get_reference_af --ne_obs (the windowed fit, then one pass for the Fisher information; WGSASSIGN_NE_WINDOW_SITES): the
+three whole-process figures, and from fisher.fisher_obs_windowed in this process the fused sweep's time per window between events
+(fisher_window_kernel).  What the resident path spends in its three kernels over the same sites (fisher_pop_kernel,
+fisher_ind_sites_kernel, pairwise_leaf_kernel) has no events of its own: `--ne --probe` runs the resident functions and the windowed
+pass once and nothing else, to be run under `rocprofv3 --kernel-trace --stats --output-format csv`, and `--ne --kernel-stats CSV` adds
+that trace's per-kernel totals to the result.
 What to expect: the device's share of an ingest (BGZF inflate, tokeniser) and the sweeps use the context's one stream and every push
 waits for it, so for a BGZF file the device work of consecutive windows is strictly serial; what overlaps a window's sweep is only
 the producer thread's reading of the next window (for plain gzip also its inflate).  The windowed run therefore costs the resident
@@ -43,14 +50,16 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 
 
-def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False):
-    """af: the frequency file of --get_pop_like, or with fit (or loo) the ID file of --get_reference_af."""
+def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False, ne=False):
+    """af: the frequency file of --get_pop_like, or with fit (or loo, or ne) the ID file of --get_reference_af."""
     env = dict(os.environ)
     env.pop("WGSASSIGN_WINDOW_SITES", None)
     env.pop("WGSASSIGN_LOO_WINDOW_SITES", None)
+    env.pop("WGSASSIGN_NE_WINDOW_SITES", None)
     env.update(env_extra)
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
-    what = ["--pop_af_IDs", af, "--get_reference_af"] + (["--loo"] if loo else []) if fit or loo else ["--pop_af_file", af, "--get_pop_like"]
+    what = (["--pop_af_IDs", af, "--get_reference_af"] + (["--loo"] if loo else []) + (["--ne_obs"] if ne else []) if fit or loo or ne
+            else ["--pop_af_file", af, "--get_pop_like"])
     t0 = time.perf_counter()
     r = subprocess.run([sys.executable, "-m", "wgsassign_amd.WGSassign", "--beagle", beagle] + what + ["--out", out],
                        cwd=os.path.dirname(out), env=env, capture_output=True, text=True)
@@ -155,8 +164,102 @@ def loo_leg(a, m, n, K, W):
     return res
 
 
+NE_KERNELS = ("fisher_window_kernel", "fisher_pop_kernel", "fisher_ind_sites_kernel", "pairwise_leaf_kernel", "pairwise_combine_kernel",
+              "fisher_stream_combine_kernel")
+NE_OUTPUTS = (".pop_af.npy", ".fisher_obs.npy", ".ne_obs.npy", ".ne_obs.txt", ".ne_ind.txt")
+
+
+def ne_files(td, n, m, K):
+    import beagle_files
+    bg, ids = os.path.join(td, "x.beagle.gz"), os.path.join(td, "ids.txt")
+    beagle_files.write_lowdepth_bgzf(bg, n, m, seed=5)
+    IDs = np.array([["Ind%d" % i, "pop%d" % (i * K // n)] for i in range(n)])
+    np.savetxt(ids, IDs, fmt="%s", delimiter="\t")
+    return bg, ids, IDs
+
+
+def ne_passes(bg, IDs, W, K, ctx, repeats):
+    """The resident functions and the windowed pass on the same file and frequencies, `repeats` times each; (all four results equal,
+    the windowed pass's stats)."""
+    from wgsassign_amd import emMAF, fisher, reader_cy
+    af, _ = emMAF.emMAF_windowed(bg, IDs, 200, 1e-4, W, ctx=ctx)
+    pops = np.unique(IDs[:, 1])
+    group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
+    beagle, _, _, _ = reader_cy.stream_to_device(bg, group_of, K, ctx=ctx, names="ends")
+    for rep in range(repeats):
+        f_r, ne_r = fisher.fisher_obs(None, af, IDs, 1, beagle=beagle)
+        ind_r = fisher.fisher_obs_ind(None, af, IDs, 1, beagle=beagle)
+    beagle.close()
+    for rep in range(repeats):
+        f_w, ne_w, mean_w, ind_w = fisher.fisher_obs_windowed(bg, af, IDs, W, ctx=ctx)
+    same = all(np.asarray(x).tobytes() == y.tobytes() for x, y in ((f_w, f_r), (ne_w, ne_r), (mean_w, np.mean(ne_r, axis=0)), (ind_w, ind_r)))
+    return same, fisher.fisher_obs_windowed.stats
+
+
+def kernel_totals(csv_path):
+    """{kernel: [calls, total ms]} of the --ne kernels from a rocprofv3 *_kernel_stats.csv."""
+    import csv
+    out = {}
+    with open(csv_path) as fh:
+        for row in csv.DictReader(fh):
+            for k in NE_KERNELS:
+                if k in row["Name"]:
+                    out[k] = [int(row["Calls"]), round(float(row["TotalDurationNs"]) / 1e6, 4)]
+    return out
+
+
+def ne_leg(a, m, n, K, W):
+    """--get_reference_af --ne_obs resident against windowed; one JSON-able dict."""
+    from wgsassign_amd import device
+    res = {"bench": "windowed_ne_obs", "snps": m, "inds": n, "pops": K, "window_sites": W, "windows": a.windows}
+    with tempfile.TemporaryDirectory() as td:
+        os.environ["WGSASSIGN_INDEX_DIR"] = td
+        bg, ids, IDs = ne_files(td, n, m, K)
+        ctx = device.get_context()
+        if a.probe:
+            same, _ = ne_passes(bg, IDs, W, K, ctx, 1)
+            return {"bench": "windowed_ne_obs_probe", "results_bit_identical": bool(same)}
+        res["file_mb"] = round(os.path.getsize(bg) / 1e6, 1)
+        variants = [("resident_s", ROOT, {})]
+        if a.parent_root:
+            variants.insert(0, ("parent_resident_s", os.path.abspath(a.parent_root), {}))
+        variants.append(("windowed_s", ROOT, {"WGSASSIGN_NE_WINDOW_SITES": str(W)}))
+        times = {name: [] for name, _, _ in variants}
+        for rep in range(a.repeats + 1):
+            for name, root, env in variants:
+                dt, err = cli_seconds(root, bg, ids, os.path.join(td, name), env, ne=True)
+                if rep:
+                    times[name].append(dt)
+                if name == "windowed_s" and ("Fisher information in %d windows" % a.windows) not in err:
+                    raise RuntimeError("the windowed run did not use %d windows: %s" % (a.windows, err[-300:]))
+        files = {name: b"".join(open(os.path.join(td, name + suffix), "rb").read() for suffix in NE_OUTPUTS) for name, _, _ in variants}
+        res["outputs_identical"] = len(set(files.values())) == 1
+        for name in ("parent_resident_s", "resident_s", "windowed_s"):
+            res[name] = spread(times[name]) if name in times else None
+        res["device"] = ctx.info()["name"].strip()
+        res["kernels_id"] = (device._lib.load().wgs_kernels_id() or b"").decode()
+        same, st = ne_passes(bg, IDs, W, K, ctx, 2)
+        res.update(results_bit_identical=bool(same), fused_sweep_ms_per_window=[round(x, 4) for x in st["sweep_ms"]],
+                   fused_sweeps_ms=round(sum(st["sweep_ms"]), 4), windowed_pass_seconds=round(st["seconds"], 3),
+                   largest_matrix_bytes=st["largest_matrix_bytes"])
+    if a.kernel_stats:
+        # one resident run and one windowed pass under the kernel trace (--probe): the resident trio against the fused sweep
+        k = kernel_totals(a.kernel_stats)
+        res["traced_kernels_calls_ms"] = k
+        trio = [k.get(x, [0, 0.0])[1] for x in ("fisher_pop_kernel", "fisher_ind_sites_kernel", "pairwise_leaf_kernel")]
+        fused = k.get("fisher_window_kernel", [0, None])[1]
+        # (the windowed pass's own row route over the file's last, shorter chunk runs two of the trio's kernels, too: a fraction of a
+        # chunk against the resident path's whole file)
+        res["traced_resident_trio_ms"] = round(sum(trio), 4)
+        res["traced_fused_ms"] = fused
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ne", action="store_true", help="measure --get_reference_af --ne_obs (the Fisher information in windows)")
+    ap.add_argument("--probe", action="store_true", help="with --ne: only run the resident functions and the windowed pass once (for a kernel trace)")
+    ap.add_argument("--kernel-stats", default=None, help="with --ne: a rocprofv3 *_kernel_stats.csv of a --ne --probe run, added to the result")
     ap.add_argument("--loo", action="store_true", help="measure --get_reference_af --loo (the leave-one-out run in windows)")
     ap.add_argument("--fit", action="store_true", help="measure --get_reference_af (the fit in windows) instead of --get_pop_like")
     ap.add_argument("--snps", type=int, default=1_000_000)
@@ -174,8 +277,8 @@ def main():
     W = (per_window + windows.ALIGN - 1) // windows.ALIGN * windows.ALIGN          # rounded UP to whole chunks of 8192
     if windows.window_count(m, W) != a.windows:
         raise SystemExit("%d sites cannot be cut into %d windows of a multiple of %d sites" % (m, a.windows, windows.ALIGN))
-    if a.fit or a.loo:
-        line = json.dumps(loo_leg(a, m, n, K, W) if a.loo else fit_leg(a, m, n, K, W))
+    if a.fit or a.loo or a.ne:
+        line = json.dumps(ne_leg(a, m, n, K, W) if a.ne else loo_leg(a, m, n, K, W) if a.loo else fit_leg(a, m, n, K, W))
         print(line)
         if a.out:
             with open(a.out, "w") as fh:

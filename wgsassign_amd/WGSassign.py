@@ -128,8 +128,9 @@ def _window_sites(args, comm, ctx):
 
 
 def windowed_fit_candidate(args, world=1):
-    """Whether these options may be fitted in site windows (emMAF.emMAF_windowed): --get_reference_af alone, on one rank.  The
-    leave-one-out re-fits, --ne_obs and the z-scores still need the whole matrix on the device."""
+    """Whether these options may be fitted in site windows (emMAF.emMAF_windowed): --get_reference_af alone, on one rank.  With
+    --loo or --ne_obs beside it the run has a route of its own (windowed_loo_candidate, windowed_ne_candidate); the z-scores still need
+    the whole matrix on the device."""
     others = (args.get_pop_like, args.loo, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score,
               args.loo_downsampled_beagle)
     return bool(args.get_reference_af) and int(world) == 1 and not any(others)
@@ -174,8 +175,9 @@ def _fit_window_sites(args, comm, ctx):
 
 def windowed_loo_candidate(args, world=1):
     """Whether these options may run in site windows end to end (emMAF.emMAF_windowed, then glassy.loo_windowed):
-    --get_reference_af --loo alone, with any --partition_sites, on one rank.  --ne_obs, the z-scores, --get_pop_like beside them
-    and --loo_downsampled_beagle (two files in lockstep under a site filter) still need the whole matrix on the device."""
+    --get_reference_af --loo alone, with any --partition_sites, on one rank.  With --ne_obs beside them the run has a route of its own
+    (windowed_ne_candidate); the z-scores, --get_pop_like beside them and --loo_downsampled_beagle (two files in lockstep under a site
+    filter) still need the whole matrix on the device."""
     others = (args.get_pop_like, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score, args.loo_downsampled_beagle)
     return bool(args.get_reference_af) and bool(args.loo) and int(world) == 1 and not any(others)
 
@@ -210,6 +212,49 @@ def _loo_window_sites(args, comm, ctx):
     m = reader_cy.ensure_index(args.beagle)[2]
     try:
         return windows.plan_loo(m, n, K, free, counts=counts, P=args.partition_sites)
+    except MemoryError as e:
+        raise SystemExit(str(e))
+
+
+def windowed_ne_candidate(args, world=1):
+    """Whether these options may run in site windows end to end with --ne_obs among them (emMAF.emMAF_windowed, then
+    fisher.fisher_obs_windowed over the frequencies just written, then glassy.loo_windowed when --loo is given):
+    --get_reference_af --ne_obs, with or without --loo and any --partition_sites, on one rank.  The z-scores, --get_pop_like beside
+    them and --loo_downsampled_beagle still need the whole matrix on the device."""
+    others = (args.get_pop_like, args.get_assignment_z_score, args.get_reference_z_score, args.loo_downsampled_beagle)
+    return bool(args.get_reference_af) and bool(args.ne_obs) and int(world) == 1 and not any(others)
+
+
+def _ne_window_sites(args, comm, ctx):
+    """The window --get_reference_af --ne_obs [--loo] runs in, or None for the resident path: WGSASSIGN_NE_WINDOW_SITES when set
+    (neither WGSASSIGN_WINDOW_SITES nor WGSASSIGN_LOO_WINDOW_SITES sends an --ne_obs run to windows), else windows only when the
+    resident matrix would not fit (windows.plan_ne), after the same first look as _fit_window_sites takes."""
+    import numpy as np
+
+    from . import reader_cy, windows
+    if not windowed_ne_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
+        return None                     # (a missing ID file is reported where it always was)
+    try:
+        W = windows.env_window_sites(name=windows.ENV_NE)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if W is not None:
+        return W
+    free = ctx.mem_info()[0]
+    if windows.surely_fits(os.path.getsize(args.beagle), free):
+        return None
+    try:
+        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
+        counts = np.unique(IDs[:, 1], return_counts=True)[1]
+    except Exception:
+        return None                     # (an unreadable ID file, too, is reported where it always was)
+    n, K = int(counts.sum()), len(counts)
+    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
+    if est is not None and windows.fits_resident_fit(est + est // 4 + 1024, n, K, free, counts):
+        return None
+    m = reader_cy.ensure_index(args.beagle)[2]
+    try:
+        return windows.plan_ne(m, n, K, free, counts=counts, loo=bool(args.loo), P=args.partition_sites)
     except MemoryError as e:
         raise SystemExit(str(e))
 
@@ -270,11 +315,13 @@ def _run(args, comm):
 
     W = _fit_window_sites(args, comm, ctx)
     W_loo = _loo_window_sites(args, comm, ctx) if W is None else None
-    if W is not None or W_loo is not None:
+    W_ne = _ne_window_sites(args, comm, ctx) if W is None and W_loo is None else None
+    if W is not None or W_loo is not None or W_ne is not None:
         # --get_reference_af alone on a file that does not fit (or WGSASSIGN_WINDOW_SITES): fitted window by window in rounds; the
         # lines and files of the resident run, and one more line on stderr.  With --loo beside it (a file that does not fit, or
-        # WGSASSIGN_LOO_WINDOW_SITES) the leave-one-out run follows in the same windows, on the frequencies just written.
-        W = W if W is not None else W_loo
+        # WGSASSIGN_LOO_WINDOW_SITES) the leave-one-out run follows in the same windows, on the frequencies just written.  With
+        # --ne_obs (a file that does not fit, or WGSASSIGN_NE_WINDOW_SITES) one pass for the Fisher information comes between them.
+        W = W if W is not None else W_loo if W_loo is not None else W_ne
         af, iters = emMAF.emMAF_windowed(args.beagle, IDs, args.maf_iter, args.maf_tole, W, out=args.out + ".pop_af.npy", ctx=ctx)
         info, stats = emMAF.emMAF_windowed.info, emMAF.emMAF_windowed.stats
         say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
@@ -291,7 +338,28 @@ def _run(args, comm):
         np.savetxt(args.out + ".pop_names.txt", pops, fmt="%s")
         say("Saved reference population names as " + str(args.out) +
             ".pop_names.txt (String: Order of pops for .pop_af.npy, .ne_obs.npy, and fisher_obs.npy files)\n")
-        if W_loo is not None:
+        if W_ne is not None:
+            say("Estimating Fisher information.")
+            A = np.load(args.out + ".pop_af.npy", mmap_mode="r")
+            f_obs, ne_obs, ne_obs_mean, ne_ind = fisher.fisher_obs_windowed(args.beagle, A, IDs, W, out=args.out, ctx=ctx)
+            del A, f_obs, ne_obs
+            stats = fisher.fisher_obs_windowed.stats
+            print("wgsassign_amd: Fisher information in %d windows of %d sites" % (stats["windows"], stats["window_sites"]), file=sys.stderr,
+                  flush=True)
+            say("Saved reference population observed Fisher information per locus as " + str(args.out) +
+                ".fisher_obs.npy (Binary - np.float32)\n")
+            say("Saved reference population effective sample size estimates per locus as " + str(args.out) +
+                ".ne_obs.npy (Binary - np.float32)\n")
+            ne_obs_mean_out = np.empty((2, len(pops)), dtype=np.dtype('U25'))
+            ne_obs_mean_out[0, :] = pops
+            ne_obs_mean_out[1, :] = ne_obs_mean
+            np.savetxt(args.out + ".ne_obs.txt", ne_obs_mean_out, fmt="%s")
+            say("Saved reference population effective sample size estimates as " + str(args.out) +
+                ".ne_obs.txt (String - np.U25)\n")
+            say("Estimating individual effective sample sizes.")
+            np.savetxt(args.out + ".ne_ind.txt", ne_ind.reshape(-1, 1), fmt="%.7f")
+            say("Save individual effective sample sizes as " + str(args.out) + ".ne_ind.txt")
+        if W_loo is not None or (W_ne is not None and args.loo):
             P = args.partition_sites
             say("Performing leave-one-out cross validation.")
             say(str(info["n"]) + " individuals to assign to " + str(len(pops)) + " populations")

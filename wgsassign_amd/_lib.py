@@ -176,6 +176,11 @@ SIGNATURES = {
     "wgs_loo_stream_push": (c_int, [c_vp, c_vp, c_vp, c_int]),
     "wgs_loo_stream_finish": (c_int, [c_vp, c_f64p, c_f32p]),
     "wgs_loo_stream_destroy": (None, [c_vp]),
+    "wgs_fisher_stream_create": (c_int, [c_vp, c_i64, c_i32, c_i64, ctypes.POINTER(c_vp)]),
+    "wgs_fisher_stream_push": (c_int, [c_vp, c_vp, c_vp, c_f32p, c_f32p]),
+    "wgs_fisher_stream_sweep_ms": (c_int, [c_vp, ctypes.POINTER(ctypes.c_float)]),
+    "wgs_fisher_stream_finish": (c_int, [c_vp, c_f32p]),
+    "wgs_fisher_stream_destroy": (None, [c_vp]),
     "wgs_score_chains_prepare": (c_int, [c_vp, c_i32, c_f64p]),
     "wgs_score_chains_walk": (c_int, [c_vp, c_f32p, c_f32p]),
     "wgs_loo": (c_int, [c_vp, c_vp, c_vp, c_i32, ctypes.c_double, c_i64, c_vp, c_i32, c_i32, c_int, c_int, c_f64p, c_f32p, c_i32p]),
@@ -191,7 +196,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 3      # = WGS_ABI_VERSION of include/wgsassign_hip.h
+ABI_VERSION = 4      # = WGS_ABI_VERSION of include/wgsassign_hip.h
 
 
 def load():

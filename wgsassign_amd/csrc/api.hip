@@ -12,6 +12,7 @@
 #include "build_id.h"
 #include "common.h"
 #include "em_state.h"
+#include "fisher_stream_checks.h"
 
 static thread_local std::string g_err;
 
@@ -782,6 +783,221 @@ static int fisher_ind_reduce(wgs_beagle *b, wgs_afset *a, int32_t i0, int32_t co
         return 1;
     HIP_TRY(hipMemcpyAsync(means_out, d_means, sizeof(float) * count, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+/* ---- --ne_obs in site windows ("Fisher information in windows").  What wgs_fisher_obs and wgs_fisher_ind_means
+ * do on one resident matrix happens here window by window, in one pass.  Per site and population nothing couples the windows.  Per
+ * individual np.mean's running float32 total (PairwisePlan above) is continued: a window starts at a multiple of 8192 sites, so its
+ * full chunks are NumPy's own, each a regular tree of 64 leaves of 128 sites -- fisher_window_kernel forms those leaf sums in the same
+ * sweep that gives f_obs and ne_obs, without a row matrix -- and the file's last, shorter chunk, whose leaves are irregular, takes the
+ * row route of fisher_ind_reduce (at most n x 8191 floats).  The totals (n floats, by individual in file order; two buffers in
+ * alternation) stay on the device between the pushes. */
+constexpr int WGS_LIVE_FISHER_STREAM = 8;   // kind in the live-object registry (5, 6, 7: the other streams): only its liveness is kept
+struct wgs_fisher_stream {
+    wgs_ctx *ctx = nullptr;
+    int device = 0;
+    int64_t n = 0, m_total = 0, pushed = 0;
+    int32_t K = 0;
+    bool finished = false;
+    float *d_total[2] = {nullptr, nullptr};
+    int cur = 0;                            // d_total[cur]: the totals over the sites pushed so far (pushed > 0)
+    int32_t *d_row_of = nullptr;            // [n] individual -> row of the leaf sums (slab after slab, column after column)
+    std::vector<int32_t> row_of;            // what d_row_of holds
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;    // bracket the fused sweep of the last push
+    float last_ms = 0.0f;
+};
+
+void wgs_fisher_stream_destroy(wgs_fisher_stream *st)
+{
+    if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
+    (void)hipSetDevice(st->device);
+    for (void *p : {(void *)st->d_total[0], (void *)st->d_total[1], (void *)st->d_row_of})
+        if (p) (void)hipFree(p);
+    if (st->ev0) (void)hipEventDestroy(st->ev0);
+    if (st->ev1) (void)hipEventDestroy(st->ev1);
+    delete st;
+}
+
+int wgs_fisher_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, wgs_fisher_stream **out)
+{
+    WGS_REQUIRE(ctx && out, "null argument");
+    WGS_REQUIRE(n > 0 && K > 0 && m_total > 0, "a Fisher stream needs individuals, populations and sites (%lld x %d over %lld sites)", (long long)n, K,
+                (long long)m_total);
+    WGS_REQUIRE(n < (1ll << 31), "%lld individuals are too many for one Fisher stream", (long long)n);
+    HIP_TRY(hipSetDevice(ctx->device));
+    wgs_fisher_stream *st = new wgs_fisher_stream();
+    wgs_live_add(st, WGS_LIVE_FISHER_STREAM, nullptr);
+    auto guard = on_failure([&] { wgs_fisher_stream_destroy(st); });
+    st->ctx = ctx;
+    st->device = ctx->device;
+    st->n = n;
+    st->K = K;
+    st->m_total = m_total;
+    for (float *&p : st->d_total) HIP_TRY(wgs_malloc(&p, sizeof(float) * (size_t)n));
+    HIP_TRY(wgs_malloc(&st->d_row_of, sizeof(int32_t) * (size_t)n));
+    HIP_TRY(hipEventCreate(&st->ev0));
+    HIP_TRY(hipEventCreate(&st->ev1));
+    guard.dismiss();
+    *out = st;
+    return 0;
+}
+
+/* One window: f_obs_rows / ne_obs_rows (host, rows x K float32, site-major) receive the window's rows of .fisher_obs.npy / .ne_obs.npy;
+ * the per-individual totals go on from where the window before left them.  The window rules of wgs_score_stream_push hold, the window
+ * has the stream's n and K and one slab per population, none of them empty: anything else is rc 2 and a message, nothing launched
+ * (fisher_stream_checks.h).  Returns when the device is done with the window. */
+int wgs_fisher_stream_push(wgs_fisher_stream *st, wgs_beagle *window, wgs_afset *window_af, float *f_obs_rows, float *ne_obs_rows)
+{
+    WGS_REQUIRE(st && window && window_af && f_obs_rows && ne_obs_rows, "null argument");
+    WGS_REQUIRE(window->ctx == st->ctx && window_af->ctx == st->ctx, "the window belongs to another context than the Fisher stream");
+    char why[256];
+    std::vector<int32_t> slab_cols(window->n_groups);
+    for (int g = 0; g < window->n_groups; ++g) slab_cols[g] = window->slabs[g].ncols;
+    if (fisher_stream_shape_refusal(window->n, window->n_groups, slab_cols.data(), window_af->K, window_af->m, window->m, st->n, st->K, why,
+                                    sizeof why) ||
+        fisher_stream_window_refusal(window->site0, window->m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, st->finished, why, sizeof why)) {
+        wgs_set_error("%s", why);
+        return 2;
+    }
+    wgs_ctx *ctx = st->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int K = st->K;
+    const int64_t n = st->n, m = window->m;
+    const int64_t full = fisher_stream_full_sites(m, WGS_WINDOW_ALIGN), tail = m - full;
+    const int64_t nleaf = full / 128;
+    // rows of the leaf sums: slab after slab, column after column
+    std::vector<int64_t> row0(K);
+    int32_t max_cols = 0;
+    for (int g = 0, r = 0; g < K; ++g) {
+        row0[g] = r;
+        r += window->slabs[g].ncols;
+        max_cols = std::max(max_cols, window->slabs[g].ncols);
+    }
+    std::vector<int32_t> row_of(n);
+    for (int64_t i = 0; i < n; ++i) row_of[i] = (int32_t)(row0[window->group_of[i]] + window->col_of[i]);
+    // np.mean's order over the window's full chunks, and over the file's last, shorter one
+    PairwisePlan plan, plan_t;
+    for (int64_t lo = 0; lo < full; lo += 8192) {            // total = total + pairwise(chunk); the file's first chunk starts it
+        pairwise_plan(lo, 8192, plan);
+        if (st->pushed + lo > 0) plan.prog.push_back(-1);
+    }
+    for (size_t l = 0; l < plan.leaf_lo.size(); ++l)
+        WGS_REQUIRE(plan.leaf_lo[l] == (int64_t)l * 128 && plan.leaf_len[l] == 128, "a full chunk's leaf %zu is not 128 sites at %zu", l, l * 128);
+    if (tail) {
+        pairwise_plan(0, tail, plan_t);
+        if (st->pushed + full > 0) plan_t.prog.push_back(-1);
+    }
+    const size_t nleaf_t = plan_t.leaf_lo.size(), nprog = plan.prog.size(), nprog_t = plan_t.prog.size();
+    const size_t mk = (size_t)m * K;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // workspace: [f (K x m) | ne (K x m) | transposed (m x K) | leaf sums (n x nleaf) | descs | prog] and, for the last chunk,
+    //            [rows (n x tail) | leaf sums (n x nleaf_t) | leaf_lo | leaf_len | prog | cols]
+    const size_t o_f = 0, o_ne = o_f + up(mk * sizeof(float)), o_t = o_ne + up(mk * sizeof(float)), o_sums = o_t + up(mk * sizeof(float)),
+                 o_desc = o_sums + up((size_t)n * nleaf * sizeof(float)), o_prog = o_desc + up(sizeof(FisherWinDesc) * K),
+                 o_rows = o_prog + up(sizeof(int32_t) * nprog), o_tsums = o_rows + up((size_t)n * tail * sizeof(float)),
+                 o_lo = o_tsums + up((size_t)n * nleaf_t * sizeof(float)), o_len = o_lo + up(sizeof(int64_t) * nleaf_t),
+                 o_tprog = o_len + up(sizeof(int32_t) * nleaf_t), o_cols = o_tprog + up(sizeof(int32_t) * nprog_t),
+                 total = o_cols + up(sizeof(int32_t) * (size_t)max_cols);
+    void *ws = nullptr;
+    if (wgs_ctx_workspace(ctx, total, &ws)) return 1;
+    char *w = reinterpret_cast<char *>(ws);
+    float *d_f = reinterpret_cast<float *>(w + o_f), *d_ne = reinterpret_cast<float *>(w + o_ne), *d_t = reinterpret_cast<float *>(w + o_t);
+    float *d_sums = reinterpret_cast<float *>(w + o_sums), *d_rows = reinterpret_cast<float *>(w + o_rows), *d_tsums = reinterpret_cast<float *>(w + o_tsums);
+    FisherWinDesc *d_descs = reinterpret_cast<FisherWinDesc *>(w + o_desc);
+    int32_t *d_prog = reinterpret_cast<int32_t *>(w + o_prog), *d_len = reinterpret_cast<int32_t *>(w + o_len),
+            *d_tprog = reinterpret_cast<int32_t *>(w + o_tprog), *d_cols = reinterpret_cast<int32_t *>(w + o_cols);
+    int64_t *d_lo = reinterpret_cast<int64_t *>(w + o_lo);
+    std::vector<FisherWinDesc> descs(K);
+    for (int g = 0; g < K; ++g) {
+        const Slab &s = window->slabs[g];
+        FisherWinDesc &d = descs[g];
+        d.slab = s.base;
+        d.th = window_af->buf + (size_t)g * window_af->m;
+        d.f_out = d_f + (size_t)g * m;
+        d.ne_out = d_ne + (size_t)g * m;
+        d.leaf_sums = d_sums + (size_t)row0[g] * nleaf;
+        d.npairs = s.npairs;
+        d.ncols = s.ncols;
+    }
+    std::vector<int32_t> cols(max_cols);
+    for (int32_t c = 0; c < max_cols; ++c) cols[c] = c;
+    HIP_TRY(hipMemcpyAsync(d_descs, descs.data(), sizeof(FisherWinDesc) * K, hipMemcpyHostToDevice, ctx->stream));
+    if (nprog) HIP_TRY(hipMemcpyAsync(d_prog, plan.prog.data(), sizeof(int32_t) * nprog, hipMemcpyHostToDevice, ctx->stream));
+    if (tail) {
+        HIP_TRY(hipMemcpyAsync(d_lo, plan_t.leaf_lo.data(), sizeof(int64_t) * nleaf_t, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_len, plan_t.leaf_len.data(), sizeof(int32_t) * nleaf_t, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_tprog, plan_t.prog.data(), sizeof(int32_t) * nprog_t, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_cols, cols.data(), sizeof(int32_t) * (size_t)max_cols, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (row_of != st->row_of) HIP_TRY(hipMemcpyAsync(st->d_row_of, row_of.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));              // the host vectors above go out of use here
+    st->row_of.swap(row_of);
+    HIP_TRY(hipEventRecord(st->ev0, ctx->stream));
+    if (launch_fisher_window(ctx, d_descs, K, m, full)) return 1;
+    HIP_TRY(hipEventRecord(st->ev1, ctx->stream));
+    int cur = st->cur;
+    if (full) {
+        if (launch_fisher_stream_combine(ctx, d_sums, (int)nleaf, st->d_row_of, d_prog, (int)nprog, (int)n, st->pushed ? st->d_total[cur] : nullptr,
+                                         st->d_total[cur ^ 1]))
+            return 1;
+        cur ^= 1;
+    }
+    if (tail) {
+        constexpr int64_t ROWS_PER_LAUNCH = 32768;           // (the individual is the grid's y)
+        for (int g = 0; g < K; ++g) {
+            const Slab &s = window->slabs[g];
+            for (int64_t c0 = 0; c0 < s.ncols; c0 += ROWS_PER_LAUNCH)
+                if (launch_fisher_ind_sites(ctx, s.base + (size_t)(full / 64) * s.npairs * 64, d_cols + c0, window_af->buf + (size_t)g * window_af->m + full,
+                                            d_rows + (size_t)(row0[g] + c0) * tail, tail, s.npairs, (int)std::min<int64_t>(ROWS_PER_LAUNCH, s.ncols - c0)))
+                    return 1;
+        }
+        for (int64_t r0 = 0; r0 < n; r0 += ROWS_PER_LAUNCH)
+            if (launch_pairwise_leaves(ctx, d_rows + (size_t)r0 * tail, (int)std::min<int64_t>(ROWS_PER_LAUNCH, n - r0), tail, d_lo, d_len, (int)nleaf_t,
+                                       d_tsums + (size_t)r0 * nleaf_t))
+                return 1;
+        if (launch_fisher_stream_combine(ctx, d_tsums, (int)nleaf_t, st->d_row_of, d_tprog, (int)nprog_t, (int)n,
+                                         st->pushed + full > 0 ? st->d_total[cur] : nullptr, st->d_total[cur ^ 1]))
+            return 1;
+        cur ^= 1;
+    }
+    if (launch_transpose_Km_to_mK(ctx, d_f, d_t, m, K)) return 1;
+    HIP_TRY(hipMemcpyAsync(f_obs_rows, d_t, mk * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (launch_transpose_Km_to_mK(ctx, d_ne, d_t, m, K)) return 1;
+    HIP_TRY(hipMemcpyAsync(ne_obs_rows, d_t, mk * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (hipEventElapsedTime(&st->last_ms, st->ev0, st->ev1) != hipSuccess) st->last_ms = 0.0f;
+    st->cur = cur;
+    st->pushed += m;
+    return 0;
+}
+
+/* Kernel time of the last push's fused sweep (fisher_window_kernel), between events. */
+int wgs_fisher_stream_sweep_ms(wgs_fisher_stream *st, float *ms)
+{
+    WGS_REQUIRE(st && ms, "null argument");
+    *ms = st->last_ms;
+    return 0;
+}
+
+/* ne_ind_out (host, n float32, by individual in file order): np.mean's float32(float64(total) / m_total).  rc 2 before all m_total sites
+ * were pushed, and for a second call. */
+int wgs_fisher_stream_finish(wgs_fisher_stream *st, float *ne_ind_out)
+{
+    WGS_REQUIRE(st && ne_ind_out, "null argument");
+    char why[256];
+    if (fisher_stream_finish_refusal(st->pushed, st->m_total, st->finished, why, sizeof why)) {
+        wgs_set_error("%s", why);
+        return 2;
+    }
+    wgs_ctx *ctx = st->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    float *d_means = st->d_total[st->cur ^ 1];
+    if (launch_fisher_stream_means(ctx, st->d_total[st->cur], (int)st->n, st->m_total, d_means)) return 1;
+    HIP_TRY(hipMemcpyAsync(ne_ind_out, d_means, sizeof(float) * (size_t)st->n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st->finished = true;
     return 0;
 }
 

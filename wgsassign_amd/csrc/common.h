@@ -345,6 +345,20 @@ int launch_fisher_ind_sites(wgs_ctx *ctx, const float4 *slab, const int32_t *d_c
 int launch_pairwise_mean(wgs_ctx *ctx, const float *d_rows, int count, int64_t m, int64_t divide_by, const int64_t *d_leaf_lo,
                          const int32_t *d_leaf_len, int nleaf, const int32_t *d_prog, int nprog, float *d_leaf_sums, const float *d_carry,
                          float *d_means);
+struct FisherWinDesc { // one population of the fused --ne_obs sweep over a site window (fisher_window_kernel)
+    const float4 *slab;
+    const float *th;
+    float *f_out, *ne_out;
+    float *leaf_sums;      // [ncols][nleaf]: per individual of the slab (column order) the 128-site leaf sums of the window's full 8192-site chunks
+    int32_t npairs, ncols;
+};
+// m sites of a window, of which the first full_sites (a multiple of 8192) lie in full chunks: nleaf = full_sites / 128 per individual
+int launch_fisher_window(wgs_ctx *ctx, const FisherWinDesc *d_descs, int32_t n_desc, int64_t m, int64_t full_sites);
+int launch_pairwise_leaves(wgs_ctx *ctx, const float *d_rows, int count, int64_t m, const int64_t *d_leaf_lo, const int32_t *d_leaf_len, int nleaf,
+                           float *d_leaf_sums);
+int launch_fisher_stream_combine(wgs_ctx *ctx, const float *d_leaf_sums, int nleaf, const int32_t *d_row_of, const int32_t *d_prog, int nprog, int n,
+                                 const float *d_carry, float *d_totals);
+int launch_fisher_stream_means(wgs_ctx *ctx, const float *d_totals, int n, int64_t m_total, float *d_means);
 int launch_em_sweep(wgs_ctx *ctx, const FitDesc *d_descs, int32_t n_fits, int64_t m, int mode);
 // the same sweep through the class codes (exact mode; every fit's descriptor carries its slab's local codes; rows = the
 // largest SlabLocal::rows among the fits)

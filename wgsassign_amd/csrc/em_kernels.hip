@@ -1262,6 +1262,134 @@ __global__ __launch_bounds__(64) void pairwise_combine_kernel(const float *__res
     means[j] = m > 0 ? (float)((double)stack[0] / (double)m) : stack[0];
 }
 
+// ---- --ne_obs in a site window (wgs_fisher_stream_push): ONE sweep over the window's population slabs for both results ----
+// Every float4 of the window is read once and fisher_term evaluated once per individual and site.  From it
+//   per site and population   the serial float32 sum over the slab's individuals, f_obs and ne_obs: the operations of
+//                             fisher_pop_kernel in its order (lane <-> site; the z/w half of an odd slab's last pair is left out);
+//   per individual and leaf   NumPy's 128-element leaf sum (pairwise_leaf_kernel) of the value fisher_ind_sites_kernel writes,
+//                             for the leaves of the window's FULL 8192-site chunks (sites below full_sites): those chunks halve down
+//                             to 64 leaves of 128 sites each, every one two tiles of the slab.  No row matrix is written.
+// A wavefront owns one leaf and walks the slab's pairs four at a time.  Accumulator r of a leaf is the serial chain over sites
+// r, r + 8, ... -- lanes r, r + 8, ..., r + 56 of the first tile, then of the second -- so the 8 values a lane holds after four
+// pairs (8 individuals) are turned round through LDS: lane -> (individual j = lane / 8, accumulator r = lane % 8), which adds its
+// eight values of the tile in site order.  All 64 lanes work; the chain costs 8 LDS writes, 8 LDS reads and 8 adds per lane
+// and 8 individuals.  The four pairs' first tile, then their second: the accumulator is carried in one register.  Rows of 72
+// floats: the lanes (j, r) of a half-wave read banks (8 j + r + 8 k) % 32, all different.  The wavefront's LDS operations execute
+// in order; the fences keep the compiler from moving them across each other.
+constexpr int FW_STRIDE = 72;
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(WAVES * 64) void fisher_window_kernel(const FisherWinDesc *__restrict__ descs, int n_desc, int64_t m,
+                                                                   int64_t full_sites, int nleaf)
+{
+    __shared__ float turn[WAVES][8 * FW_STRIDE];
+    const FisherWinDesc fd = descs[blockIdx.x % (unsigned)n_desc];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t leaf = (int64_t)(blockIdx.x / (unsigned)n_desc) * WAVES + wave;
+    const int64_t row0 = leaf * 128;
+    if (row0 >= m) return;
+    const int ntile = row0 + 64 < m ? 2 : 1;                 // the window's last leaf may be one tile, and that one partial
+    const bool sums = row0 < full_sites;                     // a leaf of a full chunk: both tiles there (full_sites <= m, a multiple of 8192)
+    float th[2], term_sum[2] = {0.0f, 0.0f};
+    double thd[2], omt[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int64_t row = row0 + 64 * t + lane;
+        th[t] = ((gf32_ptr)fd.th)[row < m ? row : m - 1];
+        thd[t] = (double)th[t];
+        omt[t] = 1.0 - thd[t];
+    }
+    float *w = turn[wave];
+    const int j = lane >> 3, r = lane & 7;
+    for (int p0 = 0; p0 < fd.npairs; p0 += 4) {
+        const int np = fd.npairs - p0 < 4 ? fd.npairs - p0 : 4;
+        float acc = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            if (t < ntile) {
+                gf4_ptr src = (gf4_ptr)fd.slab + ((leaf * 2 + t) * fd.npairs + p0) * 64 + lane;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (q < np) {
+                        const f4 v = __builtin_nontemporal_load(src + q * 64);
+                        const float a = fisher_term(v.x, v.y, th[t], thd[t], omt[t]);
+                        term_sum[t] = term_sum[t] + a;                                          // fisher_cy.pyx:28
+                        float vb = 0.0f;
+                        if (2 * (p0 + q) + 1 < fd.ncols) {
+                            const float b = fisher_term(v.z, v.w, th[t], thd[t], omt[t]);
+                            term_sum[t] = term_sum[t] + b;
+                            vb = (float)(((0.5 * (double)b) * thd[t]) * omt[t]);
+                        }
+                        if (sums) {
+                            w[(2 * q) * FW_STRIDE + lane] = (float)(((0.5 * (double)a) * thd[t]) * omt[t]);   // fisher_cy.pyx:62-63
+                            w[(2 * q + 1) * FW_STRIDE + lane] = vb;
+                        }
+                    }
+                }
+                if (sums) {
+                    wave_lds_sync();
+                    const float *x = w + j * FW_STRIDE + r;
+                    if (t == 0) acc = x[0];                                                     // r[i] = a[i]
+                    else acc = acc + x[0];
+#pragma unroll
+                    for (int k = 1; k < 8; ++k) acc = acc + x[8 * k];                           // r[i % 8] += a[i], in site order
+                    wave_lds_sync();
+                }
+            }
+        }
+        if (sums) {
+            acc = acc + __shfl_xor(acc, 1);                  // as pairwise_leaf_kernel: ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7))
+            acc = acc + __shfl_xor(acc, 2);
+            acc = acc + __shfl_xor(acc, 4);
+            const int col = 2 * p0 + j;
+            if (r == 0 && col < fd.ncols) ((gf32_wptr)fd.leaf_sums)[(int64_t)col * nleaf + leaf] = acc;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int64_t row = row0 + 64 * t + lane;
+        if (t < ntile && row < m) {
+            ((gf32_wptr)fd.f_out)[row] = term_sum[t];                                                    // 0.0f + term_sum (fisher_cy.pyx:29)
+            ((gf32_wptr)fd.ne_out)[row] = (float)(((0.5 * (double)term_sum[t]) * thd[t]) * omt[t]);      // fisher_cy.pyx:37-38
+        }
+    }
+}
+
+// The leaf sums of a window's individuals (row row_of[i] of leaf_sums: slab after slab, column after column) added in the plan's
+// order onto the running totals: pairwise_combine_kernel's stack program, with the totals indexed by individual in file order.
+__global__ __launch_bounds__(64) void fisher_stream_combine_kernel(const float *__restrict__ leaf_sums, int nleaf, const int32_t *__restrict__ row_of,
+                                                                  const int32_t *__restrict__ prog, int nprog, int n, const float *__restrict__ carry,
+                                                                  float *__restrict__ totals)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *ls = leaf_sums + (int64_t)row_of[i] * nleaf;
+    float stack[64];
+    int sp = 0;
+    if (carry) stack[sp++] = carry[i];
+    for (int p = 0; p < nprog; ++p) {
+        const int op = prog[p];
+        if (op >= 0) {
+            stack[sp++] = ls[op];
+        } else {
+            --sp;
+            stack[sp - 1] = stack[sp - 1] + stack[sp];
+        }
+    }
+    totals[i] = stack[0];
+}
+
+// np.mean's last step on the totals: float32(float64(total) / m_total).
+__global__ __launch_bounds__(64) void fisher_stream_means_kernel(const float *__restrict__ totals, int n, int64_t m_total, float *__restrict__ means)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) means[i] = (float)((double)totals[i] / (double)m_total);
+}
+
 // Test hook: div_exact against the compiler's IEEE divide on operands shaped like the EM term's
 // (den = a float32 sum widened to double, num = p1 + 2*p2 with float32 p1, p2 >= 0, num <~ 2 den,
 // plus den = 0 and tiny/huge magnitudes).  Counts bitwise mismatches.
@@ -1486,6 +1614,48 @@ int launch_pairwise_mean(wgs_ctx *ctx, const float *d_rows, int count, int64_t m
     hipLaunchKernelGGL(pairwise_leaf_kernel, grid, dim3(256), 0, ctx->stream, d_rows, m, d_leaf_lo, d_leaf_len, nleaf, d_leaf_sums);
     hipLaunchKernelGGL(pairwise_combine_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ctx->stream, d_leaf_sums, nleaf, d_prog, nprog,
                        count, divide_by, d_carry, d_means);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_fisher_window(wgs_ctx *ctx, const FisherWinDesc *d_descs, int32_t n_desc, int64_t m, int64_t full_sites)
+{
+    if (n_desc <= 0 || m <= 0) return 0;
+    WGS_REQUIRE(full_sites >= 0 && full_sites <= m && full_sites % 8192 == 0, "fisher window sweep: %lld sites in full chunks of a window of %lld",
+                (long long)full_sites, (long long)m);
+    const int64_t leaves = (m + 127) / 128;
+    const int64_t blocks = ((leaves + WAVES - 1) / WAVES) * n_desc;
+    WGS_REQUIRE(blocks < (1ll << 31), "fisher window sweep: too many workgroups");
+    hipLaunchKernelGGL(fisher_window_kernel, dim3((unsigned)blocks), dim3(WAVES * 64), 0, ctx->stream, d_descs, n_desc, m, full_sites,
+                       (int)(full_sites / 128));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_pairwise_leaves(wgs_ctx *ctx, const float *d_rows, int count, int64_t m, const int64_t *d_leaf_lo, const int32_t *d_leaf_len, int nleaf,
+                           float *d_leaf_sums)
+{
+    if (count <= 0 || m <= 0 || nleaf <= 0) return 0;
+    dim3 grid((unsigned)(((int64_t)nleaf * 8 + 255) / 256), (unsigned)count);
+    hipLaunchKernelGGL(pairwise_leaf_kernel, grid, dim3(256), 0, ctx->stream, d_rows, m, d_leaf_lo, d_leaf_len, nleaf, d_leaf_sums);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_fisher_stream_combine(wgs_ctx *ctx, const float *d_leaf_sums, int nleaf, const int32_t *d_row_of, const int32_t *d_prog, int nprog, int n,
+                                 const float *d_carry, float *d_totals)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(fisher_stream_combine_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_leaf_sums, nleaf, d_row_of, d_prog,
+                       nprog, n, d_carry, d_totals);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_fisher_stream_means(wgs_ctx *ctx, const float *d_totals, int n, int64_t m_total, float *d_means)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(fisher_stream_means_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_totals, n, m_total, d_means);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -895,6 +895,56 @@ class LooStream:
             pass
 
 
+class FisherStream:
+    """--ne_obs in site windows (wgs_fisher_stream): every push gives the window's rows of f_obs and ne_obs; np.mean's running float32
+    total of every individual's per-site terms stays on the device from push to push -- bit for bit what fisher.fisher_obs and
+    fisher.fisher_obs_ind give on one resident matrix."""
+
+    def __init__(self, n, K, m_total, ctx=None):
+        self.ctx = ctx or get_context()
+        self.n, self.K, self.m_total = int(n), int(K), int(m_total)
+        self.windows = 0
+        self.sweep_ms = []                      # kernel time of every window's fused sweep
+        h = ctypes.c_void_p()
+        check(_lib.load().wgs_fisher_stream_create(self.ctx.handle, self.n, self.K, self.m_total, ctypes.byref(h)))
+        self._h = h
+        self.ctx._children.add(self)
+        _live.add(self)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def push(self, beagle, afset):
+        """One window (population slabs; beagle.site0 must be the number of sites pushed so far, a multiple of 8192): its
+        (rows, K) float32 f_obs and ne_obs."""
+        f_obs = np.empty((beagle.m, self.K), dtype=np.float32)
+        ne_obs = np.empty((beagle.m, self.K), dtype=np.float32)
+        check(_lib.load().wgs_fisher_stream_push(self._h, beagle.handle, afset.handle, f32p(f_obs), f32p(ne_obs)))
+        ms = ctypes.c_float()
+        check(_lib.load().wgs_fisher_stream_sweep_ms(self._h, ctypes.byref(ms)))
+        self.windows += 1
+        self.sweep_ms.append(float(ms.value))
+        return f_obs, ne_obs
+
+    def finish(self):
+        """(n,) float32 per-individual means; refused before all m_total sites were pushed, and a second time."""
+        out = np.zeros(self.n, dtype=np.float32)
+        check(_lib.load().wgs_fisher_stream_finish(self._h, f32p(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            _lib.load().wgs_fisher_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def partition_sums_exact(beagle, afset, colptr=None, P=1, comm=None, literal=False):
     """utils.partition_loglikes for all n x K pairs, bit-exact (serial float32 per partition in site
     order).  With SNP shards the float32 carries travel from rank to rank in SNP order.

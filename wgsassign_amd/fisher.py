@@ -105,3 +105,108 @@ def fisher_obs_ind(L, af, IDs, t=1, beagle=None, comm=None, m_total=None, exact_
     if own:
         beagle.close()
     return out
+
+
+def continue_column_sum(running, rows):
+    """np.add.reduce(a, axis=0) of an (m, K) float32 array, continued: `running` is the reduce over the rows before `rows` (None:
+    there are none).  NumPy forms that reduce as a serial float32 chain down each column, row after row, so the chain goes on
+    from `running` over the new rows as it would have inside one call.  ONE column is a contiguous vector, which NumPy sums as
+    fisher_obs_ind's rows are summed (csrc/api.hip: PairwisePlan): pairwise within every 8192 elements, those sums added to the
+    running total in order -- so `rows` then begins at a multiple of 8192 rows, as every window does."""
+    rows = np.asarray(rows, dtype=np.float32)
+    if rows.shape[1] == 1:
+        for lo in range(0, rows.shape[0], 8192):
+            chunk = np.add.reduce(rows[lo:lo + 8192], axis=0)
+            running = chunk if running is None else running + chunk
+        return running
+    if running is None:
+        return np.add.reduce(rows, axis=0)
+    return np.add.reduce(np.concatenate([running[None], rows]), axis=0)
+
+
+def column_mean(total, m):
+    """np.mean(a, axis=0)'s last step on the column sums of m rows: the very call NumPy makes (for m > 2**24 the divisor rounds
+    to float32 there, too)."""
+    total = np.array(total, dtype=np.float32, copy=True)
+    return np.true_divide(total, m, out=total, casting="unsafe")
+
+
+def fisher_obs_windowed(path, af, IDs, window_sites=None, out=None, ctx=None):
+    """fisher_obs, np.mean(ne_obs, axis=0) and fisher_obs_ind for a Beagle FILE whose matrix need not fit the device, from ONE pass
+    over the file in consecutive windows of `window_sites` sites (a multiple of 8192, rounded down; None: WGSASSIGN_NE_WINDOW_SITES,
+    else what windows.plan_ne derives from the free device memory -- one window when everything fits).  af: the (m, K) fitted
+    frequencies, an array or an np.load(..., mmap_mode="r") view; rows [lo, hi) are uploaded per window.  Per window one fused sweep
+    (csrc/em_kernels.hip: fisher_window_kernel) gives its rows of f_obs and ne_obs and the leaf sums of NumPy's pairwise float32 sum
+    of every individual's per-site terms; the running totals stay on the device (device.FisherStream).  Returns
+    (f_obs, ne_obs, ne_obs_mean, ne_ind): f_obs, ne_obs (m, K) float32 -- np.lib.format.open_memmap files out + ".fisher_obs.npy" /
+    ".ne_obs.npy" when `out` is given, written window by window, so the host holds one window's rows --, ne_obs_mean (K,) float32 =
+    np.mean(ne_obs, axis=0) and ne_ind (n,) float32, all bit for bit what the resident functions give.
+    fisher_obs_windowed.stats: windows, window_sites, largest_matrix_bytes, matrices, seconds, sweep_ms (per window);
+    fisher_obs_windowed.info: n, m, sample_names, site_names (the first and last four), pops."""
+    import time
+
+    from . import reader_cy, windows
+    from .device import FisherStream, get_context
+    ctx = ctx or get_context()
+    t0 = time.perf_counter()
+    IDs = np.asarray(IDs)
+    pops = np.unique(IDs[:, 1])
+    group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
+    counts = np.bincount(group_of, minlength=len(pops))
+    K = len(pops)
+    if af.ndim != 2 or af.shape[1] != K:
+        raise ValueError("the allele frequencies must be an (m, %d) matrix" % K)
+    index, _, m = reader_cy.ensure_index(path)
+    if m <= 0:
+        raise ValueError("%s holds no sites" % path)
+    if af.shape[0] != m:
+        raise ValueError("the allele frequencies have %d sites, the Beagle file %d" % (af.shape[0], m))
+    if window_sites is None:
+        W = windows.env_window_sites(name=windows.ENV_NE)
+        if W is None:
+            W = (windows.plan_ne(m, len(group_of), K, ctx.mem_info()[0], counts=counts)
+                 or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN)
+    else:
+        if int(window_sites) < windows.ALIGN:
+            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
+        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+
+    def groups(sample_names):
+        if len(sample_names) != len(group_of):
+            raise AssertionError("Number of individuals in beagle and reference ID file do not match!")
+        return group_of, K
+
+    def result(suffix):
+        if out is None:
+            return np.empty((m, K), dtype=np.float32)
+        return np.lib.format.open_memmap(out + suffix, mode="w+", dtype=np.float32, shape=(m, K))
+
+    f_obs, ne_obs = result(".fisher_obs.npy"), result(".ne_obs.npy")
+    info, stream, running = {}, None, None
+    gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info, group_of=groups, n_groups=K)
+    try:
+        for b in gen:
+            if stream is None:
+                stream = FisherStream(b.n, K, m, ctx)
+            lo, hi = b.site0, b.site0 + b.m
+            afs = AFSet.from_host(np.ascontiguousarray(af[lo:hi], dtype=np.float32), ctx=ctx)
+            try:
+                f_rows, ne_rows = stream.push(b, afs)
+            finally:
+                afs.close()
+            f_obs[lo:hi] = f_rows
+            ne_obs[lo:hi] = ne_rows
+            running = continue_column_sum(running, ne_rows)        # np.mean(ne_obs, axis=0): WGSassign.py:401
+        ne_ind = stream.finish()
+        sweep_ms = list(stream.sweep_ms)
+    finally:
+        gen.close()
+        if stream is not None:
+            stream.close()
+    if out is not None:
+        f_obs.flush()
+        ne_obs.flush()
+    fisher_obs_windowed.stats = {"windows": info["windows"], "window_sites": W, "largest_matrix_bytes": info["largest_matrix_bytes"],
+                                 "matrices": info["matrices"], "seconds": time.perf_counter() - t0, "sweep_ms": sweep_ms}
+    fisher_obs_windowed.info = dict({k: info[k] for k in ("n", "m", "sample_names", "site_names")}, pops=pops)
+    return f_obs, ne_obs, column_mean(running, m), ne_ind

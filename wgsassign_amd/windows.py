@@ -26,6 +26,7 @@ FRACTION = 0.8
 RESERVE = 4 << 30
 ENV = "WGSASSIGN_WINDOW_SITES"
 ENV_LOO = "WGSASSIGN_LOO_WINDOW_SITES"      # the leave-one-out run is sent to windows by a variable of its own (see plan_loo)
+ENV_NE = "WGSASSIGN_NE_WINDOW_SITES"        # ... and so is --ne_obs (see plan_ne)
 SURELY_FITS = 64                # see surely_fits
 
 
@@ -174,4 +175,41 @@ def plan_loo(m, n, K, free_bytes, environ=None, counts=None, P=1):
         raise MemoryError("a windowed leave-one-out run needs two windows of %d sites x %d individuals on the device (%d bytes with "
                           "their %d re-fits, class codes and scoring tables); %d of the %d free bytes can be used" %
                           (ALIGN, n, 2 * ALIGN * per_site, n, max(0, budget(free_bytes)), free_bytes))
+    return W
+
+
+def ne_site_bytes(n, K, counts=None):
+    """Device bytes one site takes in a windowed --get_reference_af --ne_obs pass of n individuals in K populations (counts: the
+    individuals of every population when known, else the worst split), from what wgs_fisher_stream_push allocates per site:
+
+        matrix       16 * sum_g ceil(n_g / 2)       one slab per population, at most 16 * ((n + K) // 2)
+        frequencies  4 * K                          the window's rows of the fitted frequencies (wgs_afset)
+        results      3 * 4 * K                      f_obs and ne_obs, population-major, and the site-major copy that crosses to the host
+        leaf sums    4 * n / 128, rounded up        one float32 per individual and 128-site leaf of a full 8192-site chunk
+
+    The row matrix of the file's last, shorter chunk (n x at most 8191 float32), its leaf sums, the plans and the stream's totals do
+    not grow with the window and come out of RESERVE."""
+    n, K = int(n), int(K)
+    pairs = sum((int(c) + 1) // 2 for c in counts) if counts is not None else (n + K) // 2
+    return 16 * pairs + 4 * K + 12 * K + (4 * n + 127) // 128
+
+
+def plan_ne(m, n, K, free_bytes, environ=None, counts=None, loo=False, P=1):
+    """plan() for --get_reference_af --ne_obs: None when the resident matrix fits (fits_resident_fit) and
+    WGSASSIGN_NE_WINDOW_SITES does not ask for windows, else W (a multiple of 8192) for two windows: the fit's (plan_fit's
+    arithmetic), or the Fisher pass's when that is smaller.  loo: --loo runs beside it in the same windows, so the window is the
+    smaller of this and what plan_loo derives."""
+    forced = env_window_sites(environ, ENV_NE)
+    if forced is not None:
+        return forced
+    if fits_resident_fit(m, n, K, free_bytes, counts):
+        return None
+    per_site = max(fit_site_bytes(n, K, counts), ne_site_bytes(n, K, counts))
+    if loo:
+        per_site = max(per_site, loo_site_bytes(n, K, counts, P))
+    W = budget(free_bytes) // (2 * per_site) // ALIGN * ALIGN
+    if W < ALIGN:
+        raise MemoryError("a windowed --ne_obs run needs two windows of %d sites x %d individuals on the device (%d bytes with their "
+                          "frequency buffers, class codes and Fisher results); %d of the %d free bytes can be used" %
+                          (ALIGN, n, 2 * ALIGN * per_site, max(0, budget(free_bytes)), free_bytes))
     return W
