@@ -3,8 +3,9 @@ of tests/test_gpu_multirank.py; tests/zscore_shard_worker.py is a rank); what ra
 recorded from the real reference (tests/golden/zscore.npz, zscore_deep.npz) and to the CPU restatement those records pin
 (tests/zscore_cpu.py) -- never to the one-process device path.  Covered: the class sums handed from shard to shard with cuts
 inside tiles, first sites beyond shard 0, a shard in which an individual keeps nothing, masked chains longer than a 4096-site block
-on both sides of a cut, deep sites on both sides of a cut and next to it, the depth file's row range, the command line with
-`--gpus` and under a launcher's RANK / WORLD_SIZE, and ranks that fall out of step."""
+on both sides of a cut, deep sites on both sides of a cut and next to it, every depth class up to 21 reads on
+both sides of a cut, the depth file's row range, the command line with `--gpus` and under a launcher's RANK / WORLD_SIZE, and
+ranks that fall out of step."""
 import io
 import os
 import pickle
@@ -178,6 +179,29 @@ def test_deep_sites_on_both_sides_of_a_cut(tmp_path, oracle):
         assert 22 in kept["AD_array"][:, 2] and kept["index"].shape[0] >= 23 and kept["index"].shape[1] >= 23
         deep2 = np.flatnonzero(dl[:, 2] > 21)
         assert np.isin(deep2[deep2 < cut], kept["keep"]).any() and np.isin(deep2[deep2 >= cut], kept["keep"]).any()
+
+
+# ---------------------------------------------------------------- 5b. every depth class up to 21 reads across a cut
+def test_every_class_on_both_sides_of_a_cut(tmp_path, oracle):
+    """The class sums of the classes 64 .. 252 -- three of the class sweep's four wavefronts -- go on in shard 1 from what shard 0
+    handed over: classes with all their sites before the cut (handed on untouched), all behind it (shard 0 hands on zeros) and on
+    both sides; the depths 11 .. 21 are kept whole and their sites lie in both shards."""
+    import zscore_cases
+    jobs = worker.jobs("classes", 2, 64)
+    inputs, cuts, _ = jobs[0]
+    L, AD, IDs, A = inputs
+    cut = cuts[0]
+    assert cut % 64 and [spec["flavour"] for _, _, spec in jobs] == ["assignment", "reference"]
+    for i in zscore_cases.FULL:
+        before, after, both = zscore_cases.sides_of_cut(AD, i, cut)
+        assert len(before) and len(after) and len(both) >= 100
+    results = ranks(tmp_path, "classes", 2)
+    for result, (_, _, spec) in zip(results, jobs):
+        want = against_restatement(result, inputs, spec, oracle)
+        for i in zscore_cases.FULL:
+            assert sorted(set(want[i]["AD_array"][:, 2])) == list(range(1, 22))
+            deep = np.flatnonzero(AD[:, 2 * i] + AD[:, 2 * i + 1] >= 11)
+            assert np.isin(deep[deep < cut], want[i]["keep"]).any() and np.isin(deep[deep >= cut], want[i]["keep"]).any()
 
 
 # ---------------------------------------------------------------- 6. the depth file's rows of a range

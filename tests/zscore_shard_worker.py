@@ -20,6 +20,7 @@ for p in (HERE, ROOT):
 
 import synth_deep      # noqa: E402
 import synth_depth     # noqa: E402
+import zscore_cases    # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 BLOCKS_M, BLOCKS_CUT = 20011, 10007          # neither a multiple of 64 nor of 4096
@@ -89,6 +90,10 @@ def jobs(case, world, batch):
     if case == "deep":
         inp = deep_inputs()
         return [(inp, [BLOCKS_CUT], run("assignment", lo=1, hi=4, batch=2)), (inp, [BLOCKS_CUT], run("reference", lo=1, hi=4, batch=2))]
+    if case == "classes":                                  # every depth class up to 21 reads, the cut inside a tile
+        inp = zscore_cases.every_class()[:4]
+        cuts = [zscore_cases.CLASSES_CUT]
+        return [(inp, cuts, run("assignment", batch=3)), (inp, cuts, run("reference", batch=2))]
     if case == "outofstep":
         inp, r = recorded_cases(64)[0]
         return [(inp, even_cuts(inp[0].shape[0], world), dict(r, flavour="assignment", batch=None))]
