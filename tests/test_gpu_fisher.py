@@ -1,5 +1,7 @@
 """--ne_obs: observed Fisher information / effective sample sizes on the device
-against the golden vectors of the real reference (fisher.py / fisher_cy.pyx)."""
+against the golden vectors of the real reference (fisher.py / fisher_cy.pyx).  These are generated matrices and the AMRE data;
+tests/test_gpu_fisher_cases.py takes the same kernels through the enumerated terms of tests/fisher_cases.py -- hard calls, frequencies
+of 0 and 1, non-finite and signed-zero results, per site -- and through population slabs of every shape in the windowed sweep."""
 import contextlib
 import io
 import os

@@ -191,3 +191,16 @@ def test_fisher(oracle, golden):
     f_obs, ne_obs = oracle.fisher_obs(L, g["synth_af"].copy(), IDs, 4)
     assert same(f_obs, g["synth_f_obs"]) and same(ne_obs, g["synth_ne_obs"])
     assert same(oracle.fisher_obs_ind(L, g["synth_af"].copy(), IDs, 4), g["synth_ne_ind"])
+    # the enumerated term grids and the signed-zero populations (tests/fisher_cases.py; fisher_cases.npz by
+    # make_golden_fisher_cases.py): infinities, subnormals and the signs of zeros bit for bit, NaN where the reference has NaN;
+    # tests/test_fisher_cases_cpu.py adds the per-site rows
+    import fisher_cases
+    gc = golden("fisher_cases.npz")
+    for variant, (builder, gen) in fisher_cases.GOLDEN.items():
+        grid = getattr(fisher_cases, builder)(**gen)
+        assert fisher_cases.digest(grid) == str(gc[variant + "_digest"])
+        f_obs, ne_obs = oracle.fisher_obs(grid["L"], grid["af"].copy(), grid["IDs"], 2)
+        assert fisher_cases.same_nan(gc[variant + "_f_obs"], f_obs) and fisher_cases.same_nan(gc[variant + "_ne_obs"], ne_obs), variant
+        with np.errstate(all="ignore"):
+            ne_ind = oracle.fisher_obs_ind(grid["L"], grid["af"].copy(), grid["IDs"], 2)
+        assert fisher_cases.same_nan(gc[variant + "_ne_ind"], ne_ind), variant

@@ -1149,6 +1149,10 @@ __global__ __launch_bounds__(64) void rmse_walk_kernel(const ChainJob *__restric
 //   u  = (float)((g0*(1.0-th))*(1.0-th) + ((g1*2.0)*th)*(1.0-th) + (double)((g2*th)*th))
 //   n1 = (float)(2.0*((double)(g0+g2) - 2.0*g1));  n2 = (float)((double)(th*n1) + 2.0*(double)(g1-g0))
 //   term = -((n1/u) - (n2/u)*(n2/u))                                   (float32 divides)
+// Nothing is special-cased: u = 0, a frequency of 0 or 1, a subnormal one give the infinities and NaNs IEEE arithmetic gives the
+// reference.  The reference ADDS n_tilde = 0.5 * f * a * (1 - a) to a zeroed vector (fisher_cy.pyx:39, :65), so a product of -0.0 --
+// a negative term times a frequency of 0 or 1, a product that underflows, the term -1.0 * (+0.0) -- is stored as +0.0: every kernel
+// below stores 0.0f + (float)(...), which the build's flags (no fast-math) keep the compiler from folding away.
 __device__ __forceinline__ float fisher_term(float g0, float g1, float th, double thd, double omt)
 {
     const double g0d = (double)g0, g1d = (double)g1;
@@ -1180,7 +1184,7 @@ __global__ __launch_bounds__(WAVES * 64) void fisher_pop_kernel(const FisherDesc
     }
     if (my_row < m) {
         ((gf32_wptr)fd.f_out)[my_row] = term_sum;                                         // 0.0f + term_sum (fisher_cy.pyx:29)
-        ((gf32_wptr)fd.ne_out)[my_row] = (float)(((0.5 * (double)term_sum) * thd) * omt);  // fisher_cy.pyx:37-38
+        ((gf32_wptr)fd.ne_out)[my_row] = 0.0f + (float)(((0.5 * (double)term_sum) * thd) * omt);   // fisher_cy.pyx:37-39
     }
 }
 
@@ -1200,7 +1204,7 @@ __global__ __launch_bounds__(256) void fisher_ind_sites_kernel(const float2 *__r
     const double thd = (double)th, omt = 1.0 - thd;
     const float2 g = slab2[((((s >> 6) * npairs + (c >> 1)) << 6) + (s & 63)) * 2 + (c & 1)];
     const float term = fisher_term(g.x, g.y, th, thd, omt);
-    out[(int64_t)j * m + s] = (float)(((0.5 * (double)term) * thd) * omt);
+    out[(int64_t)j * m + s] = 0.0f + (float)(((0.5 * (double)term) * thd) * omt);              // fisher_cy.pyx:64-65
 }
 
 // ---- np.mean of a float32 row, the way NumPy forms it (fisher.py:59) ---------------------------------------------------
@@ -1322,10 +1326,10 @@ __global__ __launch_bounds__(WAVES * 64) void fisher_window_kernel(const FisherW
                         if (2 * (p0 + q) + 1 < fd.ncols) {
                             const float b = fisher_term(v.z, v.w, th[t], thd[t], omt[t]);
                             term_sum[t] = term_sum[t] + b;
-                            vb = (float)(((0.5 * (double)b) * thd[t]) * omt[t]);
+                            vb = 0.0f + (float)(((0.5 * (double)b) * thd[t]) * omt[t]);
                         }
                         if (sums) {
-                            w[(2 * q) * FW_STRIDE + lane] = (float)(((0.5 * (double)a) * thd[t]) * omt[t]);   // fisher_cy.pyx:62-63
+                            w[(2 * q) * FW_STRIDE + lane] = 0.0f + (float)(((0.5 * (double)a) * thd[t]) * omt[t]);   // fisher_cy.pyx:64-65
                             w[(2 * q + 1) * FW_STRIDE + lane] = vb;
                         }
                     }
@@ -1354,7 +1358,7 @@ __global__ __launch_bounds__(WAVES * 64) void fisher_window_kernel(const FisherW
         const int64_t row = row0 + 64 * t + lane;
         if (t < ntile && row < m) {
             ((gf32_wptr)fd.f_out)[row] = term_sum[t];                                                    // 0.0f + term_sum (fisher_cy.pyx:29)
-            ((gf32_wptr)fd.ne_out)[row] = (float)(((0.5 * (double)term_sum[t]) * thd[t]) * omt[t]);      // fisher_cy.pyx:37-38
+            ((gf32_wptr)fd.ne_out)[row] = 0.0f + (float)(((0.5 * (double)term_sum[t]) * thd[t]) * omt[t]);   // fisher_cy.pyx:37-39
         }
     }
 }
