@@ -79,6 +79,11 @@ int wgs_debug_codes_download(wgs_beagle *b, int32_t geom[8], uint8_t *ncls, uint
  * 2^20 x per_thread pseudo-random EM-shaped operand pairs whose quotient differs bitwise from the
  * compiler's IEEE double divide. */
 int wgs_debug_div_mismatch(wgs_ctx *ctx, uint64_t seed, uint64_t per_thread, uint64_t *mismatch);
+/* ... over the operands the enumerated EM terms show to exist (tests/em_cases.py): p2 of either sign, sums that cancel to a few ulps,
+ * negative numerators, denominators from the smallest float32 subnormal to 2^127, |num| / den from 2^-277 to 2^277.  mismatch[0]: the
+ * divide with its fixup, over all pairs; mismatch[1]: the fixup-free form of the hot loop, over the pairs with a positive finite
+ * denominator and a finite numerator (its precondition). */
+int wgs_debug_div_mismatch_signed(wgs_ctx *ctx, uint64_t seed, uint64_t per_thread, uint64_t mismatch[2]);
 /* ... and the accuracy of its once-refined reciprocal: the largest relative error over ALL 2^23 float32 mantissas of
  * the denominator at binary exponent `exponent` (its exactness argument needs < 2^-48; see em_kernels.hip). */
 int wgs_debug_rcp_error(wgs_ctx *ctx, int exponent, double *max_rel);

@@ -96,6 +96,17 @@ def test_em_divide_is_ieee_exact(dev):
     assert bad.value == 0, bad.value
 
 
+def test_em_divide_is_ieee_exact_on_signed_and_cancelling_operands(dev):
+    """The same divide over the operands the enumerated EM terms show to exist (tests/em_cases.py): p2 of either sign, sums that cancel
+    to a few ulps under a negative numerator, denominators from the smallest float32 subnormal to 2^127 and quotients from 2^-277 to
+    2^277 -- with the fixup against the IEEE divide on all 5.4e8 pairs, and the fixup-free form of em_sweep_kernel's hot loop wherever
+    its precondition (a positive finite denominator) holds."""
+    lib, ctx, _lib = dev
+    bad = (ctypes.c_uint64 * 2)(123, 456)
+    _lib.check(lib.wgs_debug_div_mismatch_signed(ctx.handle, 20260313, 512, bad))
+    assert (bad[0], bad[1]) == (0, 0), (bad[0], bad[1])
+
+
 def test_em_divide_reciprocal_bound_exhaustive(dev):
     """div_exact uses ONE Newton refinement of v_rcp_f64.  Its exactness argument (csrc/em_kernels.hip) needs the
     refined reciprocal within 2^-48 of 1/den: checked here for EVERY float32 mantissa of the denominator (2^23 values),

@@ -204,3 +204,37 @@ def test_fisher(oracle, golden):
         with np.errstate(all="ignore"):
             ne_ind = oracle.fisher_obs_ind(grid["L"], grid["af"].copy(), grid["IDs"], 2)
         assert fisher_cases.same_nan(gc[variant + "_ne_ind"], ne_ind), variant
+
+
+def test_em_cases(oracle, golden):
+    """The enumerated EM terms (tests/em_cases.py; em_cases.npz by make_golden_em_cases.py): sums that are subnormal, a signed zero,
+    negative, infinite or NaN, negative and cancelling numerators, frequencies outside (0, 1) -- one and two updates of every recorded
+    population and of five leave-one-out re-fits, NaN where the reference has NaN and the same bits elsewhere; the whole fits of the
+    finite variant with their iterations.  tests/test_em_cases_cpu.py holds the inputs to what they claim."""
+    import em_cases
+    g = golden("em_cases.npz")
+    for name, gen in em_cases.GOLDEN.items():
+        grid = em_cases.em_grid(**gen)
+        assert em_cases.digest(grid) == str(g[name + "_digest"])
+        members = grid["members"]
+        for k in range(len(gen["sizes"])):
+            got = em_cases.updates(oracle.emMAF_update, em_cases.columns(grid["L"], members[k]), grid["f_old"][k], 2)
+            assert em_cases.same_nan(g[name + "_updates"][:, k], got), (name, k)
+        k = gen["sizes"].index(em_cases.GOLDEN_LOO)
+        for j, c in enumerate(g[name + "_loo_cols"]):
+            got = em_cases.updates(oracle.emMAF_update, em_cases.columns(grid["L"], np.delete(members[k], c)), grid["f_old"][k], 2)
+            assert em_cases.same_nan(g[name + "_loo_updates"][:, j], got), (name, c)
+        if name == "finite":
+            assert np.isfinite(g["finite_updates"]).all() and list(g["finite_fit_iters"]) == [58, 64, 35, 37, 27, 21]
+            for k in range(len(gen["sizes"])):
+                f, it = oracle.emMAF(em_cases.columns(grid["L"], members[k]), 200, 1e-4, 2)
+                assert it == g["finite_fit_iters"][k] and same(f, g["finite_fit"][k]), k
+        else:
+            first = g["hostile_updates"][0]
+            assert np.isnan(first).any() and np.isposinf(first).any() and np.isneginf(first).any() and ((first == 0) & np.signbit(first)).any()
+    # a running float32 sum that a term has underflowed to -0.0: the reference returns -0.0 at every site
+    case = em_cases.negative_zero_sums()
+    assert em_cases.digest(case) == str(g["zeros_digest"]) and np.signbit(g["zeros_updates"]).all() and (g["zeros_updates"] == 0).all()
+    for k in range(len(case["sizes"])):
+        got = em_cases.updates(oracle.emMAF_update, em_cases.columns(case["L"], case["members"][k]), case["f_old"][k], 1)
+        assert same(got, g["zeros_updates"][:, k]), k

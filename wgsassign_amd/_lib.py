@@ -153,6 +153,7 @@ SIGNATURES = {
     "wgs_debug_codes_download": (c_int, [c_vp, c_i32p, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wgs_debug_rcp_error": (c_int, [c_vp, c_int, c_f64p]),
     "wgs_debug_div_mismatch": (c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "wgs_debug_div_mismatch_signed": (c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "wgs_debug_log_mismatch": (c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),
     "wgs_debug_log_values": (c_int, [c_vp, c_f32p, c_f32p, c_i64, c_int]),
     "wgs_assign_last_ms": (c_int, [c_vp, c_f32p]),

@@ -1021,6 +1021,25 @@ int wgs_debug_div_mismatch(wgs_ctx *ctx, uint64_t seed, uint64_t per_thread, uin
     return 0;
 }
 
+/* The same over signed, cancelling and far-apart operands (em_kernels.hip: div_check_signed_kernel): mismatch[0] of div_exact with its
+ * fixup over all 2^20 x per_thread pairs, mismatch[1] of the fixup-free form over those that meet its precondition. */
+int wgs_debug_div_mismatch_signed(wgs_ctx *ctx, uint64_t seed, uint64_t per_thread, uint64_t mismatch[2])
+{
+    WGS_REQUIRE(ctx && mismatch, "null argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    void *ws = nullptr;
+    if (wgs_ctx_workspace(ctx, 256, &ws)) return 1;
+    unsigned long long *d = reinterpret_cast<unsigned long long *>(ws);
+    HIP_TRY(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    if (launch_div_check_signed(ctx, seed, per_thread, d)) return 1;
+    unsigned long long h[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    mismatch[0] = h[0];
+    mismatch[1] = h[1];
+    return 0;
+}
+
 /* Largest relative error of the once-refined reciprocal of div_exact over all 2^23 float32 mantissas of the
  * denominator scaled by 2^exponent (the bound its exactness argument rests on: < 2^-48). */
 int wgs_debug_rcp_error(wgs_ctx *ctx, int exponent, double *max_rel)

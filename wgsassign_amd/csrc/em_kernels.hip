@@ -40,19 +40,33 @@ struct SnpState {
     float ff, omff, ff2;              // fast-mode float copies
 };
 
-// Correctly rounded double quotient num/den for den = a float32 value widened to double (or 0) and num >= 0.
+// Correctly rounded double quotient num/den for den = a float32 value widened to double (or 0) and num a double of either sign.
 // v_rcp_f64 seed (measured 2^-24.4 relative), ONE Newton refinement (r within 2^-48.7 of 1/den: checked for every
 // float32 mantissa of den, tests/test_gpu_log.py), q0 = RN(num * r), residual fma, one correction, v_div_fixup for
 // the 0/0, x/0 and NaN results of `/`.  Why one refinement suffices where a general IEEE divide needs two:
-//   * before its rounding the corrected quotient fma(rem, r, q0) is within q * 2^-97 of num/den (the residual is known
-//     to 2^-53 relative, the reciprocal to 2^-48.7, and the correction itself is only q * 2^-48.6 large);
-//   * den has 24 significant bits and num at most 53, so num/den is never closer than q * 2^-78 to the midpoint of two
-//     doubles (and never on one): with num = A * 2^a, den = B * 2^b, midpoint M * 2^u (M odd, 54 bits),
-//     |num - den * M 2^u| is a non-zero multiple of 2^(b+u), i.e. >= 2^(a-25), and dividing by den < 2^(b+24)
-//     leaves >= 2^(a-b-49) = q * 2^-78;
+//   * before its rounding the corrected quotient fma(rem, r, q0) is within |q| * 2^-97 of num/den (the residual is known
+//     to 2^-53 relative, the reciprocal to 2^-48.7, and the correction itself is only |q| * 2^-48.6 large);
+//   * den has 24 significant bits and num at most 53, so num/den is never closer than |q| * 2^-78 to the midpoint of two
+//     doubles (and never on one): with |num| = A * 2^a, |den| = B * 2^b, midpoint M * 2^u (M odd, 54 bits),
+//     | |num| - |den| * M 2^u | is a non-zero multiple of 2^(b+u), i.e. >= 2^(a-25), and dividing by |den| < 2^(b+24)
+//     leaves >= 2^(a-b-49) = |q| * 2^-78;
 // so the final rounding lands on the correctly rounded quotient -- the same bits as the compiler's IEEE divide
 // (wgs_debug_div_mismatch: 0 of 8.6e9 EM-shaped operand pairs), with two fewer FP64 instructions per term and
 // without the v_div_scale range scaling these operands never need.
+// SIGNS AND RANGE.  Both bounds are statements about magnitudes, and every step (the products, the fmas, round-to-nearest-even)
+// commutes with a change of sign of num or of den: the argument holds for num < 0 (likelihoods that sum above 1, frequencies outside
+// [0, 1]) and for den < 0 as it stands.  It needs nothing of the RATIO |num| / den either -- a sum that cancels to a few ulps under a
+// numerator 2^51 times larger is the same case -- only that no intermediate leaves the normal double range: with den a non-zero
+// float32, subnormals included (2^-149 .. 2^128), and num a sum of two float32 values (0 or 2^-149 .. 2^130), r lies in
+// 2^-128 .. 2^149, q in 2^-277 .. 2^279, the residual above 2^-331.  wgs_debug_div_mismatch_signed draws exactly these operands.
+// The one place where the sign is NOT symmetric is a ZERO: num = -0.0 over a positive den must give -0.0 (the running float32 sum of
+// the EM term can be -0.0, and -0.0 + -0.0 keeps the sign that -0.0 + +0.0 loses).  q0 = -0.0 * r has it, but a residual computed as
+// fma(-den, q0, num) = (+0.0) + (-0.0) is +0.0 and the correction fma(+0.0, r, -0.0) returns +0.0.  So the residual is formed
+// NEGATED, over = fma(den, q0, -num), and subtracted: fma(-over, r, q0).  For num = -0.0: over = (-0.0) + (+0.0) = +0.0 and
+// fma(-0.0, r, -0.0) = -0.0; for num = +0.0: over = (+0.0) + (-0.0) = +0.0 and fma(-0.0, r, +0.0) = +0.0; an exact quotient
+// (over = +0.0) keeps q0; everywhere else over is the old residual with its sign turned, bit for bit, and the negation is an input
+// modifier of the fma: the same instructions.  (Found by tests/em_cases.py: negative_zero_sums; v_div_fixup returns the signed zero
+// by itself, so only the fixup-free form was wrong.)
 __device__ __forceinline__ double refined_rcp(double den)
 {
     double r = __builtin_amdgcn_rcp(den);
@@ -69,8 +83,8 @@ __device__ __forceinline__ double div_exact(double num, double den)
 {
     const double r = refined_rcp(den);
     double q = num * r;
-    const double rem = __builtin_fma(-den, q, num);
-    q = __builtin_fma(rem, r, q);
+    const double over = __builtin_fma(den, q, -num);       // the residual, negated: keeps the sign of a zero numerator (above)
+    q = __builtin_fma(-over, r, q);
     return FIXUP ? __builtin_amdgcn_div_fixup(q, den, num) : q;
 }
 
@@ -1429,6 +1443,60 @@ __global__ void div_check_kernel(unsigned long long seed, unsigned long long per
     if (bad) atomicAdd(mismatch, bad);
 }
 
+// Test hook: div_exact beyond div_check_kernel's operands -- the ones the enumerated EM terms show to exist (tests/em_cases.py):
+// p2 of either sign (likelihoods that sum above 1, frequencies outside [0, 1]), float32 values over the whole exponent range, subnormals
+// included, and three ways to the denominator:
+//   (c & 3) == 0   den = (p0 + p1) + p2 with p2 within four ulps of -(p0 + p1): the sum cancels, num = p1 + 2 p2 is negative and up to
+//                  2^25 times larger;
+//   (c & 3) == 1   den = a float32 of its own, from the smallest subnormal to 2^127 (and, rarely, 0): |num| / den anywhere between
+//                  2^-277 and 2^277;
+//   else           den = (p0 + p1) + p2 as it comes: negative, zero and infinite sums among them.
+// mismatch[0] counts div_exact<true> against the compiler's IEEE divide over all of them, mismatch[1] div_exact<false> wherever its
+// precondition holds (a positive finite denominator, a finite numerator).  A NaN equals a NaN.  p1 is non-negative or -0.0 (a
+// product that underflows under a negative frequency): with p2 = -0.0 the numerator is -0.0, whose quotient must keep its sign.
+__global__ void div_check_signed_kernel(unsigned long long seed, unsigned long long per_thread, unsigned long long *mismatch)
+{
+    const unsigned long long tid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long bad = 0, bad_plain = 0;
+    unsigned int st = mix32((unsigned int)(tid ^ seed) + 0x9e3779b9u * (unsigned int)(seed >> 32));
+    for (unsigned long long it = 0; it < per_thread; ++it) {
+        st = mix32(st + 0x6d2b79f5u);
+        const unsigned int a = st;
+        st = mix32(st + 0x6d2b79f5u);
+        const unsigned int b = st;
+        st = mix32(st + 0x6d2b79f5u);
+        const unsigned int c = st;
+        st = mix32(st + 0x6d2b79f5u);
+        const unsigned int d = st;
+        // non-negative float32 values with exponent fields 0 .. 254: subnormals up to 2^127 and a full mantissa
+        const float p0 = __uint_as_float((((a >> 23) % 255u) << 23) | (a & 0x7FFFFFu));
+        const float p1 = (c & 0x70u) == 0 ? ((d & 0x40000000u) ? -0.0f : 0.0f) : __uint_as_float((((b >> 23) % 255u) << 23) | (b & 0x7FFFFFu));
+        float p2 = (c & 0x380u) == 0 ? 0.0f : __uint_as_float((((c >> 23) % 255u) << 23) | (c & 0x7FFFFFu));
+        const unsigned int way = c & 3u;
+        if (way == 0) {
+            const float head = p0 + p1;                                      // finite or +inf, never NaN
+            const unsigned int hb = __float_as_uint(head), off = (c >> 2) & 3u;
+            // -(head moved by up to four ulps towards or away from zero); stays a finite float32 or becomes -inf
+            const unsigned int pb = (c & 0x400u) ? hb + 1u + off : (hb > 4u ? hb - 1u - off : hb);
+            p2 = -__uint_as_float(pb < 0x7F800000u ? pb : 0x7F800000u);
+        } else if (d & 0x80000000u) {
+            p2 = -p2;
+        }
+        float s = (p0 + p1) + p2;
+        if (way == 1) s = (d & 0x3FFu) == 1 ? 0.0f : __uint_as_float((((d >> 23) % 255u) << 23) | (d & 0x7FFFFFu));
+        const double num = __builtin_fma(2.0, (double)p2, (double)p1), den = (double)s;
+        const double q2 = num / den;
+        const double q1 = div_exact<true>(num, den);
+        bad += !(__double_as_longlong(q1) == __double_as_longlong(q2) || (q1 != q1 && q2 != q2));
+        if (__builtin_isfpclass(s, FP_POS_FINITE_NONZERO) && __builtin_isfinite(num)) {
+            const double q3 = div_exact<false>(num, den);
+            bad_plain += !(__double_as_longlong(q3) == __double_as_longlong(q2));
+        }
+    }
+    if (bad) atomicAdd(mismatch, bad);
+    if (bad_plain) atomicAdd(mismatch + 1, bad_plain);
+}
+
 // Test hook: the largest relative error of refined_rcp over EVERY float32 mantissa (2^23 denominators) at the given
 // binary exponent, against the correctly rounded 1/den (IEEE divide), as the ordered integer image of the double.
 __global__ void rcp_error_kernel(int exponent, unsigned long long *max_bits)
@@ -1584,6 +1652,13 @@ int ssq_reduce_chunks(void) { return RED_CHUNKS; }
 int launch_div_check(wgs_ctx *ctx, unsigned long long seed, unsigned long long per_thread, unsigned long long *d_mismatch)
 {
     hipLaunchKernelGGL(div_check_kernel, dim3(4096), dim3(256), 0, ctx->stream, seed, per_thread, d_mismatch);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_div_check_signed(wgs_ctx *ctx, unsigned long long seed, unsigned long long per_thread, unsigned long long *d_mismatch)
+{
+    hipLaunchKernelGGL(div_check_signed_kernel, dim3(4096), dim3(256), 0, ctx->stream, seed, per_thread, d_mismatch);
     HIP_TRY(hipGetLastError());
     return 0;
 }
