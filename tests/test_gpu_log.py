@@ -87,6 +87,19 @@ def test_special_values(dev):
     assert got[5] == 0.0 and got[0] == -np.inf and got[1] == -np.inf and got[3] == np.inf
 
 
+def test_special_values_of_negative_and_subnormal_arguments(dev):
+    """The hardware log that supplies libm's special values flushes a subnormal argument to a zero of its sign: a NEGATIVE subnormal
+    must still give NaN (log of a negative number), not -inf, and a positive one its finite log (tests/score_cases.py reaches both
+    through subnormal likelihoods)."""
+    x = np.array([-1e-45, -1e-40, -1.1754942e-38, -1.1754944e-38, -1e-30, -3.4028235e38, -np.inf, 1e-40, 1.1754942e-38, 2e-45], dtype=np.float32)
+    with np.errstate(all="ignore"):
+        want = np.log(x.astype(np.float64)).astype(np.float32)
+    got = values(dev, x)
+    assert np.isnan(want[:7]).all() and np.isfinite(want[7:]).all()
+    assert np.array_equal(np.isnan(got), np.isnan(want)), got
+    assert got[7:].tobytes() == want[7:].tobytes()
+
+
 def test_em_divide_is_ieee_exact(dev):
     """The EM kernel's Newton-core divide (no v_div_scale) against the compiler's IEEE double divide
     on 4.3e9 pseudo-random EM-shaped operand pairs (incl. 0/0 and 100 binades of magnitude)."""

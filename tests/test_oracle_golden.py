@@ -238,3 +238,35 @@ def test_em_cases(oracle, golden):
     for k in range(len(case["sizes"])):
         got = em_cases.updates(oracle.emMAF_update, em_cases.columns(case["L"], case["members"][k]), case["f_old"][k], 1)
         assert same(got, g["zeros_updates"][:, k]), k
+
+
+def test_score_cases(oracle, golden):
+    """The enumerated scoring terms (tests/score_cases.py; score_cases.npz by make_golden_score_cases.py): likelihood sums that are
+    subnormal, zero, negative, above 1, infinite or NaN -- glassy_cy.loglike per site into zeros and into a vector of ordinary, -inf,
+    huge, NaN and +inf starts, glassy.assignLL, and utils.partition_loglikes for P = 1, 3 and 64, NaN where the reference has NaN and
+    the same bits elsewhere.  tests/test_score_cases_cpu.py holds the inputs to what they claim."""
+    import score_cases
+    g = golden("score_cases.npz")
+    for name in score_cases.GOLDEN:
+        case, L, A, start = score_cases.golden_inputs(name)
+        assert score_cases.digest(case) == str(g[name + "_digest"])
+        n, K, m = L.shape[1] // 2, A.shape[1], L.shape[0]
+        ref = g[name + "_loglike"]
+        assert ref.shape == (n, K, m)
+        with np.errstate(all="ignore"):
+            for i in range(n):
+                for k in range(K):
+                    vec = np.zeros(m, dtype=np.float32)
+                    oracle.loglike(L, A, vec, 2, i, k)
+                    assert score_cases.same_nan(ref[i, k], vec), (name, i, k)
+                    for P in score_cases.GOLDEN_PARTS:
+                        assert score_cases.same_nan(g[name + "_parts_%d" % P][i * P:(i + 1) * P, k], oracle.partition_loglikes(vec, P)), (name, i, k, P)
+            for row, (i, k) in zip(g[name + "_started"], score_cases.GOLDEN_START_CELLS):
+                vec = start.copy()
+                oracle.loglike(L, A, vec, 2, i, k)
+                assert score_cases.same_nan(row, vec), (name, i, k)
+            assert score_cases.same_nan(g[name + "_assignLL"], oracle.assignLL(L, A.copy(), 2)), name
+        if name == "hostile":
+            assert np.isposinf(ref).any() and np.isneginf(ref).any() and np.isnan(ref).any() and (ref[np.isfinite(ref)] > 0).any()
+        else:
+            assert not np.isposinf(ref).any() and np.isneginf(ref).any() and not (ref[np.isfinite(ref)] > 0).any()

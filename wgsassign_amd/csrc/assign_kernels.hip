@@ -65,14 +65,23 @@ __device__ __forceinline__ double log_f32arg(double x, const double2 *tab, doubl
     return __builtin_fma(r * r, q, lo_) + hi_;
 }
 
-// (float)log((double)s) for any float32 s, including the special values libm defines:
-// log(+-0) = -inf, log(+inf) = +inf, log(negative) = log(NaN) = NaN.  The hardware's float32
-// log2 returns exactly those for exactly those arguments, so one v_log_f32 supplies every
-// special value and one class test selects it -- no branches in the per-term code.
+// libm's log of a float32 that is NOT a positive finite number: log(+-0) = -inf, log(+inf) = +inf, log(negative) = log(NaN) = NaN.
+// The hardware's float32 log2 returns exactly those for exactly those arguments -- with one exception: it flushes a subnormal
+// argument to a zero of its sign before it looks at it, so a NEGATIVE SUBNORMAL sum (a subnormal g0 < 0 next to g1 = 0 at a
+// frequency whose square underflows) came out as -inf where libm says NaN (tests/test_gpu_score_cases.py).  Every negative
+// argument, -inf included, is therefore replaced by -1 first: one class test (which no denormal mode touches) and one select,
+// on the paths that only sums outside (0, +inf) take.
+__device__ __forceinline__ float log_special(float s)
+{
+    return __builtin_amdgcn_logf(__builtin_isfpclass(s, 0x0004 | 0x0008 | 0x0010) ? -1.0f : s);   // -inf | -normal | -subnormal
+}
+
+// (float)log((double)s) for any float32 s, including the special values libm defines: one v_log_f32 supplies every special
+// value (log_special) and one class test selects it -- no branches in the per-term code.
 __device__ __forceinline__ float logf_of_f32(float s, const double2 *tab)
 {
     const float v = (float)log_f32arg((double)s, tab);
-    const float special = __builtin_amdgcn_logf(s);
+    const float special = log_special(s);
     return __builtin_isfpclass(s, 0x0100 | 0x0080) ? v : special;   // +normal | +subnormal
 }
 
@@ -310,7 +319,7 @@ __global__ __launch_bounds__(256, sweep_waves_per_simd(KB, NP, MODE, PER_IND)) v
         // One tile.  MASKED (only the last, partial tile of the matrix): lanes past the last SNP are given
         // g = (1, 0) and a = 0, for which the site likelihood is exactly 1 and its log exactly 0.
         // FIX = false is the hot path: log_f32arg on every sum, whatever it is; the sums that are not
-        // positive finite numbers (0 -> -inf, negative or NaN -> NaN; +inf cannot arise) are noted in
+        // positive finite numbers (0 -> -inf, negative or NaN -> NaN, +inf -> +inf: likelihoods beyond float32) are noted in
         // `plain` and the tile is visited again with FIX = true, which adds libm's special value for
         // exactly those terms.  That is exact: log_f32arg returns a FINITE value for +-0 and +inf, and
         // finite + (+-inf or NaN) is the same whatever the finite part was; for negative or NaN sums
@@ -348,7 +357,7 @@ __global__ __launch_bounds__(256, sweep_waves_per_simd(KB, NP, MODE, PER_IND)) v
                             const float s = like_sum_exact(g0d, g1d2, g2d, a_d, PER_IND ? 1.0 - a_d : oma[j]);
                             const bool fin = __builtin_isfpclass(s, FP_POS_FINITE);
                             if (FIX) {
-                                if (!fin) acc[q][h][j] += (double)__builtin_amdgcn_logf(s);
+                                if (!fin) acc[q][h][j] += (double)log_special(s);
                             } else {
                                 plain = plain && fin;
                                 acc[q][h][j] += (double)(float)log_f32arg((double)s, tab, c8);
@@ -368,7 +377,7 @@ __global__ __launch_bounds__(256, sweep_waves_per_simd(KB, NP, MODE, PER_IND)) v
             if (t + 1 < t1) fetch(t + 1, g_nxt, a_nxt);
             const bool partial = ((t + 1) << 6) > A.m;
             const bool plain = partial ? tile(t, T{}, F{}) : tile(t, F{}, F{});
-            if (MODE == WGS_MODE_EXACT && !__all(plain)) {       // rare: a likelihood sum of exactly 0, or NaN data
+            if (MODE == WGS_MODE_EXACT && !__all(plain)) {       // rare: a likelihood sum of exactly 0, NaN or hostile data
                 if (partial) tile(t, T{}, T{}); else tile(t, F{}, T{});
             }
 #pragma unroll
@@ -677,9 +686,9 @@ __global__ __launch_bounds__(256, WGS_SCORE_CODED_WAVES) void score_coded_kernel
                             const double ad = (double)a;
                             const float ssum = like_sum_exact(g0d, g1x2, g2d, ad, 1.0 - ad);
                             v = (float)log_f32arg<CODED_LOG_REP>((double)ssum, tab);
-                            // a likelihood of exactly 0, NaN data: libm's special value (v_log_f32 returns exactly -inf / NaN there); a
+                            // a likelihood of exactly 0, NaN data: libm's special value (log_special); a
                             // branch no lane of the wavefront takes on ordinary data, instead of a quarter-rate log and a select per element
-                            if (__builtin_expect(!__builtin_isfpclass(ssum, FP_POS_FINITE), 0)) v = __builtin_amdgcn_logf(ssum);
+                            if (__builtin_expect(!__builtin_isfpclass(ssum, FP_POS_FINITE), 0)) v = log_special(ssum);
                         } else {
                             v = site_ll_fast(gl.x, gl.y, g2f, a);
                         }
@@ -792,7 +801,7 @@ __global__ __launch_bounds__(256, WGS_SCORE_CODED_WAVES) void score_coded_kernel
                                         const double ad = (double)a;
                                         const float ssum = like_sum_exact(g0d, g1x2, g2d, ad, 1.0 - ad);
                                         const float plain = (float)log_f32arg<CODED_LOG_REP>((double)ssum, tab);
-                                        v = __builtin_isfpclass(ssum, FP_POS_FINITE) ? plain : __builtin_amdgcn_logf(ssum);
+                                        v = __builtin_isfpclass(ssum, FP_POS_FINITE) ? plain : log_special(ssum);
                                     } else {
                                         v = site_ll_fast(g0, g1, g2f, a);
                                     }
@@ -1009,7 +1018,7 @@ __global__ __launch_bounds__(256, 2) void chain_cand_kernel(ScoreArgs A)
                             // NaN (log_f32arg is not defined there): such a lane marks its blocks instead
                             plain = plain && __builtin_isfpclass(s, FP_POS_FINITE);
                             const float v = (float)log_f32arg((double)s, tab, c8);
-                            const float mag = -v;                               // >= 0 for every likelihood <= 1
+                            const float mag = -v;                               // >= 0 for every likelihood <= 1 (a larger one marks the block: vmax)
                             const float r = (X0[q][h][j] + mag) - X0[q][h][j];  // RN(mag / u) * u on the predicted grid
                             acc[q][h][j] += r;                                  // exact while the block stays in the binade
                             emax[q][h][j] = __builtin_fmaxf(emax[q][h][j], __builtin_fabsf(mag - r));
