@@ -55,6 +55,14 @@ int wgs_debug_reader_comp_text(wgs_reader *r, int64_t comp_bytes, int64_t text_c
  * wgs_em_rmse_chain of an EM batch. */
 int wgs_debug_rmse1d(wgs_ctx *ctx, const float *v1, const float *v2, int64_t m, double *out, int serial,
                      int *serial_blocks);
+/* n_jobs chains of m elements each at once (a, b: n_jobs x m on the host), the way a later SNP shard of a batch of fits runs them: the
+ * jobs are built with carry 0, chain_set_carry_kernel then sets carry_in[j] from a device array, and launch_rmse_chain_batch walks
+ * them.  carry_out[j]: the running float32 value after job j (NOT divided by m); serial_blocks[j]: blocks that took the literal
+ * loop.  With nblocks = ceil(m / 4096), expo ([n_jobs][nblocks], may be NULL) receives what rmse_predict_kernel predicted and cand
+ * ([n_jobs][nblocks][6], may be NULL) what rmse_candidates_kernel composed: cand[..][2 * c + p] for the biased exponent
+ * expo - 1 + c and the entry mantissa's parity p. */
+int wgs_debug_rmse_chain_batch(wgs_ctx *ctx, const float *a, const float *b, int32_t n_jobs, int64_t m, const float *carry_in,
+                               float *carry_out, int32_t *serial_blocks, int32_t *expo, int64_t *cand);
 
 /* Sweeps this EM batch has enqueued so far through each of its four sweep kernels (csrc/em_api.hip: em_enqueue_sweep):
  * counts[0] em_sweep_kernel, [1] em_sweep_group_kernel, [2] em_coded_kernel, [3] em_coded_group_kernel.  A sweep counts once

@@ -270,3 +270,17 @@ def test_score_cases(oracle, golden):
             assert np.isposinf(ref).any() and np.isneginf(ref).any() and np.isnan(ref).any() and (ref[np.isfinite(ref)] > 0).any()
         else:
             assert not np.isposinf(ref).any() and np.isneginf(ref).any() and not (ref[np.isfinite(ref)] > 0).any()
+
+
+def test_rmse_cases(oracle, golden):
+    """The enumerated convergence chains (tests/rmse_cases.py; rmse_cases.npz by make_golden_rmse_cases.py): squares of every shift and
+    remainder against the running sum, subnormal, infinite and NaN squares, sums that overflow or stay subnormal -- emMAF_cy.rmse1d of
+    every recorded pair of vectors, NaN where the reference has NaN and the same double elsewhere.  tests/test_rmse_cases_cpu.py holds
+    the inputs to what they claim."""
+    import rmse_cases
+    g = golden("rmse_cases.npz")
+    cases = rmse_cases.golden_cases()
+    assert [repr(c) for c in cases] == list(g["names"]) and [rmse_cases.digest(c) for c in cases] == list(g["digests"])
+    for c, want in zip(cases, g["rmse1d"]):
+        got = oracle.rmse1d(np.array(c.a), np.array(c.b))
+        assert got == want or (np.isnan(got) and np.isnan(want)), (c, got, want)

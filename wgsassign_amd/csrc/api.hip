@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <chrono>
 #include <string>
+#include <vector>
 
 #include "build_id.h"
 #include "common.h"
@@ -1174,6 +1175,57 @@ static int rmse1d_impl(wgs_ctx *ctx, const float *v1, const float *v2, int64_t m
     }
     res = res / (float)m;           // emMAF_cy.pyx:32
     *out = sqrt((double)res);       // emMAF_cy.pyx:33
+    return 0;
+}
+
+/* Test hook: n_jobs chains of one length through launch_rmse_chain_batch, the carries set from a device array as a later SNP
+ * shard sets them (launch_chain_set_carry), and what the predict and candidates kernels left in the workspace. */
+int wgs_debug_rmse_chain_batch(wgs_ctx *ctx, const float *a, const float *b, int32_t n_jobs, int64_t m, const float *carry_in,
+                               float *carry_out, int32_t *serial_blocks, int32_t *expo, int64_t *cand)
+{
+    WGS_REQUIRE(ctx && a && b && carry_in && carry_out && serial_blocks, "null argument");
+    WGS_REQUIRE(n_jobs > 0 && n_jobs <= 65535 && m > 0, "rmse chain batch: %d jobs of %lld elements", (int)n_jobs, (long long)m);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t nj = (size_t)n_jobs, nb = (size_t)((m + 4095) / 4096), len = nj * (size_t)m;
+    float *d = nullptr;        // [n_jobs*m a | n_jobs*m b | n_jobs carries | n_jobs results | n_jobs serial counts]
+    void *work = nullptr;
+    ChainJob *d_jobs = nullptr;
+    HIP_TRY(wgs_malloc(&d, sizeof(float) * (2 * len + 3 * nj)));
+    if (wgs_malloc(&work, rmse_chain_workspace_bytes(m) * nj) != hipSuccess || wgs_malloc(&d_jobs, sizeof(ChainJob) * nj) != hipSuccess) {
+        (void)hipFree(d);
+        (void)hipFree(work);
+        wgs_set_error("rmse chain batch: out of device memory");
+        return 1;
+    }
+    float *d_carry = d + 2 * len, *d_out = d_carry + nj;
+    int *d_serial = reinterpret_cast<int *>(d_out + nj);
+    std::vector<ChainJob> jobs(nj);
+    for (size_t j = 0; j < nj; ++j) jobs[j] = ChainJob{d + j * (size_t)m, d + len + j * (size_t)m, 0.0f};
+    // the workspace as launch_rmse_chain_batch lays it out: cand [job][block][6], then S [job][block], then expo [job][block]
+    const long long *w_cand = reinterpret_cast<const long long *>(work);
+    const int *w_expo = reinterpret_cast<const int *>(reinterpret_cast<const double *>(w_cand + nj * nb * 6) + nj * nb);
+    int rc = 0;
+    if (hipMemcpyAsync(d, a, sizeof(float) * len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(d + len, b, sizeof(float) * len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(d_carry, carry_in, sizeof(float) * nj, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemsetAsync(d_out, 0, sizeof(float) * 2 * nj, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(d_jobs, jobs.data(), sizeof(ChainJob) * nj, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = 1;
+    if (!rc) rc = launch_chain_set_carry(ctx, d_jobs, d_carry, n_jobs);
+    if (!rc) rc = launch_rmse_chain_batch(ctx, d_jobs, n_jobs, m, d_out, work, d_serial);
+    if (!rc && (hipMemcpyAsync(carry_out, d_out, sizeof(float) * nj, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipMemcpyAsync(serial_blocks, d_serial, sizeof(int) * nj, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                (expo && hipMemcpyAsync(expo, w_expo, sizeof(int) * nj * nb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
+                (cand && hipMemcpyAsync(cand, w_cand, sizeof(long long) * nj * nb * 6, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)))
+        rc = 1;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = 1;      // (`jobs` is a local; nothing may still read it)
+    (void)hipFree(d);
+    (void)hipFree(work);
+    (void)hipFree(d_jobs);
+    if (rc) {
+        wgs_set_error("rmse chain batch: device operation failed");
+        return 1;
+    }
     return 0;
 }
 
