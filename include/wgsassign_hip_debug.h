@@ -102,6 +102,18 @@ int wgs_debug_rcp_error(wgs_ctx *ctx, int exponent, double *max_rel);
 int wgs_debug_log_mismatch(wgs_ctx *ctx, uint32_t b0, uint32_t b1, uint64_t *count, uint32_t *first);
 int wgs_debug_log_values(wgs_ctx *ctx, const float *x, float *out, int64_t n, int use_libm);
 
+/* Test hooks for the two hardware steps of the float32 modes (csrc/fast_math.h; which = 0: fast_log, the natural log the scoring
+ * kernels take of a likelihood sum; 1: fast_rcp, the reciprocal the EM kernels multiply by): the values for n float32 arguments, and
+ * an exhaustive pass over the bit patterns [b0, b1) against the correctly rounded function on the device -- log_f32arg((double)x),
+ * or the IEEE double division 1.0 / (double)x:
+ *   stats[0] the largest error in float32 ulps of the true value (ulp of a value below 2^-126: 2^-149), [1] the first argument (bit
+ *            pattern) that attains it, [2] the largest error as it is, [3] its first argument -- both over the arguments for which
+ *            the result and the true value are finite and not zero (-1 and 0 where there is none);
+ *   stats[4] arguments whose result is of another class -- finite, -inf, +inf, NaN, zero -- than the true value rounded to
+ *            float32, [5] the first of them (-1: none). */
+int wgs_debug_fast_values(wgs_ctx *ctx, int which, const float *x, float *out, int64_t n);
+int wgs_debug_fast_scan(wgs_ctx *ctx, int which, uint32_t b0, uint32_t b1, double stats[6]);
+
 /* The sums of the last wgs_score_sums per chunk of 8192 sites (the addends of np.sum's running float64 total): out (NULL: only
  * *nchunks is set) receives ceil(blocks / 2) x n*K float64, out[c * n*K + i * K + k]. */
 int wgs_debug_score_chunks(wgs_score *sc, double *out, int64_t *nchunks);

@@ -13,7 +13,7 @@ Each test forces one kernel and asserts through EMBatch.sweep_paths() that exact
     em_coded_group_kernel      the codes forced, 3, 4 and 5 re-fits per slab
 the coded ones with the smallest and the largest quotient table that codes the case (8 and 64 rows).  em_cases.negative_zero_sums
 adds the one place where the SIGN of a zero quotient reaches the result: a running sum that a term has underflowed to -0.0.  The float32 EM mode
-(WGSASSIGN_EM_MODE=fast) is an opt-in with a stated deviation and stays out."""
+(WGSASSIGN_EM_MODE=fast) of the two float32-slab kernels is held on the same inputs by tests/test_gpu_fast_cases.py (tests/fast_cases.py)."""
 import math
 
 import numpy as np

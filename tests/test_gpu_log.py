@@ -100,6 +100,86 @@ def test_special_values_of_negative_and_subnormal_arguments(dev):
     assert got[7:].tobytes() == want[7:].tobytes()
 
 
+# ---- the two hardware steps of the float32 modes (csrc/fast_math.h) ------------------------------------------------------------------
+# Their error constants are measurements of the chip, recorded in tests/fast_cases.py and DESIGN section 4; the passes are exhaustive,
+# so the recorded constants carry no margin beyond rounding up to the next half ulp, and the measured maxima may not exceed them.
+def fast_values(dev, which, x):
+    lib, ctx, _lib = dev
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    _lib.check(lib.wgs_debug_fast_values(ctx.handle, which, _lib.f32p(x), _lib.f32p(out), x.shape[0]))
+    return out
+
+
+def fast_scan(dev, which, b0, b1):
+    """dict(ulps, ulps_arg, abs, abs_arg, differ, first) over the bit patterns [b0, b1) (wgs_debug_fast_scan)."""
+    lib, ctx, _lib = dev
+    st = (ctypes.c_double * 6)()
+    _lib.check(lib.wgs_debug_fast_scan(ctx.handle, which, b0, b1, st))
+    return dict(ulps=st[0], ulps_arg=int(st[1]), abs=st[2], abs_arg=int(st[3]), differ=int(st[4]), first=None if st[5] < 0 else int(st[5]))
+
+
+def test_fast_log_exhaustive(dev):
+    """fast_log over EVERY positive finite float32, subnormals included, against log_f32arg (which the tests above tie to glibc): the
+    error in float32 ulps of the true log, and no argument whose result is of another class.  The relative form holds around x = 1
+    too, so there is no absolute part."""
+    import fast_cases as fc
+    whole = fast_scan(dev, 0, 1, 0x7F800000)
+    near_one = fast_scan(dev, 0, 126 << 23, 128 << 23)
+    subnormal = fast_scan(dev, 0, 1, 0x00800000)
+    print("fast_log: %.6f ulps at 0x%08x over every positive float32; %.6f at 0x%08x over [0.5, 2); %.6f at 0x%08x over the subnormals; %d class differences" % (
+        whole["ulps"], whole["ulps_arg"], near_one["ulps"], near_one["ulps_arg"], subnormal["ulps"], subnormal["ulps_arg"], whole["differ"]))
+    assert whole["differ"] == 0 and whole["first"] is None
+    assert 0 < whole["ulps"] <= fc.FAST_LOG_REL_ULPS
+    assert max(near_one["ulps"], subnormal["ulps"]) <= whole["ulps"]
+    assert fc.FAST_LOG_REL_ULPS - 0.5 < fc.FAST_LOG_MEASURED[0] <= fc.FAST_LOG_REL_ULPS          # the record is the measurement rounded up, no more
+
+
+def test_fast_log_special_arguments(dev):
+    """+-0 -> -inf; every negative argument, subnormal, normal or -inf -> NaN; NaN -> NaN; +inf -> +inf; 1 -> +0; positive subnormals and
+    the largest finite value their finite logs within the recorded error."""
+    import fast_cases as fc
+    x = np.array([0.0, -0.0, -1e-45, -1e-40, -1.1754942e-38, -1.1754944e-38, -1.0, -3.4028235e38, -np.inf, np.nan, np.inf, 1.0,
+                  1e-45, 1e-40, 2e-40, 1.1754942e-38, 1.1754944e-38, 3.4028235e38], dtype=np.float32)
+    got = fast_values(dev, 0, x)
+    print(got.tolist())
+    assert np.isneginf(got[:2]).all() and np.isnan(got[2:10]).all() and got[10] == np.inf
+    assert got[11] == 0.0 and not np.signbit(got[11])
+    want = np.log(x[12:].astype(np.float64))
+    assert np.isfinite(got[12:]).all() and (np.abs(got[12:] - want) <= fc.FAST_LOG_REL_ULPS * fc.ulp32(want)).all(), (got[12:], want)
+    assert abs(got[14] + 91.4) < 0.05                      # a likelihood of 2e-40: -91.4, not -inf
+
+
+def test_fast_rcp_exhaustive(dev):
+    """fast_rcp = v_rcp_f32 over EVERY finite float32 of either sign against the IEEE double division: the error where both are finite
+    and not zero, and the arguments whose result is of another class -- exactly the subnormals above 2^-128 (taken for zero: +-inf)
+    and the arguments above 2^126 (a subnormal reciprocal: +-0)."""
+    import fast_cases as fc
+    for sign in (0, 0x80000000):
+        whole = fast_scan(dev, 1, sign, sign + 0x7F800000)
+        print("fast_rcp, sign bit %d: %.6f ulps at 0x%08x; %d class differences, first 0x%08x" % (sign >> 31, whole["ulps"], whole["ulps_arg"], whole["differ"], whole["first"]))
+        assert 0 < whole["ulps"] <= fc.FAST_RCP_REL_ULPS
+        assert (whole["differ"], whole["first"]) == (fc.FAST_RCP_CLASS_DIFFERENCES[0], sign + fc.FAST_RCP_CLASS_DIFFERENCES[1])
+        assert fast_scan(dev, 1, sign, sign + 0x00200001)["differ"] == 0                         # +-0 and |x| <= 2^-128: +-inf either way
+        assert fast_scan(dev, 1, sign + 0x00200001, sign + 0x00800000)["differ"] == 0x00800000 - 0x00200001
+        assert fast_scan(dev, 1, sign + 0x00800000, sign + 0x7E800001)["differ"] == 0            # normal arguments up to 2^126
+        assert fast_scan(dev, 1, sign + 0x7E800001, sign + 0x7F800000)["differ"] == 0x7F800000 - 0x7E800001
+    assert fc.FAST_RCP_REL_ULPS - 0.5 < fc.FAST_RCP_MEASURED[0] <= fc.FAST_RCP_REL_ULPS
+
+
+def test_fast_rcp_special_arguments(dev):
+    x = np.array([0.0, -0.0, 1e-45, -1e-45, 1.1754942e-38, -1.1754942e-38, np.inf, -np.inf, np.nan, 3.4028235e38, -3.4028235e38,
+                  1.1754944e-38, -1.1754944e-38, 2.0 ** 126, 1.0, -1.0, 3.0], dtype=np.float32)
+    got = fast_values(dev, 1, x)
+    print(got.tolist())
+    assert got[0] == np.inf and got[1] == -np.inf
+    assert got[2] == np.inf and got[3] == -np.inf and got[4] == np.inf and got[5] == -np.inf       # subnormals of either sign: a zero of their sign
+    assert got[6] == 0.0 and not np.signbit(got[6]) and got[7] == 0.0 and np.signbit(got[7]) and np.isnan(got[8])
+    assert got[9] == 0.0 and not np.signbit(got[9]) and got[10] == 0.0 and np.signbit(got[10])     # a subnormal reciprocal: a zero of its sign
+    assert got[11] == np.float32(2.0 ** 126) and got[12] == -np.float32(2.0 ** 126) and got[13] == np.float32(2.0 ** -126)
+    assert got[14] == 1.0 and got[15] == -1.0 and abs(float(got[16]) - 1 / 3) <= 2.0 ** -25
+
+
 def test_em_divide_is_ieee_exact(dev):
     """The EM kernel's Newton-core divide (no v_div_scale) against the compiler's IEEE double divide
     on 4.3e9 pseudo-random EM-shaped operand pairs (incl. 0/0 and 100 binades of magnitude)."""

@@ -18,7 +18,8 @@ per wave, this table and these parts ran:
     score_coded_kernel      float and float64 tables of 16 SNPs, tables of 8 and of 4, parts 1, 5 and 16, SNPs left uncoded
     chain_cand / chain_walk parts_exact(P) against np.add.at and the literal kernel, site0, carries, per-individual columns
     loglike_site_kernel     wgs_loglike into zeros and into non-zero vectors
-The float32 mode (MODE_FAST, WGSASSIGN_PARTS=fast) is an opt-in with a stated deviation and stays out."""
+The float32 mode (MODE_FAST) of the same kernels is held on the same inputs, bit for bit to a float32 restatement and by a derived bound
+to the real-arithmetic term, by tests/test_gpu_fast_cases.py (tests/fast_cases.py)."""
 import ctypes
 import functools
 import math

@@ -157,7 +157,9 @@ SIGNATURES = {
     "wgs_debug_div_mismatch_signed": (c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "wgs_debug_log_mismatch": (c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),
     "wgs_debug_log_values": (c_int, [c_vp, c_f32p, c_f32p, c_i64, c_int]),
-    "wgs_assign_last_ms": (c_int, [c_vp, c_f32p]),
+    "wgs_debug_fast_values": (c_int, [c_vp, c_int, c_f32p, c_f32p, c_i64]),
+    "wgs_debug_fast_scan": (c_int, [c_vp, c_int, ctypes.c_uint32, ctypes.c_uint32, c_f64p]),
+    "wgs_assign_last_ms":(c_int, [c_vp, c_f32p]),
     "wgs_score_create": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_i32, c_i32, ctypes.POINTER(c_vp)]),
     "wgs_score_destroy": (None, [c_vp]),
     "wgs_score_sums": (c_int, [c_vp, c_int, c_f64p]),

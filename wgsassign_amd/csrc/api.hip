@@ -1102,6 +1102,52 @@ int wgs_debug_log_values(wgs_ctx *ctx, const float *x, float *out, int64_t n, in
     return rc;
 }
 
+int wgs_debug_fast_values(wgs_ctx *ctx, int which, const float *x, float *out, int64_t n)
+{
+    WGS_REQUIRE(ctx && x && out && n >= 0 && (which == 0 || which == 1), "bad argument");
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    float *d = nullptr;
+    HIP_TRY(wgs_malloc(&d, sizeof(float) * 2 * (size_t)n));
+    int rc = 0;
+    if (hipMemcpyAsync(d, x, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = 1;
+    if (!rc) rc = launch_fast_values(ctx, which, d, d + n, n);
+    if (!rc && (hipMemcpyAsync(out, d + n, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipStreamSynchronize(ctx->stream) != hipSuccess))
+        rc = 1;
+    (void)hipFree(d);
+    if (rc) wgs_set_error("fast values: device operation failed");
+    return rc;
+}
+
+int wgs_debug_fast_scan(wgs_ctx *ctx, int which, uint32_t b0, uint32_t b1, double stats[6])
+{
+    WGS_REQUIRE(ctx && stats && (which == 0 || which == 1) && b0 <= b1, "bad argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    FastScanRecord *d = nullptr;
+    HIP_TRY(wgs_malloc(&d, sizeof(FastScanRecord) * WGS_FAST_SCAN_RECORDS));
+    std::vector<FastScanRecord> h(WGS_FAST_SCAN_RECORDS);
+    int rc = launch_fast_scan(ctx, which, b0, b1, d);
+    if (!rc && (hipMemcpyAsync(h.data(), d, sizeof(FastScanRecord) * h.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipStreamSynchronize(ctx->stream) != hipSuccess)) {
+        wgs_set_error("fast scan: device operation failed");
+        rc = 1;
+    }
+    (void)hipFree(d);
+    if (rc) return rc;
+    FastScanRecord t = h[0];
+    for (size_t i = 1; i < h.size(); ++i) {
+        const FastScanRecord &r = h[i];
+        if (r.rel > t.rel || (r.rel == t.rel && r.rel_arg < t.rel_arg)) t.rel = r.rel, t.rel_arg = r.rel_arg;
+        if (r.abs > t.abs || (r.abs == t.abs && r.abs_arg < t.abs_arg)) t.abs = r.abs, t.abs_arg = r.abs_arg;
+        t.bad += r.bad;
+        if (r.bad_first < t.bad_first) t.bad_first = r.bad_first;
+    }
+    stats[0] = t.rel, stats[1] = (double)t.rel_arg, stats[2] = t.abs, stats[3] = (double)t.abs_arg;
+    stats[4] = (double)t.bad, stats[5] = t.bad ? (double)t.bad_first : -1.0;
+    return 0;
+}
+
 /* ------------------------------------------------------------------ thin mirrors */
 
 int wgs_emmaf_update(wgs_ctx *ctx, const float *L, int64_t m, int64_t n, float *f, int mode)

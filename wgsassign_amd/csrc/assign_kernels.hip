@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "fast_math.h"
 #include "log_table.h"
 
 namespace {
@@ -109,13 +110,19 @@ __device__ __forceinline__ float site_ll_exact(double g0d, double g1d, double g2
     return logf_of_f32((like0 + like1) + like2, tab);
 }
 
-__device__ __forceinline__ float site_ll_fast(float g0, float g1, float g2, float a)
+// One float32 term: IEEE float32 operations in this order (no contraction), then fast_log (fast_math.h).  g2 is g2_rounded(g0, g1).
+__device__ __forceinline__ float like_sum_fast(float g0, float g1, float g2, float a)
 {
     const float oma = 1.0f - a;
     const float like0 = g0 * oma * oma;
     const float like1 = g1 * 2.0f * oma * a;
     const float like2 = g2 * a * a;
-    return __builtin_amdgcn_logf((like0 + like1) + like2) * 0.69314718055994530942f;   // v_log_f32 (log2) * ln 2
+    return (like0 + like1) + like2;
+}
+
+__device__ __forceinline__ float site_ll_fast(float g0, float g1, float g2, float a)
+{
+    return fast_log(like_sum_fast(g0, g1, g2, a));
 }
 
 typedef const float __attribute__((address_space(1))) *gf32_ptr;
@@ -168,8 +175,8 @@ __global__ __launch_bounds__(256) void assign_kernel(AssignArgs A)
                             va = site_ll_exact(a0, a1, a2, fa, tab);
                             vb = site_ll_exact(b0, b1, b2, fb, tab);
                         } else {
-                            va = site_ll_fast(g.x, g.y, (1.0f - g.x) - g.y, fa);
-                            vb = site_ll_fast(g.z, g.w, (1.0f - g.z) - g.w, fb);
+                            va = site_ll_fast(g.x, g.y, (float)a2, fa);
+                            vb = site_ll_fast(g.z, g.w, (float)b2, fb);
                         }
                         acc_a[j] += (double)va;
                         acc_b[j] += (double)vb;
@@ -346,7 +353,28 @@ __global__ __launch_bounds__(256, sweep_waves_per_simd(KB, NP, MODE, PER_IND)) v
                 for (int h = 0; h < 2; ++h) {
                     const double g0d = (double)gl[h][0], g1d = (double)gl[h][1];
                     const double g1d2 = g1d * 2.0, g2d = (1.0 - g0d) - g1d;
-                    const float g2f = (1.0f - gl[h][0]) - gl[h][1];
+                    const float g2f = (float)g2d;           // the float32 mode's g2: the double one, rounded once (g2_rounded)
+                    if (MODE != WGS_MODE_EXACT) {
+                        // float32 mode: the KB sums first.  fast_log scales an argument below 2^-126 -- a subnormal, zero or negative
+                        // sum, which ordinary data has next to never -- so its five extra instructions per term are spent only where
+                        // some lane of the wavefront holds such a sum; everywhere else fast_log_normal has the same bits without them
+                        float sf[KB];
+                        bool small = false;
+#pragma unroll
+                        for (int j = 0; j < KB; ++j) {
+                            const float a = PER_IND ? (live ? a_cur[(q * 2 + h) * KB + j] : 0.0f) : af[j];
+                            sf[j] = like_sum_fast(gl[h][0], gl[h][1], g2f, a);
+                            small = small || sf[j] < 0x1p-126f;
+                        }
+                        if (__builtin_expect(__any(small), 0)) {
+#pragma unroll
+                            for (int j = 0; j < KB; ++j) acc[q][h][j] += (double)fast_log(sf[j]);
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < KB; ++j) acc[q][h][j] += (double)fast_log_normal(sf[j]);
+                        }
+                        continue;
+                    }
                     // all KB slots are computed (slots past K repeat population K-1 and are dropped in the
                     // epilogue): the tile body stays one basic block the scheduler can interleave
 #pragma unroll
@@ -362,8 +390,6 @@ __global__ __launch_bounds__(256, sweep_waves_per_simd(KB, NP, MODE, PER_IND)) v
                                 plain = plain && fin;
                                 acc[q][h][j] += (double)(float)log_f32arg((double)s, tab, c8);
                             }
-                        } else {
-                            acc[q][h][j] += (double)site_ll_fast(gl[h][0], gl[h][1], g2f, a);
                         }
                     }
                 }
@@ -675,7 +701,7 @@ __global__ __launch_bounds__(256, WGS_SCORE_CODED_WAVES) void score_coded_kernel
                 const float2 gl = make_float2(stage_x[r], stage_y[r]);
                 const double g0d = (double)gl.x, g1d = (double)gl.y;
                 const double g1x2 = g1d * 2.0, g2d = (1.0 - g0d) - g1d;
-                const float g2f = (1.0f - gl.x) - gl.y;
+                const float g2f = (float)g2d;
 #pragma unroll
                 for (int kq = 0; kq < KG; ++kq) {
                     const int k = half * KG + kq;
@@ -792,7 +818,7 @@ __global__ __launch_bounds__(256, WGS_SCORE_CODED_WAVES) void score_coded_kernel
                                 const float g0 = hh ? g.z : g.x, g1 = hh ? g.w : g.y;
                                 const double g0d = (double)g0, g1d = (double)g1;
                                 const double g1x2 = g1d * 2.0, g2d = (1.0 - g0d) - g1d;
-                                const float g2f = (1.0f - g0) - g1;
+                                const float g2f = (float)g2d;
 #pragma unroll
                                 for (int k = 0; k < KB; ++k) {
                                     const float a = P.aval[j][k];
@@ -1234,7 +1260,7 @@ __global__ void loglike_site_kernel(const float2 *__restrict__ g, const float *_
             l = !(sum >= 0.0f) ? (double)__builtin_nanf("") : l;
             vec[s] = (float)((double)vec[s] + l);
         } else {
-            vec[s] = vec[s] + site_ll_fast(gg.x, gg.y, (1.0f - gg.x) - gg.y, av);
+            vec[s] = vec[s] + site_ll_fast(gg.x, gg.y, g2_rounded(gg.x, gg.y), av);
         }
     }
 }
@@ -1264,6 +1290,66 @@ __global__ void log_values_kernel(const float *x, float *out, int64_t n, int use
     const double2 *tab = load_log_table(tab_lds);
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     for (; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = use_libm ? (float)log((double)x[i]) : logf_of_f32(x[i], tab);
+}
+
+// Test hooks for the float32 modes' primitives (fast_math.h).  which = 0: fast_log, 1: fast_rcp.
+__global__ void fast_values_kernel(int which, const float *x, float *out, int64_t n)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = which == 0 ? fast_log(x[i]) : fast_rcp(x[i]);
+}
+
+// finite non-zero 0 | -inf 1 | +inf 2 | NaN 3 | zero 4
+__device__ __forceinline__ int value_class(double v)
+{
+    return v != v ? 3 : (v == 0.0 ? 4 : (__builtin_isinf(v) ? (v < 0.0 ? 1 : 2) : 0));
+}
+
+// Every float32 bit pattern of [b0, b1) against the correctly rounded function on the device: log_f32arg((double)x) (tied to glibc
+// for every positive float32 by tests/test_gpu_log.py) or the IEEE double division 1.0 / (double)x.  Where both are finite and not
+// zero the error counts, in float32 ulps of the true value (ulp = 2^(exponent - 23), no smaller than 2^-149) and as it is; where
+// their classes differ the argument counts.  One record per wavefront, reduced by the host (wgs_debug_fast_scan).
+__global__ __launch_bounds__(256) void fast_scan_kernel(int which, unsigned int b0, unsigned int b1, FastScanRecord *out)
+{
+    __shared__ double2 tab_lds[WGS_LOG_N * WGS_LOG_REP];
+    const double2 *tab = load_log_table(tab_lds);
+    FastScanRecord r;
+    r.rel = r.abs = -1.0;
+    r.rel_arg = r.abs_arg = 0;
+    r.bad = 0;
+    r.bad_first = 0xFFFFFFFFu;
+    for (unsigned long long b = (unsigned long long)b0 + blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; b < b1;
+         b += (unsigned long long)gridDim.x * blockDim.x) {
+        const float x = __uint_as_float((unsigned int)b);
+        const double got = (double)(which == 0 ? fast_log(x) : fast_rcp(x));
+        const double want = which == 0 ? log_f32arg((double)x, tab) : 1.0 / (double)x;
+        // (the correctly rounded float32 decides the class of the true value: a reciprocal below the subnormals is a zero)
+        const int cg = value_class(got), cw = value_class((double)(float)want);
+        if (cg != cw) {
+            ++r.bad;
+            if ((unsigned int)b < r.bad_first) r.bad_first = (unsigned int)b;
+        } else if (cg == 0) {
+            const double err = __builtin_fabs(got - want);
+            int e;
+            (void)__builtin_frexp(want, &e);                      // |want| = f * 2^e, f in [0.5, 1): exponent e - 1
+            const double ulps = __builtin_ldexp(err, -((e - 1 < -126 ? -126 : e - 1) - 23));
+            if (ulps > r.rel) r.rel = ulps, r.rel_arg = (unsigned int)b;
+            if (err > r.abs) r.abs = err, r.abs_arg = (unsigned int)b;
+        }
+    }
+    // (a lane's arguments ascend, so its record holds the first argument of each maximum; ties between lanes go to the smaller one)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double rel = __shfl_down(r.rel, off, 64), ab = __shfl_down(r.abs, off, 64);
+        const unsigned int rel_arg = __shfl_down(r.rel_arg, off, 64), abs_arg = __shfl_down(r.abs_arg, off, 64);
+        const unsigned long long bad = __shfl_down(r.bad, off, 64);
+        const unsigned int bad_first = __shfl_down(r.bad_first, off, 64);
+        if (rel > r.rel || (rel == r.rel && rel_arg < r.rel_arg)) r.rel = rel, r.rel_arg = rel_arg;
+        if (ab > r.abs || (ab == r.abs && abs_arg < r.abs_arg)) r.abs = ab, r.abs_arg = abs_arg;
+        r.bad += bad;
+        if (bad_first < r.bad_first) r.bad_first = bad_first;
+    }
+    if ((threadIdx.x & 63) == 0) out[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = r;
 }
 
 // One compile-time dispatcher for every kernel family of this file: the launchers receive what the plan decided (common.h: ScorePlan)
@@ -1315,6 +1401,21 @@ int launch_log_values(wgs_ctx *ctx, const float *d_x, float *d_out, int64_t n, i
 {
     if (ensure_log_table(ctx)) return 1;
     hipLaunchKernelGGL(log_values_kernel, dim3(1024), dim3(256), 0, ctx->stream, d_x, d_out, n, use_libm);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_fast_values(wgs_ctx *ctx, int which, const float *d_x, float *d_out, int64_t n)
+{
+    hipLaunchKernelGGL(fast_values_kernel, dim3(1024), dim3(256), 0, ctx->stream, which, d_x, d_out, n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_fast_scan(wgs_ctx *ctx, int which, unsigned int b0, unsigned int b1, FastScanRecord *d_out)
+{
+    if (ensure_log_table(ctx)) return 1;
+    hipLaunchKernelGGL(fast_scan_kernel, dim3(WGS_FAST_SCAN_RECORDS / 4), dim3(256), 0, ctx->stream, which, b0, b1, d_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

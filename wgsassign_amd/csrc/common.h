@@ -490,6 +490,17 @@ int launch_chain_walk(wgs_ctx *ctx, const WalkArgs &w);
 int launch_log_mismatch(wgs_ctx *ctx, unsigned int b0, unsigned int b1, unsigned long long *d_count, unsigned int *d_first);
 int launch_log_values(wgs_ctx *ctx, const float *d_x, float *d_out, int64_t n, int use_libm);
 int launch_loglike_site(wgs_ctx *ctx, const float2 *g, const float *a, float *vec, int64_t m, int mode);
+// Test hooks for the float32 modes' primitives (fast_math.h; which = 0: fast_log, 1: fast_rcp): their values, and what one
+// wavefront found on its share of a range of bit patterns (fast_scan_kernel; wgs_debug_fast_scan reduces the records).
+struct FastScanRecord {
+    double rel, abs;               // largest error in float32 ulps of the true value / as it is; -1: nothing compared
+    unsigned int rel_arg, abs_arg; // the first argument (bit pattern) that attains each
+    unsigned long long bad;        // arguments whose result is of another class than the correctly rounded one
+    unsigned int bad_first, pad;
+};
+constexpr int WGS_FAST_SCAN_RECORDS = 4096;
+int launch_fast_values(wgs_ctx *ctx, int which, const float *d_x, float *d_out, int64_t n);
+int launch_fast_scan(wgs_ctx *ctx, int which, unsigned int b0, unsigned int b1, FastScanRecord *d_out);   // d_out[WGS_FAST_SCAN_RECORDS]
 
 int launch_scatter_rows(wgs_beagle *b, const float *d_rows, int64_t row0, int64_t nrows);
 int launch_gather_rows(wgs_beagle *b, float *d_rows, int64_t row0, int64_t nrows);

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "fast_math.h"
 
 namespace {
 
@@ -120,15 +121,21 @@ __device__ __forceinline__ void term_exact(float g0, float g1, const SnpState &s
     term_exact_shared<FIXUP>(g0d, g1d, (1.0 - g0d) - g1d, st, tmp, ok);
 }
 
-// Fast mode: the same expression evaluated in float32 (one reciprocal), same accumulation order.
-__device__ __forceinline__ void term_fast(float g0, float g1, const SnpState &st, float &tmp)
+// Fast mode: the same expression evaluated in float32 (one reciprocal), same accumulation order: IEEE float32 operations in this
+// order (no contraction) around fast_rcp (fast_math.h).  g2 = g2_rounded(g0, g1): formed as the reference forms it, once per (SNP,
+// individual).  v_rcp_f32 takes a subnormal argument for zero, so a doubled sum below 2^-126 in magnitude is scaled by 2^32, and the
+// numerator with it -- both exact, the quotient unchanged: a term whose sum is a subnormal float32 (1e-40) keeps its finite quotient
+// instead of +-inf (tests/test_gpu_fast_cases.py).  A sum of zero still gives x/0 = +-inf and 0/0 = NaN.
+__device__ __forceinline__ void term_fast(float g0, float g1, float g2, const SnpState &st, float &tmp)
 {
     const float p0 = g0 * st.omff * st.omff;
     const float p1 = g1 * st.ff2 * st.omff;
-    const float p2 = ((1.0f - g0) - g1) * st.ff * st.ff;
+    const float p2 = g2 * st.ff * st.ff;
     const float s = (p0 + p1) + p2;
     const float num = p1 + 2.0f * p2;
-    tmp = tmp + num * __builtin_amdgcn_rcpf(2.0f * s);
+    const float d = 2.0f * s;
+    const float k = __builtin_fabsf(d) < 0x1p-126f ? 0x1p32f : 1.0f;
+    tmp = tmp + (num * k) * fast_rcp(d * k);
 }
 
 // One fit per wavefront, nontemporal slab loads (each byte is used once: fits of different populations; fits that
@@ -202,8 +209,8 @@ __global__ __launch_bounds__(WAVES * 64) void em_sweep_kernel(const FitDesc *__r
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const f4 v = cur[u];
-                    term_fast(v.x, v.y, st, tmp);
-                    term_fast(v.z, v.w, st, tmp);
+                    term_fast(v.x, v.y, g2_rounded(v.x, v.y), st, tmp);
+                    term_fast(v.z, v.w, g2_rounded(v.z, v.w), st, tmp);
                 }
             }
         } else {
@@ -212,10 +219,10 @@ __global__ __launch_bounds__(WAVES * 64) void em_sweep_kernel(const FitDesc *__r
                 const f4 v = cur[u];
                 const int ia = 2 * (p0 + u), ib = ia + 1;
                 if (ia < fd.ncols && ia != fd.skip) {
-                    if (MODE == WGS_MODE_EXACT) term_exact<true>(v.x, v.y, st, tmp, dummy_ok); else term_fast(v.x, v.y, st, tmp);
+                    if (MODE == WGS_MODE_EXACT) term_exact<true>(v.x, v.y, st, tmp, dummy_ok); else term_fast(v.x, v.y, g2_rounded(v.x, v.y), st, tmp);
                 }
                 if (ib < fd.ncols && ib != fd.skip) {
-                    if (MODE == WGS_MODE_EXACT) term_exact<true>(v.z, v.w, st, tmp, dummy_ok); else term_fast(v.z, v.w, st, tmp);
+                    if (MODE == WGS_MODE_EXACT) term_exact<true>(v.z, v.w, st, tmp, dummy_ok); else term_fast(v.z, v.w, g2_rounded(v.z, v.w), st, tmp);
                 }
             }
         }
@@ -301,9 +308,10 @@ __global__ __launch_bounds__(WAVES * 64) void em_sweep_group_kernel(const FitDes
             for (int f = 0; f < FG; ++f)
                 if (on[f] && (!checked || col != fd[f].skip)) term_exact_shared<true>(g0d, g1d, g2d, st[f], tmp[f], ok);
         } else {
+            const float g2 = g2_rounded(g0, g1);
 #pragma unroll
             for (int f = 0; f < FG; ++f)
-                if (on[f] && (!checked || col != fd[f].skip)) term_fast(g0, g1, st[f], tmp[f]);
+                if (on[f] && (!checked || col != fd[f].skip)) term_fast(g0, g1, g2, st[f], tmp[f]);
         }
     };
     for (int p0 = 0; p0 < npairs; p0 += U) {
