@@ -19,7 +19,9 @@ extern "C" {
  *                                     2 s): which sweep of a fit finds the codes is then decided by a count, not by a race
  *   em_fuse_without_agreement         wgs_em_fit runs two iterations per sweep whenever THIS rank can, without the ranks' agreement
  *                                     (replays the defect of commit 807a461: the collectives' tags must catch it)
- *   em_coded_extra_lds                bytes of LDS em_coded_kernel requests beyond its table (occupancy experiment) */
+ *   em_coded_extra_lds                bytes of LDS em_coded_kernel requests beyond its table (occupancy experiment)
+ *   staging_bytes                     size of the device buffer wgs_beagle_upload_rows / wgs_beagle_download_rows stage their rows through
+ *                                     (0 = the 256 MB of the product: their loops then run once for anything a test can afford) */
 int wgs_debug_hook(const char *name, int64_t value);
 
 /* The literal one-lane-per-chain kernel behind wgs_assign_parts_exact, whatever P. */
@@ -113,6 +115,15 @@ int wgs_debug_log_values(wgs_ctx *ctx, const float *x, float *out, int64_t n, in
  *            float32, [5] the first of them (-1: none). */
 int wgs_debug_fast_values(wgs_ctx *ctx, int which, const float *x, float *out, int64_t n);
 int wgs_debug_fast_scan(wgs_ctx *ctx, int which, uint32_t b0, uint32_t b1, double stats[6]);
+
+/* Test hook for the one step of the synthetic generators (csrc/beagle_kernels.hip) that goes through the device math library: the
+ * population frequency pop_freq (cospif, logf, sqrtf) of the m global sites site0 .. site0 + m - 1 of one group, as synth_kernel and
+ * synth_quality_kernel take it (the same device function), and the expf(-depth) their Poisson inversion starts from.  Everything else
+ * of the generators is plain IEEE arithmetic, which tests/synth_twin.py restates exactly from these two. */
+int wgs_debug_synth_freq(wgs_ctx *ctx, uint64_t seed, int64_t site0, int64_t m, int32_t group, double depth, float *p_out, float *cdf0_out);
+
+/* The m values at wgs_afset_col_dev(a, col), copied to the host on the context's stream: what a kernel handed that pointer reads. */
+int wgs_debug_afset_col(wgs_afset *a, int32_t col, float *out);
 
 /* The sums of the last wgs_score_sums per chunk of 8192 sites (the addends of np.sum's running float64 total): out (NULL: only
  * *nchunks is set) receives ceil(blocks / 2) x n*K float64, out[c * n*K + i * K + k]. */

@@ -6,7 +6,8 @@ normalised, rounded to 6 decimals (what ANGSD writes as text) and cast to float3
 as (g0, g1) pairs per (SNP, individual) exactly like reader_cy.pyx:71-77 lays them out.
 
 This is test infrastructure (NumPy); the at-scale generator used by bench.py runs on the
-device (wgsassign_amd/csrc/synth.hip).
+device (wgsassign_amd/csrc/beagle_kernels.hip: synth_kernel, synth_quality_kernel).  This file is the twin of that generator's
+MODEL, with NumPy's random stream; tests/synth_twin.py is the twin of its BITS, Philox stream included.
 """
 import hashlib
 import struct

@@ -158,6 +158,8 @@ SIGNATURES = {
     "wgs_debug_log_mismatch": (c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),
     "wgs_debug_log_values": (c_int, [c_vp, c_f32p, c_f32p, c_i64, c_int]),
     "wgs_debug_fast_values": (c_int, [c_vp, c_int, c_f32p, c_f32p, c_i64]),
+    "wgs_debug_synth_freq": (c_int, [c_vp, ctypes.c_uint64, c_i64, c_i64, c_i32, ctypes.c_double, c_f32p, c_f32p]),
+    "wgs_debug_afset_col": (c_int, [c_vp, c_i32, c_f32p]),
     "wgs_debug_fast_scan": (c_int, [c_vp, c_int, ctypes.c_uint32, ctypes.c_uint32, c_f64p]),
     "wgs_assign_last_ms":(c_int, [c_vp, c_f32p]),
     "wgs_score_create": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_i32, c_i32, ctypes.POINTER(c_vp)]),

@@ -91,7 +91,7 @@ void wgs_live_destroy_children(void *parent)
 extern "C" int wgs_debug_hook(const char *name, int64_t value)
 {
     WGS_REQUIRE(name, "null argument");
-    static const char *known[] = {"codes_alloc_delay_ms", "codes_alloc_release_after_sweeps", "em_fuse_without_agreement", "em_coded_extra_lds"};
+    static const char *known[] = {"codes_alloc_delay_ms", "codes_alloc_release_after_sweeps", "em_fuse_without_agreement", "em_coded_extra_lds", "staging_bytes"};
     bool ok = false;
     for (const char *k : known) ok = ok || strcmp(k, name) == 0;
     WGS_REQUIRE(ok, "unknown test hook '%s'", name);
@@ -474,7 +474,8 @@ int wgs_em_stream_move_window(wgs_em *em, int64_t site0, int64_t rows)
 static int64_t staging_rows(const wgs_beagle *b, int64_t nrows)
 {
     const int64_t row_bytes = b->n * 2 * (int64_t)sizeof(float);
-    int64_t r = (256ll << 20) / row_bytes;
+    const int64_t hook = wgs_hook("staging_bytes");              // (test hook: the loops below run more than once on a small matrix)
+    int64_t r = (hook > 0 ? hook : (256ll << 20)) / row_bytes;
     if (r < 1) r = 1;
     return std::min(r, nrows);
 }
@@ -546,8 +547,7 @@ int wgs_beagle_synth_quality(wgs_beagle *b, uint64_t seed, double depth, int32_t
 {
     WGS_REQUIRE(b, "null argument");
     HIP_TRY(hipSetDevice(b->ctx->device));
-    wgs_beagle_drop_codes(b);
-    return launch_synth_quality(b, seed, depth, n_bins, quals, probs);
+    return launch_synth_quality(b, seed, depth, n_bins, quals, probs);      // (drops the class codes once it has accepted the bins)
 }
 
 /* ------------------------------------------------------------------ allele-frequency sets */
@@ -1100,6 +1100,33 @@ int wgs_debug_log_values(wgs_ctx *ctx, const float *x, float *out, int64_t n, in
     (void)hipFree(d);
     if (rc) wgs_set_error("log values: device operation failed");
     return rc;
+}
+
+int wgs_debug_synth_freq(wgs_ctx *ctx, uint64_t seed, int64_t site0, int64_t m, int32_t group, double depth, float *p_out, float *cdf0_out)
+{
+    WGS_REQUIRE(ctx && p_out && cdf0_out && m > 0 && site0 >= 0 && group >= 0, "bad argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    float *d = nullptr;
+    HIP_TRY(wgs_malloc(&d, sizeof(float) * ((size_t)m + 1)));
+    int rc = launch_synth_freq(ctx, seed, site0, m, group, depth, d, d + m);
+    if (!rc && (hipMemcpyAsync(p_out, d, sizeof(float) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipMemcpyAsync(cdf0_out, d + m, sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipStreamSynchronize(ctx->stream) != hipSuccess))
+        rc = 1;
+    (void)hipFree(d);
+    if (rc) wgs_set_error("synth freq: device operation failed");
+    return rc;
+}
+
+int wgs_debug_afset_col(wgs_afset *a, int32_t col, float *out)
+{
+    WGS_REQUIRE(a && out, "null argument");
+    const float *d = wgs_afset_col_dev(a, col);
+    WGS_REQUIRE(d, "column %d outside 0..%d", (int)col, (int)a->K - 1);
+    HIP_TRY(hipSetDevice(a->ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, d, sizeof(float) * (size_t)a->m, hipMemcpyDeviceToHost, a->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(a->ctx->stream));
+    return 0;
 }
 
 int wgs_debug_fast_values(wgs_ctx *ctx, int which, const float *x, float *out, int64_t n)

@@ -90,6 +90,8 @@ __device__ __forceinline__ float pop_freq(uint64_t seed, int64_t gsnp, int g)
     float p = anc + 0.08f * z;
     return fminf(fmaxf(p, 0.01f), 0.99f);
 }
+// P(depth = 0), where both generators start their Poisson inversion.
+__device__ __forceinline__ float synth_cdf0(float depth) { return expf(-depth); }
 
 // (g0, g1) of one (SNP, individual): genotype ~ Binomial(2, p); depth ~ Poisson(depth)
 // truncated at 15; alt reads ~ Binomial(depth, {e, 1/2, 1-e}[g]); GL_g ∝ P(reads | g), normalised,
@@ -167,7 +169,7 @@ __global__ void synth_quality_kernel(float4 *__restrict__ slab, int64_t m, int n
     const int64_t total = ((m + 63) / 64) * npairs * 64;
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const float cdf0 = expf(-depth);
+    const float cdf0 = synth_cdf0(depth);
     for (; e < total; e += stride) {
         const int lane = (int)(e & 63);
         const int64_t tp = e >> 6;
@@ -195,7 +197,7 @@ __global__ void synth_kernel(float4 *__restrict__ slab, int64_t m, int npairs, i
     const int64_t total = ((m + 63) / 64) * npairs * 64;
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const float cdf0 = expf(-depth);
+    const float cdf0 = synth_cdf0(depth);
     for (; e < total; e += stride) {
         const int lane = (int)(e & 63);
         const int64_t tp = e >> 6;
@@ -213,6 +215,17 @@ __global__ void synth_kernel(float4 *__restrict__ slab, int64_t m, int npairs, i
         }
         slab[e] = out;
     }
+}
+
+// Test hook (wgs_debug_synth_freq): the two steps of the generators that go through the device math library, as the kernels above
+// take them -- pop_freq of m consecutive global sites of one group, and synth_cdf0.
+__global__ void synth_freq_kernel(float *__restrict__ p_out, float *__restrict__ cdf0_out, int64_t m, int group, int64_t site0, uint64_t seed,
+                                  float depth)
+{
+    int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    if (s == 0) *cdf0_out = synth_cdf0(depth);
+    for (; s < m; s += stride) p_out[s] = pop_freq(seed, site0 + s, group);
 }
 
 inline unsigned grid_for(int64_t total)
@@ -271,6 +284,7 @@ int launch_synth_quality(wgs_beagle *b, uint64_t seed, double depth, int nq, con
         qb.e[i] = i < nq ? (float)pow(10.0, -quals[i] / 10.0) : 0.0f;
         qb.cdf[i] = i < nq ? (float)run : 1.0f;
     }
+    wgs_beagle_drop_codes(b);                        // the matrix changes from here on; a refusal above leaves it and its codes alone
     for (int g = 0; g < b->n_groups; ++g) {
         Slab &sl = b->slabs[g];
         if (sl.ncols == 0) continue;
@@ -279,6 +293,13 @@ int launch_synth_quality(wgs_beagle *b, uint64_t seed, double depth, int nq, con
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    return 0;
+}
+
+int launch_synth_freq(wgs_ctx *ctx, uint64_t seed, int64_t site0, int64_t m, int group, double depth, float *d_p, float *d_cdf0)
+{
+    hipLaunchKernelGGL(synth_freq_kernel, dim3(grid_for(m)), dim3(256), 0, ctx->stream, d_p, d_cdf0, m, group, site0, seed, (float)depth);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -506,5 +506,6 @@ int launch_scatter_rows(wgs_beagle *b, const float *d_rows, int64_t row0, int64_
 int launch_gather_rows(wgs_beagle *b, float *d_rows, int64_t row0, int64_t nrows);
 int launch_synth(wgs_beagle *b, uint64_t seed, double depth);
 int launch_synth_quality(wgs_beagle *b, uint64_t seed, double depth, int nq, const double *quals, const double *probs);
+int launch_synth_freq(wgs_ctx *ctx, uint64_t seed, int64_t site0, int64_t m, int group, double depth, float *d_p, float *d_cdf0);
 int launch_transpose_mK_to_Km(wgs_ctx *ctx, const float *src_mK, float *dst_Km, int64_t m, int32_t K);
 int launch_transpose_Km_to_mK(wgs_ctx *ctx, const float *src_Km, float *dst_mK, int64_t m, int32_t K);
