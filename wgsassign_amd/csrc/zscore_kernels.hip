@@ -32,7 +32,9 @@ __device__ __forceinline__ float zs_logf(float s, const double2 *tab)
     q = __builtin_fma(r, q, 1.0 / 3.0);
     q = __builtin_fma(r, q, -0.5);
     const float v = (float)(__builtin_fma(r * r, q, lo_) + hi_);
-    const float special = __builtin_amdgcn_logf(s);            // -inf / +inf / NaN exactly where libm returns them
+    // -inf / +inf / NaN exactly where libm returns them: v_log_f32 takes a subnormal for a zero of its sign, so a negative subnormal
+    // (libm: NaN) would come out as -inf -- every negative argument goes in as -1 (log_special of assign_kernels.hip)
+    const float special = __builtin_amdgcn_logf(__builtin_isfpclass(s, 0x0004 | 0x0008 | 0x0010) ? -1.0f : s);   // -inf | -normal | -subnormal
     return __builtin_isfpclass(s, 0x0100 | 0x0080) ? v : special;
 }
 
