@@ -129,6 +129,18 @@ int wgs_debug_afset_col(wgs_afset *a, int32_t col, float *out);
  * *nchunks is set) receives ceil(blocks / 2) x n*K float64, out[c * n*K + i * K + k]. */
 int wgs_debug_score_chunks(wgs_score *sc, double *out, int64_t *nchunks);
 
+/* The three kernels that turn the scoring sweeps' 4096-site block sums into the n x K float64 totals (csrc/assign_kernels.hip), each
+ * launched ONCE through the launcher of the product path on host arrays the caller makes up; `cells` stands for n*K.
+ *   block_prefix   S (nblocks x cells, read and rewritten): out[cell] = the blocks added in np.sum's order, total = total +
+ *                  (S[2c] + S[2c+1]); with keep_prefix S[b] becomes the total before block b's chunk (b even) or that + the old
+ *                  S[b - 1] (b odd), otherwise S comes back unchanged; chunks (NULL: the kernel is handed a null pointer) receives
+ *                  ceil(nblocks / 2) x cells chunk sums.  nblocks = 0 is allowed (S may be NULL).
+ *   chunk_total    out[cell] = ((carry + C[0]) + C[1]) + ... over nchunks x cells chunk sums; carry NULL: from 0.0.
+ *   combine_parts  S[e] = ((Sp[0][e] + Sp[1][e]) + ...) over parts x total partial sums. */
+int wgs_debug_block_prefix(wgs_ctx *ctx, double *S, int32_t nblocks, int64_t cells, int keep_prefix, double *out, double *chunks);
+int wgs_debug_chunk_total(wgs_ctx *ctx, const double *chunks, int32_t nchunks, int64_t cells, const double *carry, double *out);
+int wgs_debug_combine_parts(wgs_ctx *ctx, const double *Sp, int64_t total, int32_t parts, double *S);
+
 /* What the last wgs_score_sums of this object decided before it enqueued anything (csrc/score_api.hip: score_plan_sums):
  * info[0] 0 = the sweep over the float32 slabs, 1 = through the class codes; [1] populations per register batch and [2] pairs of
  * individuals per wavefront of the sweep; [3], [4] the same of the chain kernel of wgs_score_chains_prepare (both known from

@@ -101,10 +101,27 @@ def test_window_edges(files, oracle, m, windows):
         assert np.array_equal(glassy.assignLL_windowed(path, view, W1), out)
 
 
-def test_the_carry_does_work(files):
+def test_the_carry_does_work(files, oracle, tmp_path):
     """Five windows of 8192 sites and three of 16384: a window that restarted NumPy's running total instead of continuing it would
-    differ from the resident totals in the last bits."""
+    differ from the resident totals in the last bits -- on the order case, that is, which comes first here.  The generated matrix
+    behind it cannot show the order: every partial float64 sum of its cells is exact (window total plus window total, math.fsum and
+    np.sum agree in all 350 cells), so what it holds is that the windows lose and repeat nothing.  The case of tests/order_cases.py
+    (7 blocks, the last one ragged: a window of 16384 sites and a short one of two chunks) is built so that its block sums are exact
+    and its totals are not: there the restarting twin differs from np.sum in at least eight cells, and the windows must not."""
+    import order_cases as oc
     from wgsassign_amd import glassy
+    shape = (7, "ragged")
+    vals = oc.reference(oracle, shape)
+    want, S = oc.expected(vals), oc.block_sums(vals)
+    assert oc.different_cells(oc.restart_order(S, 16384), want) >= oc.MIN_DIFFERENT
+    assert oc.different_cells(oc.restart_order(S, 8192), want) == 0                  # (total + chunk either way: 8192 can never show)
+    L, A_order = oc.matrix_of(shape)
+    order_path = str(tmp_path / "order.beagle.gz")
+    with gzip.open(order_path, "wb", compresslevel=1) as fh:
+        fh.write(oc.beagle_text(L))
+    got = glassy.assignLL_windowed(order_path, np.ascontiguousarray(A_order), 16384)
+    assert glassy.assignLL_windowed.stats["windows"] == 2
+    assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
     path, A = files(40000, 70, 5)
     a = glassy.assignLL_windowed(path, A, 8192)
     assert glassy.assignLL_windowed.stats["windows"] == 5

@@ -195,6 +195,9 @@ SIGNATURES = {
     "wgs_debug_hook": (c_int, [ctypes.c_char_p, c_i64]),
     "wgs_debug_score_chunks": (c_int, [c_vp, c_f64p, ctypes.POINTER(c_i64)]),
     "wgs_debug_score_plan": (c_int, [c_vp, c_i32p]),
+    "wgs_debug_block_prefix": (c_int, [c_vp, c_f64p, c_i32, c_i64, c_int, c_f64p, c_f64p]),
+    "wgs_debug_chunk_total": (c_int, [c_vp, c_f64p, c_i32, c_i64, c_f64p, c_f64p]),
+    "wgs_debug_combine_parts": (c_int, [c_vp, c_f64p, c_i64, c_i32, c_f64p]),
     "wgs_debug_comm_tag_kernels": (c_int, [c_vp, c_i32, c_f64p, c_i32, c_f64p]),
     "wgs_debug_parts_exact_literal": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_i32, c_f32p, c_f32p]),
     "wgs_assign": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_int, c_f64p]),

@@ -372,6 +372,80 @@ int wgs_debug_score_chunks(wgs_score *sc, double *out, int64_t *nchunks)
     return 0;
 }
 
+/* Test hooks (include/wgsassign_hip_debug.h): the three kernels that add float64 block sums, each launched once on arrays made up
+ * by the caller -- uploaded, one launch_* of the product path, downloaded.  `in` (n_in doubles, may be NULL) goes to the front of a
+ * device buffer of n_all doubles, which *d receives; the rest of it is written by the kernel before it is read. */
+static int debug_sums_upload(wgs_ctx *ctx, const double *in, size_t n_in, size_t n_all, double **d)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(wgs_malloc(d, sizeof(double) * std::max<size_t>(n_all, 1)));
+    if (in && n_in && hipMemcpyAsync(*d, in, sizeof(double) * n_in, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+        (void)hipFree(*d);
+        wgs_set_error("block sums: upload failed");
+        return 1;
+    }
+    return 0;
+}
+
+static int debug_sums_finish(wgs_ctx *ctx, double *d, int rc)
+{
+    if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        wgs_set_error("block sums: device operation failed");
+        rc = 1;
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
+int wgs_debug_block_prefix(wgs_ctx *ctx, double *S, int32_t nblocks, int64_t cells, int keep_prefix, double *out, double *chunks)
+{
+    WGS_REQUIRE(ctx && out && nblocks >= 0 && cells > 0 && (S || nblocks == 0), "bad argument");
+    const size_t nS = (size_t)nblocks * cells, nC = (size_t)((nblocks + 1) / 2) * cells;
+    double *d = nullptr;                                   // S | out | chunks
+    if (debug_sums_upload(ctx, S, nS, nS + cells + nC, &d)) return 1;
+    int rc = launch_block_prefix(ctx, d, nblocks, cells, d + nS, keep_prefix, chunks ? d + nS + cells : nullptr);
+    if (!rc && ((nS && hipMemcpyAsync(S, d, sizeof(double) * nS, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
+                hipMemcpyAsync(out, d + nS, sizeof(double) * cells, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                (chunks && nC && hipMemcpyAsync(chunks, d + nS + cells, sizeof(double) * nC, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))) {
+        wgs_set_error("block prefix: download failed");
+        rc = 1;
+    }
+    return debug_sums_finish(ctx, d, rc);
+}
+
+int wgs_debug_chunk_total(wgs_ctx *ctx, const double *chunks, int32_t nchunks, int64_t cells, const double *carry, double *out)
+{
+    WGS_REQUIRE(ctx && out && nchunks >= 0 && cells > 0 && (chunks || nchunks == 0), "bad argument");
+    const size_t nC = (size_t)nchunks * cells;
+    double *d = nullptr;                                   // chunks | out | carry
+    if (debug_sums_upload(ctx, chunks, nC, nC + 2 * cells, &d)) return 1;
+    int rc = 0;
+    if (carry && hipMemcpyAsync(d + nC + cells, carry, sizeof(double) * cells, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+        wgs_set_error("chunk total: upload failed");
+        rc = 1;
+    }
+    if (!rc) rc = launch_chunk_total(ctx, d, nchunks, cells, carry ? d + nC + cells : nullptr, d + nC);
+    if (!rc && hipMemcpyAsync(out, d + nC, sizeof(double) * cells, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
+        wgs_set_error("chunk total: download failed");
+        rc = 1;
+    }
+    return debug_sums_finish(ctx, d, rc);
+}
+
+int wgs_debug_combine_parts(wgs_ctx *ctx, const double *Sp, int64_t total, int32_t parts, double *S)
+{
+    WGS_REQUIRE(ctx && Sp && S && total > 0 && parts >= 1, "bad argument");
+    const size_t nP = (size_t)total * parts;
+    double *d = nullptr;                                   // Sp | S
+    if (debug_sums_upload(ctx, Sp, nP, nP + total, &d)) return 1;
+    int rc = launch_combine_parts(ctx, d, d + nP, total, parts);
+    if (!rc && hipMemcpyAsync(S, d + nP, sizeof(double) * total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
+        wgs_set_error("combine parts: download failed");
+        rc = 1;
+    }
+    return debug_sums_finish(ctx, d, rc);
+}
+
 /* The same sums continued from the SNP shards before this one: out[i*K + k] = (((carry_in + C0) + C1) + ...) over this
  * shard's 8192-site chunk sums C (kept by wgs_score_sums), i.e. np.sum(vec, dtype=float) of glassy.py:38 carried on in
  * NumPy's own order when every shard starts at a multiple of 8192 sites (comm.shard_range sees to that).  carry_in (host,
