@@ -51,7 +51,8 @@ const char *wgs_last_error(void);
  * wgs_depth_download_rows, the deep tier of the z-scores (wgs_zscore_deep_sites, wgs_zkeep_create_deep), and the z-scores over SNP
  * shards (wgs_zscore_classes_sharded, wgs_em_fit_masked_sharded, wgs_depth_ingest_set_first_row, WGS_OP_Z_CLASS, WGS_OP_Z_CHAIN), and
  * windowed scoring (wgs_score_stream_*, wgs_beagle_set_window).  4: --ne_obs in site windows (wgs_fisher_stream_*); no existing
- * signature changed. */
+ * signature changed.  --get_assignment_z_score in site windows (wgs_zsum_*, wgs_zscore_classes_carry, wgs_zscore_stats_dev,
+ * wgs_depth_copy_rows, wgs_depth_ingest_set_selectors) was ADDED under 4. */
 #define WGS_ABI_VERSION 4
 int wgs_version(void);
 /* sha256[:16] over every source of the library / over the sources of the EM and scoring kernels (em_kernels.hip,
@@ -676,6 +677,43 @@ int wgs_em_fit_masked(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_
  * rc 2 only when kept_total[slot] is 0. */
 int wgs_em_fit_masked_sharded(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, int32_t max_iter, double tole,
                               const int64_t *kept_total, wgs_comm *comm, int32_t *iters_out);
+
+/* ---- --get_assignment_z_score in site windows: what is defined over all sites of an individual is continued
+ * from window to window on the device.  A wgs_zsum holds, for `count` individuals, (a) the running sums of the class sweep and (b) per
+ * (individual, array) of the three per-site arrays the state of np.sum's float32 order: NumPy adds the sums of consecutive
+ * 8192-element chunks -- each its pairwise routine's tree over 64 leaves of 128 -- serially to a running float32 that starts at +0.0,
+ * so the state is that running value and the fewer than 8192 elements of the open chunk.  Added under ABI version 4: new symbols only. */
+typedef struct wgs_zsum wgs_zsum;
+int wgs_zsum_create(wgs_ctx *ctx, int32_t count, wgs_zsum **out);
+void wgs_zsum_destroy(wgs_zsum *zs);
+/* wgs_zscore_classes for the next window of a pass: `d` is the depth table of the window's matrix.  The first call on a state runs
+ * the sweep from 0, every later one from the running sums the call before left on the device (a class without a site in the window
+ * hands them on untouched).  counts_out, first_out (LOCAL site numbers, -1: none) and over_out speak of this window alone -- the
+ * caller adds counts and `over` and keeps the smallest site0 + first -- and sums_out are the running sums after this window. */
+int wgs_zscore_classes_carry(wgs_depth *d, int32_t i0, int32_t count, wgs_zsum *zs, int32_t *counts_out, float *sums_out, int32_t *first_out,
+                             int32_t *over_out);
+/* wgs_zscore_stats that downloads nothing: *dev_out = DEVICE pointer to [3][*all_out] floats -- W_l_obs, W_l, var_W_l, inside each
+ * the individuals' compacted arrays one after the other (kept_out[j] floats each) -- owned by `zk`, valid until its next call of
+ * this function or its destruction.  *all_out = 0 (and *dev_out = NULL) when nobody kept a site. */
+int wgs_zscore_stats_dev(wgs_zkeep *zk, const float *tables, const float *const *freq_dev, const float **dev_out, int64_t *all_out);
+/* A window's arrays into the sums: dev_arrays as wgs_zscore_stats_dev leaves them ([3][all], device), kept[j] elements of individual
+ * slot j.  Per (individual, array) the push completes the open chunk with the first elements, reduces every full chunk in NumPy's order
+ * (all chunks of all individuals and arrays in one launch), adds the chunk sums to the running value in chunk order and stores the new
+ * open chunk.  Waits for the stream: the arrays may be released when it returns. */
+int wgs_zsum_push(wgs_zsum *zs, const float *dev_arrays, int64_t all, const int64_t *kept);
+/* total_out[j] = elements pushed for individual slot j so far; total % 8192 of them are in its open chunk. */
+int wgs_zsum_totals(wgs_zsum *zs, int64_t *total_out);
+/* run_out[j][a] = the running float32 over the closed chunks; tails_out = the open chunks, packed: for j, for a = 0..2, total[j] % 8192
+ * floats.  The caller closes the sum as NumPy does: run + np.sum(tail) -- exact, because a running value that started at +0.0 is
+ * never -0.0 -- and adds nothing for an empty tail. */
+int wgs_zsum_finish(wgs_zsum *zs, float *run_out, float *tails_out);
+/* Rows [src_row0, src_row0 + nrows) of one depth table into rows dst_row0 .. of another of the same individuals, on the device: a depth
+ * file is read ONCE per pass through a small table of its own (one chunk of the file at a time) and its rows go on to the window's
+ * table from there, whichever window edge the chunk straddles. */
+int wgs_depth_copy_rows(wgs_depth *dst, int64_t dst_row0, wgs_depth *src, int64_t src_row0, int64_t nrows);
+/* WGS_DEPTH_COUNTS: the selectors of the table's rows 0 .. nrows - 1 for the chunks to come (majmin[row][2], each 0..3), in place of
+ * those wgs_depth_ingest_create was given -- for an ingest whose table takes every chunk at row 0. */
+int wgs_depth_ingest_set_selectors(wgs_depth_ingest *g, const uint8_t *majmin, int64_t nrows);
 
 /* Blocks of 4096 elements that fell back to the serial loop in the last wgs_em_rmse_chain of an EM batch (diagnostics). */
 int wgs_em_last_chain_serial_blocks(wgs_em *em);

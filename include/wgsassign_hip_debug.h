@@ -155,6 +155,11 @@ int wgs_debug_score_plan(wgs_score *sc, int32_t info[8]);
  * [0] = 1 when the check reported a difference, [1] the other rank, [2..9] this rank's row, [10..17] the other's. */
 int wgs_debug_comm_tag_kernels(wgs_ctx *ctx, int32_t world, const double *rows, int32_t as_rank, double *fault_out);
 
+/* Test hook for the window-to-window float32 sums (wgs_zsum_*): a push of HOST arrays -- host_arrays[3][all], inside each the
+ * individuals' kept[j] elements one after the other -- through the kernels of wgs_zsum_push.  A state comes from wgs_zsum_create and is
+ * read with wgs_zsum_totals / wgs_zsum_finish. */
+int wgs_debug_zsum_push(wgs_zsum *zs, const float *host_arrays, int64_t all, const int64_t *kept);
+
 /* Cross-check only: FLOAT64 partition sums parts[(i*P + p)*K + k] (labels = global site index % P) and totals from the
  * round-1 kernel (lanes <-> pairs of individuals, tile ranges combined with float64 atomics): ~1e-5 from the
  * reference's serial float32 partition sums, not reproducible run to run.  Not on the product path. */

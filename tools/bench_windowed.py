@@ -6,6 +6,7 @@
     python tools/bench_windowed.py --fit [...] [--out profiles/windowed_fit_bench.json]      # the same for --get_reference_af
     python tools/bench_windowed.py --loo [...] [--out profiles/windowed_loo_bench.json]      # the same for --get_reference_af --loo
     python tools/bench_windowed.py --ne [...] [--out profiles/windowed_ne_obs_bench.json]    # the same for --get_reference_af --ne_obs
+    python tools/bench_windowed.py --z [...] [--out profiles/z_windowed.json]                # the same for --get_assignment_z_score
 
 The file comes from tools/beagle_files.py (seeded, seconds to write).  Every end-to-end figure is the wall time of one
 `python -m wgsassign_amd.WGSassign --get_pop_like` process -- interpreter start, HIP initialisation, ingest, scoring, the text
@@ -31,6 +32,10 @@ three whole-process figures, and from fisher.fisher_obs_windowed in this process
 fisher_ind_sites_kernel, pairwise_leaf_kernel) has no events of its own: `--ne --probe` runs the resident functions and the windowed
 pass once and nothing else, to be run under `rocprofv3 --kernel-trace --stats --output-format csv`, and `--ne --kernel-stats CSV` adds
 that trace's per-kernel totals to the result.
+--z measures --get_assignment_z_score (two passes over the Beagle file and the depth file in windows; WGSASSIGN_Z_WINDOW_SITES): the
+whole-process figures with a plain-text depth file beside the BGZF Beagle file, their ratio windowed / resident, and from one
+zscore.assignment_z_scores_windowed in this process the seconds of each pass, the depth ingest's text bytes per pass against the
+file's, and the bytes that crossed to the host.  No time target is set: the number to record is that ratio.
 What to expect: the device's share of an ingest (BGZF inflate, tokeniser) and the sweeps use the context's one stream and every push
 waits for it, so for a BGZF file the device work of consecutive windows is strictly serial; what overlaps a window's sweep is only
 the producer thread's reading of the next window (for plain gzip also its inflate).  The windowed run therefore costs the resident
@@ -50,15 +55,18 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 
 
-def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False, ne=False):
-    """af: the frequency file of --get_pop_like, or with fit (or loo, or ne) the ID file of --get_reference_af."""
+def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False, ne=False, z=None):
+    """af: the frequency file of --get_pop_like, or with fit (or loo, or ne) the ID file of --get_reference_af.  z: the further
+    arguments of --get_assignment_z_score (ID, names and depth files), which then stands in place of --get_pop_like."""
     env = dict(os.environ)
     env.pop("WGSASSIGN_WINDOW_SITES", None)
     env.pop("WGSASSIGN_LOO_WINDOW_SITES", None)
     env.pop("WGSASSIGN_NE_WINDOW_SITES", None)
+    env.pop("WGSASSIGN_Z_WINDOW_SITES", None)
     env.update(env_extra)
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
     what = (["--pop_af_IDs", af, "--get_reference_af"] + (["--loo"] if loo else []) + (["--ne_obs"] if ne else []) if fit or loo or ne
+            else ["--pop_af_file", af, "--get_assignment_z_score"] + list(z) if z is not None
             else ["--pop_af_file", af, "--get_pop_like"])
     t0 = time.perf_counter()
     r = subprocess.run([sys.executable, "-m", "wgsassign_amd.WGSassign", "--beagle", beagle] + what + ["--out", out],
@@ -255,8 +263,57 @@ def ne_leg(a, m, n, K, W):
     return res
 
 
+def z_leg(a, m, n, K, W):
+    """--get_assignment_z_score resident against windowed; one JSON-able dict."""
+    import beagle_files
+    import bench_depth_ingest
+    from wgsassign_amd import device, zscore
+    res = {"bench": "windowed_assignment_z_score", "snps": m, "inds": n, "pops": K, "window_sites": W, "windows": a.windows}
+    with tempfile.TemporaryDirectory() as td:
+        os.environ["WGSASSIGN_INDEX_DIR"] = td
+        bg, ids, names, af = (os.path.join(td, x) for x in ("x.beagle.gz", "ids.txt", "names.txt", "x.pop_af.npy"))
+        beagle_files.write_lowdepth_bgzf(bg, n, m, seed=5)
+        IDs = np.array([["Ind%d" % i, "pop%d" % (i * K // n)] for i in range(n)])
+        np.savetxt(ids, IDs, fmt="%s", delimiter="\t")
+        pops = np.unique(IDs[:, 1])
+        np.savetxt(names, pops, fmt="%s")
+        np.save(af, np.random.default_rng(5).uniform(0.05, 0.95, size=(m, K)).astype(np.float32))
+        paths, depth_text_bytes, _ = bench_depth_ingest.write_files(td, m, n, ("text",), False)
+        ad = paths["text"]
+        res.update(file_mb=round(os.path.getsize(bg) / 1e6, 1), depth_file_mb=round(depth_text_bytes / 1e6, 1))
+        more = ["--pop_af_IDs", ids, "--pop_names", names, "--ind_ad_file", ad]
+        variants = [("resident_s", ROOT, {})]
+        if a.parent_root:
+            variants.insert(0, ("parent_resident_s", os.path.abspath(a.parent_root), {}))
+        variants.append(("windowed_s", ROOT, {"WGSASSIGN_Z_WINDOW_SITES": str(W)}))
+        times = {name: [] for name, _, _ in variants}
+        for rep in range(a.repeats + 1):
+            for name, root, env in variants:
+                dt, err = cli_seconds(root, bg, af, os.path.join(td, name), env, z=more)
+                if rep:
+                    times[name].append(dt)
+                if name == "windowed_s" and ("passes over %d windows" % a.windows) not in err:
+                    raise RuntimeError("the windowed run did not use %d windows: %s" % (a.windows, err[-300:]))
+        files = {name: open(os.path.join(td, name + ".z_ind.txt"), "rb").read() for name, _, _ in variants}
+        res["outputs_identical"] = len(set(files.values())) == 1
+        for name in ("parent_resident_s", "resident_s", "windowed_s"):
+            res[name] = spread(times[name]) if name in times else None
+        res["windowed_over_resident"] = round(res["windowed_s"]["median"] / res["resident_s"]["median"], 3)
+        ctx = device.get_context()
+        res["device"] = ctx.info()["name"].strip()
+        A = np.load(af, mmap_mode="r")
+        for rep in range(2):
+            zscore.assignment_z_scores_windowed(bg, ad, A, IDs, pops, window_sites=W, say=lambda *_: None, ctx=ctx)
+        st = zscore.assignment_z_scores_windowed.stats
+        res.update(rounds=st["rounds"], pass_a_seconds=[round(x, 3) for x in st["seconds_a"]], pass_b_seconds=[round(x, 3) for x in st["seconds_b"]],
+                   depth_text_bytes=depth_text_bytes, depth_text_bytes_per_pass=[int(d["text_bytes"]) for d in st["depth_a"] + st["depth_b"]],
+                   downloaded_bytes=int(st["downloaded_bytes"]))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--z", action="store_true", help="measure --get_assignment_z_score (the z-scores in windows)")
     ap.add_argument("--ne", action="store_true", help="measure --get_reference_af --ne_obs (the Fisher information in windows)")
     ap.add_argument("--probe", action="store_true", help="with --ne: only run the resident functions and the windowed pass once (for a kernel trace)")
     ap.add_argument("--kernel-stats", default=None, help="with --ne: a rocprofv3 *_kernel_stats.csv of a --ne --probe run, added to the result")
@@ -266,6 +323,7 @@ def main():
     ap.add_argument("--inds", type=int, default=200)
     ap.add_argument("--pops", type=int, default=5)
     ap.add_argument("--windows", type=int, default=4)
+    ap.add_argument("--window-sites", type=int, default=0, help="the window itself (a multiple of 8192) instead of --windows")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--parent-root", default=None, help="a built checkout of the parent commit")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
@@ -275,10 +333,17 @@ def main():
     m, n, K = a.snps, a.inds, a.pops
     per_window = (m + a.windows - 1) // a.windows
     W = (per_window + windows.ALIGN - 1) // windows.ALIGN * windows.ALIGN          # rounded UP to whole chunks of 8192
+    if a.window_sites:                                                             # (--z: windows of 262144 sites by default)
+        W = a.window_sites // windows.ALIGN * windows.ALIGN
+        a.windows = windows.window_count(m, W)
+    elif a.z:
+        W = 262144
+        a.windows = windows.window_count(m, W)
     if windows.window_count(m, W) != a.windows:
         raise SystemExit("%d sites cannot be cut into %d windows of a multiple of %d sites" % (m, a.windows, windows.ALIGN))
-    if a.fit or a.loo or a.ne:
-        line = json.dumps(ne_leg(a, m, n, K, W) if a.ne else loo_leg(a, m, n, K, W) if a.loo else fit_leg(a, m, n, K, W))
+    if a.fit or a.loo or a.ne or a.z:
+        line = json.dumps(z_leg(a, m, n, K, W) if a.z else ne_leg(a, m, n, K, W) if a.ne else loo_leg(a, m, n, K, W) if a.loo
+                          else fit_leg(a, m, n, K, W))
         print(line)
         if a.out:
             with open(a.out, "w") as fh:

@@ -82,11 +82,16 @@ SET_WINDOW_SITES = ("the matrix was expected to fit the device and does not: set
                     "score the file in site windows")
 
 
-def with_windows_hint(error, candidate=False):
+SET_WINDOW_SITES_Z = ("the matrix was expected to fit the device and does not: set WGSASSIGN_Z_WINDOW_SITES (a multiple of 8192 sites) to "
+                      "compute the z-scores in site windows")
+
+
+def with_windows_hint(error, candidate=False, z_candidate=False):
     """The error of a resident run whose matrix did not fit the device, saying what windows cover -- or, when the options were
-    those windows cover (candidate: the file was only judged to fit), how to ask for them; any other error as it is."""
+    those windows cover (candidate: the file was only judged to fit; z_candidate: --get_assignment_z_score alone, which has a
+    variable of its own), how to ask for them; any other error as it is."""
     if isinstance(error, RuntimeError) and all(part in str(error) for part in SLAB_ALLOC_FAILED):
-        return RuntimeError(str(error) + ": " + (SET_WINDOW_SITES if candidate else WINDOWS_ONLY))
+        return RuntimeError(str(error) + ": " + (SET_WINDOW_SITES_Z if z_candidate else SET_WINDOW_SITES if candidate else WINDOWS_ONLY))
     return error
 
 
@@ -259,6 +264,103 @@ def _ne_window_sites(args, comm, ctx):
         raise SystemExit(str(e))
 
 
+def windowed_z_candidate(args, world=1):
+    """Whether these options may run in site windows (zscore.assignment_z_scores_windowed): --get_assignment_z_score alone, on one
+    rank.  Its frequencies come from --pop_af_file, so nothing couples the windows but sums that are carried on the device.
+    --get_reference_z_score needs masked leave-one-out re-fits over the whole file and keeps the resident path, as do several ranks."""
+    others = (args.get_reference_af, args.loo, args.ne_obs, args.get_pop_like, args.get_reference_z_score, args.loo_downsampled_beagle)
+    return bool(args.get_assignment_z_score) and int(world) == 1 and not any(others)
+
+
+def _z_individuals(args, n):
+    """How many individuals --ind_start / --ind_end leave of n, for the plan alone (the run checks the range as it always did)."""
+    lo = args.ind_start if args.ind_start else 0
+    hi = args.ind_end if args.ind_end else n
+    return max(1, min(n, hi) - max(0, lo))
+
+
+def _z_window_sites(args, comm, ctx):
+    """(window, individuals per round) --get_assignment_z_score runs in, or None for the resident path: WGSASSIGN_Z_WINDOW_SITES when
+    set (no other variable sends the z-scores to windows), else windows only when the resident matrix, depth table and frequencies
+    would not fit (windows.plan_z), after the same first look as _window_sites takes."""
+    import numpy as np
+
+    from . import reader_cy, windows
+    if not windowed_z_candidate(args, comm.world) or not (args.pop_af_file and os.path.isfile(args.pop_af_file)):
+        return None                     # (a missing frequency file is reported where it always was)
+    try:
+        forced = windows.env_window_sites(name=windows.ENV_Z)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if forced is not None:
+        return forced, None             # (the rounds of individuals are planned once the file's shape is known)
+    free = ctx.mem_info()[0]
+    if windows.surely_fits(os.path.getsize(args.beagle), free):
+        return None
+    try:
+        A = np.load(args.pop_af_file, mmap_mode="r")
+    except Exception:
+        return None                     # (an unreadable frequency file, too, is reported where it always was)
+    if A.ndim != 2:
+        return None
+    with reader_cy.BeagleStream(args.beagle, threads=1) as st:
+        n = st.n
+    count = _z_individuals(args, n)
+    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
+    if est is not None and windows.fits_resident_z(est + est // 4 + 1024, n, A.shape[1], count, free):
+        return None
+    m = reader_cy.ensure_index(args.beagle)[2]
+    try:
+        return windows.plan_z(m, n, A.shape[1], count, free)
+    except MemoryError as e:
+        raise SystemExit(str(e))
+
+
+def _run_z_windowed(args, comm, ctx, plan, say, summary):
+    """--get_assignment_z_score alone on files that do not fit (or WGSASSIGN_Z_WINDOW_SITES): two passes over the Beagle file and the
+    depth file in site windows; the checks, lines and file of the resident run in their order, and one more line on stderr."""
+    import numpy as np
+
+    from . import reader_cy, zscore
+    W, batch = plan
+    index, _, m = reader_cy.ensure_index(args.beagle)
+    with reader_cy.BeagleStream(args.beagle, threads=1) as st:
+        n = st.n
+    assert os.path.isfile(args.pop_af_IDs), "Population ID file does not exist!!"
+    IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
+    A = np.load(args.pop_af_file, mmap_mode="r")
+    majmin = None
+    if args.ind_counts_file:
+        majmin = zscore.read_majmin(args.ind_majmin_file)
+        if majmin.shape[0] != m:
+            raise ValueError("%s has the selectors of %d sites, the Beagle file %d" % (args.ind_majmin_file, majmin.shape[0], m))
+    else:
+        assert os.path.isfile(args.ind_ad_file), "Individual allele depths file does not exist!"
+    assert os.path.isfile(args.pop_names), "Population names file does not exist!!"
+    pops = np.loadtxt(args.pop_names, dtype="str")
+    assert (n == IDs.shape[0]), "Number of individuals in beagle and reference ID file do not match!"
+    if args.allele_count_threshold is not None:
+        assert (args.allele_count_threshold >= 0), "Allele count threshold needs to be greater than/equal to 0!"
+    allele_count_threshold = args.allele_count_threshold or 0
+    ind_start, ind_end = zscore.ind_range(n, args.ind_start, args.ind_end)
+    lines = []
+    z_out = zscore.assignment_z_scores_windowed(args.beagle, args.ind_counts_file or args.ind_ad_file, A, IDs, np.atleast_1d(pops),
+                                                allele_count_threshold, args.single_read_threshold, ind_start, ind_end, window_sites=W,
+                                                say=lines.append, counts=majmin is not None, majmin=majmin, batch=batch, ctx=ctx)
+    info, stats = zscore.assignment_z_scores_windowed.info, zscore.assignment_z_scores_windowed.stats
+    say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
+    summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
+    say("Parsing population ID file.")
+    say("Parsing population allele frequency file.")
+    say("Parsing individual allele depths file.")
+    for ln in lines:
+        say(ln)
+    print("wgsassign_amd: z-scores in %d rounds of 2 passes over %d windows of %d sites (%d bytes downloaded)" %
+          (stats["rounds"], stats["windows"], stats["window_sites"], stats["downloaded_bytes"]), file=sys.stderr, flush=True)
+    np.savetxt(args.out + ".z_ind.txt", z_out, fmt="%.7f")
+    say("Saved " + str(ind_end - ind_start) + " individual z-scores as " + str(args.out) + ".z_ind.txt (text)")
+
+
 def _run(args, comm):
     """The hot-path options on device-resident data.  Under torchrun (one process per GPU) the SNPs are
     sharded over the ranks: every rank parses and holds only its contiguous SNP range; the EM convergence sums,
@@ -385,6 +487,12 @@ def _run(args, comm):
         comm.barrier()
         return
 
+    z_plan = _z_window_sites(args, comm, ctx)
+    if z_plan is not None:
+        _run_z_windowed(args, comm, ctx, z_plan, say, summary)
+        comm.barrier()
+        return
+
     scored = None
     if args.loo_downsampled_beagle:
         # WGSassign.py:172-198 with names-only passes: every rank derives the same two site masks, then
@@ -422,7 +530,7 @@ def _run(args, comm):
             beagle, sample_names, site_names, m = reader_cy.stream_to_device(
                 args.beagle, group_of, n_groups, ctx=ctx, rank=comm.rank, world=comm.world, comm=comm, names="ends")
         except RuntimeError as e:
-            hinted = with_windows_hint(e, windowed_candidate(args, comm.world))
+            hinted = with_windows_hint(e, windowed_candidate(args, comm.world), windowed_z_candidate(args, comm.world))
             if hinted is e:
                 raise
             raise hinted from e

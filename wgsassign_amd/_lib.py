@@ -79,6 +79,16 @@ SIGNATURES = {
     "wgs_zkeep_destroy": (None, [c_vp]),
     "wgs_zkeep_sites": (c_int, [c_vp, c_i32, c_i32p]),
     "wgs_zscore_stats": (c_int, [c_vp, c_f32p, ctypes.POINTER(c_vp), c_f32p, c_f32p, c_f32p]),
+    "wgs_zsum_create": (c_int, [c_vp, c_i32, ctypes.POINTER(c_vp)]),
+    "wgs_zsum_destroy": (None, [c_vp]),
+    "wgs_zscore_classes_carry": (c_int, [c_vp, c_i32, c_i32, c_vp, c_i32p, c_f32p, c_i32p, c_i32p]),
+    "wgs_zscore_stats_dev": (c_int, [c_vp, c_f32p, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)]),
+    "wgs_zsum_push": (c_int, [c_vp, c_vp, c_i64, ctypes.POINTER(c_i64)]),
+    "wgs_zsum_totals": (c_int, [c_vp, ctypes.POINTER(c_i64)]),
+    "wgs_zsum_finish": (c_int, [c_vp, c_f32p, c_f32p]),
+    "wgs_debug_zsum_push": (c_int, [c_vp, c_f32p, c_i64, ctypes.POINTER(c_i64)]),
+    "wgs_depth_copy_rows": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64]),
+    "wgs_depth_ingest_set_selectors": (c_int, [c_vp, c_vp, c_i64]),
     "wgs_em_fit_masked": (c_int, [c_vp, c_vp, c_i32p, c_i32, ctypes.c_double, c_i32p]),
     "wgs_em_fit_masked_sharded": (c_int, [c_vp, c_vp, c_i32p, c_i32, ctypes.c_double, ctypes.POINTER(c_i64), c_vp, c_i32p]),
     "wgs_em_create": (c_int, [c_vp, c_i32, c_i32p, c_i32p, c_int, ctypes.POINTER(c_vp)]),

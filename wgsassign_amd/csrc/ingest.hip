@@ -1409,6 +1409,21 @@ int wgs_depth_ingest_set_first_row(wgs_depth_ingest *gi, int64_t first_row)
     return 0;
 }
 
+int wgs_depth_ingest_set_selectors(wgs_depth_ingest *gi, const uint8_t *majmin, int64_t nrows)
+{
+    wgs_ingest *g = reinterpret_cast<wgs_ingest *>(gi);
+    WGS_REQUIRE(g && g->depth && majmin, "null argument");
+    WGS_REQUIRE(g->dp.tpi == 4, "the (major, minor) selectors go with WGS_DEPTH_COUNTS, and only with it");
+    WGS_REQUIRE(nrows >= 0 && nrows <= g->m_rows, "selectors of %lld rows for a table of %lld", (long long)nrows, (long long)g->m_rows);
+    for (int64_t i = 0; i < 2 * nrows; ++i) WGS_REQUIRE(majmin[i] <= 3, "row %lld: selector %d outside 0..3", (long long)(i / 2), (int)majmin[i]);
+    if (nrows == 0) return 0;
+    HIP_TRY(hipSetDevice(g->ctx->device));
+    HIP_TRY(hipStreamSynchronize(g->ctx->stream));           // (the chunk before has been tokenised)
+    HIP_TRY(hipMemcpyAsync(g->dp.sel.p, majmin, (size_t)(2 * nrows), hipMemcpyHostToDevice, g->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(g->ctx->stream));
+    return 0;
+}
+
 int wgs_depth_ingest_next(wgs_depth_ingest *gi, int64_t row0, int64_t *file_rows, int64_t *rows_written)
 {
     wgs_ingest *g = reinterpret_cast<wgs_ingest *>(gi);

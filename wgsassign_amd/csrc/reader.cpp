@@ -2005,7 +2005,8 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 bool chunk_reserve(TextPipe *p, TextChunk *c, size_t want)
 {
     if (c->data && want + TEXT_PAD <= c->cap) return true;
-    const size_t cap = want + TEXT_PAD;
+    // a multiple of 16: the ingest copies the text in whole 16-byte units, (len + TEXT_PAD) rounded up, which must not pass the buffer's end
+    const size_t cap = (want + TEXT_PAD + 15) & ~(size_t)15;
     char *q = (char *)p->alloc.alloc(cap, p->alloc.user);
     if (!q) return false;
     if (c->len) memcpy(q, c->data, c->len);

@@ -43,6 +43,32 @@ struct wgs_zkeep {
     std::vector<int64_t> total;
     int32_t *d_deep_map = nullptr;        // [count][WGS_Z_DEEP_MAP], nullptr: no individual of the set kept a deep depth
     float *d_deep_rows = nullptr;         // [rows][WGS_Z_DEEP_ROW]
+    float *d_stats = nullptr;             // wgs_zscore_stats_dev: the three compacted arrays of the last call, [3][stats_all]
+    int64_t stats_all = 0;
+};
+
+// np.sum's float32 order continued from site window to site window (zscore_kernels.hip: zsum_*): per (individual, array) the running
+// float32 over the closed 8192-element chunks and the elements of the open one.  Also the class sweep's running sums of a windowed pass.
+constexpr int WGS_ZSUM_CHUNK = 8192, WGS_ZSUM_ARRAYS = 3;
+constexpr int WGS_LIVE_ZSUM = 6;          // (score_api.hip: 5) no parent, only its liveness is kept
+struct ZSumJob {
+    const float *x;            // the window's compacted array of this (individual, array): k elements
+    float *tail, *run;         // the open chunk (WGS_ZSUM_CHUNK floats) and the running value
+    int64_t k;
+    int64_t cbase;             // where this job's chunk sums begin
+    int32_t fill, nfull;       // elements in the open chunk before the push; chunks the push closes
+};
+struct wgs_zsum {
+    wgs_ctx *ctx = nullptr;
+    int32_t count = 0;
+    float *d_run = nullptr;    // [count][3]
+    float *d_tail = nullptr;   // [count][3][WGS_ZSUM_CHUNK]
+    float *d_class = nullptr;  // [count][256][3]: zclass_kernel's running sums (wgs_zscore_classes_carry)
+    float *d_csum = nullptr;   // chunk sums of a push
+    size_t csum_cap = 0;
+    ZSumJob *d_jobs = nullptr; // [count * 3]
+    std::vector<int64_t> total;            // elements pushed per individual
+    int64_t class_windows = 0;             // windows wgs_zscore_classes_carry has swept
 };
 
 int zs_fill_inds(wgs_beagle *b, int32_t i0, int32_t count, std::vector<ZInd> &out);
@@ -62,3 +88,5 @@ int launch_zcompact(wgs_ctx *ctx, const ZCompactJob *d_jobs, int n_jobs, int64_t
 int launch_zdepth_scatter(wgs_ctx *ctx, const int32_t *d_rows, int64_t nrows, int64_t n, int64_t row0, int64_t mpad, uchar2 *depth, int32_t *bad);
 int launch_zdepth_gather(wgs_ctx *ctx, const uchar2 *depth, int64_t nrows, int64_t n, int64_t row0, int64_t mpad, int32_t *d_rows);
 int launch_zsites(wgs_ctx *ctx, int64_t m, const unsigned long long *mask, const uint32_t *off, int32_t *out);
+// the jobs' full chunks reduced in NumPy's order into csum, added to the running values in chunk order, the new open chunks stored
+int launch_zsum_push(wgs_ctx *ctx, const ZSumJob *d_jobs, int n_jobs, int max_full, float *csum);

@@ -266,7 +266,7 @@ void wgs_zkeep_destroy(wgs_zkeep *zk)
 {
     if (!zk || !wgs_live_remove(zk)) return;
     (void)hipSetDevice(zk->b->ctx->device);
-    for (void *p : {(void *)zk->d_inds, (void *)zk->mask, (void *)zk->off, (void *)zk->d_total, (void *)zk->d_deep_map, (void *)zk->d_deep_rows})
+    for (void *p : {(void *)zk->d_inds, (void *)zk->mask, (void *)zk->off, (void *)zk->d_total, (void *)zk->d_deep_map, (void *)zk->d_deep_rows, (void *)zk->d_stats})
         if (p) (void)hipFree(p);
     delete zk;
 }
@@ -361,42 +361,256 @@ int wgs_zkeep_sites(wgs_zkeep *zk, int32_t slot, int32_t *sites_out)
     return 0;
 }
 
-int wgs_zscore_stats(wgs_zkeep *zk, const float *tables, const float *const *freq_dev, float *wobs_out, float *wl_out, float *var_out)
+}   // extern "C"
+
+// The statistic sweep of a kept-site set into d_out = [3][all] (W_l_obs | W_l | var_W_l, the individuals one after the other inside
+// each), enqueued on the context's stream; the small inputs live in `bufs` until the caller has waited for the stream.
+static int zstats_enqueue(wgs_zkeep *zk, const float *tables, const float *const *freq_dev, const std::vector<int64_t> &obase, int64_t all,
+                          ZBufs &bufs, float *d_out)
 {
-    WGS_REQUIRE(zk && tables && freq_dev && wobs_out && wl_out && var_out, "null argument");
     wgs_beagle *b = zk->b;
     wgs_ctx *ctx = b->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
     const int count = zk->count;
-    std::vector<int64_t> obase(count);
-    int64_t all = 0;
-    for (int j = 0; j < count; ++j) {
-        WGS_REQUIRE(freq_dev[j], "individual %d has no frequency vector", zk->i0 + j);
-        obase[j] = all;
-        all += zk->total[j];
-    }
-    if (all == 0) return 0;
-    ZBufs bufs;
-    float *d_tabs = nullptr, *d_out = nullptr;
+    float *d_tabs = nullptr;
     const float **d_fptr = nullptr;
     int64_t *d_obase = nullptr;
     const size_t tab_bytes = sizeof(float) * 6 * WGS_Z_NKEYS * count;
     HIP_TRY(bufs.get(&d_tabs, tab_bytes));
     HIP_TRY(bufs.get(&d_fptr, sizeof(float *) * count));
     HIP_TRY(bufs.get(&d_obase, sizeof(int64_t) * count));
+    HIP_TRY(hipMemcpyAsync(d_tabs, tables, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_fptr, freq_dev, sizeof(float *) * count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_obase, obase.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, ctx->stream));
+    return launch_zstat(ctx, zk->d_inds, count, zk->d->table, b->m, zk->d->mpad, d_tabs, d_fptr, zk->d_deep_map, zk->d_deep_rows, zk->mask, zk->off,
+                        d_obase, d_out, d_out + all, d_out + 2 * all);
+}
+
+static int zstats_layout(wgs_zkeep *zk, const float *const *freq_dev, std::vector<int64_t> &obase, int64_t *all_out)
+{
+    const int count = zk->count;
+    obase.resize(count);
+    int64_t all = 0;
+    for (int j = 0; j < count; ++j) {
+        WGS_REQUIRE(freq_dev[j], "individual %d has no frequency vector", zk->i0 + j);
+        obase[j] = all;
+        all += zk->total[j];
+    }
+    *all_out = all;
+    return 0;
+}
+
+extern "C" {
+
+int wgs_zscore_stats(wgs_zkeep *zk, const float *tables, const float *const *freq_dev, float *wobs_out, float *wl_out, float *var_out)
+{
+    WGS_REQUIRE(zk && tables && freq_dev && wobs_out && wl_out && var_out, "null argument");
+    wgs_ctx *ctx = zk->b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<int64_t> obase;
+    int64_t all = 0;
+    if (int rc = zstats_layout(zk, freq_dev, obase, &all)) return rc;
+    if (all == 0) return 0;
+    ZBufs bufs;
+    float *d_out = nullptr;
     if (bufs.get(&d_out, sizeof(float) * 3 * all) != hipSuccess) {
         wgs_set_error("hipMalloc of %zu bytes for the per-site statistics failed", sizeof(float) * 3 * (size_t)all);
         return 1;
     }
-    HIP_TRY(hipMemcpyAsync(d_tabs, tables, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_fptr, freq_dev, sizeof(float *) * count, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_obase, obase.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, ctx->stream));
-    if (launch_zstat(ctx, zk->d_inds, count, zk->d->table, b->m, zk->d->mpad, d_tabs, d_fptr, zk->d_deep_map, zk->d_deep_rows, zk->mask, zk->off, d_obase,
-                     d_out, d_out + all, d_out + 2 * all))
-        return 1;
+    if (int rc = zstats_enqueue(zk, tables, freq_dev, obase, all, bufs, d_out)) return rc;
     HIP_TRY(hipMemcpyAsync(wobs_out, d_out, sizeof(float) * all, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(wl_out, d_out + all, sizeof(float) * all, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(var_out, d_out + 2 * all, sizeof(float) * all, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int wgs_zscore_stats_dev(wgs_zkeep *zk, const float *tables, const float *const *freq_dev, const float **dev_out, int64_t *all_out)
+{
+    WGS_REQUIRE(zk && tables && freq_dev && dev_out && all_out, "null argument");
+    wgs_ctx *ctx = zk->b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<int64_t> obase;
+    int64_t all = 0;
+    if (int rc = zstats_layout(zk, freq_dev, obase, &all)) return rc;
+    if (zk->d_stats) (void)hipFree(zk->d_stats);
+    zk->d_stats = nullptr;
+    zk->stats_all = 0;
+    *dev_out = nullptr;
+    *all_out = all;
+    if (all == 0) return 0;
+    if (wgs_malloc(&zk->d_stats, sizeof(float) * 3 * all) != hipSuccess) {
+        zk->d_stats = nullptr;
+        wgs_set_error("hipMalloc of %zu bytes for the per-site statistics failed", sizeof(float) * 3 * (size_t)all);
+        return 1;
+    }
+    zk->stats_all = all;
+    ZBufs bufs;
+    if (int rc = zstats_enqueue(zk, tables, freq_dev, obase, all, bufs, zk->d_stats)) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));              // (the tables in `bufs` go with this call)
+    *dev_out = zk->d_stats;
+    return 0;
+}
+
+void wgs_zsum_destroy(wgs_zsum *zs)
+{
+    if (!zs || !wgs_live_remove(zs)) return;
+    (void)hipSetDevice(zs->ctx->device);
+    (void)hipStreamSynchronize(zs->ctx->stream);
+    for (void *p : {(void *)zs->d_run, (void *)zs->d_tail, (void *)zs->d_class, (void *)zs->d_csum, (void *)zs->d_jobs})
+        if (p) (void)hipFree(p);
+    delete zs;
+}
+
+int wgs_zsum_create(wgs_ctx *ctx, int32_t count, wgs_zsum **out)
+{
+    WGS_REQUIRE(ctx && out, "null argument");
+    WGS_REQUIRE(count > 0 && count <= 16384, "a sum state holds between 1 and 16384 individuals, not %d", count);
+    HIP_TRY(hipSetDevice(ctx->device));
+    wgs_zsum *zs = new wgs_zsum();
+    wgs_live_add(zs, WGS_LIVE_ZSUM, nullptr);
+    auto guard = on_failure([&] { wgs_zsum_destroy(zs); });
+    zs->ctx = ctx;
+    zs->count = count;
+    zs->total.assign(count, 0);
+    const size_t cells = (size_t)count * WGS_ZSUM_ARRAYS;
+    HIP_TRY(wgs_malloc(&zs->d_run, sizeof(float) * cells));
+    if (wgs_malloc(&zs->d_tail, sizeof(float) * cells * WGS_ZSUM_CHUNK) != hipSuccess) {
+        zs->d_tail = nullptr;
+        wgs_set_error("hipMalloc of %zu bytes for the open chunks of %d individuals failed", sizeof(float) * cells * WGS_ZSUM_CHUNK, count);
+        return 1;
+    }
+    HIP_TRY(wgs_malloc(&zs->d_class, sizeof(float) * 3 * 256 * (size_t)count));
+    HIP_TRY(wgs_malloc(&zs->d_jobs, sizeof(ZSumJob) * cells));
+    HIP_TRY(hipMemsetAsync(zs->d_run, 0, sizeof(float) * cells, ctx->stream));                 // +0.0: where np.sum starts
+    HIP_TRY(hipMemsetAsync(zs->d_class, 0, sizeof(float) * 3 * 256 * (size_t)count, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    guard.dismiss();
+    *out = zs;
+    return 0;
+}
+
+int wgs_zsum_push(wgs_zsum *zs, const float *dev_arrays, int64_t all, const int64_t *kept)
+{
+    WGS_REQUIRE(zs && kept, "null argument");
+    wgs_ctx *ctx = zs->ctx;
+    const int count = zs->count;
+    int64_t sum = 0;
+    for (int j = 0; j < count; ++j) {
+        WGS_REQUIRE(kept[j] >= 0 && kept[j] < (int64_t)1 << 31, "individual slot %d: %lld elements in one push", j, (long long)kept[j]);
+        sum += kept[j];
+    }
+    WGS_REQUIRE(sum == all, "the push holds %lld elements per array, the kept counts add up to %lld", (long long)all, (long long)sum);
+    WGS_REQUIRE(all == 0 || dev_arrays, "null argument");
+    if (all == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<ZSumJob> jobs((size_t)count * WGS_ZSUM_ARRAYS);
+    int64_t obase = 0, cbase = 0;
+    int max_full = 0;
+    for (int j = 0; j < count; ++j) {
+        const int32_t fill = (int32_t)(zs->total[j] % WGS_ZSUM_CHUNK);
+        const int32_t nfull = (int32_t)((fill + kept[j]) / WGS_ZSUM_CHUNK);
+        for (int a = 0; a < WGS_ZSUM_ARRAYS; ++a) {
+            const size_t e = (size_t)j * WGS_ZSUM_ARRAYS + a;
+            jobs[e] = ZSumJob{dev_arrays + (size_t)a * all + obase, zs->d_tail + e * WGS_ZSUM_CHUNK, zs->d_run + e, kept[j], cbase, fill, nfull};
+            cbase += nfull;
+        }
+        if (nfull > max_full) max_full = nfull;
+        obase += kept[j];
+    }
+    if ((size_t)cbase > zs->csum_cap) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (zs->d_csum) (void)hipFree(zs->d_csum);
+        zs->d_csum = nullptr;
+        zs->csum_cap = 0;
+        HIP_TRY(wgs_malloc(&zs->d_csum, sizeof(float) * (size_t)cbase));
+        zs->csum_cap = (size_t)cbase;
+    }
+    HIP_TRY(hipMemcpyAsync(zs->d_jobs, jobs.data(), sizeof(ZSumJob) * jobs.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (launch_zsum_push(ctx, zs->d_jobs, (int)jobs.size(), max_full, zs->d_csum)) return 1;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));              // (`jobs` and the caller's arrays may go)
+    for (int j = 0; j < count; ++j) zs->total[j] += kept[j];
+    return 0;
+}
+
+int wgs_zsum_totals(wgs_zsum *zs, int64_t *total_out)
+{
+    WGS_REQUIRE(zs && total_out, "null argument");
+    for (int j = 0; j < zs->count; ++j) total_out[j] = zs->total[j];
+    return 0;
+}
+
+int wgs_zsum_finish(wgs_zsum *zs, float *run_out, float *tails_out)
+{
+    WGS_REQUIRE(zs && run_out && tails_out, "null argument");
+    wgs_ctx *ctx = zs->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t cells = (size_t)zs->count * WGS_ZSUM_ARRAYS;
+    HIP_TRY(hipMemcpyAsync(run_out, zs->d_run, sizeof(float) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    size_t at = 0;
+    for (int j = 0; j < zs->count; ++j) {
+        const size_t fill = (size_t)(zs->total[j] % WGS_ZSUM_CHUNK);
+        for (int a = 0; a < WGS_ZSUM_ARRAYS && fill; ++a) {
+            const size_t e = (size_t)j * WGS_ZSUM_ARRAYS + a;
+            HIP_TRY(hipMemcpyAsync(tails_out + at, zs->d_tail + e * WGS_ZSUM_CHUNK, sizeof(float) * fill, hipMemcpyDeviceToHost, ctx->stream));
+            at += fill;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int wgs_zscore_classes_carry(wgs_depth *d, int32_t i0, int32_t count, wgs_zsum *zs, int32_t *counts_out, float *sums_out, int32_t *first_out,
+                             int32_t *over_out)
+{
+    WGS_REQUIRE(d && zs && counts_out && sums_out && first_out && over_out, "null argument");
+    WGS_REQUIRE(d->b, "the depth table was created without a matrix (wgs_depth_create_shape)");
+    WGS_REQUIRE(count == zs->count, "the sum state holds %d individuals, the sweep %d", zs->count, count);
+    wgs_beagle *b = d->b;
+    wgs_ctx *ctx = b->ctx;
+    WGS_REQUIRE(ctx == zs->ctx, "the sum state and the depth table belong to different contexts");
+    std::vector<ZInd> inds;
+    if (int rc = zs_fill_inds(b, i0, count, inds)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ZBufs bufs;
+    ZInd *d_inds = nullptr;
+    int32_t *cnt = nullptr, *first = nullptr, *over = nullptr;
+    const size_t cells = (size_t)count * 256;
+    HIP_TRY(bufs.get(&d_inds, sizeof(ZInd) * count));
+    HIP_TRY(bufs.get(&cnt, sizeof(int32_t) * cells));
+    HIP_TRY(bufs.get(&first, sizeof(int32_t) * cells));
+    HIP_TRY(bufs.get(&over, sizeof(int32_t) * count));
+    HIP_TRY(hipMemcpyAsync(d_inds, inds.data(), sizeof(ZInd) * count, hipMemcpyHostToDevice, ctx->stream));
+    // the first window starts the chains at 0, every later one goes on from what the window before left in the state
+    if (launch_zclass(ctx, d_inds, count, d->table, b->m, d->mpad, cnt, zs->d_class, first, over, zs->class_windows > 0)) return 1;
+    std::vector<int32_t> h_cnt(cells), h_first(cells);
+    std::vector<float> h_sums(3 * cells);
+    HIP_TRY(hipMemcpyAsync(h_cnt.data(), cnt, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_first.data(), first, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_sums.data(), zs->d_class, sizeof(float) * 3 * cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(over_out, over, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    zs->class_windows += 1;
+    for (int j = 0; j < count; ++j) {
+        memcpy(counts_out + (size_t)j * WGS_Z_NKEYS, h_cnt.data() + (size_t)j * 256, sizeof(int32_t) * WGS_Z_NKEYS);
+        memcpy(first_out + (size_t)j * WGS_Z_NKEYS, h_first.data() + (size_t)j * 256, sizeof(int32_t) * WGS_Z_NKEYS);
+        memcpy(sums_out + (size_t)j * WGS_Z_NKEYS * 3, h_sums.data() + (size_t)j * 256 * 3, sizeof(float) * 3 * WGS_Z_NKEYS);
+    }
+    return 0;
+}
+
+int wgs_depth_copy_rows(wgs_depth *dst, int64_t dst_row0, wgs_depth *src, int64_t src_row0, int64_t nrows)
+{
+    WGS_REQUIRE(dst && src && dst != src, "null argument");
+    WGS_REQUIRE(dst->ctx == src->ctx && dst->n == src->n, "the two depth tables differ in context or individuals (%lld, %lld)",
+                (long long)dst->n, (long long)src->n);
+    WGS_REQUIRE(nrows >= 0 && dst_row0 >= 0 && dst_row0 + nrows <= dst->m && src_row0 >= 0 && src_row0 + nrows <= src->m,
+                "rows [%lld, %lld) of %lld into rows [%lld, %lld) of %lld", (long long)src_row0, (long long)(src_row0 + nrows), (long long)src->m,
+                (long long)dst_row0, (long long)(dst_row0 + nrows), (long long)dst->m);
+    if (nrows == 0) return 0;
+    wgs_ctx *ctx = dst->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpy2DAsync(dst->table + dst_row0, (size_t)dst->mpad * sizeof(uchar2), src->table + src_row0, (size_t)src->mpad * sizeof(uchar2),
+                             (size_t)nrows * sizeof(uchar2), (size_t)dst->n, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -480,6 +694,19 @@ int wgs_em_fit_masked_sharded(wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot
 {
     WGS_REQUIRE(kept_total, "null argument");
     return em_fit_masked(em, zk, fit_slot, max_iter, tole, kept_total, comm, iters_out);
+}
+
+/* Test hook (include/wgsassign_hip_debug.h): a push of HOST arrays -- [3][all], as wgs_zsum_push takes them on the device. */
+int wgs_debug_zsum_push(wgs_zsum *zs, const float *host_arrays, int64_t all, const int64_t *kept)
+{
+    WGS_REQUIRE(zs && kept && (all == 0 || host_arrays) && all >= 0, "null argument");
+    if (all == 0) return wgs_zsum_push(zs, nullptr, 0, kept);
+    HIP_TRY(hipSetDevice(zs->ctx->device));
+    ZBufs bufs;
+    float *d_x = nullptr;
+    HIP_TRY(bufs.get(&d_x, sizeof(float) * 3 * (size_t)all));
+    HIP_TRY(hipMemcpyAsync(d_x, host_arrays, sizeof(float) * 3 * (size_t)all, hipMemcpyHostToDevice, zs->ctx->stream));
+    return wgs_zsum_push(zs, d_x, all, kept);                // (waits for the stream before it returns)
 }
 
 }   // extern "C"

@@ -374,7 +374,82 @@ __global__ __launch_bounds__(256) void zsites_kernel(int64_t m, const unsigned l
     }
 }
 
+// np.sum of a contiguous float32 array, continued from window to window: NumPy adds the sums of consecutive 8192-element chunks to a
+// running float32 that starts at +0.0, and a full chunk is its pairwise routine's balanced tree over 64 leaves of 128 elements, a leaf
+// being eight strided accumulators r[k] = a[k] + a[8 + k] + ... + a[120 + k] closed as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)).
+// One workgroup per (chunk, individual, array).  The chunk is the elements [8192 c, 8192 (c + 1)) of the open chunk's `fill` elements
+// followed by the window's array; it is staged through LDS with coalesced loads, leaf l at float offset 136 l: the eight floats of
+// padding per leaf put the 32 lanes of a half-wave (4 leaves x 8 accumulators, stride 136 = 8 mod 32) on 32 distinct banks for every
+// ds_read_b32 of the accumulator loop.  Thread <-> (leaf, accumulator) for two leaves, then 64 threads close the leaves and the fixed
+// tree runs level by level.  Every add is one float32 rounding (the file is built without contraction; there is nothing to contract).
+constexpr int ZSUM_LEAF_PITCH = 136;
+__global__ __launch_bounds__(256) void zsum_chunk_kernel(const ZSumJob *__restrict__ jobs, float *__restrict__ csum)
+{
+    __shared__ float v[64 * ZSUM_LEAF_PITCH];
+    __shared__ float r[512];
+    const ZSumJob J = jobs[blockIdx.y];
+    if ((int)blockIdx.x >= J.nfull) return;                 // (uniform over the workgroup)
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * WGS_ZSUM_CHUNK;
+    for (int e = tid; e < WGS_ZSUM_CHUNK; e += 256) {
+        const int64_t g = e0 + e;                           // < nfull * 8192 <= fill + k
+        v[e + (e >> 7) * (ZSUM_LEAF_PITCH - 128)] = g < J.fill ? J.tail[g] : J.x[g - J.fill];
+    }
+    __syncthreads();
+    for (int h = 0; h < 2; ++h) {
+        const int leaf = (tid >> 3) + 32 * h, k = tid & 7;
+        const float *p = v + leaf * ZSUM_LEAF_PITCH + k;
+        float s = p[0];
+        for (int i = 1; i < 16; ++i) s = s + p[8 * i];
+        r[leaf * 8 + k] = s;
+    }
+    __syncthreads();
+    float *node = v;                                        // (the staged chunk has been read)
+    if (tid < 64) {
+        const float *q = r + tid * 8;
+        node[tid] = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+    }
+    __syncthreads();
+    for (int w = 32; w >= 1; w >>= 1) {
+        float s = 0.0f;
+        if (tid < w) s = node[2 * tid] + node[2 * tid + 1];
+        __syncthreads();
+        if (tid < w) node[tid] = s;
+        __syncthreads();
+    }
+    if (tid == 0) csum[J.cbase + blockIdx.x] = node[0];
+}
+
+// Behind the chunk sums, per (individual, array): the running value takes them serially in chunk order, and what the push leaves
+// behind its last full chunk becomes the open chunk -- appended to the old one when the push closed none, else taken from the
+// window's array alone (the old elements went into the first chunk, which zsum_chunk_kernel has read by now: stream order).
+__global__ __launch_bounds__(256) void zsum_close_kernel(const ZSumJob *__restrict__ jobs, const float *__restrict__ csum)
+{
+    const ZSumJob J = jobs[blockIdx.x];
+    const int tid = threadIdx.x;
+    if (tid == 0 && J.nfull > 0) {
+        float s = *J.run;
+        for (int c = 0; c < J.nfull; ++c) s = s + csum[J.cbase + c];
+        *J.run = s;
+    }
+    if (J.nfull == 0) {
+        for (int64_t e = tid; e < J.k; e += 256) J.tail[J.fill + e] = J.x[e];                 // fill + k < 8192
+    } else {
+        const int64_t src0 = (int64_t)J.nfull * WGS_ZSUM_CHUNK - J.fill;
+        const int64_t left = J.fill + J.k - (int64_t)J.nfull * WGS_ZSUM_CHUNK;                // < 8192
+        for (int64_t e = tid; e < left; e += 256) J.tail[e] = J.x[src0 + e];
+    }
+}
+
 }  // namespace
+
+int launch_zsum_push(wgs_ctx *ctx, const ZSumJob *d_jobs, int n_jobs, int max_full, float *csum)
+{
+    if (max_full > 0) hipLaunchKernelGGL(zsum_chunk_kernel, dim3(max_full, n_jobs), dim3(256), 0, ctx->stream, d_jobs, csum);
+    hipLaunchKernelGGL(zsum_close_kernel, dim3(n_jobs), dim3(256), 0, ctx->stream, d_jobs, csum);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 static int zs_ensure_log_table(wgs_ctx *ctx)
 {

@@ -18,6 +18,9 @@ window is there.  What may be used is FRACTION (0.8, the share wgs_loo gives its
 RESERVE (4 GiB, at most a quarter of the free memory: the ingest's text and line arrays -- up to 3 GiB of text per chunk
 when the device inflates -- the block sums of a sweep, the context's workspace).  A resident matrix needs m sites of it;
 windowed scoring holds TWO windows (the one being scored and the one being filled), each with its frequencies and codes.
+
+The other windowed routes have their own arithmetic below (fit_site_bytes, loo_site_bytes, ne_site_bytes, z_site_bytes) and, but for
+the fit, a variable of their own.
 """
 import os
 
@@ -27,6 +30,7 @@ RESERVE = 4 << 30
 ENV = "WGSASSIGN_WINDOW_SITES"
 ENV_LOO = "WGSASSIGN_LOO_WINDOW_SITES"      # the leave-one-out run is sent to windows by a variable of its own (see plan_loo)
 ENV_NE = "WGSASSIGN_NE_WINDOW_SITES"        # ... and so is --ne_obs (see plan_ne)
+ENV_Z = "WGSASSIGN_Z_WINDOW_SITES"          # ... and --get_assignment_z_score (see plan_z)
 SURELY_FITS = 64                # see surely_fits
 
 
@@ -213,3 +217,70 @@ def plan_ne(m, n, K, free_bytes, environ=None, counts=None, loo=False, P=1):
                           "frequency buffers, class codes and Fisher results); %d of the %d free bytes can be used" %
                           (ALIGN, n, 2 * ALIGN * per_site, max(0, budget(free_bytes)), free_bytes))
     return W
+
+
+Z_RESIDENT_BATCH = 64           # individuals per launch of the resident z-score path (zscore.assignment_z_scores)
+
+
+def z_state_bytes(count):
+    """Device bytes that `count` individuals carry from window to window in a windowed --get_assignment_z_score (csrc/zscore.h:
+    wgs_zsum), charged ONCE, not per site: per individual three open chunks of 8192 float32, three running values, the class sweep's
+    256 x 3 running sums and three job records of 48 bytes."""
+    return int(count) * (3 * ALIGN * 4 + 3 * 4 + 256 * 3 * 4 + 3 * 48)
+
+
+def z_site_bytes(n, K, count):
+    """Device bytes one site of ONE window takes in a windowed --get_assignment_z_score of n individuals against K populations, `count`
+    of them in the batch, from what the library allocates per site:
+
+        matrix       16 * ceil(n / 2)               one group, as --get_pop_like lays it out
+        depths       2 * n                          one byte pair per (individual, site) (csrc/zscore.h: wgs_depth)
+        frequencies  4 * K                          the window's rows of the frequency file (wgs_afset)
+        mask words   12 * count / 64, rounded up    per (individual of the batch, tile of 64 sites) the kept-site word and its offset
+                                                    (wgs_zkeep; the deep-site list of pass A takes the same and is gone by then)
+        statistics   12 * count                     the three compacted float32 arrays, at most one element per (individual, site)
+
+    The window that is being filled beside it is one more MATRIX (reader_cy.stream_windows holds two), nothing else: plan_z adds it."""
+    n, K, count = int(n), int(K), int(count)
+    return 16 * ((n + 1) // 2) + 2 * n + 4 * K + (12 * count + 63) // 64 + 12 * count
+
+
+def fits_resident_z(m, n, K, count, free_bytes):
+    """Whether the resident z-score run fits: matrix, depth table and frequencies of all m sites, and the masks and statistics of one
+    batch of at most Z_RESIDENT_BATCH individuals."""
+    return int(m) * z_site_bytes(n, K, min(int(count), Z_RESIDENT_BATCH)) <= budget(free_bytes)
+
+
+def z_batch(W, n, K, count, free_bytes):
+    """Individuals per round for windows of W sites: all `count` when their state and one window's objects fit beside the second
+    matrix, else the largest half, quarter, ... of them that does (at least one)."""
+    batch = max(1, int(count))
+    while batch > 1 and z_state_bytes(batch) + int(W) * (z_site_bytes(n, K, batch) + 16 * ((int(n) + 1) // 2)) > budget(free_bytes):
+        batch = (batch + 1) // 2
+    return batch
+
+
+def plan_z(m, n, K, count, free_bytes, environ=None):
+    """plan() for --get_assignment_z_score of `count` individuals: None when the resident objects fit (fits_resident_z) and
+    WGSASSIGN_Z_WINDOW_SITES does not ask for windows, else (W, batch): windows of W sites (a multiple of 8192) and rounds of `batch`
+    individuals.  batch = count -- one round, two passes over the files -- whenever the state of all of them (z_state_bytes) leaves
+    room for a window of 8192 sites beside the second matrix; otherwise the largest half, quarter, ... of them that does."""
+    forced = env_window_sites(environ, ENV_Z)
+    m, n, K, count = int(m), int(n), int(K), int(count)
+    if forced is None and fits_resident_z(m, n, K, count, free_bytes):
+        return None
+    batch = count
+    while True:
+        per_site = z_site_bytes(n, K, batch) + 16 * ((n + 1) // 2)
+        room = budget(free_bytes) - z_state_bytes(batch)
+        W = room // per_site // ALIGN * ALIGN if room > 0 else 0
+        if W >= ALIGN or batch == 1:
+            break
+        batch = (batch + 1) // 2
+    if forced is not None:
+        return forced, z_batch(forced, n, K, count, free_bytes)
+    if W < ALIGN:
+        raise MemoryError("windowed z-scores need two windows of %d sites x %d individuals on the device (%d bytes with the depths, "
+                          "frequencies, masks and statistics of one) and %d bytes of state per individual; %d of the %d free bytes can be "
+                          "used" % (ALIGN, n, ALIGN * per_site, z_state_bytes(1), max(0, budget(free_bytes)), free_bytes))
+    return W, batch

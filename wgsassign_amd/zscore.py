@@ -20,6 +20,11 @@ shard to shard (wgs_zscore_classes_sharded), the deep sites as lists put togethe
 as a carry (wgs_em_fit_masked_sharded), and the per-site arrays themselves, which rank 0 receives and concatenates in rank order --
 site order -- so that np.sum forms its pairwise sums over the same arrays as one process would.  Rank 0 prints and returns the
 z-scores; the other ranks return None.
+
+Site windows (assignment_z_scores_windowed): the assignment flavour for files whose matrix and depth table do
+not fit the device, on one rank.  The same hand-overs in time: the class sums stay on the device from window to window (ZSum.classes),
+and the three float32 sums are formed THERE in np.sum's own order -- serial over 8192-element chunks, each a pairwise tree -- from
+device arrays that are never downloaded (KeepSet.stats_dev, ZSum.push); the depth file is read once per pass (DepthWindows).
 """
 import ctypes
 import math
@@ -266,6 +271,15 @@ class KeepSet:
         cuts = np.cumsum(self.kept)[:-1]
         return [np.split(o, cuts) for o in out]
 
+    def stats_dev(self, tables, freq_dev):
+        """stats() that downloads nothing: (device pointer to [3][all] float32 owned by this set, all) -- what ZSum.push takes."""
+        tables = np.ascontiguousarray(tables, dtype=np.float32)
+        assert tables.shape == (self.count, N_CLASSES, 6)
+        ptrs = (ctypes.c_void_p * self.count)(*[int(p) for p in freq_dev])
+        dev, total = ctypes.c_void_p(), ctypes.c_int64()
+        check(_lib.load().wgs_zscore_stats_dev(self._h, f32p(tables), ptrs, ctypes.byref(dev), ctypes.byref(total)))
+        return dev, int(total.value)
+
     def close(self):
         if self._h:
             _lib.load().wgs_zkeep_destroy(self._h)
@@ -459,9 +473,11 @@ def stat_tables(summaries):
 
 
 def _finish(i, kept, wobs, wl, var, say):
-    W_l_obs = np.sum(wobs, dtype=np.float32)
-    z_mu = np.sum(wl)
-    z_var = np.sum(var)
+    return _finish_sums(i, kept, np.sum(wobs, dtype=np.float32), np.sum(wl), np.sum(var), say)
+
+
+def _finish_sums(i, kept, W_l_obs, z_mu, z_var, say):
+    """z and the printed lines of an individual from its three float32 sums."""
     with np.errstate(divide="ignore", invalid="ignore"):
         z_tmp = (W_l_obs - z_mu) / np.sqrt(z_var)
     say("Finished individual " + str(i))
@@ -598,3 +614,356 @@ def reference_z_scores(beagle, depth, IDs, group_of, maf_iter=200, maf_tole=1e-4
         em.close()
         keep.close()
     return z_out if not sharded(comm) or comm.rank == 0 else None
+
+
+# ---------------------------------------------------------------- --get_assignment_z_score in site windows
+class ZSum:
+    """What a batch of individuals carries from site window to site window on the device (wgs_zsum): the class sweep's running sums
+    and, per (individual, array) of the three per-site arrays, np.sum's float32 order -- the running value over the closed
+    8192-element chunks and the open chunk."""
+
+    def __init__(self, count, ctx=None):
+        from .device import get_context
+        self.ctx = ctx or get_context()
+        self.count = int(count)
+        self.downloaded = 0                          # bytes that crossed to the host through this object
+        h = ctypes.c_void_p()
+        check(_lib.load().wgs_zsum_create(self.ctx.handle, self.count, ctypes.byref(h)))
+        self._h = h
+        self.ctx._children.add(self)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def classes(self, depth, i0):
+        """The class sweep over the next window (wgs_zscore_classes_carry): counts, first sites (LOCAL, -1: none) and `over` of this
+        window, and the running sums after it."""
+        count = self.count
+        cnt = np.empty((count, N_CLASSES), dtype=np.int32)
+        sums = np.empty((count, N_CLASSES, 3), dtype=np.float32)
+        first = np.empty((count, N_CLASSES), dtype=np.int32)
+        over = np.empty(count, dtype=np.int32)
+        check(_lib.load().wgs_zscore_classes_carry(depth.handle, int(i0), count, self._h, i32p(cnt), f32p(sums), i32p(first), i32p(over)))
+        self.downloaded += cnt.nbytes + sums.nbytes + first.nbytes + over.nbytes
+        return cnt, sums, first, over
+
+    def push(self, dev, total, kept):
+        kept = np.ascontiguousarray(kept, dtype=np.int64)
+        check(_lib.load().wgs_zsum_push(self._h, dev, int(total), kept.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+
+    def push_host(self, arrays, kept):
+        """Test hook (wgs_debug_zsum_push): arrays (3, all) float32 on the host."""
+        arrays = np.ascontiguousarray(arrays, dtype=np.float32)
+        kept = np.ascontiguousarray(kept, dtype=np.int64)
+        assert arrays.ndim == 2 and arrays.shape[0] == 3
+        check(_lib.load().wgs_debug_zsum_push(self._h, f32p(arrays), arrays.shape[1], kept.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+
+    def totals(self):
+        out = np.zeros(self.count, dtype=np.int64)
+        check(_lib.load().wgs_zsum_totals(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def state(self):
+        """(totals (count,), run (count, 3) float32, tails: [j][a] float32 arrays of totals[j] % 8192 elements) as the device holds them."""
+        totals = self.totals()
+        fill = totals % 8192
+        run = np.zeros((self.count, 3), dtype=np.float32)
+        packed = np.zeros(max(1, 3 * int(fill.sum())), dtype=np.float32)
+        check(_lib.load().wgs_zsum_finish(self._h, f32p(run), f32p(packed)))
+        self.downloaded += run.nbytes + 12 * int(fill.sum())
+        tails, at = [], 0
+        for j in range(self.count):
+            tails.append([packed[at + a * fill[j]:at + (a + 1) * fill[j]] for a in range(3)])
+            at += 3 * int(fill[j])
+        return totals, run, tails
+
+    def finish(self):
+        """(totals, sums (count, 3) float32): np.sum of everything pushed.  The ragged last chunk is closed here as NumPy closes it,
+        run + np.sum(tail): exact, because a running value that started at +0.0 is never -0.0; nothing is added for an empty tail."""
+        totals, run, tails = self.state()
+        sums = np.empty((self.count, 3), dtype=np.float32)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for j in range(self.count):
+                for a in range(3):
+                    sums[j, a] = run[j, a] + np.sum(tails[j][a]) if tails[j][a].size else run[j, a]
+        return totals, sums
+
+    def close(self):
+        if self._h:
+            _lib.load().wgs_zsum_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _ShapeTable:
+    """A depth table of its own shape (wgs_depth_create_shape): the landing place of a depth file's chunks."""
+
+    def __init__(self, ctx, rows, n):
+        h = ctypes.c_void_p()
+        check(_lib.load().wgs_depth_create_shape(ctx.handle, int(rows), int(n), ctypes.byref(h)))
+        self.handle, self.rows = h, int(rows)
+
+    def close(self):
+        if self.handle:
+            _lib.load().wgs_depth_destroy(self.handle)
+            self.handle = None
+
+
+DEPTH_WINDOW_CHUNK = 8 << 20         # text bytes per chunk of a windowed depth pass
+
+
+class DepthWindows:
+    """ONE pass over a depth file whose rows go to consecutive window tables: one reader and one ingest stay open, the file is read
+    once, and its chunks land in a small table of their own (at row 0) from which the rows are copied on the device to the window
+    that owns them (wgs_depth_copy_rows) -- whichever edge a chunk straddles.  Line numbers in messages are the file's, and the
+    number of data lines is compared with m at the end of the pass (finish).  counts=True: ANGSD counts with the (m, 2) selectors
+    `majmin`, of which every chunk is handed the rows [lines so far, ...).  A .npy file (pairs) is read through np.load(mmap_mode="r")
+    rows.  .stats after finish: wgs_depth_ingest_stats of the pass (text files)."""
+
+    def __init__(self, path, m, n, ctx, counts=False, majmin=None, chunk_bytes=None, threads=None):
+        from .reader_cy import host_threads
+        self.path, self.m, self.n, self.ctx, self.counts = str(path), int(m), int(n), ctx, bool(counts)
+        self.lines, self.lo, self.pending = 0, 0, 0      # data lines read; rows [lo, lo + pending) of the staging table wait for a window
+        self.stats, self._r, self._g, self._stage, self._npy = None, ctypes.c_void_p(), ctypes.c_void_p(), None, None
+        if self.path.endswith(".npy") and not counts:
+            AD = np.load(self.path, mmap_mode="r")
+            if AD.ndim != 2 or AD.shape[0] != self.m or AD.shape[1] < 2 * self.n:
+                raise ValueError("allele depths have shape %s, the Beagle file has %d sites and %d individuals" % (AD.shape, self.m, self.n))
+            self._npy = AD
+            return
+        lib = _lib.load()
+        tpi = 4 if counts else 2
+        chunk = int(chunk_bytes or DEPTH_WINDOW_CHUNK)
+        # a data line holds at least tpi * n tokens of one character and a separator each: a bound on the lines of one chunk, with
+        # room for the carried partial line and a BGZF member beyond the chunk's size.  (A chunk that still held more lines would be
+        # refused below, not truncated.)
+        self.stage_rows = max(1024, 2 * (max(chunk, 65536) + (1 << 17)) // (2 * tpi * self.n) + 1024)
+        if counts:
+            self.majmin = np.ascontiguousarray(majmin, dtype=np.uint8)
+            if self.majmin.shape != (self.m, 2):
+                raise ValueError("the allele selectors have shape %s, the table %d sites" % (self.majmin.shape, self.m))
+        try:
+            check(lib.wgs_reader_open_table(os.fsencode(self.path), int(threads or host_threads()), 1 if counts else 0, ctypes.byref(self._r)))
+            self._stage = _ShapeTable(ctx, self.stage_rows, self.n)
+            sel = self._selectors() if counts else None
+            check(lib.wgs_depth_ingest_create(self._stage.handle, self._r, 1 if counts else 0, sel.ctypes.data if counts else None, -1, chunk,
+                                              ctypes.byref(self._g)))
+        except ValueError as e:
+            self.close()
+            raise self._named(e) from None
+        except Exception:
+            self.close()
+            raise
+
+    def _named(self, e):
+        return e if self.path in str(e) else ValueError("%s: %s" % (self.path, e))
+
+    def _selectors(self):
+        """The selectors of the staging table's rows for the next chunk: the file's rows [lines, lines + stage_rows)."""
+        sel = np.zeros((self.stage_rows, 2), dtype=np.uint8)
+        rows = self.majmin[self.lines:self.lines + self.stage_rows]
+        sel[:len(rows)] = rows
+        return sel
+
+    def _next_chunk(self):
+        lib = _lib.load()
+        got, wrote = ctypes.c_int64(), ctypes.c_int64()
+        try:
+            if self.counts and self.lines:
+                sel = self._selectors()
+                check(lib.wgs_depth_ingest_set_selectors(self._g, sel.ctypes.data, self.stage_rows))
+            check(lib.wgs_depth_ingest_next(self._g, 0, ctypes.byref(got), ctypes.byref(wrote)))
+        except ValueError as e:
+            raise self._named(e) from None
+        if got.value and wrote.value != got.value:
+            raise RuntimeError("%s: a chunk of %d data lines does not fit the %d rows it is staged in" % (self.path, got.value, self.stage_rows))
+        self.lines += got.value
+        self.lo, self.pending = 0, got.value
+        return got.value
+
+    def fill(self, table, rows):
+        """The file's next `rows` data rows into rows [0, rows) of the DepthTable `table`."""
+        rows, at = int(rows), 0
+        if self._npy is not None:
+            step = max(1, (64 << 20) // (8 * self.n))
+            for r in range(0, rows, step):
+                table.upload_rows(np.asarray(self._npy[self.lines + r:self.lines + min(rows, r + step)]), r)
+            self.lines += rows
+            return
+        while at < rows:
+            if not self.pending and not self._next_chunk():
+                raise ValueError("%s has %d data lines, %d sites were expected" % (self.path, self.lines, self.m))
+            take = min(self.pending, rows - at)
+            check(_lib.load().wgs_depth_copy_rows(table.handle, at, self._stage.handle, self.lo, take))
+            at, self.lo, self.pending = at + take, self.lo + take, self.pending - take
+
+    def finish(self):
+        """The end of the pass: whatever the file still holds is read and counted, and the total must be m."""
+        if self._npy is None:
+            while self._next_chunk():
+                pass
+            if self.lines != self.m:
+                raise ValueError("%s has %d data lines, %d sites were expected" % (self.path, self.lines, self.m))
+            stats = np.zeros(8, dtype=np.float64)
+            check(_lib.load().wgs_depth_ingest_stats(self._g, stats.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+            self.stats = dict(zip(("host_peak_bytes", "device_ms", "host_lines", "text_bytes", "lines", "chunks", "members_on_device",
+                                   "tokenise_ms"), stats.tolist()))
+        self.close()
+        return self.stats
+
+    def close(self):
+        lib = _lib.load()
+        if self._g:
+            lib.wgs_depth_ingest_destroy(self._g)
+            self._g = ctypes.c_void_p()
+        if self._r:
+            lib.wgs_reader_close(self._r)
+            self._r = ctypes.c_void_p()
+        if self._stage is not None:
+            self._stage.close()
+            self._stage = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def merge_windows(cnt_tot, first_glob, over_tot, site0, cnt, first, over):
+    """One more window into the class sweep's host totals: counts and `over` add (int64), a first site is the smallest GLOBAL number
+    site0 + local among the windows that have the class (-1: none yet).  Windows come in site order, so the first one to have a class
+    sets it."""
+    cnt_tot += cnt
+    over_tot += over
+    new = (first_glob < 0) & (first >= 0)
+    first_glob[new] = int(site0) + first[new].astype(np.int64)
+
+
+def assignment_z_scores_windowed(path, depth_path, A, IDs, pops, n_threshold=0, single_read_threshold=False, ind_start=0, ind_end=None,
+                                 window_sites=None, say=print, details=None, deep=True, counts=False, majmin=None, batch=None, ctx=None,
+                                 depth_chunk_bytes=None):
+    """assignment_z_scores for a Beagle FILE and a depth FILE whose matrix and depth table need not fit the device: two passes over
+    both files in consecutive windows of `window_sites` sites (a multiple of 8192, rounded down; None: WGSASSIGN_Z_WINDOW_SITES, else
+    what windows.plan_z derives -- one window when everything fits), all individuals of [ind_start, ind_end) together (or in rounds
+    of `batch` individuals, each with its two passes, when windows.plan_z says their state does not fit beside a window).
+      Pass A: the class sweep with its running sums carried from window to window (ZSum.classes); counts, `over` and first sites are
+              put together here as global numbers; windows with sites deeper than 21 reads list them (wgs_zscore_deep_sites).
+      Then the dictionaries, the key filter and the tables, once, as the resident path forms them.
+      Pass B: per window the mask, the statistic sweep into device arrays and the push into np.sum's order (ZSum.push); the
+              frequency columns are rows [site0, site0 + m_w) of A (an array or an np.load(..., mmap_mode="r") view).
+    z, every printed line and the assertions of the key filter are those of the resident run, bit for bit.  details (a list) receives
+    per individual the dictionary, the tables, kept (sites kept) and the sums -- no per-site array.  Host memory does not grow with m.
+    .stats: windows, window_sites, rounds, seconds_a / seconds_b and depth_a / depth_b (the depth ingest's statistics) per round,
+    downloaded_bytes; .info: n, m, sample_names, site_names (first and last four)."""
+    import time
+
+    from . import reader_cy, windows
+    from .device import AFSet, get_context
+    ctx = ctx or get_context()
+    index, _, m = reader_cy.ensure_index(path)
+    if m <= 0:
+        raise ValueError("%s holds no sites" % path)
+    if A.ndim != 2 or A.shape[0] != m:
+        raise ValueError("the allele frequency file has %d sites, the Beagle file %d" % (A.shape[0], m))
+    with reader_cy.BeagleStream(path, threads=1) as st:
+        n = st.n
+    ind_end = n if ind_end is None else ind_end
+    total = ind_end - ind_start
+    if window_sites is None:
+        planned = windows.plan_z(m, n, A.shape[1], total, ctx.mem_info()[0])
+        W, batch = planned if planned is not None else (max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN, batch)
+    else:
+        if int(window_sites) < windows.ALIGN:
+            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
+        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+    batch = windows.z_batch(W, n, A.shape[1], total, ctx.mem_info()[0]) if not batch else min(int(batch), total)
+    rounds = list(_batches(ind_start, ind_end, batch))
+    if len(rounds) > 1:
+        say("wgsassign_amd: the z-scores of %d individuals run in %d rounds of at most %d" % (total, len(rounds), batch))
+    z_out = np.empty((total, 1), dtype=np.float32)
+    info = {}
+    stats = dict(windows=0, window_sites=W, rounds=len(rounds), seconds_a=[], seconds_b=[], depth_a=[], depth_b=[], downloaded_bytes=0)
+
+    def one_pass(zs, body):
+        """body(b, depth) for every window of the file, the window's depth rows in place; the depth ingest's statistics."""
+        dw = DepthWindows(depth_path, m, n, ctx, counts, majmin, depth_chunk_bytes)
+        gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info)
+        try:
+            for b in gen:
+                depth = DepthTable(b)
+                try:
+                    dw.fill(depth, b.m)
+                    body(b, depth)
+                finally:
+                    depth.close()
+            return dw.finish()
+        finally:
+            gen.close()
+            dw.close()
+
+    for i0, count in rounds:
+        zs = ZSum(count, ctx)
+        try:
+            cnt_tot = np.zeros((count, N_CLASSES), dtype=np.int64)
+            first_glob = np.full((count, N_CLASSES), -1, dtype=np.int64)
+            over_tot = np.zeros(count, dtype=np.int64)
+            last = {}
+            parts = [[] for _ in range(count)]
+
+            def pass_a(b, depth):
+                cnt, sums, first, over = zs.classes(depth, i0)
+                merge_windows(cnt_tot, first_glob, over_tot, b.site0, cnt, first, over)
+                last["sums"] = sums
+                if deep and over.any():
+                    for j, (site, ad, g) in enumerate(list_deep_sites(depth, i0, count, over)):
+                        if len(site):
+                            parts[j].append((site.astype(np.int64) + b.site0, ad, g))
+                            zs.downloaded += site.nbytes + ad.nbytes + g.nbytes
+
+            t0 = time.perf_counter()
+            stats["depth_a"].append(one_pass(zs, pass_a))
+            stats["seconds_a"].append(time.perf_counter() - t0)
+            empty = (np.empty(0, dtype=np.int64), np.empty((0, 2), dtype=np.int32), np.empty((0, 2), dtype=np.float32))
+            listed = [concat_deep(p) if p else empty for p in parts] if deep and over_tot.any() else None
+            summ = dictionaries(i0, cnt_tot, first_glob, last["sums"], over_tot, listed, n_threshold, single_read_threshold, deep)
+            key_mean, key_comp = mask_tables(summ)
+            dmap, drows = deep_tables(summ)
+            tabs, tparts = stat_tables(summ)
+            cols = [int(np.argwhere(pops == IDs[i0 + j, 1])[0][0]) for j in range(count)]
+            kept_tot = np.zeros(count, dtype=np.int64)
+
+            def pass_b(b, depth):
+                keep = KeepSet(depth, i0, key_mean, key_comp, dmap, drows)
+                afs = AFSet.from_host(np.ascontiguousarray(A[b.site0:b.site0 + b.m], dtype=np.float32), ctx=ctx)
+                try:
+                    dev, all_kept = keep.stats_dev(tabs, [afs.col_dev(k) for k in cols])
+                    zs.push(dev, all_kept, keep.kept)
+                    kept_tot[:] += keep.kept
+                finally:
+                    afs.close()
+                    keep.close()
+
+            t0 = time.perf_counter()
+            stats["depth_b"].append(one_pass(zs, pass_b))
+            stats["seconds_b"].append(time.perf_counter() - t0)
+            totals, sums3 = zs.finish()
+            assert np.array_equal(totals, kept_tot)
+            for j in range(count):
+                r = _finish_sums(i0 + j, kept_tot[j], sums3[j, 0], sums3[j, 1], sums3[j, 2], say)
+                z_out[i0 + j - ind_start, 0] = r["z"]
+                if details is not None:
+                    details.append(dict(summ[j], fac=tparts[j][0], like=tparts[j][1], index=tparts[j][2], kept=int(kept_tot[j]), **r))
+            stats["downloaded_bytes"] += zs.downloaded
+        finally:
+            zs.close()
+    stats["windows"] = info.get("windows", 0)
+    assignment_z_scores_windowed.stats = stats
+    assignment_z_scores_windowed.info = dict({k: info.get(k) for k in ("m", "sample_names", "site_names")}, n=n)
+    return z_out
