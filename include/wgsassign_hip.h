@@ -52,7 +52,8 @@ const char *wgs_last_error(void);
  * shards (wgs_zscore_classes_sharded, wgs_em_fit_masked_sharded, wgs_depth_ingest_set_first_row, WGS_OP_Z_CLASS, WGS_OP_Z_CHAIN), and
  * windowed scoring (wgs_score_stream_*, wgs_beagle_set_window).  4: --ne_obs in site windows (wgs_fisher_stream_*); no existing
  * signature changed.  --get_assignment_z_score in site windows (wgs_zsum_*, wgs_zscore_classes_carry, wgs_zscore_stats_dev,
- * wgs_depth_copy_rows, wgs_depth_ingest_set_selectors) was ADDED under 4. */
+ * wgs_depth_copy_rows, wgs_depth_ingest_set_selectors) was ADDED under 4, and so was --get_reference_z_score in site windows
+ * (wgs_em_stream_push_masked). */
 #define WGS_ABI_VERSION 4
 int wgs_version(void);
 /* sha256[:16] over every source of the library / over the sources of the EM and scoring kernels (em_kernels.hip,
@@ -714,6 +715,22 @@ int wgs_depth_copy_rows(wgs_depth *dst, int64_t dst_row0, wgs_depth *src, int64_
 /* WGS_DEPTH_COUNTS: the selectors of the table's rows 0 .. nrows - 1 for the chunks to come (majmin[row][2], each 0..3), in place of
  * those wgs_depth_ingest_create was given -- for an ingest whose table takes every chunk at row 0. */
 int wgs_depth_ingest_set_selectors(wgs_depth_ingest *g, const uint8_t *majmin, int64_t nrows);
+
+/* ---- --get_reference_z_score in site windows: the leave-one-out fit of every individual's population whose
+ * stopping test runs over THAT individual's kept sites (wgs_em_fit_masked), window by window.  wgs_em_stream_push_masked is
+ * wgs_em_stream_push_keep without sums, plus the window's kept-site set: the exact chain of (fit, t) named in chain_fit / chain_iter runs
+ * over (f_t, f_t-1) at the sites slot fit_slot[fit] of `zk` kept in this window, compacted in site order (every chain job of an iteration
+ * by one launch), goes on from C[t][fit] and leaves its carry there -- as the chain of wgs_em_fit_masked_sharded goes from SNP shard to
+ * SNP shard.  A fit whose individual kept nothing in this window hands C[t][fit] on bit for bit.  A final fit is clamped and stays in
+ * the batch (wgs_em_f_dev).  Nothing joins S, nothing of the window's size crosses to the host, and nothing is read back between the
+ * iterations: the host reads C once per round (wgs_em_stream_read) and decides with wgs_em_fit_masked's rule, carry against the
+ * kept sites of ALL windows.  The compacted vectors (2 x n_fits x the window's largest kept count, zero behind a fit's own count) are
+ * the stream's and grow when a window needs more.  Refused before any launch (rc 2): what wgs_em_stream_push_keep refuses, a `zk` made
+ * from another matrix than the batch's, a fit_slot outside `zk`, a chain of an iteration beyond its fit's run_iters.  `zk` and its
+ * depth table must be destroyed before wgs_em_stream_move_window moves the matrix.  Added under ABI version 4: a new symbol only. */
+int wgs_em_stream_push_masked(wgs_em_stream *stream, wgs_em *window_em, wgs_zkeep *zk, const int32_t *fit_slot, const int32_t *run_iters,
+                              const int32_t *final, const float *clamp_lo, const float *clamp_hi, const int32_t *chain_fit,
+                              const int32_t *chain_iter, int32_t n_chain);
 
 /* Blocks of 4096 elements that fell back to the serial loop in the last wgs_em_rmse_chain of an EM batch (diagnostics). */
 int wgs_em_last_chain_serial_blocks(wgs_em *em);

@@ -23,15 +23,38 @@ def bgzf_member(chunk, level=6):
     return bgzf_member_raw(co.compress(chunk) + co.flush(), zlib.crc32(chunk), len(chunk))
 
 
-def lowdepth_pool(n, pool, seed=1, depth=2.0):
-    """(text rows as uint8 (pool, 27 n), values float32 (pool, 2 n)): '\\td.dddddd' per likelihood, three per individual."""
+def lowdepth_reads(n, pool, seed=1, depth=2.0):
+    """(ref, alt) read counts of the pool's rows, int64 (pool, n) each: what lowdepth_pool forms its likelihoods from."""
     rng = np.random.default_rng(seed)
     p = np.clip(rng.beta(0.8, 0.8, size=(pool, 1)) + rng.normal(0.0, 0.08, size=(pool, n)), 0.01, 0.99)
     geno = rng.binomial(2, p)
     d = rng.poisson(depth, size=(pool, n))
+    alt = rng.binomial(d, np.array([0.01, 0.5, 0.99])[geno])
+    return d - alt, alt
+
+
+def write_lowdepth_depths(path, n, m, pool=512, seed=1):
+    """The allele-depth file (text, --ind_ad_file) that goes with write_lowdepth_bgzf(path, n, m, pool, seed): line s holds the read
+    counts behind the likelihoods of the Beagle file's line s.  Returns the text bytes."""
+    ref, alt = lowdepth_reads(n, min(pool, m), seed)
+    AD = np.empty((ref.shape[0], 2 * n), dtype=np.int64)
+    AD[:, 0::2], AD[:, 1::2] = ref, alt
+    rows = [(" ".join(map(str, r)) + "\n").encode() for r in AD]
+    pick = np.random.default_rng(seed + 1).integers(0, len(rows), size=m)
+    total = 0
+    with open(path, "wb") as fh:
+        for s in range(0, m, 65536):
+            data = b"".join(rows[k] for k in pick[s:s + 65536])
+            total += len(data)
+            fh.write(data)
+    return total
+
+
+def lowdepth_pool(n, pool, seed=1, depth=2.0):
+    """(text rows as uint8 (pool, 27 n), values float32 (pool, 2 n)): '\\td.dddddd' per likelihood, three per individual."""
+    ref, alt = lowdepth_reads(n, pool, seed, depth)
+    d = ref + alt
     e = 0.01
-    alt = rng.binomial(d, np.array([e, 0.5, 1.0 - e])[geno])
-    ref = d - alt
     l0, l1, l2 = (1 - e) ** ref * e ** alt, 0.5 ** d, (1 - e) ** alt * e ** ref
     tot = l0 + l1 + l2
     a = np.rint(l0 / tot * 1e6).astype(np.int64)

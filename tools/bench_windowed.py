@@ -7,6 +7,7 @@
     python tools/bench_windowed.py --loo [...] [--out profiles/windowed_loo_bench.json]      # the same for --get_reference_af --loo
     python tools/bench_windowed.py --ne [...] [--out profiles/windowed_ne_obs_bench.json]    # the same for --get_reference_af --ne_obs
     python tools/bench_windowed.py --z [...] [--out profiles/z_windowed.json]                # the same for --get_assignment_z_score
+    python tools/bench_windowed.py --zref [...] [--out profiles/zref_windowed.json]          # the same for --get_reference_z_score
 
 The file comes from tools/beagle_files.py (seeded, seconds to write).  Every end-to-end figure is the wall time of one
 `python -m wgsassign_amd.WGSassign --get_pop_like` process -- interpreter start, HIP initialisation, ingest, scoring, the text
@@ -39,7 +40,13 @@ file's, and the bytes that crossed to the host.  No time target is set: the numb
 What to expect: the device's share of an ingest (BGZF inflate, tokeniser) and the sweeps use the context's one stream and every push
 waits for it, so for a BGZF file the device work of consecutive windows is strictly serial; what overlaps a window's sweep is only
 the producer thread's reading of the next window (for plain gzip also its inflate).  The windowed run therefore costs the resident
-run plus, per window, a reader opened through the index, an ingest created, and the launches and synchronisations of one sweep."""
+run plus, per window, a reader opened through the index, an ingest created, and the launches and synchronisations of one sweep.
+--zref measures --get_reference_z_score (pass A, the fit rounds of the masked leave-one-out fits and the final round, each a pass over
+both files; WGSASSIGN_ZREF_WINDOW_SITES): the whole-process figures, their ratio windowed / resident with the pass count, and from one
+zscore.reference_z_scores_windowed in this process the seconds of every pass, the fit rounds, the horizons used, and the bytes that
+crossed to the host.  The resident run's stopping iterations (minimum, median, maximum, and how many fits were exhausted) are read
+from its printed lines: the first horizon (zscore.ZREF_FIRST_HORIZON) is to be set from that record.  What to expect:
+(1 + fit rounds + 1) passes x the cost of one windowed pass, plus the resident fit time x (iterations run / iterations needed)."""
 import argparse
 import json
 import os
@@ -55,17 +62,20 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 
 
-def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False, ne=False, z=None):
+def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False, ne=False, z=None, zref=None):
     """af: the frequency file of --get_pop_like, or with fit (or loo, or ne) the ID file of --get_reference_af.  z: the further
-    arguments of --get_assignment_z_score (ID, names and depth files), which then stands in place of --get_pop_like."""
+    arguments of --get_assignment_z_score (ID, names and depth files), which then stands in place of --get_pop_like.  zref: all the
+    arguments of --get_reference_z_score (af is not looked at).  cli_seconds.stdout: what the last command printed."""
     env = dict(os.environ)
     env.pop("WGSASSIGN_WINDOW_SITES", None)
     env.pop("WGSASSIGN_LOO_WINDOW_SITES", None)
     env.pop("WGSASSIGN_NE_WINDOW_SITES", None)
     env.pop("WGSASSIGN_Z_WINDOW_SITES", None)
+    env.pop("WGSASSIGN_ZREF_WINDOW_SITES", None)
     env.update(env_extra)
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
     what = (["--pop_af_IDs", af, "--get_reference_af"] + (["--loo"] if loo else []) + (["--ne_obs"] if ne else []) if fit or loo or ne
+            else ["--get_reference_z_score"] + list(zref) if zref is not None
             else ["--pop_af_file", af, "--get_assignment_z_score"] + list(z) if z is not None
             else ["--pop_af_file", af, "--get_pop_like"])
     t0 = time.perf_counter()
@@ -74,6 +84,7 @@ def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False, ne=False
     dt = time.perf_counter() - t0
     if r.returncode != 0:
         raise RuntimeError("the command line failed in %s:\n%s" % (root, r.stderr[-2000:]))
+    cli_seconds.stdout = r.stdout
     return dt, r.stderr
 
 
@@ -311,8 +322,64 @@ def z_leg(a, m, n, K, W):
     return res
 
 
+def zref_leg(a, m, n, K, W):
+    """--get_reference_z_score resident against windowed; one JSON-able dict."""
+    import beagle_files
+    from wgsassign_amd import device, zscore
+    res = {"bench": "windowed_reference_z_score", "snps": m, "inds": n, "pops": K, "window_sites": W, "windows": a.windows}
+    with tempfile.TemporaryDirectory() as td:
+        os.environ["WGSASSIGN_INDEX_DIR"] = td
+        bg, ids, names = (os.path.join(td, x) for x in ("x.beagle.gz", "ids.txt", "names.txt"))
+        beagle_files.write_lowdepth_bgzf(bg, n, m, seed=5)
+        IDs = np.array([["Ind%d" % i, "pop%d" % (i * K // n)] for i in range(n)])
+        np.savetxt(ids, IDs, fmt="%s", delimiter="\t")
+        pops = np.unique(IDs[:, 1])
+        group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
+        np.savetxt(names, pops, fmt="%s")
+        # the read counts behind the Beagle file's likelihoods: the masked fits need kept sites, which unrelated depths do not give
+        ad = os.path.join(td, "ad.txt")
+        depth_text_bytes = beagle_files.write_lowdepth_depths(ad, n, m, seed=5)
+        res.update(file_mb=round(os.path.getsize(bg) / 1e6, 1), depth_file_mb=round(depth_text_bytes / 1e6, 1))
+        argv = ["--pop_af_IDs", ids, "--pop_names", names, "--ind_ad_file", ad]
+        variants = [("resident_s", ROOT, {})]
+        if a.parent_root:
+            variants.insert(0, ("parent_resident_s", os.path.abspath(a.parent_root), {}))
+        variants.append(("windowed_s", ROOT, {"WGSASSIGN_ZREF_WINDOW_SITES": str(W)}))
+        times = {name: [] for name, _, _ in variants}
+        resident_lines = []
+        for rep in range(a.repeats + 1):
+            for name, root, env in variants:
+                dt, err = cli_seconds(root, bg, None, os.path.join(td, name), env, zref=argv)
+                print("%s: %.1f s" % (name, dt), file=sys.stderr, flush=True)
+                if rep:
+                    times[name].append(dt)
+                if name == "resident_s":
+                    resident_lines = cli_seconds.stdout.splitlines()
+                if name == "windowed_s" and ("passes over %d windows" % a.windows) not in err:
+                    raise RuntimeError("the windowed run did not use %d windows: %s" % (a.windows, err[-300:]))
+        files = {name: open(os.path.join(td, name + ".reference_z_ind.txt"), "rb").read() for name, _, _ in variants}
+        res["outputs_identical"] = len(set(files.values())) == 1
+        for name in ("parent_resident_s", "resident_s", "windowed_s"):
+            res[name] = spread(times[name]) if name in times else None
+        res["windowed_over_resident"] = round(res["windowed_s"]["median"] / res["resident_s"]["median"], 3)
+        # the resident run's stopping iterations, from its own lines: what the first horizon is to be set from
+        stops = [int(ln.rsplit(" ", 1)[1]) for ln in resident_lines if ln.startswith("EM (MAF) converged at iteration: ")]
+        res["resident_stopping_iterations"] = ({"min": min(stops), "median": statistics.median(stops), "max": max(stops), "fits": len(stops),
+                                                "exhausted": n - len(stops)} if stops else {"fits": 0, "exhausted": n})
+        ctx = device.get_context()
+        res["device"] = ctx.info()["name"].strip()
+        for rep in range(2):
+            zscore.reference_z_scores_windowed(bg, ad, IDs, group_of, 200, 1e-4, window_sites=W, say=lambda *_: None, ctx=ctx)
+        st = zscore.reference_z_scores_windowed.stats
+        res.update(rounds=st["rounds"], passes=st["passes"], fit_rounds=st["fit_rounds"], horizons=st["horizons"], first_horizon=st["first_horizon"],
+                   pass_a_seconds=[round(x, 3) for x in st["seconds_a"]], fit_round_seconds=[[round(x, 3) for x in r] for r in st["seconds_fit"]],
+                   final_round_seconds=[[round(x, 3) for x in r] for r in st["seconds_final"]], downloaded_bytes=int(st["downloaded_bytes"]))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--zref", action="store_true", help="measure --get_reference_z_score (the reference z-scores in windows)")
     ap.add_argument("--z", action="store_true", help="measure --get_assignment_z_score (the z-scores in windows)")
     ap.add_argument("--ne", action="store_true", help="measure --get_reference_af --ne_obs (the Fisher information in windows)")
     ap.add_argument("--probe", action="store_true", help="with --ne: only run the resident functions and the windowed pass once (for a kernel trace)")
@@ -336,13 +403,13 @@ def main():
     if a.window_sites:                                                             # (--z: windows of 262144 sites by default)
         W = a.window_sites // windows.ALIGN * windows.ALIGN
         a.windows = windows.window_count(m, W)
-    elif a.z:
+    elif a.z or a.zref:
         W = 262144
         a.windows = windows.window_count(m, W)
     if windows.window_count(m, W) != a.windows:
         raise SystemExit("%d sites cannot be cut into %d windows of a multiple of %d sites" % (m, a.windows, windows.ALIGN))
-    if a.fit or a.loo or a.ne or a.z:
-        line = json.dumps(z_leg(a, m, n, K, W) if a.z else ne_leg(a, m, n, K, W) if a.ne else loo_leg(a, m, n, K, W) if a.loo
+    if a.fit or a.loo or a.ne or a.z or a.zref:
+        line = json.dumps(zref_leg(a, m, n, K, W) if a.zref else z_leg(a, m, n, K, W) if a.z else ne_leg(a, m, n, K, W) if a.ne else loo_leg(a, m, n, K, W) if a.loo
                           else fit_leg(a, m, n, K, W))
         print(line)
         if a.out:

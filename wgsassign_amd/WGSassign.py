@@ -86,12 +86,18 @@ SET_WINDOW_SITES_Z = ("the matrix was expected to fit the device and does not: s
                       "compute the z-scores in site windows")
 
 
-def with_windows_hint(error, candidate=False, z_candidate=False):
+SET_WINDOW_SITES_ZREF = ("the matrix was expected to fit the device and does not: set WGSASSIGN_ZREF_WINDOW_SITES (a multiple of 8192 sites) "
+                         "to compute the reference z-scores in site windows")
+
+
+def with_windows_hint(error, candidate=False, z_candidate=False, zref_candidate=False):
     """The error of a resident run whose matrix did not fit the device, saying what windows cover -- or, when the options were
     those windows cover (candidate: the file was only judged to fit; z_candidate: --get_assignment_z_score alone, which has a
-    variable of its own), how to ask for them; any other error as it is."""
+    variable of its own; zref_candidate: --get_reference_z_score alone, which has another), how to ask for them; any other error
+    as it is."""
     if isinstance(error, RuntimeError) and all(part in str(error) for part in SLAB_ALLOC_FAILED):
-        return RuntimeError(str(error) + ": " + (SET_WINDOW_SITES_Z if z_candidate else SET_WINDOW_SITES if candidate else WINDOWS_ONLY))
+        return RuntimeError(str(error) + ": " + (SET_WINDOW_SITES_Z if z_candidate else SET_WINDOW_SITES_ZREF if zref_candidate else
+                                                 SET_WINDOW_SITES if candidate else WINDOWS_ONLY))
     return error
 
 
@@ -267,7 +273,8 @@ def _ne_window_sites(args, comm, ctx):
 def windowed_z_candidate(args, world=1):
     """Whether these options may run in site windows (zscore.assignment_z_scores_windowed): --get_assignment_z_score alone, on one
     rank.  Its frequencies come from --pop_af_file, so nothing couples the windows but sums that are carried on the device.
-    --get_reference_z_score needs masked leave-one-out re-fits over the whole file and keeps the resident path, as do several ranks."""
+    --get_reference_z_score needs masked leave-one-out re-fits whose stopping test runs over the whole file: it has a route of its own
+    (windowed_zref_candidate, zscore.reference_z_scores_windowed) and is not this function's; several ranks keep the resident path."""
     others = (args.get_reference_af, args.loo, args.ne_obs, args.get_pop_like, args.get_reference_z_score, args.loo_downsampled_beagle)
     return bool(args.get_assignment_z_score) and int(world) == 1 and not any(others)
 
@@ -359,6 +366,91 @@ def _run_z_windowed(args, comm, ctx, plan, say, summary):
           (stats["rounds"], stats["windows"], stats["window_sites"], stats["downloaded_bytes"]), file=sys.stderr, flush=True)
     np.savetxt(args.out + ".z_ind.txt", z_out, fmt="%.7f")
     say("Saved " + str(ind_end - ind_start) + " individual z-scores as " + str(args.out) + ".z_ind.txt (text)")
+
+
+def windowed_zref_candidate(args, world=1):
+    """Whether these options may run in site windows (zscore.reference_z_scores_windowed): --get_reference_z_score alone, on one
+    rank -- with its ID and name files, the depth options, the thresholds, the individual range, --maf_iter and --maf_tole.  The
+    masked leave-one-out fits are carried from window to window like the chain of a SNP shard; several ranks keep the resident path."""
+    others = (args.get_reference_af, args.loo, args.ne_obs, args.get_pop_like, args.get_assignment_z_score, args.loo_downsampled_beagle)
+    return bool(args.get_reference_z_score) and int(world) == 1 and not any(others)
+
+
+def _zref_window_sites(args, comm, ctx):
+    """(window, individuals per round) --get_reference_z_score runs in, or None for the resident path: WGSASSIGN_ZREF_WINDOW_SITES
+    when set (no other variable sends this option to windows), else windows only when the resident matrix, depth table and one batch
+    of masked fits would not fit (windows.plan_zref), after the same first look as _z_window_sites takes."""
+    import numpy as np
+
+    from . import reader_cy, windows
+    if not windowed_zref_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
+        return None                     # (a missing ID file is reported where it always was)
+    try:
+        forced = windows.env_window_sites(name=windows.ENV_ZREF)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if forced is not None:
+        return forced, None             # (the rounds of individuals are planned once the file's shape is known)
+    free = ctx.mem_info()[0]
+    if windows.surely_fits(os.path.getsize(args.beagle), free):
+        return None
+    try:
+        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
+        counts = np.unique(IDs[:, 1], return_counts=True)[1]
+    except Exception:
+        return None                     # (an unreadable ID file, too, is reported where it always was)
+    n, K = int(counts.sum()), len(counts)
+    count = _z_individuals(args, n)
+    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
+    if est is not None and windows.fits_resident_zref(est + est // 4 + 1024, n, K, count, free, counts):
+        return None
+    m = reader_cy.ensure_index(args.beagle)[2]
+    try:
+        return windows.plan_zref(m, n, K, count, free, args.maf_iter, counts=counts)
+    except MemoryError as e:
+        raise SystemExit(str(e))
+
+
+def _run_zref_windowed(args, comm, ctx, plan, IDs, group_of, say, summary):
+    """--get_reference_z_score alone on files that do not fit (or WGSASSIGN_ZREF_WINDOW_SITES): passes over the Beagle file and the
+    depth file in site windows; the checks, lines and file of the resident run in their order, and one more line on stderr."""
+    import numpy as np
+
+    from . import reader_cy, zscore
+    W, batch = plan
+    index, _, m = reader_cy.ensure_index(args.beagle)
+    with reader_cy.BeagleStream(args.beagle, threads=1) as st:
+        n = st.n
+    assert os.path.isfile(args.pop_af_IDs), "Population ID file does not exist!!"
+    majmin = None
+    if args.ind_counts_file:
+        majmin = zscore.read_majmin(args.ind_majmin_file)
+        if majmin.shape[0] != m:
+            raise ValueError("%s has the selectors of %d sites, the Beagle file %d" % (args.ind_majmin_file, majmin.shape[0], m))
+    else:
+        assert os.path.isfile(args.ind_ad_file), "Individual allele depths file does not exist!"
+    assert os.path.isfile(args.pop_names), "Population names file does not exist!!"
+    assert (n == IDs.shape[0]), "Number of individuals in beagle and reference ID file do not match!"
+    if args.allele_count_threshold is not None:
+        assert (args.allele_count_threshold >= 0), "Allele count threshold needs to be greater than/equal to 0!"
+    allele_count_threshold = args.allele_count_threshold or 0
+    ind_start, ind_end = zscore.ind_range(n, args.ind_start, args.ind_end)
+    lines = []
+    z_out = zscore.reference_z_scores_windowed(args.beagle, args.ind_counts_file or args.ind_ad_file, IDs, group_of, args.maf_iter,
+                                               args.maf_tole, allele_count_threshold, args.single_read_threshold, ind_start, ind_end,
+                                               window_sites=W, say=lines.append, counts=majmin is not None, majmin=majmin, batch=batch,
+                                               ctx=ctx)
+    info, stats = zscore.reference_z_scores_windowed.info, zscore.reference_z_scores_windowed.stats
+    say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
+    summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
+    say("Parsing population ID file.")
+    say("Parsing individual allele depths file.")
+    for ln in lines:
+        say(ln)
+    print("wgsassign_amd: reference z-scores in %d rounds of individuals, %d passes over %d windows of %d sites (%d bytes downloaded)" %
+          (stats["rounds"], stats["passes"], stats["windows"], stats["window_sites"], stats["downloaded_bytes"]), file=sys.stderr, flush=True)
+    np.savetxt(args.out + ".reference_z_ind.txt", z_out, fmt="%.7f")
+    say("Saved " + str(ind_end - ind_start) + " individual z-scores as " + str(args.out) + ".reference_z_ind.txt (text)")
 
 
 def _run(args, comm):
@@ -493,6 +585,12 @@ def _run(args, comm):
         comm.barrier()
         return
 
+    zref_plan = _zref_window_sites(args, comm, ctx)
+    if zref_plan is not None:
+        _run_zref_windowed(args, comm, ctx, zref_plan, IDs, group_of, say, summary)
+        comm.barrier()
+        return
+
     scored = None
     if args.loo_downsampled_beagle:
         # WGSassign.py:172-198 with names-only passes: every rank derives the same two site masks, then
@@ -530,7 +628,8 @@ def _run(args, comm):
             beagle, sample_names, site_names, m = reader_cy.stream_to_device(
                 args.beagle, group_of, n_groups, ctx=ctx, rank=comm.rank, world=comm.world, comm=comm, names="ends")
         except RuntimeError as e:
-            hinted = with_windows_hint(e, windowed_candidate(args, comm.world), windowed_z_candidate(args, comm.world))
+            hinted = with_windows_hint(e, windowed_candidate(args, comm.world), windowed_z_candidate(args, comm.world),
+                                       zref_candidate=windowed_zref_candidate(args, comm.world))
             if hinted is e:
                 raise
             raise hinted from e

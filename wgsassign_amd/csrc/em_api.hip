@@ -12,6 +12,8 @@
 #include "common.h"
 #include "em_state.h"
 #include "em_stream_checks.h"
+#include "em_stream_masked_checks.h"
+#include "zscore.h"
 
 // Enqueues `units` fits or fit groups as launch(first, count) over slices of at most `per_launch` of them.
 template <class Launch> static int em_launch_sliced(size_t units, size_t per_launch, Launch launch)
@@ -777,6 +779,12 @@ struct wgs_em_stream {
     void *d_chain_work = nullptr;
     size_t chain_work_bytes = 0;
     int32_t *d_from = nullptr;          // [n_fits] wgs_em_stream_push_keep: the iterations of every fit whose sums S holds already
+    // wgs_em_stream_push_masked: the compacted (f_t, f_t-1) of every fit over its kept sites of the window, [n_fits][stride] each, and
+    // the compaction jobs of one push (one per chain job)
+    float *d_ca = nullptr, *d_cb = nullptr;
+    size_t compact_cap = 0;             // floats in each of the two
+    size_t cjob_cap = 0;
+    ZCompactJob *h_cjobs = nullptr, *d_cjobs = nullptr;
 };
 
 void wgs_em_stream_destroy(wgs_em_stream *st)
@@ -784,9 +792,9 @@ void wgs_em_stream_destroy(wgs_em_stream *st)
     if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
     (void)hipSetDevice(st->device);
     for (void *p : {(void *)st->d_S, (void *)st->d_C, (void *)st->d_win, (void *)st->d_descs, (void *)st->d_groups, (void *)st->d_jobs,
-                    (void *)st->d_cell, (void *)st->d_chain_out, st->d_chain_work, (void *)st->d_from})
+                    (void *)st->d_cell, (void *)st->d_chain_out, st->d_chain_work, (void *)st->d_from, (void *)st->d_ca, (void *)st->d_cb, (void *)st->d_cjobs})
         if (p) (void)hipFree(p);
-    for (void *p : {(void *)st->h_descs, (void *)st->h_groups, (void *)st->h_jobs, (void *)st->h_cell})
+    for (void *p : {(void *)st->h_descs, (void *)st->h_groups, (void *)st->h_jobs, (void *)st->h_cell, (void *)st->h_cjobs})
         if (p) (void)hipHostFree(p);
     delete st;
 }
@@ -856,6 +864,38 @@ static int em_stream_chain_room(wgs_em_stream *st, size_t jobs, int64_t m)
     return 0;
 }
 
+// Room for the compacted vectors of a masked push (2 x n_fits x stride floats, grown when a window keeps more) and for its compaction
+// jobs (one per chain job).
+static int em_stream_masked_room(wgs_em_stream *st, size_t jobs, int64_t stride)
+{
+    wgs_ctx *ctx = st->ctx;
+    const size_t floats = (size_t)st->n_fits * (size_t)stride;
+    if (floats > st->compact_cap) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (void *p : {(void *)st->d_ca, (void *)st->d_cb})
+            if (p) HIP_TRY(hipFree(p));
+        st->d_ca = st->d_cb = nullptr;
+        st->compact_cap = 0;
+        if (wgs_malloc(&st->d_ca, sizeof(float) * floats) != hipSuccess || wgs_malloc(&st->d_cb, sizeof(float) * floats) != hipSuccess) {
+            wgs_set_error("hipMalloc of 2 x %zu bytes for the compacted frequencies failed", sizeof(float) * floats);
+            return 1;
+        }
+        st->compact_cap = floats;
+    }
+    if (jobs > st->cjob_cap) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (st->d_cjobs) HIP_TRY(hipFree(st->d_cjobs));
+        if (st->h_cjobs) HIP_TRY(hipHostFree(st->h_cjobs));
+        st->d_cjobs = st->h_cjobs = nullptr;
+        st->cjob_cap = 0;
+        const size_t cap = std::max(jobs, (size_t)st->n_fits * 8);
+        HIP_TRY(wgs_malloc(&st->d_cjobs, sizeof(ZCompactJob) * cap));
+        HIP_TRY(hipHostMalloc(&st->h_cjobs, sizeof(ZCompactJob) * cap, hipHostMallocDefault));
+        st->cjob_cap = cap;
+    }
+    return 0;
+}
+
 /* One window, through its EM batch `em` (made from the window matrix; one fit per fit of the stream).  The matrix's first site must
  * be the number of sites pushed in this round and a multiple of WGS_WINDOW_ALIGN, every window but the last holds a multiple of
  * WGS_WINDOW_ALIGN sites, and the batch has the stream's number of fits: anything else is refused before a kernel is launched.
@@ -867,10 +907,13 @@ static int em_stream_chain_room(wgs_em_stream *st, size_t jobs, int64_t m)
  *   add_sums         != 0: the window's sum of every iteration t a fit runs is added to S[t][fit].
  * Returns when the device is done with the window: its matrix may be refilled, f_out holds the final fits' rows. */
 // Both pushes.  keep: final fits are clamped and stay in the batch (no f_out); sums_from (keep only; may be NULL: no sums): the sum of
-// iteration t of a fit joins S only for t > sums_from[fit].
+// iteration t of a fit joins S only for t > sums_from[fit].  zk / fit_slot (both or neither; wgs_em_stream_push_masked): the chain of a
+// fit runs over the sites slot fit_slot[fit] of zk kept in this window -- (f_t, f_t-1) compacted in site order, every chain job of
+// an iteration by ONE launch -- and a fit that kept nothing here leaves C[t][fit] as it is.
 static int em_stream_push_window(wgs_em_stream *st, wgs_em *em, const int32_t *run_iters, const int32_t *final, const float *clamp_lo,
                                  const float *clamp_hi, const int32_t *chain_fit, const int32_t *chain_iter, int32_t n_chain, int add_sums,
-                                 float *f_out, int64_t f_stride, bool keep, const int32_t *sums_from)
+                                 float *f_out, int64_t f_stride, bool keep, const int32_t *sums_from, wgs_zkeep *zk = nullptr,
+                                 const int32_t *fit_slot = nullptr)
 {
     WGS_REQUIRE(st && em && run_iters, "null argument");
     wgs_beagle *window = em->b;
@@ -885,7 +928,8 @@ static int em_stream_push_window(wgs_em_stream *st, wgs_em *em, const int32_t *r
     if (em_stream_window_refusal(window->site0, m, em->cap_m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why) ||
         em_stream_plan_refusal(n, st->max_iter, run_iters, final, clamp_lo && clamp_hi, keep || f_out != nullptr, keep ? m : f_stride, m, chain_fit,
                                chain_iter, n_chain, &T, &any_final, why, sizeof why) ||
-        (sums_from && em_stream_sums_from_refusal(n, run_iters, sums_from, why, sizeof why))) {
+        (sums_from && em_stream_sums_from_refusal(n, run_iters, sums_from, why, sizeof why)) ||
+        (zk && em_stream_masked_refusal(window, zk->b, n, zk->count, fit_slot, why, sizeof why))) {
         wgs_set_error("%s", why);
         return 2;
     }
@@ -893,6 +937,13 @@ static int em_stream_push_window(wgs_em_stream *st, wgs_em *em, const int32_t *r
     wgs_ctx *ctx = st->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     if (em_stream_chain_room(st, (size_t)n_chain, m)) return 1;
+    const int64_t stride = zk ? em_stream_masked_stride(n, fit_slot, zk->total.data()) : 0;
+    if (zk) {
+        if (em_stream_masked_room(st, (size_t)n_chain, stride)) return 1;
+        // what lies behind a fit's kept count stays 0 through every iteration of this push: (0 - 0)^2 adds nothing
+        HIP_TRY(hipMemsetAsync(st->d_ca, 0, sizeof(float) * (size_t)n * stride, ctx->stream));
+        HIP_TRY(hipMemsetAsync(st->d_cb, 0, sizeof(float) * (size_t)n * stride, ctx->stream));
+    }
     if (sums_from) {
         if (!st->d_from) HIP_TRY(wgs_malloc(&st->d_from, sizeof(int32_t) * (size_t)n));
         HIP_TRY(hipMemcpyAsync(st->d_from, sums_from, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -905,7 +956,7 @@ static int em_stream_push_window(wgs_em_stream *st, wgs_em *em, const int32_t *r
     em->prev.assign(n, 1);
     std::vector<int32_t> list;
     list.reserve(n);
-    int next_chain = 0;
+    int next_chain = 0, n_jobs = 0;         // chains of the plan looked at; chain jobs written (fewer when a masked fit kept nothing here)
     for (int t = 1; t <= T; ++t) {
         const int s = (t - 1) % st->slots;
         if (t > 1 && s == 0) HIP_TRY(hipStreamSynchronize(ctx->stream));      // the ring of pinned descriptors goes round
@@ -922,19 +973,32 @@ static int em_stream_push_window(wgs_em_stream *st, wgs_em *em, const int32_t *r
         if (add_sums && !sums_from && launch_em_stream_add_sums(ctx, st->d_win, st->d_S + (size_t)(t - 1) * n, n)) return 1;
         if (sums_from && launch_em_stream_add_sums_above(ctx, st->d_win, st->d_S + (size_t)(t - 1) * n, st->d_from, t, n)) return 1;
         // the chains of iteration t, over what this sweep wrote and what it read
-        const int first = next_chain;
+        const int first = n_jobs;
         while (next_chain < n_chain && chain_iter[next_chain] == t) {
-            const int j = chain_fit[next_chain];
-            st->h_jobs[next_chain] = ChainJob{em_f(em, j, em->cur[j]), em_f(em, j, em->prev[j]), 0.0f};
-            st->h_cell[next_chain] = (int32_t)((size_t)(t - 1) * n + j);
-            ++next_chain;
+            const int j = chain_fit[next_chain++];
+            const float *cur = em_f(em, j, em->cur[j]), *prev = em_f(em, j, em->prev[j]);
+            if (zk) {
+                if (zk->total[fit_slot[j]] == 0) continue;   // nothing kept in this window: C[t][fit] is handed on bit for bit
+                float *va = st->d_ca + (size_t)j * stride, *vb = st->d_cb + (size_t)j * stride;
+                st->h_cjobs[n_jobs] = ZCompactJob{cur, prev, va, vb, fit_slot[j]};
+                cur = va;
+                prev = vb;
+            }
+            st->h_jobs[n_jobs] = ChainJob{cur, prev, 0.0f};
+            st->h_cell[n_jobs] = (int32_t)((size_t)(t - 1) * n + j);
+            ++n_jobs;
         }
-        for (int i = first; i < next_chain; i += n) {        // (at most one chain per fit shares the workspace)
-            const int cnt = std::min(n, next_chain - i);
+        if (zk && n_jobs > first) {                          // every chain job of this iteration compacted by one launch
+            HIP_TRY(hipMemcpyAsync(st->d_cjobs + first, st->h_cjobs + first, sizeof(ZCompactJob) * (n_jobs - first), hipMemcpyHostToDevice,
+                                   ctx->stream));
+            if (launch_zcompact(ctx, st->d_cjobs + first, n_jobs - first, m, zk->mask, zk->off)) return 1;
+        }
+        for (int i = first; i < n_jobs; i += n) {            // (at most one chain per fit shares the workspace)
+            const int cnt = std::min(n, n_jobs - i);
             HIP_TRY(hipMemcpyAsync(st->d_jobs + i, st->h_jobs + i, sizeof(ChainJob) * cnt, hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(hipMemcpyAsync(st->d_cell + i, st->h_cell + i, sizeof(int32_t) * cnt, hipMemcpyHostToDevice, ctx->stream));
             if (launch_em_stream_chain_load(ctx, st->d_jobs + i, st->d_cell + i, st->d_C, cnt)) return 1;
-            if (launch_rmse_chain_batch(ctx, st->d_jobs + i, cnt, m, st->d_chain_out, st->d_chain_work, nullptr)) return 1;
+            if (launch_rmse_chain_batch(ctx, st->d_jobs + i, cnt, zk ? stride : m, st->d_chain_out, st->d_chain_work, nullptr)) return 1;
             if (launch_em_stream_chain_store(ctx, st->d_chain_out, st->d_cell + i, st->d_C, cnt)) return 1;
         }
     }
@@ -968,6 +1032,18 @@ int wgs_em_stream_push_keep(wgs_em_stream *st, wgs_em *em, const int32_t *run_it
 {
     return em_stream_push_window(st, em, run_iters, final, clamp_lo, clamp_hi, chain_fit, chain_iter, n_chain, sums_from != nullptr, nullptr, 0,
                                  true, sums_from);
+}
+
+/* wgs_em_stream_push_keep with no sums for fits whose stopping test runs over a site subset (the masked leave-one-out fits of
+ * --get_reference_z_score): the chain of (fit, t) runs over the sites slot fit_slot[fit] of `zk` kept in this window, from C[t][fit] to
+ * C[t][fit]; a fit that kept nothing here hands its carry on.  Nothing joins S, nothing is read back between the iterations. */
+int wgs_em_stream_push_masked(wgs_em_stream *st, wgs_em *em, wgs_zkeep *zk, const int32_t *fit_slot, const int32_t *run_iters,
+                              const int32_t *final, const float *clamp_lo, const float *clamp_hi, const int32_t *chain_fit,
+                              const int32_t *chain_iter, int32_t n_chain)
+{
+    WGS_REQUIRE(zk, "null argument");
+    return em_stream_push_window(st, em, run_iters, final, clamp_lo, clamp_hi, chain_fit, chain_iter, n_chain, 0, nullptr, 0, true, nullptr, zk,
+                                 fit_slot);
 }
 
 /* The round's one read-back: S (max_iter x n_fits float64) and C (max_iter x n_fits float32), either may be NULL.  rc 2 before all

@@ -831,12 +831,39 @@ class EMStream:
                                                   None if frm is None else i32p(frm)))
         self.windows += 1
 
+    def push_masked(self, em, keep, fit_slot, run_iters, final=None, clamp_lo=None, clamp_hi=None, chains=()):
+        """push_keep() without sums for fits whose stopping test runs over a site subset (wgs_em_stream_push_masked): the chain of
+        (fit, iteration) runs over the sites slot fit_slot[fit] of the zscore.KeepSet `keep` kept in this window; a fit that kept
+        nothing here hands its carry on.  keep must have been made from em's matrix."""
+        run = np.ascontiguousarray(run_iters, dtype=np.int32)
+        slot = np.ascontiguousarray(fit_slot, dtype=np.int32)
+        if run.shape != (self.n_fits,) or slot.shape != (self.n_fits,):
+            raise ValueError("run_iters and fit_slot must have one entry per fit")
+        fin = None if final is None else np.ascontiguousarray(final, dtype=np.int32)
+        lo = None if clamp_lo is None else np.ascontiguousarray(clamp_lo, dtype=np.float32)
+        hi = None if clamp_hi is None else np.ascontiguousarray(clamp_hi, dtype=np.float32)
+        for a in (fin, lo, hi):
+            if a is not None and a.shape != (self.n_fits,):
+                raise ValueError("final and the clamps must have one entry per fit")
+        cf = np.ascontiguousarray([c[0] for c in chains], dtype=np.int32)
+        ci = np.ascontiguousarray([c[1] for c in chains], dtype=np.int32)
+        check(_lib.load().wgs_em_stream_push_masked(self._h, em.handle, keep.handle, i32p(slot), i32p(run), None if fin is None else i32p(fin),
+                                                    None if lo is None else f32p(lo), None if hi is None else f32p(hi),
+                                                    i32p(cf) if len(cf) else None, i32p(ci) if len(ci) else None, len(cf)))
+        self.windows += 1
+
     def read(self):
         """(S, C) of the round just pushed, (maf_iter, n_fits) float64 / float32; the next push begins the next round."""
         S = np.zeros((self.maf_iter, self.n_fits), dtype=np.float64)
         C = np.zeros((self.maf_iter, self.n_fits), dtype=np.float32)
         check(_lib.load().wgs_em_stream_read(self._h, f64p(S) if S.size else None, f32p(C) if C.size else None))
         return S, C
+
+    def read_carries(self):
+        """read() of C alone -- the rounds of masked fits add no sums."""
+        C = np.zeros((self.maf_iter, self.n_fits), dtype=np.float32)
+        check(_lib.load().wgs_em_stream_read(self._h, None, f32p(C) if C.size else None))
+        return C
 
     def close(self):
         if self._h:

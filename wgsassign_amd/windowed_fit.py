@@ -190,3 +190,92 @@ def fit(backend, n_fits, maf_iter, tole, m_total, guard=0.0, lookahead=None, fir
         if scheme.rounds > limit:
             raise RuntimeError("the windowed fit did not settle in %d rounds" % scheme.rounds)
     return scheme.iters.copy(), scheme
+
+
+class ChainPlan:
+    """What one round of masked fits does in every window: run_iters[k] iterations of fit k from 0.25; final: every fit is run to its
+    stopping iteration and clamped; chains: (fit, iteration) pairs sorted by iteration."""
+
+    def __init__(self, number, run_iters, final, chains):
+        self.number = int(number)
+        self.run_iters = np.ascontiguousarray(run_iters, dtype=np.int32)
+        self.final = bool(final)
+        self.chains = sorted(((int(k), int(t)) for k, t in chains), key=lambda c: (c[1], c[0]))
+
+
+class ChainScheme:
+    """The rounds of fits whose stopping test runs over a site subset of the fit's own (zscore.reference_z_scores_windowed): fit k
+    stops at the first t <= maf_iter with chain_diff(carry of iteration t over ITS kept sites of all windows, kept_total[k]) < tole
+    -- em_chain_converged, what wgs_em_fit_masked decides with every iteration -- or is exhausted (frequencies of maf_iter,
+    iteration count 0).  No sum decides anything here, so there is no band and no chain round: a FIT ROUND walks the exact chain of
+    EVERY iteration above walked[k] up to the fit's horizon, for every fit not yet decided, and one read of the carries decides all
+    of them.  A pass over the files costs about ten times what the fits of a window cost, so walking chains
+    that turn out not to be needed is the cheap side: the design that never needs a second pass merely to decide is the right one.
+    A fit neither stopped nor exhausted at its horizon gets another round with the horizon doubled, capped at maf_iter; that round
+    runs the fit from 0.25 again but walks only the iterations above the old horizon -- the carries of the earlier ones are final
+    (they said "not converged"), so every (window, iteration, fit) chain is walked exactly once.  When every fit is decided, one
+    FINAL round runs each to its stop.
+
+        horizon[k]  iterations the next fit round runs fit k for        walked[k]  iterations whose carries were read and decided
+        stop[k]     None, or the iteration the frequencies are taken from        iters[k]   stop[k], or 0 when exhausted"""
+
+    def __init__(self, n_fits, maf_iter, tole, first_horizon):
+        self.n_fits, self.maf_iter, self.tole = int(n_fits), max(0, int(maf_iter)), float(tole)
+        h = min(self.maf_iter, max(1, int(first_horizon)))
+        self.horizon = [h] * self.n_fits
+        self.walked = [0] * self.n_fits
+        self.stop = [None] * self.n_fits
+        self.iters = np.zeros(self.n_fits, dtype=np.int32)
+        self.fit_rounds = 0
+        self.horizons = []                  # the largest horizon of every fit round
+        self.chain_iterations = 0
+        self.finished = False
+        if self.maf_iter == 0:              # emMAF.py:20 never enters its loop: f = 0.25, nothing to decide
+            self.stop = [0] * self.n_fits
+
+    def decided(self):
+        return all(s is not None for s in self.stop)
+
+    def plan(self):
+        """The next round: a fit round while a fit is undecided (the decided ones rest), else the final round."""
+        if self.decided():
+            return ChainPlan(self.fit_rounds + 1, list(self.stop), True, [])
+        run = [0 if self.stop[k] is not None else self.horizon[k] for k in range(self.n_fits)]
+        chains = [(k, t) for k in range(self.n_fits) if self.stop[k] is None for t in range(self.walked[k] + 1, self.horizon[k] + 1)]
+        return ChainPlan(self.fit_rounds + 1, run, False, chains)
+
+    def after_round(self, plan, C, kept_total):
+        """C[t-1][k]: the float32 carry of iteration t after the last window, for the chains this round walked (other cells are not
+        looked at); kept_total[k]: the sites fit k's individual kept over ALL windows (> 0)."""
+        if plan.final:
+            self.finished = True
+            return
+        self.fit_rounds += 1
+        self.horizons.append(int(plan.run_iters.max()))
+        self.chain_iterations += len(plan.chains)
+        for k in range(self.n_fits):
+            if self.stop[k] is not None:
+                continue
+            for t in range(self.walked[k] + 1, self.horizon[k] + 1):
+                if chain_diff(C[t - 1][k], kept_total[k]) < self.tole:
+                    self.stop[k], self.iters[k] = t, t
+                    break
+            else:
+                self.walked[k] = self.horizon[k]
+                if self.horizon[k] >= self.maf_iter:            # exhausted: f_maf_iter, the reference prints nothing
+                    self.stop[k], self.iters[k] = self.maf_iter, 0
+                else:
+                    self.horizon[k] = min(self.maf_iter, 2 * self.horizon[k])
+
+
+def fit_masked(backend, n_fits, maf_iter, tole, first_horizon):
+    """Rounds until every fit has run its final round.  backend.run_round(plan) -> (C, kept_total) runs the plan in every window of the
+    files, in file order (C may be None for the final round).  Returns (iters (n_fits,) int32, the scheme)."""
+    scheme = ChainScheme(n_fits, maf_iter, tole, first_horizon)
+    while not scheme.finished:
+        plan = scheme.plan()
+        C, kept_total = backend.run_round(plan)
+        scheme.after_round(plan, C, kept_total)
+        if scheme.fit_rounds > scheme.maf_iter.bit_length() + 2:
+            raise RuntimeError("the masked fits did not settle in %d rounds" % scheme.fit_rounds)
+    return scheme.iters.copy(), scheme

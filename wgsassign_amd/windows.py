@@ -19,8 +19,8 @@ RESERVE (4 GiB, at most a quarter of the free memory: the ingest's text and line
 when the device inflates -- the block sums of a sweep, the context's workspace).  A resident matrix needs m sites of it;
 windowed scoring holds TWO windows (the one being scored and the one being filled), each with its frequencies and codes.
 
-The other windowed routes have their own arithmetic below (fit_site_bytes, loo_site_bytes, ne_site_bytes, z_site_bytes) and, but for
-the fit, a variable of their own.
+The other windowed routes have their own arithmetic below (fit_site_bytes, loo_site_bytes, ne_site_bytes, z_site_bytes,
+zref_site_bytes) and, but for the fit, a variable of their own.
 """
 import os
 
@@ -31,6 +31,7 @@ ENV = "WGSASSIGN_WINDOW_SITES"
 ENV_LOO = "WGSASSIGN_LOO_WINDOW_SITES"      # the leave-one-out run is sent to windows by a variable of its own (see plan_loo)
 ENV_NE = "WGSASSIGN_NE_WINDOW_SITES"        # ... and so is --ne_obs (see plan_ne)
 ENV_Z = "WGSASSIGN_Z_WINDOW_SITES"          # ... and --get_assignment_z_score (see plan_z)
+ENV_ZREF = "WGSASSIGN_ZREF_WINDOW_SITES"    # ... and --get_reference_z_score (see plan_zref)
 SURELY_FITS = 64                # see surely_fits
 
 
@@ -283,4 +284,87 @@ def plan_z(m, n, K, count, free_bytes, environ=None):
         raise MemoryError("windowed z-scores need two windows of %d sites x %d individuals on the device (%d bytes with the depths, "
                           "frequencies, masks and statistics of one) and %d bytes of state per individual; %d of the %d free bytes can be "
                           "used" % (ALIGN, n, ALIGN * per_site, z_state_bytes(1), max(0, budget(free_bytes)), free_bytes))
+    return W, batch
+
+
+def _slab_pairs(n, K, counts=None):
+    """float4 columns of the population slabs: per population one per pair of its individuals (fit_site_bytes)."""
+    return sum((int(c) + 1) // 2 for c in counts) if counts is not None else (int(n) + int(K)) // 2
+
+
+def _zref_fits_bytes(count):
+    """Per site what an EM batch of `count` fits holds: two float32 frequency buffers per fit and the per-tile float64 partial sums
+    (loo_site_bytes counts the same for its n re-fits)."""
+    return 8 * int(count) + (8 * int(count) + 63) // 64
+
+
+def zref_state_bytes(count, maf_iter=200):
+    """Device bytes that `count` individuals carry from window to window in a windowed --get_reference_z_score, charged ONCE:
+    z_state_bytes and the fit stream's tables (wgs_em_stream: maf_iter x count float64 sums, unused here, and float32 carries)."""
+    return z_state_bytes(count) + 12 * max(1, int(maf_iter)) * int(count)
+
+
+def zref_site_bytes(n, K, count, counts=None):
+    """Device bytes one site of ONE window takes in a windowed --get_reference_z_score of n individuals in K populations (counts: the
+    individuals of every population when known, else the worst split), `count` of them in the batch: z_site_bytes without a frequency
+    file, with the population slabs in place of the one slab, plus what the batch of masked leave-one-out fits adds per site:
+
+        matrix       16 * sum_g ceil(n_g / 2)       one slab per population, at most 16 * ((n + K) // 2)
+        depths       2 * n                          one byte pair per (individual, site)
+        mask words   12 * count / 64, rounded up    the kept-site word and its offset per (individual of the batch, tile)
+        statistics   12 * count                     the three compacted float32 arrays
+        frequencies  2 * 4 * count                  wgs_em_create's two float32 buffers per fit
+        sums         8 * count / 64, rounded up     its per-tile float64 partial sums
+        compacted    2 * 4 * count                  (f_t, f_t-1) over the kept sites of every fit (wgs_em_stream_push_masked): at most
+                                                    one pair per (fit, site)
+
+    The class codes an EM sweep may build are left out, as surely_fits leaves them out: their allocation is asked for on its own and
+    a sweep does without them when it fails.  The window that is being filled beside it is one more matrix with its batch of fits
+    (the batch stays with its matrix): plan_zref adds both."""
+    n, K, count = int(n), int(K), int(count)
+    return 16 * _slab_pairs(n, K, counts) + 2 * n + (12 * count + 63) // 64 + 12 * count + _zref_fits_bytes(count) + 8 * count
+
+
+def fits_resident_zref(m, n, K, count, free_bytes, counts=None):
+    """Whether the resident --get_reference_z_score fits: matrix and depth table of all m sites and one batch of at most
+    Z_RESIDENT_BATCH masked fits with their masks, statistics and compacted vectors."""
+    return int(m) * zref_site_bytes(n, K, min(int(count), Z_RESIDENT_BATCH), counts) <= budget(free_bytes)
+
+
+def _zref_window_bytes(n, K, batch, counts=None):
+    """Per site of a window with the second matrix and its batch of fits beside it."""
+    return zref_site_bytes(n, K, batch, counts) + 16 * _slab_pairs(n, K, counts) + _zref_fits_bytes(batch)
+
+
+def zref_batch(W, n, K, count, free_bytes, maf_iter=200, counts=None):
+    """Individuals per round for windows of W sites: all `count` when their state and the two windows' objects fit, else the largest
+    half, quarter, ... of them that does (at least one)."""
+    batch = max(1, int(count))
+    while batch > 1 and zref_state_bytes(batch, maf_iter) + int(W) * _zref_window_bytes(n, K, batch, counts) > budget(free_bytes):
+        batch = (batch + 1) // 2
+    return batch
+
+
+def plan_zref(m, n, K, count, free_bytes, maf_iter=200, environ=None, counts=None):
+    """plan() for --get_reference_z_score of `count` individuals: None when the resident objects fit (fits_resident_zref) and
+    WGSASSIGN_ZREF_WINDOW_SITES does not ask for windows, else (W, batch): windows of W sites (a multiple of 8192) and rounds of `batch`
+    individuals, halved as plan_z halves them until a window of 8192 sites fits beside their state."""
+    forced = env_window_sites(environ, ENV_ZREF)
+    m, n, K, count = int(m), int(n), int(K), int(count)
+    if forced is None and fits_resident_zref(m, n, K, count, free_bytes, counts):
+        return None
+    batch = count
+    while True:
+        per_site = _zref_window_bytes(n, K, batch, counts)
+        room = budget(free_bytes) - zref_state_bytes(batch, maf_iter)
+        W = room // per_site // ALIGN * ALIGN if room > 0 else 0
+        if W >= ALIGN or batch == 1:
+            break
+        batch = (batch + 1) // 2
+    if forced is not None:
+        return forced, zref_batch(forced, n, K, count, free_bytes, maf_iter, counts)
+    if W < ALIGN:
+        raise MemoryError("windowed reference z-scores need two windows of %d sites x %d individuals on the device (%d bytes with the "
+                          "depths, masks, statistics and masked fits of one) and %d bytes of state per individual; %d of the %d free bytes "
+                          "can be used" % (ALIGN, n, ALIGN * per_site, zref_state_bytes(1, maf_iter), max(0, budget(free_bytes)), free_bytes))
     return W, batch

@@ -25,6 +25,9 @@ Site windows (assignment_z_scores_windowed): the assignme
 not fit the device, on one rank.  The same hand-overs in time: the class sums stay on the device from window to window (ZSum.classes),
 and the three float32 sums are formed THERE in np.sum's own order -- serial over 8192-element chunks, each a pairwise tree -- from
 device arrays that are never downloaded (KeepSet.stats_dev, ZSum.push); the depth file is read once per pass (DepthWindows).
+reference_z_scores_windowed is the reference flavour in the same windows: beside those sums the convergence chain of every masked
+leave-one-out fit is carried from window to window on the device (device.EMStream.push_masked), in rounds that
+windowed_fit.ChainScheme keeps.
 """
 import ctypes
 import math
@@ -846,6 +849,54 @@ def merge_windows(cnt_tot, first_glob, over_tot, site0, cnt, first, over):
     first_glob[new] = int(site0) + first[new].astype(np.int64)
 
 
+def window_pass(path, depth_path, m, n, W, ctx, info, body, counts=False, majmin=None, depth_chunk_bytes=None, group_of=None, n_groups=1):
+    """ONE pass over a Beagle file and its depth file in windows of W sites: body(b, depth) for every window, the window's depth rows
+    in place (DepthWindows); what was made from the window is closed before the next one is asked for.  group_of / n_groups: the
+    windows carry one slab per population.  Returns the depth ingest's statistics."""
+    from . import reader_cy
+    dw = DepthWindows(depth_path, m, n, ctx, counts, majmin, depth_chunk_bytes)
+    gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info, group_of=group_of, n_groups=n_groups)
+    try:
+        for b in gen:
+            depth = DepthTable(b)
+            try:
+                dw.fill(depth, b.m)
+                body(b, depth)
+            finally:
+                depth.close()
+        return dw.finish()
+    finally:
+        gen.close()
+        dw.close()
+
+
+def class_pass(zs, i0, count, deep, one_pass):
+    """Pass A of the windowed z-scores: the class sweep with its running sums carried from window to window (ZSum.classes), counts,
+    `over` and first sites put together as global numbers, the deep sites of every window listed.  one_pass(body) runs a pass.
+    Returns (cnt_tot, first_glob, sums after the last window, over_tot, listed -- as `dictionaries` takes them -- and the depth
+    ingest's statistics)."""
+    cnt_tot = np.zeros((count, N_CLASSES), dtype=np.int64)
+    first_glob = np.full((count, N_CLASSES), -1, dtype=np.int64)
+    over_tot = np.zeros(count, dtype=np.int64)
+    last = {}
+    parts = [[] for _ in range(count)]
+
+    def pass_a(b, depth):
+        cnt, sums, first, over = zs.classes(depth, i0)
+        merge_windows(cnt_tot, first_glob, over_tot, b.site0, cnt, first, over)
+        last["sums"] = sums
+        if deep and over.any():
+            for j, (site, ad, g) in enumerate(list_deep_sites(depth, i0, count, over)):
+                if len(site):
+                    parts[j].append((site.astype(np.int64) + b.site0, ad, g))
+                    zs.downloaded += site.nbytes + ad.nbytes + g.nbytes
+
+    depth_stats = one_pass(pass_a)
+    empty = (np.empty(0, dtype=np.int64), np.empty((0, 2), dtype=np.int32), np.empty((0, 2), dtype=np.float32))
+    listed = [concat_deep(p) if p else empty for p in parts] if deep and over_tot.any() else None
+    return cnt_tot, first_glob, last["sums"], over_tot, listed, depth_stats
+
+
 def assignment_z_scores_windowed(path, depth_path, A, IDs, pops, n_threshold=0, single_read_threshold=False, ind_start=0, ind_end=None,
                                  window_sites=None, say=print, details=None, deep=True, counts=False, majmin=None, batch=None, ctx=None,
                                  depth_chunk_bytes=None):
@@ -891,48 +942,17 @@ def assignment_z_scores_windowed(path, depth_path, A, IDs, pops, n_threshold=0, 
     info = {}
     stats = dict(windows=0, window_sites=W, rounds=len(rounds), seconds_a=[], seconds_b=[], depth_a=[], depth_b=[], downloaded_bytes=0)
 
-    def one_pass(zs, body):
-        """body(b, depth) for every window of the file, the window's depth rows in place; the depth ingest's statistics."""
-        dw = DepthWindows(depth_path, m, n, ctx, counts, majmin, depth_chunk_bytes)
-        gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info)
-        try:
-            for b in gen:
-                depth = DepthTable(b)
-                try:
-                    dw.fill(depth, b.m)
-                    body(b, depth)
-                finally:
-                    depth.close()
-            return dw.finish()
-        finally:
-            gen.close()
-            dw.close()
+    def one_pass(body):
+        return window_pass(path, depth_path, m, n, W, ctx, info, body, counts, majmin, depth_chunk_bytes)
 
     for i0, count in rounds:
         zs = ZSum(count, ctx)
         try:
-            cnt_tot = np.zeros((count, N_CLASSES), dtype=np.int64)
-            first_glob = np.full((count, N_CLASSES), -1, dtype=np.int64)
-            over_tot = np.zeros(count, dtype=np.int64)
-            last = {}
-            parts = [[] for _ in range(count)]
-
-            def pass_a(b, depth):
-                cnt, sums, first, over = zs.classes(depth, i0)
-                merge_windows(cnt_tot, first_glob, over_tot, b.site0, cnt, first, over)
-                last["sums"] = sums
-                if deep and over.any():
-                    for j, (site, ad, g) in enumerate(list_deep_sites(depth, i0, count, over)):
-                        if len(site):
-                            parts[j].append((site.astype(np.int64) + b.site0, ad, g))
-                            zs.downloaded += site.nbytes + ad.nbytes + g.nbytes
-
             t0 = time.perf_counter()
-            stats["depth_a"].append(one_pass(zs, pass_a))
+            cnt_tot, first_glob, class_sums, over_tot, listed, depth_a = class_pass(zs, i0, count, deep, one_pass)
+            stats["depth_a"].append(depth_a)
             stats["seconds_a"].append(time.perf_counter() - t0)
-            empty = (np.empty(0, dtype=np.int64), np.empty((0, 2), dtype=np.int32), np.empty((0, 2), dtype=np.float32))
-            listed = [concat_deep(p) if p else empty for p in parts] if deep and over_tot.any() else None
-            summ = dictionaries(i0, cnt_tot, first_glob, last["sums"], over_tot, listed, n_threshold, single_read_threshold, deep)
+            summ = dictionaries(i0, cnt_tot, first_glob, class_sums, over_tot, listed, n_threshold, single_read_threshold, deep)
             key_mean, key_comp = mask_tables(summ)
             dmap, drows = deep_tables(summ)
             tabs, tparts = stat_tables(summ)
@@ -951,7 +971,7 @@ def assignment_z_scores_windowed(path, depth_path, A, IDs, pops, n_threshold=0, 
                     keep.close()
 
             t0 = time.perf_counter()
-            stats["depth_b"].append(one_pass(zs, pass_b))
+            stats["depth_b"].append(one_pass(pass_b))
             stats["seconds_b"].append(time.perf_counter() - t0)
             totals, sums3 = zs.finish()
             assert np.array_equal(totals, kept_tot)
@@ -966,4 +986,210 @@ def assignment_z_scores_windowed(path, depth_path, A, IDs, pops, n_threshold=0, 
     stats["windows"] = info.get("windows", 0)
     assignment_z_scores_windowed.stats = stats
     assignment_z_scores_windowed.info = dict({k: info.get(k) for k in ("m", "sample_names", "site_names")}, n=n)
+    return z_out
+
+
+# ---------------------------------------------------------------- --get_reference_z_score in site windows
+ZREF_FIRST_HORIZON = 32         # iterations the first fit round runs every masked fit for (not measured: DESIGN.md section 5.1)
+ENV_ZREF_HORIZON = "WGSASSIGN_ZREF_HORIZON"
+RESIDENT_BLOCK = 64             # individuals per batch of the resident run, whose printed lines come block by block
+
+
+def zref_first_horizon(first_horizon=None, environ=None):
+    """The first horizon of the masked fits: the keyword, else WGSASSIGN_ZREF_HORIZON, else ZREF_FIRST_HORIZON; at least 1."""
+    if first_horizon is None:
+        value = (os.environ if environ is None else environ).get(ENV_ZREF_HORIZON)
+        if value is not None and str(value).strip():
+            try:
+                first_horizon = int(str(value).strip())
+            except ValueError:
+                raise ValueError("%s must be a number of iterations (an integer >= 1), got %r" % (ENV_ZREF_HORIZON, value))
+        else:
+            first_horizon = ZREF_FIRST_HORIZON
+    if int(first_horizon) < 1:
+        raise ValueError("the first horizon of the masked fits is at least 1 iteration, not %d" % int(first_horizon))
+    return int(first_horizon)
+
+
+def resident_order(ind_start, ind_end, converged, six, block=RESIDENT_BLOCK):
+    """The lines of the resident reference run in its order: per block of 64 individuals from ind_start first the lines
+    `EM (MAF) converged at iteration: t` of the block's fits (converged[i]: the line or None), then each individual's six lines
+    (six[i]).  Both are indexed by i - ind_start."""
+    out = []
+    for i0, count in _batches(ind_start, ind_end, block):
+        out.extend(converged[i - ind_start] for i in range(i0, i0 + count) if converged[i - ind_start] is not None)
+        for i in range(i0, i0 + count):
+            out.extend(six[i - ind_start])
+    return out
+
+
+class _MaskedRounds:
+    """windowed_fit.fit_masked's backend for one round of individuals [i0, i0 + count): a round is one pass over both files; every
+    window gets its KeepSet and goes through the EMBatch of its matrix (count fits, made once per matrix and pass and kept while the
+    matrix moves: the KeepSet and the DepthTable are closed before it does) into one device.EMStream.  The final round leaves every
+    fit clamped in its batch, sweeps the statistic against it and pushes the arrays into the ZSum."""
+
+    def __init__(self, one_pass, stream, zs, i0, count, ind_start, group_of, sizes, tables, stats):
+        self.one_pass, self.stream, self.zs, self.i0, self.count, self.ind_start = one_pass, stream, zs, int(i0), int(count), int(ind_start)
+        self.ids = np.arange(self.i0, self.i0 + self.count, dtype=np.int32)
+        self.groups = np.ascontiguousarray(group_of[self.ids], dtype=np.int32)
+        lo = 1 / (2 * (np.asarray(sizes, dtype=np.float64)[self.groups] - 1 + 1))      # EMBatch.clamp(j, size - 1)
+        self.lo, self.hi = lo.astype(np.float32), (1 - lo).astype(np.float32)
+        self.key_mean, self.key_comp, self.dmap, self.drows, self.tabs = tables
+        self.slots = np.arange(self.count, dtype=np.int32)
+        self.stats = stats
+        self.kept_total = None
+        self.carry_bytes = 0
+
+    def run_round(self, plan):
+        import time
+
+        from .device import EMBatch
+        kept = np.zeros(self.count, dtype=np.int64)
+        batches = {}
+
+        def body(b, depth):
+            em = batches.get(id(b))
+            if em is None:
+                em = batches[id(b)] = EMBatch(b, self.groups, self.ids)
+                b.window_em = em
+            keep = KeepSet(depth, self.i0, self.key_mean, self.key_comp, self.dmap, self.drows)
+            try:
+                self.stream.push_masked(em, keep, self.slots, plan.run_iters, np.ones(self.count, dtype=np.int32) if plan.final else None,
+                                        self.lo, self.hi, plan.chains)
+                kept[:] += keep.kept
+                if plan.final:
+                    dev, all_kept = keep.stats_dev(self.tabs, [em.f_dev(j) for j in range(self.count)])
+                    self.zs.push(dev, all_kept, keep.kept)
+            finally:
+                keep.close()
+
+        t0 = time.perf_counter()
+        try:
+            depth_stats = self.one_pass(body)
+        finally:
+            for em in batches.values():
+                em.close()
+        C = self.stream.read_carries()
+        self.carry_bytes += C.nbytes
+        self.stats["seconds_final" if plan.final else "seconds_fit"][-1].append(time.perf_counter() - t0)
+        self.stats["depth_final" if plan.final else "depth_fit"][-1].append(depth_stats)
+        if self.kept_total is None:
+            for j in range(self.count):             # (what wgs_em_fit_masked says of the resident run's fit of this individual)
+                if kept[j] == 0:
+                    raise ValueError("fit %d: no site was kept" % ((self.i0 + j - self.ind_start) % RESIDENT_BLOCK))
+            self.kept_total = kept
+        elif not np.array_equal(kept, self.kept_total):
+            raise RuntimeError("the files changed between two passes: the kept sites differ")
+        return C, self.kept_total
+
+
+def reference_z_scores_windowed(path, depth_path, IDs, group_of, maf_iter=200, maf_tole=1e-4, n_threshold=0, single_read_threshold=False,
+                                ind_start=0, ind_end=None, window_sites=None, say=print, details=None, deep=True, counts=False,
+                                majmin=None, batch=None, ctx=None, depth_chunk_bytes=None, first_horizon=None):
+    """reference_z_scores for a Beagle FILE and a depth FILE whose matrix and depth table need not fit the device, on one rank: passes
+    over both files in consecutive windows of `window_sites` sites (a multiple of 8192, rounded down; None:
+    WGSASSIGN_ZREF_WINDOW_SITES, else what windows.plan_zref derives -- one window when everything fits), one slab per population
+    (group_of as --get_reference_af builds it), all individuals of [ind_start, ind_end) together (or in rounds of `batch`
+    individuals, each with its own passes, when windows.plan_zref says their state does not fit beside a window).
+      Pass A       exactly that of assignment_z_scores_windowed (class_pass); then the dictionaries, the key filter and the tables, once.
+      Fit rounds   per window the KeepSet and one EMStream.push_masked: every undecided fit runs from 0.25 to its horizon and the
+                   exact float32 chain of EVERY iteration not yet decided goes on over the individual's kept sites of the window, its
+                   carry staying on the device; after the last window one read of the carries decides with the resident rule
+                   (windowed_fit.ChainScheme: device.chain_diff against the kept sites of all windows).  A fit undecided at its
+                   horizon gets another round with the horizon doubled.  first_horizon: the first one (None: WGSASSIGN_ZREF_HORIZON,
+                   else ZREF_FIRST_HORIZON); correctness does not depend on it, the number of passes does.
+      Final round  per window every fit run to its stop and clamped with n_pop - 1 in its batch, the statistic sweep against it into
+                   device arrays and the push into np.sum's order (ZSum.push).
+    z, every printed line -- in the resident run's order: blocks of 64 individuals from ind_start, whatever the rounds here were --
+    the iteration counts and the assertions of the key filter are those of the resident run, bit for bit.  A population with a
+    single individual raises the resident path's ValueError before the first pass; an individual that kept no site in any window
+    raises wgs_em_fit_masked's message after the first fit round.  details (a list) receives per individual the dictionary, the
+    tables, kept (sites kept), it (the iteration count) and the sums -- no per-site array.  Host memory does not grow with m.
+    .stats: windows, window_sites, rounds, fit_rounds and horizons per round of individuals, first_horizon, passes, seconds_a /
+    seconds_fit / seconds_final and depth_a / depth_fit / depth_final (the depth ingest's statistics) per pass, downloaded_bytes;
+    .info: n, m, sample_names, site_names (first and last four)."""
+    import time
+
+    from . import reader_cy, windowed_fit, windows
+    from .device import EMStream, get_context
+    ctx = ctx or get_context()
+    index, _, m = reader_cy.ensure_index(path)
+    if m <= 0:
+        raise ValueError("%s holds no sites" % path)
+    with reader_cy.BeagleStream(path, threads=1) as st:
+        n = st.n
+    group_of = np.ascontiguousarray(group_of, dtype=np.int32)
+    if group_of.shape != (n,):
+        raise ValueError("group_of must have one entry for each of the %d individuals of %s" % (n, path))
+    n_groups = int(np.max(group_of)) + 1
+    sizes = np.bincount(group_of, minlength=n_groups)
+    ind_end = n if ind_end is None else ind_end
+    total = ind_end - ind_start
+    if np.any(sizes[group_of[ind_start:ind_end]] < 2):
+        raise ValueError("a population with a single individual has nobody left for the leave-one-out fit")
+    horizon = zref_first_horizon(first_horizon)
+    free = ctx.mem_info()[0]
+    if window_sites is None:
+        planned = windows.plan_zref(m, n, n_groups, total, free, maf_iter, counts=sizes)
+        W, batch = planned if planned is not None else (max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN, batch)
+    else:
+        if int(window_sites) < windows.ALIGN:
+            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
+        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+    batch = windows.zref_batch(W, n, n_groups, total, free, maf_iter, sizes) if not batch else min(int(batch), total)
+    rounds = list(_batches(ind_start, ind_end, batch))
+    if len(rounds) > 1:
+        say("wgsassign_amd: the z-scores of %d individuals run in %d rounds of at most %d" % (total, len(rounds), batch))
+    z_out = np.empty((total, 1), dtype=np.float32)
+    info = {}
+    stats = dict(windows=0, window_sites=W, rounds=len(rounds), fit_rounds=[], horizons=[], first_horizon=horizon, passes=0, seconds_a=[],
+                 seconds_fit=[], seconds_final=[], depth_a=[], depth_fit=[], depth_final=[], downloaded_bytes=0)
+    converged, six = [None] * total, [None] * total
+
+    def one_pass(body):
+        stats["passes"] += 1
+        return window_pass(path, depth_path, m, n, W, ctx, info, body, counts, majmin, depth_chunk_bytes, group_of, n_groups)
+
+    for i0, count in rounds:
+        zs = ZSum(count, ctx)
+        stream = None
+        try:
+            t0 = time.perf_counter()
+            cnt_tot, first_glob, class_sums, over_tot, listed, depth_a = class_pass(zs, i0, count, deep, one_pass)
+            stats["depth_a"].append(depth_a)
+            stats["seconds_a"].append(time.perf_counter() - t0)
+            summ = dictionaries(i0, cnt_tot, first_glob, class_sums, over_tot, listed, n_threshold, single_read_threshold, deep)
+            key_mean, key_comp = mask_tables(summ)
+            dmap, drows = deep_tables(summ)
+            tabs, tparts = stat_tables(summ)
+            for key in ("seconds_fit", "seconds_final", "depth_fit", "depth_final"):
+                stats[key].append([])
+            stream = EMStream(count, maf_iter, m, ctx)
+            backend = _MaskedRounds(one_pass, stream, zs, i0, count, ind_start, group_of, sizes, (key_mean, key_comp, dmap, drows, tabs), stats)
+            iters, scheme = windowed_fit.fit_masked(backend, count, maf_iter, maf_tole, horizon)
+            stats["fit_rounds"].append(scheme.fit_rounds)
+            stats["horizons"].append(list(scheme.horizons))
+            totals, sums3 = zs.finish()
+            assert np.array_equal(totals, backend.kept_total)
+            for j in range(count):
+                lines = []
+                r = _finish_sums(i0 + j, totals[j], sums3[j, 0], sums3[j, 1], sums3[j, 2], lines.append)
+                six[i0 + j - ind_start] = lines
+                if iters[j]:
+                    converged[i0 + j - ind_start] = "EM (MAF) converged at iteration: " + str(int(iters[j]))
+                z_out[i0 + j - ind_start, 0] = r["z"]
+                if details is not None:
+                    details.append(dict(summ[j], fac=tparts[j][0], like=tparts[j][1], index=tparts[j][2], kept=int(totals[j]),
+                                        it=int(iters[j]), **r))
+            stats["downloaded_bytes"] += zs.downloaded + backend.carry_bytes
+        finally:
+            if stream is not None:
+                stream.close()
+            zs.close()
+    for line in resident_order(ind_start, ind_end, converged, six):
+        say(line)
+    stats["windows"] = info.get("windows", 0)
+    reference_z_scores_windowed.stats = stats
+    reference_z_scores_windowed.info = dict({k: info.get(k) for k in ("m", "sample_names", "site_names")}, n=n)
     return z_out
