@@ -53,7 +53,7 @@ const char *wgs_last_error(void);
  * windowed scoring (wgs_score_stream_*, wgs_beagle_set_window).  4: --ne_obs in site windows (wgs_fisher_stream_*); no existing
  * signature changed.  --get_assignment_z_score in site windows (wgs_zsum_*, wgs_zscore_classes_carry, wgs_zscore_stats_dev,
  * wgs_depth_copy_rows, wgs_depth_ingest_set_selectors) was ADDED under 4, and so was --get_reference_z_score in site windows
- * (wgs_em_stream_push_masked). */
+ * (wgs_em_stream_push_masked), and --loo_downsampled_beagle in site windows (wgs_loo_stream_push_scored). */
 #define WGS_ABI_VERSION 4
 int wgs_version(void);
 /* sha256[:16] over every source of the library / over the sources of the EM and scoring kernels (em_kernels.hip,
@@ -357,6 +357,11 @@ int wgs_em_stream_push_keep(wgs_em_stream *stream, wgs_em *window_em, const int3
  *                            totals and walks the partition chains on from the carries (labels (site0 + s) % P; the literal chains beyond
  *                            WGS_MAX_BLOCK_PARALLEL_PARTS partitions).  The window rules of wgs_score_stream_push hold, the window has
  *                            the stream's n and K and the batch is the n re-fits; anything else: rc 2 and a message, nothing launched;
+ *   wgs_loo_stream_push_scored  the same with the matrix that is scored given apart (--loo_downsampled_beagle: the downsampled file's window
+ *                            of the same kept sites; wgs_loo's `scored`): the column table comes from window_em and window_af, the sweep,
+ *                            the chunk sums and the chains read scored_window.  It must be of the stream's context and have the fitted
+ *                            window's n, m, site0, n_groups and group_of: anything else is rc 2 and a message, nothing launched, the
+ *                            stream unchanged.  scored_window == the matrix of window_em is wgs_loo_stream_push;
  *   wgs_loo_stream_finish    the one read-back: ll_out (host, n*K float64), parts_out (host, n*P*K float32, index (i*P + p)*K + k; NULL
  *                            when P == 0).  rc 2 before all m_total sites were pushed;
  *   wgs_loo_stream_destroy   a no-op for a stream that is gone already.  Like the other streams, to be destroyed before its context. */
@@ -364,6 +369,7 @@ int wgs_em_stream_push_keep(wgs_em_stream *stream, wgs_em *window_em, const int3
 typedef struct wgs_loo_stream wgs_loo_stream;
 int wgs_loo_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, int32_t P, wgs_loo_stream **out);
 int wgs_loo_stream_push(wgs_loo_stream *stream, wgs_em *window_em, wgs_afset *window_af, int mode);
+int wgs_loo_stream_push_scored(wgs_loo_stream *stream, wgs_em *window_em, wgs_beagle *scored_window, wgs_afset *window_af, int mode);
 int wgs_loo_stream_finish(wgs_loo_stream *stream, double *ll_out, float *parts_out);
 void wgs_loo_stream_destroy(wgs_loo_stream *stream);
 

@@ -5,6 +5,7 @@
                                    [--parent-root DIR] [--out profiles/windowed_bench.json]
     python tools/bench_windowed.py --fit [...] [--out profiles/windowed_fit_bench.json]      # the same for --get_reference_af
     python tools/bench_windowed.py --loo [...] [--out profiles/windowed_loo_bench.json]      # the same for --get_reference_af --loo
+    python tools/bench_windowed.py --loo-ds [...] [--out profiles/windowed_loo_ds_bench.json]  # ... with --loo_downsampled_beagle
     python tools/bench_windowed.py --ne [...] [--out profiles/windowed_ne_obs_bench.json]    # the same for --get_reference_af --ne_obs
     python tools/bench_windowed.py --z [...] [--out profiles/z_windowed.json]                # the same for --get_assignment_z_score
     python tools/bench_windowed.py --zref [...] [--out profiles/zref_windowed.json]          # the same for --get_reference_z_score
@@ -27,6 +28,10 @@ WGSASSIGN_LOO_WINDOW_SITES): the three whole-process figures, and from one emMAF
 the rounds, the seconds of every round, the first horizons' iterations against the iterations the re-fits needed, and the resident
 re-fit and scoring seconds of glassy.loo_device on the same file.  What to expect there: rounds x the windowed pass, plus the resident
 re-fit time x (iterations run / iterations needed), plus the per-window launches.
+--loo-ds measures --get_reference_af --loo --loo_downsampled_beagle (both files in windows of kept sites;
+WGSASSIGN_LOO_DS_WINDOW_SITES): the downsampled file holds the first four fifths of the reference file's sites under another seed, so
+the reference file's mask drops its last fifth; --windows counts windows of KEPT sites.  The whole-process figures resident against
+windowed, and from glassy.loo_windowed in this process the rounds, their seconds and how often the downsampled file was read.
 --ne measures --get_reference_af --ne_obs (the windowed fit, then one pass for the Fisher information; WGSASSIGN_NE_WINDOW_SITES): the
 three whole-process figures, and from fisher.fisher_obs_windowed in this process the fused sweep's time per window between events
 (fisher_window_kernel).  What the resident path spends in its three kernels over the same sites (fisher_pop_kernel,
@@ -62,19 +67,21 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 
 
-def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False, ne=False, z=None, zref=None):
+def cli_seconds(root, beagle, af, out, env_extra, fit=False, loo=False, ne=False, z=None, zref=None, loo_ds=None):
     """af: the frequency file of --get_pop_like, or with fit (or loo, or ne) the ID file of --get_reference_af.  z: the further
     arguments of --get_assignment_z_score (ID, names and depth files), which then stands in place of --get_pop_like.  zref: all the
-    arguments of --get_reference_z_score (af is not looked at).  cli_seconds.stdout: what the last command printed."""
+    arguments of --get_reference_z_score (af is not looked at).  loo_ds: the file of --loo_downsampled_beagle (with loo).  cli_seconds.stdout: what the last command printed."""
     env = dict(os.environ)
     env.pop("WGSASSIGN_WINDOW_SITES", None)
     env.pop("WGSASSIGN_LOO_WINDOW_SITES", None)
+    env.pop("WGSASSIGN_LOO_DS_WINDOW_SITES", None)
     env.pop("WGSASSIGN_NE_WINDOW_SITES", None)
     env.pop("WGSASSIGN_Z_WINDOW_SITES", None)
     env.pop("WGSASSIGN_ZREF_WINDOW_SITES", None)
     env.update(env_extra)
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
-    what = (["--pop_af_IDs", af, "--get_reference_af"] + (["--loo"] if loo else []) + (["--ne_obs"] if ne else []) if fit or loo or ne
+    what = (["--pop_af_IDs", af, "--get_reference_af"] + (["--loo"] if loo else []) + (["--loo_downsampled_beagle", loo_ds] if loo_ds else []) +
+            (["--ne_obs"] if ne else []) if fit or loo or ne
             else ["--get_reference_z_score"] + list(zref) if zref is not None
             else ["--pop_af_file", af, "--get_assignment_z_score"] + list(z) if z is not None
             else ["--pop_af_file", af, "--get_pop_like"])
@@ -180,6 +187,53 @@ def loo_leg(a, m, n, K, W):
         beagle.close()
         res.update(resident_refit_seconds=round(tm.get("em_seconds", 0.0), 4), resident_score_seconds=round(tm.get("score_seconds", 0.0), 4),
                    resident_iterations_enqueued=tm.get("em_iterations_enqueued"), totals_bit_identical=bool(ll.tobytes() == ll_r.tobytes()))
+    return res
+
+
+def loo_ds_leg(a, m, n, K):
+    """--get_reference_af --loo --loo_downsampled_beagle resident against windowed; one JSON-able dict.  m: the reference file's sites;
+    four fifths of them are kept."""
+    import beagle_files
+    from wgsassign_amd import device, emMAF, glassy, windows
+    kept = m * 4 // 5
+    W = ((kept + a.windows - 1) // a.windows + windows.ALIGN - 1) // windows.ALIGN * windows.ALIGN
+    if a.window_sites:
+        W = a.window_sites // windows.ALIGN * windows.ALIGN
+    nwin = windows.window_count(kept, W)
+    res = {"bench": "windowed_loo_downsampled", "snps": m, "kept_snps": kept, "inds": n, "pops": K, "window_sites": W, "windows": nwin}
+    with tempfile.TemporaryDirectory() as td:
+        os.environ["WGSASSIGN_INDEX_DIR"] = td
+        bg, ds, ids = os.path.join(td, "x.beagle.gz"), os.path.join(td, "d.beagle.gz"), os.path.join(td, "ids.txt")
+        beagle_files.write_lowdepth_bgzf(bg, n, m, seed=5)
+        beagle_files.write_lowdepth_bgzf(ds, n, kept, seed=6)
+        IDs = np.array([["Ind%d" % i, "pop%d" % (i * K // n)] for i in range(n)])
+        np.savetxt(ids, IDs, fmt="%s", delimiter="\t")
+        res.update(file_mb=round(os.path.getsize(bg) / 1e6, 1), downsampled_file_mb=round(os.path.getsize(ds) / 1e6, 1))
+        variants = [("resident_s", ROOT, {}), ("windowed_s", ROOT, {"WGSASSIGN_LOO_DS_WINDOW_SITES": str(W)})]
+        times = {name: [] for name, _, _ in variants}
+        for rep in range(a.repeats + 1):
+            for name, root, env in variants:
+                dt, err = cli_seconds(root, bg, ids, os.path.join(td, name), env, loo=True, loo_ds=ds)
+                if rep:
+                    times[name].append(dt)
+                if name == "windowed_s" and ("rounds of %d windows of %d kept sites" % (nwin, W)) not in err:
+                    raise RuntimeError("the windowed run did not use %d windows: %s" % (nwin, err[-300:]))
+        files = {name: open(os.path.join(td, name + ".pop_af.npy"), "rb").read() +
+                 open(os.path.join(td, name + ".pop_like_LOO_downsampled.tsv"), "rb").read() for name, _, _ in variants}
+        res["outputs_identical"] = len(set(files.values())) == 1
+        for name in ("resident_s", "windowed_s"):
+            res[name] = spread(times[name])
+        res["windowed_over_resident"] = round(res["windowed_s"]["median"] / res["resident_s"]["median"], 3)
+        ctx = device.get_context()
+        res["device"] = ctx.info()["name"].strip()
+        keep = np.arange(m) < kept
+        for rep in range(2):
+            af, pop_iters = emMAF.emMAF_windowed(bg, IDs, 200, 1e-4, W, ctx=ctx, keep=keep)
+            glassy.loo_windowed(bg, af, IDs, 200, 1e-4, W, 1, need_parts=False, pop_iters=pop_iters, ctx=ctx, keep=keep, scored_path=ds)
+        st = glassy.loo_windowed.stats
+        res.update(fit_rounds=emMAF.emMAF_windowed.stats["rounds"], rounds=st["rounds"], round_seconds=[round(x, 3) for x in st["round_seconds"]],
+                   extension_rounds=st["extension_rounds"], scored_passes=st["scored_passes"], matrices=st["matrices"],
+                   largest_matrix_bytes=st["largest_matrix_bytes"])
     return res
 
 
@@ -385,6 +439,7 @@ def main():
     ap.add_argument("--probe", action="store_true", help="with --ne: only run the resident functions and the windowed pass once (for a kernel trace)")
     ap.add_argument("--kernel-stats", default=None, help="with --ne: a rocprofv3 *_kernel_stats.csv of a --ne --probe run, added to the result")
     ap.add_argument("--loo", action="store_true", help="measure --get_reference_af --loo (the leave-one-out run in windows)")
+    ap.add_argument("--loo-ds", action="store_true", help="measure --get_reference_af --loo --loo_downsampled_beagle (two files in windows)")
     ap.add_argument("--fit", action="store_true", help="measure --get_reference_af (the fit in windows) instead of --get_pop_like")
     ap.add_argument("--snps", type=int, default=1_000_000)
     ap.add_argument("--inds", type=int, default=200)
@@ -398,6 +453,13 @@ def main():
     import beagle_files
     from wgsassign_amd import device, glassy, reader_cy, windows
     m, n, K = a.snps, a.inds, a.pops
+    if a.loo_ds:
+        line = json.dumps(loo_ds_leg(a, m, n, K))
+        print(line)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     per_window = (m + a.windows - 1) // a.windows
     W = (per_window + windows.ALIGN - 1) // windows.ALIGN * windows.ALIGN          # rounded UP to whole chunks of 8192
     if a.window_sites:                                                             # (--z: windows of 262144 sites by default)

@@ -90,14 +90,19 @@ SET_WINDOW_SITES_ZREF = ("the matrix was expected to fit the device and does not
                          "to compute the reference z-scores in site windows")
 
 
-def with_windows_hint(error, candidate=False, z_candidate=False, zref_candidate=False):
+SET_WINDOW_SITES_LOO_DS = ("the two matrices were expected to fit the device and do not: set WGSASSIGN_LOO_DS_WINDOW_SITES (a multiple of 8192 "
+                           "sites) to run the leave-one-out on downsampled likelihoods in site windows")
+
+
+def with_windows_hint(error, candidate=False, z_candidate=False, zref_candidate=False, loo_ds_candidate=False):
     """The error of a resident run whose matrix did not fit the device, saying what windows cover -- or, when the options were
     those windows cover (candidate: the file was only judged to fit; z_candidate: --get_assignment_z_score alone, which has a
-    variable of its own; zref_candidate: --get_reference_z_score alone, which has another), how to ask for them; any other error
-    as it is."""
+    variable of its own; zref_candidate: --get_reference_z_score alone, which has another; loo_ds_candidate: --get_reference_af --loo
+    --loo_downsampled_beagle, which has a third), how to ask for them; any other error as it is."""
     if isinstance(error, RuntimeError) and all(part in str(error) for part in SLAB_ALLOC_FAILED):
         return RuntimeError(str(error) + ": " + (SET_WINDOW_SITES_Z if z_candidate else SET_WINDOW_SITES_ZREF if zref_candidate else
-                                                 SET_WINDOW_SITES if candidate else WINDOWS_ONLY))
+                                                 SET_WINDOW_SITES_LOO_DS if loo_ds_candidate else SET_WINDOW_SITES if candidate else
+                                                 WINDOWS_ONLY))
     return error
 
 
@@ -187,8 +192,8 @@ def _fit_window_sites(args, comm, ctx):
 def windowed_loo_candidate(args, world=1):
     """Whether these options may run in site windows end to end (emMAF.emMAF_windowed, then glassy.loo_windowed):
     --get_reference_af --loo alone, with any --partition_sites, on one rank.  With --ne_obs beside them the run has a route of its own
-    (windowed_ne_candidate); the z-scores, --get_pop_like beside them and --loo_downsampled_beagle (two files in lockstep under a site
-    filter) still need the whole matrix on the device."""
+    (windowed_ne_candidate), and so it has with --loo_downsampled_beagle (two files in lockstep under a site filter:
+    windowed_loo_ds_candidate); the z-scores and --get_pop_like beside them still need the whole matrix on the device."""
     others = (args.get_pop_like, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score, args.loo_downsampled_beagle)
     return bool(args.get_reference_af) and bool(args.loo) and int(world) == 1 and not any(others)
 
@@ -225,6 +230,93 @@ def _loo_window_sites(args, comm, ctx):
         return windows.plan_loo(m, n, K, free, counts=counts, P=args.partition_sites)
     except MemoryError as e:
         raise SystemExit(str(e))
+
+
+def windowed_loo_ds_candidate(args, world=1):
+    """Whether these options may run in site windows with a downsampled file scored (emMAF.emMAF_windowed under the reference file's
+    site mask, then glassy.loo_windowed with both masks and the second file): --get_reference_af --loo --loo_downsampled_beagle, with any
+    --partition_sites, on one rank.  With --ne_obs, --get_pop_like or a z-score option beside them the run stays resident."""
+    others = (args.get_pop_like, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score)
+    return bool(args.get_reference_af) and bool(args.loo) and bool(args.loo_downsampled_beagle) and int(world) == 1 and not any(others)
+
+
+def _loo_ds_window_sites(args, comm, ctx, m_kept=None):
+    """The window of KEPT sites --get_reference_af --loo --loo_downsampled_beagle runs in, or None for the resident path:
+    WGSASSIGN_LOO_DS_WINDOW_SITES when set (no other variable sends this run to windows), else windows only when the two resident
+    matrices would not fit (windows.plan_loo_ds): a pair of files whose compressed sizes together say that they fit
+    (windows.surely_fits) is looked at no further.  m_kept: the sites both files keep under their masks, when the caller has them
+    (None: the reference file's sites, which bound them)."""
+    import numpy as np
+
+    from . import reader_cy, windows
+    if not windowed_loo_ds_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
+        return None                     # (a missing ID file is reported where it always was)
+    try:
+        W = windows.env_window_sites(name=windows.ENV_LOO_DS)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if W is not None:
+        return W
+    free = ctx.mem_info()[0]
+    if windows.surely_fits(os.path.getsize(args.beagle) + os.path.getsize(args.loo_downsampled_beagle), free):
+        return None
+    try:
+        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
+        counts = np.unique(IDs[:, 1], return_counts=True)[1]
+    except Exception:
+        return None                     # (an unreadable ID file, too, is reported where it always was)
+    n, K = int(counts.sum()), len(counts)
+    if m_kept is None:
+        m_kept = reader_cy.ensure_index(args.beagle)[2]
+    try:
+        return windows.plan_loo_ds(m_kept, n, K, free, counts=counts, P=args.partition_sites)
+    except MemoryError as e:
+        raise SystemExit(str(e))
+
+
+def _run_loo_ds_windowed(args, ctx, W, IDs, pops, sample_names, keep_ref, keep_ds, say):
+    """--get_reference_af --loo --loo_downsampled_beagle on files that do not fit (or WGSASSIGN_LOO_DS_WINDOW_SITES), after the names
+    passes and the two site masks of the resident run: the fit over the kept sites of the reference file in windows, then the
+    leave-one-out run in the same windows with the downsampled file's windows scored beside them; the lines and files of the resident
+    run in their order, and one more line on stderr."""
+    import numpy as np
+
+    from . import emMAF, glassy, utils
+    P = args.partition_sites
+    say("Parsing reference population ID file.")
+    assert (len(sample_names) == IDs.shape[0]), "Number of individuals in beagle and reference ID file do not match!"
+    af, iters = emMAF.emMAF_windowed(args.beagle, IDs, args.maf_iter, args.maf_tole, W, out=args.out + ".pop_af.npy", ctx=ctx, keep=keep_ref)
+    for it in iters:
+        if it > 0:
+            say("EM (MAF) converged at iteration: " + str(int(it)))
+    del af
+    say("Saved reference population allele frequencies as " + str(args.out) + ".pop_af.npy (Binary - np.float32)\n")
+    say("Column order of populations is: " + str(pops))
+    np.savetxt(args.out + ".pop_names.txt", pops, fmt="%s")
+    say("Saved reference population names as " + str(args.out) +
+        ".pop_names.txt (String: Order of pops for .pop_af.npy, .ne_obs.npy, and fisher_obs.npy files)\n")
+    say("Performing leave-one-out cross validation.")
+    say(str(len(sample_names)) + " individuals to assign to " + str(len(pops)) + " populations")
+    say("Using downsampled GLs for likelihood evaluation in LOO assignment.")
+    A = np.load(args.out + ".pop_af.npy", mmap_mode="r")
+    ll, parts, loo_iters = glassy.loo_windowed(args.beagle, A, IDs, args.maf_iter, args.maf_tole, W, P, need_parts=P > 1, pop_iters=iters,
+                                               ctx=ctx, keep=keep_ref, scored_path=args.loo_downsampled_beagle, scored_keep=keep_ds)
+    del A
+    stats = glassy.loo_windowed.stats
+    for it in loo_iters:
+        if it > 0:
+            say("EM (MAF) converged at iteration: " + str(int(it)))
+    print("wgsassign_amd: leave-one-out on downsampled likelihoods in %d rounds of %d windows of %d kept sites (the downsampled file read "
+          "%d time)" % (stats["rounds"], stats["windows"], stats["window_sites"], stats["scored_passes"]), file=sys.stderr, flush=True)
+    outfile = f"{args.out}.pop_like_LOO_downsampled.tsv"
+    partfile = f"{args.out}.pop_like_LOO_downsampled_partitions_{P}.tsv.gz"
+    utils.write_ass_mats(outfile, ll, sample_names, pops, print_part_column=False, sample_locations=IDs[:, 1], doing_LOO=True)
+    say(f"Saved leave-one-out cross validation log likelihoods as {outfile}")
+    if P > 1:
+        utils.write_ass_mats(partfile, parts, sample_names, pops, partition_count=P, print_part_column=True,
+                             sample_locations=IDs[:, 1], doing_LOO=True)
+        say(f"Saved leave-one-out cross validation log likelihoods from partitioned sites as {partfile}")
+    say(f"Column order of populations is: {pops}")
 
 
 def windowed_ne_candidate(args, world=1):
@@ -619,10 +711,24 @@ def _run(args, comm):
             print(f"\tFiltered out {int(np.sum(~keep_ds))} sites not present in the target site list.")
         if kept_ref != [x for x, k in zip(names_ds, keep_ds) if k]:
             raise ValueError("Site names in full and downsampled Beagle do not match after filtering.")
-        beagle, _, site_names, m = reader_cy.stream_to_device(args.beagle, group_of, n_groups, ctx=ctx, rank=comm.rank,
-                                                              world=comm.world, keep=keep_ref, comm=comm)
-        scored, _, _, _ = reader_cy.stream_to_device(args.loo_downsampled_beagle, group_of, n_groups, ctx=ctx,
-                                                     rank=comm.rank, world=comm.world, keep=keep_ds, comm=comm)
+        W_ds = _loo_ds_window_sites(args, comm, ctx, m_kept=len(kept_ref))
+        if W_ds is not None:
+            # --get_reference_af --loo --loo_downsampled_beagle on files that do not fit (or WGSASSIGN_LOO_DS_WINDOW_SITES): both files
+            # in windows of kept sites; the names of both files still live on the host
+            del names_ref, names_ds, kept_ref
+            _run_loo_ds_windowed(args, ctx, W_ds, IDs, pops, sample_names, keep_ref, keep_ds, say)
+            comm.barrier()
+            return
+        try:
+            beagle, _, site_names, m = reader_cy.stream_to_device(args.beagle, group_of, n_groups, ctx=ctx, rank=comm.rank,
+                                                                  world=comm.world, keep=keep_ref, comm=comm)
+            scored, _, _, _ = reader_cy.stream_to_device(args.loo_downsampled_beagle, group_of, n_groups, ctx=ctx,
+                                                         rank=comm.rank, world=comm.world, keep=keep_ds, comm=comm)
+        except RuntimeError as e:
+            hinted = with_windows_hint(e, loo_ds_candidate=windowed_loo_ds_candidate(args, comm.world))
+            if hinted is e:
+                raise
+            raise hinted from e
     else:
         try:
             beagle, sample_names, site_names, m = reader_cy.stream_to_device(

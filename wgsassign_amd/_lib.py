@@ -191,6 +191,7 @@ SIGNATURES = {
     "wgs_em_stream_push_masked": (c_int, [c_vp, c_vp, c_vp, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32]),
     "wgs_loo_stream_create": (c_int, [c_vp, c_i64, c_i32, c_i64, c_i32, ctypes.POINTER(c_vp)]),
     "wgs_loo_stream_push": (c_int, [c_vp, c_vp, c_vp, c_int]),
+    "wgs_loo_stream_push_scored": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int]),
     "wgs_loo_stream_finish": (c_int, [c_vp, c_f64p, c_f32p]),
     "wgs_loo_stream_destroy": (None, [c_vp]),
     "wgs_fisher_stream_create": (c_int, [c_vp, c_i64, c_i32, c_i64, ctypes.POINTER(c_vp)]),

@@ -49,3 +49,19 @@ inline int loo_stream_window_refusal(int64_t site0, int64_t rows, int64_t pushed
                       (long long)rows, (long long)align);
     return 0;
 }
+
+// wgs_loo_stream_push_scored: the matrix that is scored in place of the window the re-fits were made from (the downsampled file's window)
+// must be that window's twin -- the same individuals, kept sites and first site, the same population slabs in the same file order.
+inline int loo_stream_scored_refusal(int64_t n_scored, int64_t rows_scored, int64_t site0_scored, int32_t groups_scored, const int32_t *group_of_scored,
+                                     int64_t n, int64_t rows, int64_t site0, int32_t groups, const int32_t *group_of, char *msg, size_t msg_len)
+{
+    LOO_STREAM_REFUSE(n_scored == n, "the scored window holds %lld individuals, the fitted window %lld", (long long)n_scored, (long long)n);
+    LOO_STREAM_REFUSE(rows_scored == rows, "the scored window holds %lld sites, the fitted window %lld", (long long)rows_scored, (long long)rows);
+    LOO_STREAM_REFUSE(site0_scored == site0, "the scored window starts at site %lld, the fitted window at site %lld", (long long)site0_scored,
+                      (long long)site0);
+    LOO_STREAM_REFUSE(groups_scored == groups, "the scored window has %d population slabs, the fitted window %d", groups_scored, groups);
+    for (int64_t i = 0; i < n; ++i)
+        LOO_STREAM_REFUSE(group_of_scored[i] == group_of[i], "individual %lld is of population %d in the scored window, of population %d in the fitted one",
+                          (long long)i, group_of_scored[i], group_of[i]);
+    return 0;
+}

@@ -1089,14 +1089,29 @@ int wgs_loo_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, i
 int wgs_loo_stream_push(wgs_loo_stream *st, wgs_em *window_em, wgs_afset *window_af, int mode)
 {
     WGS_REQUIRE(st && window_em && window_af, "null argument");
+    return wgs_loo_stream_push_scored(st, window_em, window_em->b, window_af, mode);
+}
+
+/* wgs_loo_stream_push with the matrix that is SCORED given apart from the one the re-fits were made from (--loo_downsampled_beagle in
+ * site windows: `scored_window` is the downsampled file's window of the same kept sites; wgs_loo's `scored`).  The column table still
+ * comes from window_em and window_af; the sweep, the chunk sums and the partition chains read scored_window.  A scored window of another
+ * context, with another n, m, site0 or n_groups, or with another group_of than the fitted window's: rc 2 and a message, nothing
+ * launched, the stream as it was.  scored_window == the matrix of window_em is wgs_loo_stream_push. */
+int wgs_loo_stream_push_scored(wgs_loo_stream *st, wgs_em *window_em, wgs_beagle *scored_window, wgs_afset *window_af, int mode)
+{
+    WGS_REQUIRE(st && window_em && scored_window && window_af, "null argument");
     WGS_REQUIRE(mode == WGS_MODE_EXACT || mode == WGS_MODE_FAST, "unknown mode %d", mode);
     wgs_beagle *window = window_em->b;
     WGS_REQUIRE(window->ctx == st->ctx && window_af->ctx == st->ctx, "the window belongs to another context than the leave-one-out stream");
+    WGS_REQUIRE(scored_window->ctx == st->ctx, "the scored window belongs to another context than the leave-one-out stream");
     char why[256];
     if (loo_stream_shape_refusal(window->n, window->n_groups, window_em->n_fits, window_af->K, window_af->m, window->m, st->n, st->K, why,
                                  sizeof why) ||
         loo_stream_fits_refusal(st->n, window_em->group.data(), window_em->skip_local.data(), window->group_of.data(), why, sizeof why) ||
-        loo_stream_window_refusal(window->site0, window->m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why)) {
+        loo_stream_window_refusal(window->site0, window->m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why) ||
+        (scored_window != window &&
+         loo_stream_scored_refusal(scored_window->n, scored_window->m, scored_window->site0, scored_window->n_groups, scored_window->group_of.data(),
+                                   window->n, window->m, window->site0, window->n_groups, window->group_of.data(), why, sizeof why))) {
         wgs_set_error("%s", why);
         return 2;
     }
@@ -1114,7 +1129,7 @@ int wgs_loo_stream_push(wgs_loo_stream *st, wgs_em *window_em, wgs_afset *window
     }
     wgs_score *sc = nullptr;
     auto guard = on_failure([&] { wgs_score_destroy(sc); });
-    if (int rc = wgs_score_create(window, window_af, colptr.data(), 0, (int32_t)n, &sc)) return rc;
+    if (int rc = wgs_score_create(scored_window, window_af, colptr.data(), 0, (int32_t)n, &sc)) return rc;
     if (score_sums_enqueue(sc, P > 0 ? WGS_MODE_EXACT : mode)) return 1;
     sc->have_prefix = P > 0;
     const double *before = st->pushed ? st->d_run[st->cur] : nullptr;      // the totals over the windows before this one
@@ -1133,7 +1148,7 @@ int wgs_loo_stream_push(wgs_loo_stream *st, wgs_em *window_em, wgs_afset *window
             HIP_TRY(hipMemcpyAsync(st->h_carry.data(), st->d_carry, sizeof(float) * chains, hipMemcpyDeviceToHost, ctx->stream));
         }
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (int rc = parts_exact_literal(window, window_af, colptr.data(), P, before ? st->h_carry.data() : nullptr, st->h_parts.data())) return rc;
+        if (int rc = parts_exact_literal(scored_window, window_af, colptr.data(), P, before ? st->h_carry.data() : nullptr, st->h_parts.data())) return rc;
         HIP_TRY(hipMemcpyAsync(st->d_carry, st->h_parts.data(), sizeof(float) * chains, hipMemcpyHostToDevice, ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -896,11 +896,16 @@ class LooStream:
     def handle(self):
         return self._h
 
-    def push(self, em, afset, mode=None):
+    def push(self, em, afset, mode=None, scored=None):
         """Scores one window: `em` holds its n re-fits at their stopping iterations, clamped (EMStream.push_keep); afset the
-        window's rows of the full-population frequencies.  em.b.site0 must be the number of sites pushed so far."""
+        window's rows of the full-population frequencies.  em.b.site0 must be the number of sites pushed so far.  scored (a
+        DeviceBeagle, optional): the matrix that is scored in place of em's own -- the downsampled file's window of the same sites
+        (wgs_loo_stream_push_scored)."""
         mode = default_mode() if mode is None else mode
-        check(_lib.load().wgs_loo_stream_push(self._h, em.handle, afset.handle, mode))
+        if scored is None:
+            check(_lib.load().wgs_loo_stream_push(self._h, em.handle, afset.handle, mode))
+        else:
+            check(_lib.load().wgs_loo_stream_push_scored(self._h, em.handle, scored.handle, afset.handle, mode))
         self.windows += 1
 
     def finish(self):

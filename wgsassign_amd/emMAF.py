@@ -105,7 +105,7 @@ class _DeviceRounds:
         return S, C
 
 
-def emMAF_windowed(path, IDs, maf_iter, tole, window_sites=None, out=None, ctx=None):
+def emMAF_windowed(path, IDs, maf_iter, tole, window_sites=None, out=None, ctx=None, keep=None):
     """emMAF_populations for a Beagle FILE whose matrix need not fit the device: the sites are fitted in consecutive windows of
     `window_sites` sites (a multiple of 8192, rounded down; None: WGSASSIGN_WINDOW_SITES, else what windows.plan_fit derives from
     the free device memory), in rounds over the file (windowed_fit.py: the stopping iteration of every fit from sums and chains
@@ -115,7 +115,9 @@ def emMAF_windowed(path, IDs, maf_iter, tole, window_sites=None, out=None, ctx=N
     emMAF_windowed.stats: rounds, windows, window_sites, chain_iterations, largest_matrix_bytes, matrices, seconds,
     round_seconds, iterations_round1 (EM iterations round 1 ran per site, all fits) against iterations_needed (the sum of the
     fits' stopping iterations);
-    emMAF_windowed.info: n, m, sample_names, site_names (the first and last four), pops."""
+    emMAF_windowed.info: n, m, sample_names, site_names (the first and last four), pops.
+    keep (a bool array over the file's rows): the fits run over the KEPT sites, numbered as stream_to_device(path, keep=keep) numbers
+    them -- m, the rows of af, the windows and the names are those of kept sites (reader_cy.stream_windows)."""
     import time
 
     from . import reader_cy, windowed_fit, windows
@@ -128,6 +130,11 @@ def emMAF_windowed(path, IDs, maf_iter, tole, window_sites=None, out=None, ctx=N
     counts = np.bincount(group_of, minlength=len(pops))
     K = len(pops)
     index, _, m = reader_cy.ensure_index(path)
+    if keep is not None:
+        keep = np.asarray(keep, dtype=bool)
+        if keep.ndim != 1 or len(keep) != m:
+            raise ValueError("the site mask has %d entries, %s holds %d sites" % (keep.size, path, m))
+        m = int(np.count_nonzero(keep))
     if m <= 0:
         raise ValueError("%s holds no sites" % path)
     if window_sites is None:
@@ -148,7 +155,7 @@ def emMAF_windowed(path, IDs, maf_iter, tole, window_sites=None, out=None, ctx=N
     info, stats = {}, {"round_seconds": []}
     stream = EMStream(K, maf_iter, m, ctx)
     rounds = _DeviceRounds(None, stream, counts, af, stats)
-    gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info, group_of=groups, n_groups=K, again=rounds.again)
+    gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info, group_of=groups, n_groups=K, again=rounds.again, keep=keep)
     rounds.windows = gen
     try:
         iters, scheme = windowed_fit.fit(rounds, K, maf_iter, tole, m, EMBatch.GUARD)

@@ -277,10 +277,13 @@ def loo_first_iters(group_of, pop_iters, maf_iter, margin=None):
 class _LooRounds:
     """windowed_fit's backend for the leave-one-out re-fits: a round is one pass of reader_cy.stream_windows, every window pushed
     through the EMBatch of its matrix (n re-fits, kept for every window and round) into one device.EMStream; in the last round --
-    every fit final -- the batch stays on the device and the window is scored into one device.LooStream."""
+    every fit final -- the batch stays on the device and the window is scored into one device.LooStream.  scored (optional): a second
+    reader_cy.stream_windows, over the file whose likelihoods are scored; it is advanced in the last round only, one window beside
+    every re-fit batch, so that file is read once."""
 
-    def __init__(self, windows, stream, loo, group_of, counts, af, stats, mode):
+    def __init__(self, windows, stream, loo, group_of, counts, af, stats, mode, scored=None):
         self.windows, self.stream, self.loo, self.group_of, self.af, self.stats, self.mode = windows, stream, loo, group_of, af, stats, mode
+        self.scored, self.scored_passes = scored, 0
         lo = 1 / (2 * (np.asarray(counts, dtype=np.float64)[group_of] - 1 + 1))        # glassy.py:80-85 with n_pop = |pop| - 1, as EMBatch.clamp forms them
         self.lo, self.hi = lo.astype(np.float32), (1 - lo).astype(np.float32)
         self.batches = {}
@@ -307,7 +310,14 @@ class _LooRounds:
             if final:
                 afs = AFSet.from_host(np.ascontiguousarray(self.af[b.site0:b.site0 + b.m], dtype=np.float32), ctx=self.stream.ctx)
                 try:
-                    self.loo.push(em, afs, self.mode)
+                    sb = None
+                    if self.scored is not None:
+                        sb = next(self.scored, None)    # the downsampled file's window of the same kept sites
+                        if sb is None:
+                            raise RuntimeError("the scored file ran out of windows before the fitted one")
+                        if sb.site0 == 0:
+                            self.scored_passes += 1
+                    self.loo.push(em, afs, self.mode, scored=sb)
                 finally:
                     afs.close()
             pushed += b.m
@@ -320,7 +330,7 @@ class _LooRounds:
 
 
 def loo_windowed(path, af, IDs, maf_iter, maf_tole, window_sites=None, num_partitions=1, need_parts=True, pop_iters=None,
-                 first_iters=None, ctx=None):
+                 first_iters=None, ctx=None, keep=None, scored_path=None, scored_keep=None):
     """loo_device for a Beagle FILE whose matrix need not fit the device: (logl (n, K) float32, parts (n*P, K) float32, iters (n,)),
     bit for bit what loo_device returns on the resident matrix of the same file.  The sites are taken in consecutive windows of
     `window_sites` sites (a multiple of 8192, rounded down; None: WGSASSIGN_LOO_WINDOW_SITES, else what windows.plan_loo derives
@@ -332,9 +342,17 @@ def loo_windowed(path, af, IDs, maf_iter, maf_tole, window_sites=None, num_parti
     window.  Unlike loo(), af is NOT mutated.  pop_iters (K,): the iteration counts of the full fits, from which the re-fits' first
     horizons are taken (loo_first_iters); first_iters (n,) gives them outright; neither: round 1 runs maf_iter iterations.
     Prints nothing.
+    keep (a bool array over the file's rows): the run is over the KEPT sites, numbered as stream_to_device(path, keep=keep) numbers
+    them (partition labels, np.sum's chunks, the rows of af, the windows: reader_cy.stream_windows).  scored_path: a second Beagle
+    file whose likelihoods are SCORED in place of those the re-fits are made from (--loo_downsampled_beagle; loo_device's `scored`),
+    under its own mask scored_keep (None: unfiltered); window w of both files holds the same kept sites.  The rounds before the
+    last stream `path` alone; the last round advances the second stream beside the first, so the second file is read once
+    (stats: scored_passes == 1).  The sample names and the kept counts of the two files must agree.  With scored_path and
+    window_sites=None, WGSASSIGN_LOO_DS_WINDOW_SITES and windows.plan_loo_ds stand in for the variable and the plan named above.
     loo_windowed.stats: rounds, windows, window_sites, chain_iterations, largest_matrix_bytes, matrices, seconds, round_seconds,
     iterations_round1 (the sum of the first horizons) against iterations_needed (the sum of the stopping iterations),
-    extension_rounds, refit_bytes_to_host (0: no re-fit frequencies cross to the host);
+    extension_rounds, refit_bytes_to_host (0: no re-fit frequencies cross to the host), scored_passes (passes over scored_path;
+    matrices and largest_matrix_bytes count both files' matrices: at most four);
     loo_windowed.info: n, m, sample_names, site_names (the first and last four), pops."""
     import time
 
@@ -354,15 +372,36 @@ def loo_windowed(path, af, IDs, maf_iter, maf_tole, window_sites=None, num_parti
     exact_parts = os.environ.get("WGSASSIGN_PARTS", "exact") != "fast" and (need_parts or P > 1)
     if P > 1 and not exact_parts:
         raise ValueError("WGSASSIGN_PARTS=fast (float64 partition sums) is not provided in site windows")
-    index, _, m = reader_cy.ensure_index(path)
+    if scored_keep is not None and scored_path is None:
+        raise ValueError("scored_keep is the site mask of scored_path: it cannot be given without that file")
+
+    def kept_sites(file, mask):
+        m_file = reader_cy.ensure_index(file)[2]
+        if mask is None:
+            return None, m_file
+        mask = np.asarray(mask, dtype=bool)
+        if mask.ndim != 1 or len(mask) != m_file:
+            raise ValueError("the site mask has %d entries, %s holds %d sites" % (mask.size, file, m_file))
+        return mask, int(np.count_nonzero(mask))
+
+    keep, m = kept_sites(path, keep)
     if m <= 0:
         raise ValueError("%s holds no sites" % path)
+    if scored_path is not None:
+        # the resident route's checks (WGSassign.py:172-198), before anything is fitted
+        with reader_cy.BeagleStream(path, threads=1) as st, reader_cy.BeagleStream(scored_path, threads=1) as st_scored:
+            if list(st.sample_names) != list(st_scored.sample_names):
+                raise ValueError("Sample names in downsampled Beagle file do not match original.")
+        scored_keep, m_scored = kept_sites(scored_path, scored_keep)
+        if m_scored != m:
+            raise ValueError("Site names in full and downsampled Beagle do not match after filtering.")
     if af.shape[0] != m:
         raise ValueError("the allele frequency file has %d sites, the Beagle file %d" % (af.shape[0], m))
     if window_sites is None:
-        W = windows.env_window_sites(name=windows.ENV_LOO)
+        W = windows.env_window_sites(name=windows.ENV_LOO_DS if scored_path is not None else windows.ENV_LOO)
         if W is None:
-            W = windows.plan_loo(m, n, K, ctx.mem_info()[0], counts=counts, P=P) or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN
+            planned = (windows.plan_loo_ds if scored_path is not None else windows.plan_loo)(m, n, K, ctx.mem_info()[0], counts=counts, P=P)
+            W = planned or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN
     else:
         if int(window_sites) < windows.ALIGN:
             raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
@@ -375,11 +414,14 @@ def loo_windowed(path, af, IDs, maf_iter, maf_tole, window_sites=None, num_parti
             raise AssertionError("Number of individuals in beagle and reference ID file do not match!")
         return group_of, K
 
-    info, stats = {}, {"round_seconds": []}
+    info, info_scored, stats = {}, {}, {"round_seconds": []}
     stream = EMStream(n, maf_iter, m, ctx)
     loo_stream = LooStream(n, K, m, P if exact_parts else 0, ctx)
-    rounds = _LooRounds(None, stream, loo_stream, group_of, counts, af, stats, default_mode())
-    gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info, group_of=groups, n_groups=K, again=rounds.again)
+    gen_scored = None
+    if scored_path is not None:     # (a generator: nothing is opened before the last round takes its first window)
+        gen_scored = reader_cy.stream_windows(scored_path, W, ctx=ctx, info=info_scored, group_of=groups, n_groups=K, keep=scored_keep)
+    rounds = _LooRounds(None, stream, loo_stream, group_of, counts, af, stats, default_mode(), scored=gen_scored)
+    gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info, group_of=groups, n_groups=K, again=rounds.again, keep=keep)
     rounds.windows = gen
     try:
         iters, scheme = windowed_fit.fit(rounds, n, maf_iter, maf_tole, m, EMBatch.GUARD, first_iters=first_iters, hold_final=True)
@@ -387,14 +429,17 @@ def loo_windowed(path, af, IDs, maf_iter, maf_tole, window_sites=None, num_parti
     finally:
         rounds.want_more = False
         gen.close()
+        if gen_scored is not None:
+            gen_scored.close()
         for em in rounds.batches.values():
             em.close()
         loo_stream.close()
         stream.close()
     stats.update(rounds=scheme.rounds, windows=info["windows"], window_sites=W, chain_iterations=scheme.chain_iterations,
-                 largest_matrix_bytes=info["largest_matrix_bytes"], matrices=info["matrices"], seconds=time.perf_counter() - t0,
+                 largest_matrix_bytes=max(info["largest_matrix_bytes"], info_scored.get("largest_matrix_bytes", 0)),
+                 matrices=info["matrices"] + info_scored.get("matrices", 0), seconds=time.perf_counter() - t0,
                  iterations_round1=scheme.iterations_round1, iterations_needed=int(sum(scheme.stop)),
-                 extension_rounds=scheme.extension_rounds, refit_bytes_to_host=0)
+                 extension_rounds=scheme.extension_rounds, refit_bytes_to_host=0, scored_passes=rounds.scored_passes)
     loo_windowed.stats = stats
     loo_windowed.info = dict({k: info[k] for k in ("n", "m", "sample_names", "site_names")}, pops=pops)
     with np.errstate(over="ignore"):

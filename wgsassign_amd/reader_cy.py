@@ -504,7 +504,7 @@ def stream_to_device(path, group_of=None, n_groups=1, ctx=None, threads=None, ra
         return beagle, list(st.sample_names), site_names, m_total
 
 
-def stream_windows(path, window_sites, ctx=None, threads=None, info=None, group_of=None, n_groups=1, again=None):
+def stream_windows(path, window_sites, ctx=None, threads=None, info=None, group_of=None, n_groups=1, again=None, keep=None):
     """The sites of a Beagle file as consecutive device windows of `window_sites` sites (a multiple of 8192; the last window
     may be shorter): a generator of DeviceBeagle objects (one group, as --get_pop_like scores) with site0 = the window's first
     site.  TWO device matrices of window_sites rows exist at most and are filled in alternation (DeviceBeagle.set_window moves a
@@ -521,13 +521,27 @@ def stream_windows(path, window_sites, ctx=None, threads=None, info=None, group_
     group_of / n_groups (optional; group_of may be a callable(sample_names) -> (group_of, n_groups)): the windows carry the
     population slabs a fit needs instead of the one-group layout.  again (optional, a callable): asked once the caller is done
     with the file's last window; while it answers True the windows start over at site 0 ON THE SAME MATRICES (a pass more of a
-    windowed fit: an EM batch attached to a matrix as its `window_em` stays with it, DeviceBeagle.set_window)."""
+    windowed fit: an EM batch attached to a matrix as its `window_em` stays with it, DeviceBeagle.set_window).
+    keep (optional, a bool array over the file's rows, e.g. utils.site_mask): the windows hold the KEPT sites -- W of them each, the
+    last window fewer -- and number them as the resident matrix of stream_to_device(keep=...) does: site0, info["m"] and the names are
+    those of kept sites.  A window's reader starts at its first kept row and ends with its last (windows.kept_windows), and its slice
+    of the mask goes to the ingest."""
+    from . import windows as _windows
     from .device import DeviceBeagle
     W = int(window_sites)
     if W < 8192 or W % 8192:
         raise ValueError("a window holds a multiple of 8192 sites, not %d" % W)
     info = {} if info is None else info
     index, _, m = ensure_index(path)
+    spans = None
+    if keep is not None:
+        keep = np.asarray(keep, dtype=bool)
+        if keep.ndim != 1 or len(keep) != m:
+            raise ValueError("the site mask has %d entries, %s holds %d sites" % (keep.size, path, m))
+        spans = _windows.kept_windows(keep, W)
+        m = int(np.count_nonzero(keep))
+        if m == 0:
+            raise ValueError("%s holds no sites" % path)
     nwin = (m + W - 1) // W
     info.update(m=m, windows=nwin, matrices=0, largest_matrix_bytes=0, site_names=[])
     bufs = [None, None]
@@ -537,7 +551,8 @@ def stream_windows(path, window_sites, ctx=None, threads=None, info=None, group_
     def open_window(w):
         lo = w * W
         rows = min(W, m - lo)
-        st = BeagleStream(path, threads, index=index, first_row=lo)
+        r0, r1 = (lo, lo + rows) if spans is None else spans[w][2:]
+        st = BeagleStream(path, threads, index=index, first_row=r0)
         opened.append(st)
         if "n" not in info:
             info.update(n=st.n, sample_names=list(st.sample_names))
@@ -550,7 +565,7 @@ def stream_windows(path, window_sites, ctx=None, threads=None, info=None, group_
             info["largest_matrix_bytes"] = max(info["largest_matrix_bytes"], b.nbytes())
         else:
             b.set_window(lo, rows)
-        return st, b, rows, st.ingest_begin(b, 0, rows, None, names="ends")
+        return st, b, rows, st.ingest_begin(b, 0, r1 - r0, None if spans is None else keep[r0:r1], names="ends")
 
     try:
         head, tail = [], []

@@ -19,8 +19,8 @@ RESERVE (4 GiB, at most a quarter of the free memory: the ingest's text and line
 when the device inflates -- the block sums of a sweep, the context's workspace).  A resident matrix needs m sites of it;
 windowed scoring holds TWO windows (the one being scored and the one being filled), each with its frequencies and codes.
 
-The other windowed routes have their own arithmetic below (fit_site_bytes, loo_site_bytes, ne_site_bytes, z_site_bytes,
-zref_site_bytes) and, but for the fit, a variable of their own.
+The other windowed routes have their own arithmetic below (fit_site_bytes, loo_site_bytes, loo_ds_site_bytes, ne_site_bytes,
+z_site_bytes, zref_site_bytes) and, but for the fit, a variable of their own.
 """
 import os
 
@@ -32,6 +32,7 @@ ENV_LOO = "WGSASSIGN_LOO_WINDOW_SITES"      # the leave-one-out run is sent to w
 ENV_NE = "WGSASSIGN_NE_WINDOW_SITES"        # ... and so is --ne_obs (see plan_ne)
 ENV_Z = "WGSASSIGN_Z_WINDOW_SITES"          # ... and --get_assignment_z_score (see plan_z)
 ENV_ZREF = "WGSASSIGN_ZREF_WINDOW_SITES"    # ... and --get_reference_z_score (see plan_zref)
+ENV_LOO_DS = "WGSASSIGN_LOO_DS_WINDOW_SITES"    # ... and --loo with --loo_downsampled_beagle (see plan_loo_ds)
 SURELY_FITS = 64                # see surely_fits
 
 
@@ -181,6 +182,68 @@ def plan_loo(m, n, K, free_bytes, environ=None, counts=None, P=1):
                           "their %d re-fits, class codes and scoring tables); %d of the %d free bytes can be used" %
                           (ALIGN, n, 2 * ALIGN * per_site, n, max(0, budget(free_bytes)), free_bytes))
     return W
+
+
+def loo_ds_site_bytes(n, K, counts=None, P=1):
+    """Device bytes one KEPT site takes in a windowed --get_reference_af --loo --loo_downsampled_beagle: loo_site_bytes for the
+    window of the reference file, plus what the window of the downsampled file -- the matrix that is scored -- adds per site:
+
+        matrix       16 * sum_g ceil(n_g / 2)       one more set of population slabs (csrc/api.hip: wgs_beagle_create), at most
+                                                    16 * ((n + K) // 2)
+        class codes  1 + 8 * 254 + 8                the codes a scoring sweep may build on the scored matrix (csrc/codes.hip:
+                     + sum_g (4 * ceil(n_g / 4)     wgs_beagle_codes, for_scoring_only): class counts, the dictionary, the encoder's
+                              + 1)                  records, and per slab the codes and the per-tile row counts -- without the slabs'
+                                                    own numbering and dictionaries, which only an EM sweep asks for
+
+    The re-fits never look at the scored matrix, so it carries no EM batch."""
+    n, K = int(n), int(K)
+    if counts is not None:
+        pairs = sum((int(c) + 1) // 2 for c in counts)
+        quads = sum((int(c) + 3) // 4 for c in counts)
+    else:
+        pairs, quads = (n + K) // 2, (n + 3 * K) // 4
+    return loo_site_bytes(n, K, counts, P) + 16 * pairs + (1 + 8 * 254 + 8) + 4 * quads + K
+
+
+def fits_resident_loo_ds(m, n, K, free_bytes, counts=None):
+    """Whether the TWO resident matrices of m kept sites fit the budget: the reference file's with its EM batch and codes
+    (fit_site_bytes) and the downsampled file's with the codes of a scoring sweep."""
+    return int(m) * (fit_site_bytes(n, K, counts) + loo_ds_site_bytes(n, K, counts) - loo_site_bytes(n, K, counts)) <= budget(free_bytes)
+
+
+def plan_loo_ds(m_kept, n, K, free_bytes, environ=None, counts=None, P=1):
+    """plan() for --get_reference_af --loo --loo_downsampled_beagle over m_kept kept sites: None when two resident matrices fit
+    (fits_resident_loo_ds) and WGSASSIGN_LOO_DS_WINDOW_SITES does not ask for windows, else W (a multiple of 8192 KEPT sites) for
+    two windows of each file, the reference file's with their batches of n re-fits."""
+    forced = env_window_sites(environ, ENV_LOO_DS)
+    if forced is not None:
+        return forced
+    if fits_resident_loo_ds(m_kept, n, K, free_bytes, counts):
+        return None
+    per_site = loo_ds_site_bytes(n, K, counts, P)
+    W = budget(free_bytes) // (2 * per_site) // ALIGN * ALIGN
+    if W < ALIGN:
+        raise MemoryError("a windowed leave-one-out run on downsampled likelihoods needs two windows of %d sites x %d individuals of both "
+                          "files on the device (%d bytes with their %d re-fits, class codes and scoring tables); %d of the %d free bytes "
+                          "can be used" % (ALIGN, n, 2 * ALIGN * per_site, n, max(0, budget(free_bytes)), free_bytes))
+    return W
+
+
+def kept_windows(keep, W):
+    """Windows of W KEPT sites under a site mask, as file rows: for every window (kept_lo, kept_count, row_first, row_end) -- the
+    window holds the kept sites [kept_lo, kept_lo + kept_count), which lie in the file rows [row_first, row_end); row_first and
+    row_end - 1 are kept rows, so a window's slice of the mask neither begins nor ends in dropped rows, and the dropped rows
+    between two windows belong to neither.  A pure function of the mask and W; a mask that keeps nothing has no windows."""
+    import numpy as np
+    W = int(W)
+    if W < 1:
+        raise ValueError("a window holds at least one site")
+    kept_rows = np.flatnonzero(np.asarray(keep, dtype=bool))
+    out = []
+    for lo in range(0, len(kept_rows), W):
+        hi = min(len(kept_rows), lo + W)
+        out.append((lo, hi - lo, int(kept_rows[lo]), int(kept_rows[hi - 1]) + 1))
+    return out
 
 
 def ne_site_bytes(n, K, counts=None):
