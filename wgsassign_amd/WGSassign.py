@@ -12,6 +12,8 @@ import os
 import sys
 from datetime import datetime
 
+from . import windows
+
 parser = argparse.ArgumentParser(prog="WGSassign")
 parser.add_argument("-b", "--beagle", metavar="FILE",
                     help="Filepath to genotype likelihoods in gzipped Beagle format from ANGSD")
@@ -65,310 +67,101 @@ for _flag in ("--pop_like", "--pop_like_IDs", "--mixture_iter"):
     parser.add_argument(_flag, help=argparse.SUPPRESS)
 
 
-def windowed_candidate(args, world=1):
-    """Whether these options may be scored in site windows (glassy.assignLL_windowed): --get_pop_like alone, on one rank.
-    Every other option needs the whole matrix on the device (the EM fit's convergence test couples all sites; the z-scores and
-    the leave-one-out re-fits build on it), and a rank of several holds a shard, not a file."""
-    others = (args.get_reference_af, args.loo, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score,
-              args.loo_downsampled_beagle)
-    return bool(args.get_pop_like) and int(world) == 1 and not any(others)
 
+# ---- the windowed routes: one table, one selector -------------------------------------------------------------
+
+# the options that decide the route; every other argument (--partition_sites, the files, the thresholds) goes with any of them
+OPTION_FLAGS = ("get_reference_af", "loo", "ne_obs", "get_pop_like", "get_assignment_z_score", "get_reference_z_score",
+                "loo_downsampled_beagle")
 
 WINDOWS_ONLY = "windowed scoring (WGSASSIGN_WINDOW_SITES) covers --get_pop_like on one rank only"
 SLAB_ALLOC_FAILED = ("hipMalloc of", "for population slab")       # csrc/api.hip: wgs_beagle_create, when the matrix does not fit the device
-
-
 SET_WINDOW_SITES = ("the matrix was expected to fit the device and does not: set WGSASSIGN_WINDOW_SITES (a multiple of 8192 sites) to "
                     "score the file in site windows")
-
-
+SET_WINDOW_SITES_FIT = ("the matrix was expected to fit the device and does not: set WGSASSIGN_WINDOW_SITES (a multiple of 8192 sites) to "
+                        "fit the file in site windows")
 SET_WINDOW_SITES_Z = ("the matrix was expected to fit the device and does not: set WGSASSIGN_Z_WINDOW_SITES (a multiple of 8192 sites) to "
                       "compute the z-scores in site windows")
-
-
 SET_WINDOW_SITES_ZREF = ("the matrix was expected to fit the device and does not: set WGSASSIGN_ZREF_WINDOW_SITES (a multiple of 8192 sites) "
                          "to compute the reference z-scores in site windows")
-
-
 SET_WINDOW_SITES_LOO_DS = ("the two matrices were expected to fit the device and do not: set WGSASSIGN_LOO_DS_WINDOW_SITES (a multiple of 8192 "
                            "sites) to run the leave-one-out on downsampled likelihoods in site windows")
 
 
-def with_windows_hint(error, candidate=False, z_candidate=False, zref_candidate=False, loo_ds_candidate=False):
-    """The error of a resident run whose matrix did not fit the device, saying what windows cover -- or, when the options were
-    those windows cover (candidate: the file was only judged to fit; z_candidate: --get_assignment_z_score alone, which has a
-    variable of its own; zref_candidate: --get_reference_z_score alone, which has another; loo_ds_candidate: --get_reference_af --loo
-    --loo_downsampled_beagle, which has a third), how to ask for them; any other error as it is."""
-    if isinstance(error, RuntimeError) and all(part in str(error) for part in SLAB_ALLOC_FAILED):
-        return RuntimeError(str(error) + ": " + (SET_WINDOW_SITES_Z if z_candidate else SET_WINDOW_SITES_ZREF if zref_candidate else
-                                                 SET_WINDOW_SITES_LOO_DS if loo_ds_candidate else SET_WINDOW_SITES if candidate else
-                                                 WINDOWS_ONLY))
-    return error
-
-
-def _window_sites(args, comm, ctx):
-    """The window --get_pop_like is scored in, or None for the resident path: WGSASSIGN_WINDOW_SITES when set, else windows only
-    when the resident matrix would not fit (windows.plan).  A file whose compressed size alone says that it fits (windows.surely_fits)
-    is looked at no further; beyond that the decision costs a cold BGZF file no pass of its own: what its one-pass ingest would
-    allocate (the estimate plus a quarter) is tried first."""
+def _shape_from_frequencies(args):
+    """(n, K, None) from --pop_af_file (K) and the Beagle header (n); None when the frequency file cannot tell (an unreadable one
+    is reported where it always was)."""
     import numpy as np
 
-    from . import reader_cy, windows
-    if not windowed_candidate(args, comm.world) or not (args.pop_af_file and os.path.isfile(args.pop_af_file)):
-        return None                     # (a missing frequency file is reported where it always was)
-    try:
-        W = windows.env_window_sites()
-    except ValueError as e:
-        raise SystemExit(str(e))
-    if W is not None:
-        return W
-    free = ctx.mem_info()[0]
-    if windows.surely_fits(os.path.getsize(args.beagle), free):
-        return None
+    from . import reader_cy
     try:
         A = np.load(args.pop_af_file, mmap_mode="r")
     except Exception:
-        return None                     # (an unreadable frequency file, too, is reported where it always was)
+        return None
     if A.ndim != 2:
         return None
     with reader_cy.BeagleStream(args.beagle, threads=1) as st:
-        n = st.n
-    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
-    if est is not None and windows.fits_resident(est + est // 4 + 1024, n, A.shape[1], free):
-        return None
-    m = reader_cy.ensure_index(args.beagle)[2]
-    try:
-        return windows.plan(m, n, A.shape[1], free)
-    except MemoryError as e:
-        raise SystemExit(str(e))
+        return st.n, A.shape[1], None
 
 
-def windowed_fit_candidate(args, world=1):
-    """Whether these options may be fitted in site windows (emMAF.emMAF_windowed): --get_reference_af alone, on one rank.  With
-    --loo or --ne_obs beside it the run has a route of its own (windowed_loo_candidate, windowed_ne_candidate); the z-scores still need
-    the whole matrix on the device."""
-    others = (args.get_pop_like, args.loo, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score,
-              args.loo_downsampled_beagle)
-    return bool(args.get_reference_af) and int(world) == 1 and not any(others)
-
-
-SET_WINDOW_SITES_FIT = ("the matrix was expected to fit the device and does not: set WGSASSIGN_WINDOW_SITES (a multiple of 8192 sites) to "
-                        "fit the file in site windows")
-
-
-def _fit_window_sites(args, comm, ctx):
-    """The window --get_reference_af is fitted in, or None for the resident path: WGSASSIGN_WINDOW_SITES when set, else windows
-    only when the resident matrix would not fit (windows.plan_fit), after the same first look as _window_sites takes."""
+def _shape_from_ids(args):
+    """(n, K, counts) from --pop_af_IDs; None when the file cannot tell (an unreadable one is reported where it always was)."""
     import numpy as np
-
-    from . import reader_cy, windows
-    if not windowed_fit_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
-        return None                     # (a missing ID file is reported where it always was)
-    try:
-        W = windows.env_window_sites()
-    except ValueError as e:
-        raise SystemExit(str(e))
-    if W is not None:
-        return W
-    free = ctx.mem_info()[0]
-    if windows.surely_fits(os.path.getsize(args.beagle), free):
-        return None
     try:
         IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
         counts = np.unique(IDs[:, 1], return_counts=True)[1]
     except Exception:
-        return None                     # (an unreadable ID file, too, is reported where it always was)
-    n, K = int(counts.sum()), len(counts)
-    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
-    if est is not None and windows.fits_resident_fit(est + est // 4 + 1024, n, K, free, counts):
         return None
-    m = reader_cy.ensure_index(args.beagle)[2]
-    try:
-        return windows.plan_fit(m, n, K, free, counts=counts)
-    except MemoryError as e:
-        raise SystemExit(str(e))
+    return int(counts.sum()), len(counts), counts
 
 
-def windowed_loo_candidate(args, world=1):
-    """Whether these options may run in site windows end to end (emMAF.emMAF_windowed, then glassy.loo_windowed):
-    --get_reference_af --loo alone, with any --partition_sites, on one rank.  With --ne_obs beside them the run has a route of its own
-    (windowed_ne_candidate), and so it has with --loo_downsampled_beagle (two files in lockstep under a site filter:
-    windowed_loo_ds_candidate); the z-scores and --get_pop_like beside them still need the whole matrix on the device."""
-    others = (args.get_pop_like, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score, args.loo_downsampled_beagle)
-    return bool(args.get_reference_af) and bool(args.loo) and int(world) == 1 and not any(others)
+class _Route:
+    """One windowed route of the command line.  requires / allows: the OPTION_FLAGS it needs and those that may stand beside them (any
+    other sends the run to the resident path); env: its variable; shape: the input file that tells n, K and the populations' sizes,
+    and how; fits(m, n, K, counts, count, free): its resident-fit test for the estimated sites of a file without a cached index (None:
+    the sites are counted outright); plan(m, n, K, counts, count, free, args): its planner; hint: what with_windows_hint says of it;
+    sizes: the files whose compressed sizes windows.surely_fits looks at; rounds: the plan is (window, individuals per round) and
+    count the individuals --ind_start / --ind_end leave."""
+
+    def __init__(self, requires, allows, env, shape, fits, plan, hint=None, sizes=("beagle",), rounds=False):
+        self.requires, self.allows, self.env, self.fits, self.plan, self.hint = requires, allows, env, fits, plan, hint
+        self.shape_file, self.shape = shape
+        self.sizes, self.rounds = sizes, rounds
+
+    def candidate(self, args, world):
+        """All required options, one rank, and no option but the required and the allowed."""
+        beside = [flag for flag in OPTION_FLAGS if flag not in self.requires + self.allows]
+        return all(bool(getattr(args, flag)) for flag in self.requires) and int(world) == 1 and not any(getattr(args, flag) for flag in beside)
 
 
-def _loo_window_sites(args, comm, ctx):
-    """The window --get_reference_af --loo runs in, or None for the resident path: WGSASSIGN_LOO_WINDOW_SITES when set
-    (WGSASSIGN_WINDOW_SITES alone sends no leave-one-out run to windows), else windows only when the resident matrix would not
-    fit (windows.plan_loo), after the same first look as _fit_window_sites takes."""
-    import numpy as np
-
-    from . import reader_cy, windows
-    if not windowed_loo_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
-        return None                     # (a missing ID file is reported where it always was)
-    try:
-        W = windows.env_window_sites(name=windows.ENV_LOO)
-    except ValueError as e:
-        raise SystemExit(str(e))
-    if W is not None:
-        return W
-    free = ctx.mem_info()[0]
-    if windows.surely_fits(os.path.getsize(args.beagle), free):
-        return None
-    try:
-        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
-        counts = np.unique(IDs[:, 1], return_counts=True)[1]
-    except Exception:
-        return None                     # (an unreadable ID file, too, is reported where it always was)
-    n, K = int(counts.sum()), len(counts)
-    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
-    if est is not None and windows.fits_resident_fit(est + est // 4 + 1024, n, K, free, counts):
-        return None
-    m = reader_cy.ensure_index(args.beagle)[2]
-    try:
-        return windows.plan_loo(m, n, K, free, counts=counts, P=args.partition_sites)
-    except MemoryError as e:
-        raise SystemExit(str(e))
+_FREQUENCIES, _IDS = ("pop_af_file", _shape_from_frequencies), ("pop_af_IDs", _shape_from_ids)
 
 
-def windowed_loo_ds_candidate(args, world=1):
-    """Whether these options may run in site windows with a downsampled file scored (emMAF.emMAF_windowed under the reference file's
-    site mask, then glassy.loo_windowed with both masks and the second file): --get_reference_af --loo --loo_downsampled_beagle, with any
-    --partition_sites, on one rank.  With --ne_obs, --get_pop_like or a z-score option beside them the run stays resident."""
-    others = (args.get_pop_like, args.ne_obs, args.get_assignment_z_score, args.get_reference_z_score)
-    return bool(args.get_reference_af) and bool(args.loo) and bool(args.loo_downsampled_beagle) and int(world) == 1 and not any(others)
+def _fits_fit(m, n, K, counts, count, free):
+    return windows.fits_resident_fit(m, n, K, free, counts)
 
 
-def _loo_ds_window_sites(args, comm, ctx, m_kept=None):
-    """The window of KEPT sites --get_reference_af --loo --loo_downsampled_beagle runs in, or None for the resident path:
-    WGSASSIGN_LOO_DS_WINDOW_SITES when set (no other variable sends this run to windows), else windows only when the two resident
-    matrices would not fit (windows.plan_loo_ds): a pair of files whose compressed sizes together say that they fit
-    (windows.surely_fits) is looked at no further.  m_kept: the sites both files keep under their masks, when the caller has them
-    (None: the reference file's sites, which bound them)."""
-    import numpy as np
-
-    from . import reader_cy, windows
-    if not windowed_loo_ds_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
-        return None                     # (a missing ID file is reported where it always was)
-    try:
-        W = windows.env_window_sites(name=windows.ENV_LOO_DS)
-    except ValueError as e:
-        raise SystemExit(str(e))
-    if W is not None:
-        return W
-    free = ctx.mem_info()[0]
-    if windows.surely_fits(os.path.getsize(args.beagle) + os.path.getsize(args.loo_downsampled_beagle), free):
-        return None
-    try:
-        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
-        counts = np.unique(IDs[:, 1], return_counts=True)[1]
-    except Exception:
-        return None                     # (an unreadable ID file, too, is reported where it always was)
-    n, K = int(counts.sum()), len(counts)
-    if m_kept is None:
-        m_kept = reader_cy.ensure_index(args.beagle)[2]
-    try:
-        return windows.plan_loo_ds(m_kept, n, K, free, counts=counts, P=args.partition_sites)
-    except MemoryError as e:
-        raise SystemExit(str(e))
-
-
-def _run_loo_ds_windowed(args, ctx, W, IDs, pops, sample_names, keep_ref, keep_ds, say):
-    """--get_reference_af --loo --loo_downsampled_beagle on files that do not fit (or WGSASSIGN_LOO_DS_WINDOW_SITES), after the names
-    passes and the two site masks of the resident run: the fit over the kept sites of the reference file in windows, then the
-    leave-one-out run in the same windows with the downsampled file's windows scored beside them; the lines and files of the resident
-    run in their order, and one more line on stderr."""
-    import numpy as np
-
-    from . import emMAF, glassy, utils
-    P = args.partition_sites
-    say("Parsing reference population ID file.")
-    assert (len(sample_names) == IDs.shape[0]), "Number of individuals in beagle and reference ID file do not match!"
-    af, iters = emMAF.emMAF_windowed(args.beagle, IDs, args.maf_iter, args.maf_tole, W, out=args.out + ".pop_af.npy", ctx=ctx, keep=keep_ref)
-    for it in iters:
-        if it > 0:
-            say("EM (MAF) converged at iteration: " + str(int(it)))
-    del af
-    say("Saved reference population allele frequencies as " + str(args.out) + ".pop_af.npy (Binary - np.float32)\n")
-    say("Column order of populations is: " + str(pops))
-    np.savetxt(args.out + ".pop_names.txt", pops, fmt="%s")
-    say("Saved reference population names as " + str(args.out) +
-        ".pop_names.txt (String: Order of pops for .pop_af.npy, .ne_obs.npy, and fisher_obs.npy files)\n")
-    say("Performing leave-one-out cross validation.")
-    say(str(len(sample_names)) + " individuals to assign to " + str(len(pops)) + " populations")
-    say("Using downsampled GLs for likelihood evaluation in LOO assignment.")
-    A = np.load(args.out + ".pop_af.npy", mmap_mode="r")
-    ll, parts, loo_iters = glassy.loo_windowed(args.beagle, A, IDs, args.maf_iter, args.maf_tole, W, P, need_parts=P > 1, pop_iters=iters,
-                                               ctx=ctx, keep=keep_ref, scored_path=args.loo_downsampled_beagle, scored_keep=keep_ds)
-    del A
-    stats = glassy.loo_windowed.stats
-    for it in loo_iters:
-        if it > 0:
-            say("EM (MAF) converged at iteration: " + str(int(it)))
-    print("wgsassign_amd: leave-one-out on downsampled likelihoods in %d rounds of %d windows of %d kept sites (the downsampled file read "
-          "%d time)" % (stats["rounds"], stats["windows"], stats["window_sites"], stats["scored_passes"]), file=sys.stderr, flush=True)
-    outfile = f"{args.out}.pop_like_LOO_downsampled.tsv"
-    partfile = f"{args.out}.pop_like_LOO_downsampled_partitions_{P}.tsv.gz"
-    utils.write_ass_mats(outfile, ll, sample_names, pops, print_part_column=False, sample_locations=IDs[:, 1], doing_LOO=True)
-    say(f"Saved leave-one-out cross validation log likelihoods as {outfile}")
-    if P > 1:
-        utils.write_ass_mats(partfile, parts, sample_names, pops, partition_count=P, print_part_column=True,
-                             sample_locations=IDs[:, 1], doing_LOO=True)
-        say(f"Saved leave-one-out cross validation log likelihoods from partitioned sites as {partfile}")
-    say(f"Column order of populations is: {pops}")
-
-
-def windowed_ne_candidate(args, world=1):
-    """Whether these options may run in site windows end to end with --ne_obs among them (emMAF.emMAF_windowed, then
-    fisher.fisher_obs_windowed over the frequencies just written, then glassy.loo_windowed when --loo is given):
-    --get_reference_af --ne_obs, with or without --loo and any --partition_sites, on one rank.  The z-scores, --get_pop_like beside
-    them and --loo_downsampled_beagle still need the whole matrix on the device."""
-    others = (args.get_pop_like, args.get_assignment_z_score, args.get_reference_z_score, args.loo_downsampled_beagle)
-    return bool(args.get_reference_af) and bool(args.ne_obs) and int(world) == 1 and not any(others)
-
-
-def _ne_window_sites(args, comm, ctx):
-    """The window --get_reference_af --ne_obs [--loo] runs in, or None for the resident path: WGSASSIGN_NE_WINDOW_SITES when set
-    (neither WGSASSIGN_WINDOW_SITES nor WGSASSIGN_LOO_WINDOW_SITES sends an --ne_obs run to windows), else windows only when the
-    resident matrix would not fit (windows.plan_ne), after the same first look as _fit_window_sites takes."""
-    import numpy as np
-
-    from . import reader_cy, windows
-    if not windowed_ne_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
-        return None                     # (a missing ID file is reported where it always was)
-    try:
-        W = windows.env_window_sites(name=windows.ENV_NE)
-    except ValueError as e:
-        raise SystemExit(str(e))
-    if W is not None:
-        return W
-    free = ctx.mem_info()[0]
-    if windows.surely_fits(os.path.getsize(args.beagle), free):
-        return None
-    try:
-        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
-        counts = np.unique(IDs[:, 1], return_counts=True)[1]
-    except Exception:
-        return None                     # (an unreadable ID file, too, is reported where it always was)
-    n, K = int(counts.sum()), len(counts)
-    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
-    if est is not None and windows.fits_resident_fit(est + est // 4 + 1024, n, K, free, counts):
-        return None
-    m = reader_cy.ensure_index(args.beagle)[2]
-    try:
-        return windows.plan_ne(m, n, K, free, counts=counts, loo=bool(args.loo), P=args.partition_sites)
-    except MemoryError as e:
-        raise SystemExit(str(e))
-
-
-def windowed_z_candidate(args, world=1):
-    """Whether these options may run in site windows (zscore.assignment_z_scores_windowed): --get_assignment_z_score alone, on one
-    rank.  Its frequencies come from --pop_af_file, so nothing couples the windows but sums that are carried on the device.
-    --get_reference_z_score needs masked leave-one-out re-fits whose stopping test runs over the whole file: it has a route of its own
-    (windowed_zref_candidate, zscore.reference_z_scores_windowed) and is not this function's; several ranks keep the resident path."""
-    others = (args.get_reference_af, args.loo, args.ne_obs, args.get_pop_like, args.get_reference_z_score, args.loo_downsampled_beagle)
-    return bool(args.get_assignment_z_score) and int(world) == 1 and not any(others)
+ROUTES = {
+    "score": _Route(("get_pop_like",), (), windows.ENV, _FREQUENCIES, hint=SET_WINDOW_SITES,
+                    fits=lambda m, n, K, counts, count, free: windows.fits_resident(m, n, K, free),
+                    plan=lambda m, n, K, counts, count, free, args: windows.plan(m, n, K, free)),
+    "fit": _Route(("get_reference_af",), (), windows.ENV, _IDS, hint=SET_WINDOW_SITES_FIT, fits=_fits_fit,
+                  plan=lambda m, n, K, counts, count, free, args: windows.plan_fit(m, n, K, free, counts=counts)),
+    "loo": _Route(("get_reference_af", "loo"), (), windows.ENV_LOO, _IDS, fits=_fits_fit,
+                  plan=lambda m, n, K, counts, count, free, args: windows.plan_loo(m, n, K, free, counts=counts, P=args.partition_sites)),
+    "loo_ds": _Route(("get_reference_af", "loo", "loo_downsampled_beagle"), (), windows.ENV_LOO_DS, _IDS, hint=SET_WINDOW_SITES_LOO_DS,
+                     fits=None, sizes=("beagle", "loo_downsampled_beagle"),
+                     plan=lambda m, n, K, counts, count, free, args: windows.plan_loo_ds(m, n, K, free, counts=counts, P=args.partition_sites)),
+    "ne": _Route(("get_reference_af", "ne_obs"), ("loo",), windows.ENV_NE, _IDS, fits=_fits_fit,
+                 plan=lambda m, n, K, counts, count, free, args: windows.plan_ne(m, n, K, free, counts=counts, loo=bool(args.loo),
+                                                                                  P=args.partition_sites)),
+    "z": _Route(("get_assignment_z_score",), (), windows.ENV_Z, _FREQUENCIES, hint=SET_WINDOW_SITES_Z, rounds=True,
+                fits=lambda m, n, K, counts, count, free: windows.fits_resident_z(m, n, K, count, free),
+                plan=lambda m, n, K, counts, count, free, args: windows.plan_z(m, n, K, count, free)),
+    "zref": _Route(("get_reference_z_score",), (), windows.ENV_ZREF, _IDS, hint=SET_WINDOW_SITES_ZREF, rounds=True,
+                   fits=lambda m, n, K, counts, count, free: windows.fits_resident_zref(m, n, K, count, free, counts),
+                   plan=lambda m, n, K, counts, count, free, args: windows.plan_zref(m, n, K, count, free, args.maf_iter, counts=counts)),
+}
 
 
 def _z_individuals(args, n):
@@ -378,142 +171,305 @@ def _z_individuals(args, n):
     return max(1, min(n, hi) - max(0, lo))
 
 
-def _z_window_sites(args, comm, ctx):
-    """(window, individuals per round) --get_assignment_z_score runs in, or None for the resident path: WGSASSIGN_Z_WINDOW_SITES when
-    set (no other variable sends the z-scores to windows), else windows only when the resident matrix, depth table and frequencies
-    would not fit (windows.plan_z), after the same first look as _window_sites takes."""
-    import numpy as np
-
-    from . import reader_cy, windows
-    if not windowed_z_candidate(args, comm.world) or not (args.pop_af_file and os.path.isfile(args.pop_af_file)):
-        return None                     # (a missing frequency file is reported where it always was)
+def _route_window_sites(route, args, comm, ctx, m=None):
+    """The window a route's options run in -- (window, individuals per round) for a route with rounds --, or None for the resident
+    path: the route's variable when it is set (no other variable sends the run to windows; the device is asked nothing, and the
+    rounds are planned once the file's shape is known), else windows only when the resident objects would not fit (the route's
+    planner).  A file whose compressed size alone says that it fits (windows.surely_fits) is looked at no further; beyond that the
+    decision costs a cold BGZF file no pass of its own: what its one-pass ingest would allocate (the estimate plus a quarter) is tried
+    first.  m: the sites, when the caller has them.  A missing or unreadable input file is left to the resident path, which reports
+    it where it always did."""
+    from . import reader_cy
+    shape_file = getattr(args, route.shape_file)
+    if not route.candidate(args, comm.world) or not (shape_file and os.path.isfile(shape_file)):
+        return None
     try:
-        forced = windows.env_window_sites(name=windows.ENV_Z)
+        forced = windows.env_window_sites(name=route.env)
     except ValueError as e:
         raise SystemExit(str(e))
     if forced is not None:
-        return forced, None             # (the rounds of individuals are planned once the file's shape is known)
+        return (forced, None) if route.rounds else forced
     free = ctx.mem_info()[0]
-    if windows.surely_fits(os.path.getsize(args.beagle), free):
+    if windows.surely_fits(sum(os.path.getsize(getattr(args, file)) for file in route.sizes), free):
         return None
+    shape = route.shape(args)
+    if shape is None:
+        return None
+    n, K, counts = shape
+    count = _z_individuals(args, n) if route.rounds else None
+    if m is None:
+        est = None if route.fits is None or reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
+        if est is not None and route.fits(est + est // 4 + 1024, n, K, counts, count, free):
+            return None
+        m = reader_cy.ensure_index(args.beagle)[2]
     try:
-        A = np.load(args.pop_af_file, mmap_mode="r")
-    except Exception:
-        return None                     # (an unreadable frequency file, too, is reported where it always was)
-    if A.ndim != 2:
-        return None
-    with reader_cy.BeagleStream(args.beagle, threads=1) as st:
-        n = st.n
-    count = _z_individuals(args, n)
-    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
-    if est is not None and windows.fits_resident_z(est + est // 4 + 1024, n, A.shape[1], count, free):
-        return None
-    m = reader_cy.ensure_index(args.beagle)[2]
-    try:
-        return windows.plan_z(m, n, A.shape[1], count, free)
+        return route.plan(m, n, K, counts, count, free, args)
     except MemoryError as e:
         raise SystemExit(str(e))
 
 
-def _run_z_windowed(args, comm, ctx, plan, say, summary):
-    """--get_assignment_z_score alone on files that do not fit (or WGSASSIGN_Z_WINDOW_SITES): two passes over the Beagle file and the
-    depth file in site windows; the checks, lines and file of the resident run in their order, and one more line on stderr."""
-    import numpy as np
+def windowed_candidate(args, world=1):
+    """Whether these options may be scored in site windows (glassy.assignLL_windowed): --get_pop_like alone, on one rank.  (A rank
+    of several holds a shard, not a file.)"""
+    return ROUTES["score"].candidate(args, world)
 
-    from . import reader_cy, zscore
-    W, batch = plan
-    index, _, m = reader_cy.ensure_index(args.beagle)
-    with reader_cy.BeagleStream(args.beagle, threads=1) as st:
-        n = st.n
-    assert os.path.isfile(args.pop_af_IDs), "Population ID file does not exist!!"
-    IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
-    A = np.load(args.pop_af_file, mmap_mode="r")
-    majmin = None
-    if args.ind_counts_file:
-        majmin = zscore.read_majmin(args.ind_majmin_file)
-        if majmin.shape[0] != m:
-            raise ValueError("%s has the selectors of %d sites, the Beagle file %d" % (args.ind_majmin_file, majmin.shape[0], m))
-    else:
-        assert os.path.isfile(args.ind_ad_file), "Individual allele depths file does not exist!"
-    assert os.path.isfile(args.pop_names), "Population names file does not exist!!"
-    pops = np.loadtxt(args.pop_names, dtype="str")
-    assert (n == IDs.shape[0]), "Number of individuals in beagle and reference ID file do not match!"
-    if args.allele_count_threshold is not None:
-        assert (args.allele_count_threshold >= 0), "Allele count threshold needs to be greater than/equal to 0!"
-    allele_count_threshold = args.allele_count_threshold or 0
-    ind_start, ind_end = zscore.ind_range(n, args.ind_start, args.ind_end)
-    lines = []
-    z_out = zscore.assignment_z_scores_windowed(args.beagle, args.ind_counts_file or args.ind_ad_file, A, IDs, np.atleast_1d(pops),
-                                                allele_count_threshold, args.single_read_threshold, ind_start, ind_end, window_sites=W,
-                                                say=lines.append, counts=majmin is not None, majmin=majmin, batch=batch, ctx=ctx)
-    info, stats = zscore.assignment_z_scores_windowed.info, zscore.assignment_z_scores_windowed.stats
-    say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
-    summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
-    say("Parsing population ID file.")
-    say("Parsing population allele frequency file.")
-    say("Parsing individual allele depths file.")
-    for ln in lines:
-        say(ln)
-    print("wgsassign_amd: z-scores in %d rounds of 2 passes over %d windows of %d sites (%d bytes downloaded)" %
-          (stats["rounds"], stats["windows"], stats["window_sites"], stats["downloaded_bytes"]), file=sys.stderr, flush=True)
-    np.savetxt(args.out + ".z_ind.txt", z_out, fmt="%.7f")
-    say("Saved " + str(ind_end - ind_start) + " individual z-scores as " + str(args.out) + ".z_ind.txt (text)")
+
+def windowed_fit_candidate(args, world=1):
+    """Whether these options may be fitted in site windows (emMAF.emMAF_windowed): --get_reference_af alone, on one rank."""
+    return ROUTES["fit"].candidate(args, world)
+
+
+def windowed_loo_candidate(args, world=1):
+    """Whether these options may run in site windows end to end (emMAF.emMAF_windowed, then glassy.loo_windowed):
+    --get_reference_af --loo alone, with any --partition_sites, on one rank."""
+    return ROUTES["loo"].candidate(args, world)
+
+
+def windowed_loo_ds_candidate(args, world=1):
+    """... with a downsampled file scored (both files in lockstep under their site masks): --get_reference_af --loo
+    --loo_downsampled_beagle, with any --partition_sites, on one rank."""
+    return ROUTES["loo_ds"].candidate(args, world)
+
+
+def windowed_ne_candidate(args, world=1):
+    """... with --ne_obs among them (fisher.fisher_obs_windowed between the fit and the leave-one-out run): --get_reference_af
+    --ne_obs, with or without --loo and any --partition_sites, on one rank."""
+    return ROUTES["ne"].candidate(args, world)
+
+
+def windowed_z_candidate(args, world=1):
+    """Whether these options may run in site windows (zscore.assignment_z_scores_windowed): --get_assignment_z_score alone, on one
+    rank."""
+    return ROUTES["z"].candidate(args, world)
 
 
 def windowed_zref_candidate(args, world=1):
     """Whether these options may run in site windows (zscore.reference_z_scores_windowed): --get_reference_z_score alone, on one
-    rank -- with its ID and name files, the depth options, the thresholds, the individual range, --maf_iter and --maf_tole.  The
-    masked leave-one-out fits are carried from window to window like the chain of a SNP shard; several ranks keep the resident path."""
-    others = (args.get_reference_af, args.loo, args.ne_obs, args.get_pop_like, args.get_assignment_z_score, args.loo_downsampled_beagle)
-    return bool(args.get_reference_z_score) and int(world) == 1 and not any(others)
+    rank."""
+    return ROUTES["zref"].candidate(args, world)
+
+
+def _window_sites(args, comm, ctx):
+    """The window --get_pop_like is scored in, or None for the resident path (_route_window_sites)."""
+    return _route_window_sites(ROUTES["score"], args, comm, ctx)
+
+
+def _fit_window_sites(args, comm, ctx):
+    """The window --get_reference_af is fitted in, or None."""
+    return _route_window_sites(ROUTES["fit"], args, comm, ctx)
+
+
+def _loo_window_sites(args, comm, ctx):
+    """The window --get_reference_af --loo runs in, or None."""
+    return _route_window_sites(ROUTES["loo"], args, comm, ctx)
+
+
+def _loo_ds_window_sites(args, comm, ctx, m_kept=None):
+    """The window of KEPT sites --get_reference_af --loo --loo_downsampled_beagle runs in, or None.  m_kept: the sites both files keep
+    under their masks, when the caller has them (None: the reference file's sites, which bound them)."""
+    return _route_window_sites(ROUTES["loo_ds"], args, comm, ctx, m_kept)
+
+
+def _ne_window_sites(args, comm, ctx):
+    """The window --get_reference_af --ne_obs [--loo] runs in, or None."""
+    return _route_window_sites(ROUTES["ne"], args, comm, ctx)
+
+
+def _z_window_sites(args, comm, ctx):
+    """(window, individuals per round) --get_assignment_z_score runs in, or None."""
+    return _route_window_sites(ROUTES["z"], args, comm, ctx)
 
 
 def _zref_window_sites(args, comm, ctx):
-    """(window, individuals per round) --get_reference_z_score runs in, or None for the resident path: WGSASSIGN_ZREF_WINDOW_SITES
-    when set (no other variable sends this option to windows), else windows only when the resident matrix, depth table and one batch
-    of masked fits would not fit (windows.plan_zref), after the same first look as _z_window_sites takes."""
+    """(window, individuals per round) --get_reference_z_score runs in, or None."""
+    return _route_window_sites(ROUTES["zref"], args, comm, ctx)
+
+
+def with_windows_hint(error, candidate=False, z_candidate=False, zref_candidate=False, loo_ds_candidate=False):
+    """The error of a resident run whose matrix did not fit the device, saying what windows cover -- or, when the options were
+    those of a route (candidate: --get_pop_like alone, whose file was only judged to fit; z_candidate, zref_candidate,
+    loo_ds_candidate: the routes with a variable of their own), how to ask for them; any other error as it is."""
+    if isinstance(error, RuntimeError) and all(part in str(error) for part in SLAB_ALLOC_FAILED):
+        asked = [name for name, given in (("z", z_candidate), ("zref", zref_candidate), ("loo_ds", loo_ds_candidate), ("score", candidate))
+                 if given]
+        return RuntimeError(str(error) + ": " + (ROUTES[asked[0]].hint if asked else WINDOWS_ONLY))
+    return error
+
+
+def _raise_hinted(error, args, world):
+    """Raise with_windows_hint's error for these options in place of a slab allocation that failed; any other error as it came."""
+    hinted = with_windows_hint(error, *(ROUTES[name].candidate(args, world) for name in ("score", "z", "zref", "loo_ds")))
+    if hinted is error:
+        raise error
+    raise hinted from error
+
+
+# ---- output blocks that the resident and the windowed runs share ----------------------------------------------------------------------
+
+def _say_converged(iters, say):
+    for it in iters:
+        if it > 0:
+            say("EM (MAF) converged at iteration: " + str(int(it)))
+
+
+def _save_names(args, pops, say, root=True):
+    """The lines of the frequency file (written by the caller) and the population names file with its line."""
+    import numpy as np
+    say("Saved reference population allele frequencies as " + str(args.out) + ".pop_af.npy (Binary - np.float32)\n")
+    say("Column order of populations is: " + str(pops))
+    if root:
+        np.savetxt(args.out + ".pop_names.txt", pops, fmt="%s")
+    say("Saved reference population names as " + str(args.out) +
+        ".pop_names.txt (String: Order of pops for .pop_af.npy, .ne_obs.npy, and fisher_obs.npy files)\n")
+
+
+def _save_ne_obs(args, pops, say, ne_obs_mean, ne_ind, per_locus=None, root=True):
+    """The --ne_obs files and lines.  per_locus: (f_obs, ne_obs) still to be saved (None: the windowed pass has written them);
+    ne_obs_mean: np.mean(ne_obs, axis=0), on the root; ne_ind: called for the individuals' sizes on every rank once their line is out."""
+    import numpy as np
+    if root and per_locus is not None:
+        np.save(args.out + ".fisher_obs", per_locus[0])
+    say("Saved reference population observed Fisher information per locus as " + str(args.out) +
+        ".fisher_obs.npy (Binary - np.float32)\n")
+    if root and per_locus is not None:
+        np.save(args.out + ".ne_obs", per_locus[1])
+    say("Saved reference population effective sample size estimates per locus as " + str(args.out) +
+        ".ne_obs.npy (Binary - np.float32)\n")
+    if root:
+        ne_obs_mean_out = np.empty((2, len(pops)), dtype=np.dtype('U25'))
+        ne_obs_mean_out[0, :] = pops
+        ne_obs_mean_out[1, :] = ne_obs_mean
+        np.savetxt(args.out + ".ne_obs.txt", ne_obs_mean_out, fmt="%s")
+    say("Saved reference population effective sample size estimates as " + str(args.out) +
+        ".ne_obs.txt (String - np.U25)\n")
+    say("Estimating individual effective sample sizes.")
+    ne_ind = ne_ind()
+    if root:
+        np.savetxt(args.out + ".ne_ind.txt", ne_ind.reshape(-1, 1), fmt="%.7f")
+    say("Save individual effective sample sizes as " + str(args.out) + ".ne_ind.txt")
+
+
+def _save_loo(args, ll, parts, sample_names, pops, IDs, say, suffix=""):
+    """The leave-one-out files and lines (on the root): the totals, and the partition sums when there are several partitions."""
+    from . import utils
+    P = args.partition_sites
+    outfile = f"{args.out}.pop_like_LOO{suffix}.tsv"
+    partfile = f"{args.out}.pop_like_LOO{suffix}_partitions_{P}.tsv.gz"
+    utils.write_ass_mats(outfile, ll, sample_names, pops, print_part_column=False, sample_locations=IDs[:, 1], doing_LOO=True)
+    say(f"Saved leave-one-out cross validation log likelihoods as {outfile}")
+    if P > 1:
+        utils.write_ass_mats(partfile, parts, sample_names, pops, partition_count=P, print_part_column=True,
+                             sample_locations=IDs[:, 1], doing_LOO=True)
+        say(f"Saved leave-one-out cross validation log likelihoods from partitioned sites as {partfile}")
+    say(f"Column order of populations is: {pops}")
+
+
+# ---- the windowed runs: the lines and files of the resident run in their order, and one more line per pass on stderr -------------------
+
+def _run_score_windowed(args, ctx, W, say, summary):
+    """--get_pop_like alone on a file that does not fit (or WGSASSIGN_WINDOW_SITES): scored window by window."""
     import numpy as np
 
-    from . import reader_cy, windows
-    if not windowed_zref_candidate(args, comm.world) or not (args.pop_af_IDs and os.path.isfile(args.pop_af_IDs)):
-        return None                     # (a missing ID file is reported where it always was)
-    try:
-        forced = windows.env_window_sites(name=windows.ENV_ZREF)
-    except ValueError as e:
-        raise SystemExit(str(e))
-    if forced is not None:
-        return forced, None             # (the rounds of individuals are planned once the file's shape is known)
-    free = ctx.mem_info()[0]
-    if windows.surely_fits(os.path.getsize(args.beagle), free):
-        return None
-    try:
-        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
-        counts = np.unique(IDs[:, 1], return_counts=True)[1]
-    except Exception:
-        return None                     # (an unreadable ID file, too, is reported where it always was)
-    n, K = int(counts.sum()), len(counts)
-    count = _z_individuals(args, n)
-    est = None if reader_cy._index_is_cached(args.beagle) else reader_cy.estimate_sites(args.beagle)
-    if est is not None and windows.fits_resident_zref(est + est // 4 + 1024, n, K, count, free, counts):
-        return None
-    m = reader_cy.ensure_index(args.beagle)[2]
-    try:
-        return windows.plan_zref(m, n, K, count, free, args.maf_iter, counts=counts)
-    except MemoryError as e:
-        raise SystemExit(str(e))
+    from . import glassy
+    A = np.load(args.pop_af_file, mmap_mode="r")
+    out = glassy.assignLL_windowed(args.beagle, A, W, ctx=ctx)
+    info, stats = glassy.assignLL_windowed.info, glassy.assignLL_windowed.stats
+    say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
+    summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
+    say("Parsing population allele frequency file.")
+    say("Calculating likelihood of population assignment")
+    say(str(info["n"]) + " individuals to assign to " + str(A.shape[1]) + " populations")
+    print("wgsassign_amd: scored in %d windows of %d sites" % (stats["windows"], stats["window_sites"]), file=sys.stderr, flush=True)
+    np.savetxt(args.out + ".pop_like.txt", out.astype(np.float32), fmt="%.7f")
+    say("Saved population assignment log likelihoods as " + str(args.out) + ".pop_like.txt (text)")
 
 
-def _run_zref_windowed(args, comm, ctx, plan, IDs, group_of, say, summary):
-    """--get_reference_z_score alone on files that do not fit (or WGSASSIGN_ZREF_WINDOW_SITES): passes over the Beagle file and the
-    depth file in site windows; the checks, lines and file of the resident run in their order, and one more line on stderr."""
+def _loo_windowed(args, ctx, W, IDs, pops, sample_names, pop_iters, say, keep_ref=None, keep_ds=None):
+    """The leave-one-out run in the windows of the fit, on the frequencies it has just written; with --loo_downsampled_beagle the
+    downsampled file's windows are scored beside them (keep_ref, keep_ds: the two site masks)."""
+    import numpy as np
+
+    from . import glassy
+    P, scored = args.partition_sites, args.loo_downsampled_beagle
+    say("Performing leave-one-out cross validation.")
+    say(str(len(sample_names)) + " individuals to assign to " + str(len(pops)) + " populations")
+    if scored:
+        say("Using downsampled GLs for likelihood evaluation in LOO assignment.")
+    A = np.load(args.out + ".pop_af.npy", mmap_mode="r")
+    ll, parts, loo_iters = glassy.loo_windowed(args.beagle, A, IDs, args.maf_iter, args.maf_tole, W, P, need_parts=P > 1, pop_iters=pop_iters,
+                                               ctx=ctx, keep=keep_ref, scored_path=scored, scored_keep=keep_ds)
+    del A
+    stats = glassy.loo_windowed.stats
+    _say_converged(loo_iters, say)
+    if scored:
+        print("wgsassign_amd: leave-one-out on downsampled likelihoods in %d rounds of %d windows of %d kept sites (the downsampled file "
+              "read %d time)" % (stats["rounds"], stats["windows"], stats["window_sites"], stats["scored_passes"]), file=sys.stderr, flush=True)
+    else:
+        print("wgsassign_amd: leave-one-out in %d rounds of %d windows of %d sites" % (stats["rounds"], stats["windows"], stats["window_sites"]),
+              file=sys.stderr, flush=True)
+    _save_loo(args, ll, parts, sample_names, pops, IDs, say, "_downsampled" if scored else "")
+
+
+def _run_fit_windowed(args, ctx, W, IDs, pops, say, summary):
+    """--get_reference_af on a file that does not fit (or WGSASSIGN_WINDOW_SITES): fitted window by window in rounds.  With --ne_obs
+    (WGSASSIGN_NE_WINDOW_SITES) one pass for the Fisher information follows, over the frequencies just written; with --loo
+    (WGSASSIGN_LOO_WINDOW_SITES, or beside --ne_obs) the leave-one-out run, in the same windows."""
+    import numpy as np
+
+    from . import emMAF, fisher
+    af, iters = emMAF.emMAF_windowed(args.beagle, IDs, args.maf_iter, args.maf_tole, W, out=args.out + ".pop_af.npy", ctx=ctx)
+    info, stats = emMAF.emMAF_windowed.info, emMAF.emMAF_windowed.stats
+    say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
+    summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
+    say("Parsing reference population ID file.")
+    _say_converged(iters, say)
+    print("wgsassign_amd: fitted in %d rounds of %d windows of %d sites" % (stats["rounds"], stats["windows"], stats["window_sites"]),
+          file=sys.stderr, flush=True)
+    del af
+    _save_names(args, pops, say)
+    if args.ne_obs:
+        say("Estimating Fisher information.")
+        A = np.load(args.out + ".pop_af.npy", mmap_mode="r")
+        f_obs, ne_obs, ne_obs_mean, ne_ind = fisher.fisher_obs_windowed(args.beagle, A, IDs, W, out=args.out, ctx=ctx)
+        del A, f_obs, ne_obs
+        stats = fisher.fisher_obs_windowed.stats
+        print("wgsassign_amd: Fisher information in %d windows of %d sites" % (stats["windows"], stats["window_sites"]), file=sys.stderr,
+              flush=True)
+        _save_ne_obs(args, pops, say, ne_obs_mean, lambda: ne_ind)
+    if args.loo:
+        _loo_windowed(args, ctx, W, IDs, pops, info["sample_names"], iters, say)
+
+
+def _run_loo_ds_windowed(args, ctx, W, IDs, pops, sample_names, keep_ref, keep_ds, say):
+    """--get_reference_af --loo --loo_downsampled_beagle on files that do not fit (or WGSASSIGN_LOO_DS_WINDOW_SITES), after the names
+    passes and the two site masks of the resident run: the fit over the kept sites of the reference file in windows, then the
+    leave-one-out run in the same windows with the downsampled file's windows scored beside them."""
+    from . import emMAF
+    say("Parsing reference population ID file.")
+    assert (len(sample_names) == IDs.shape[0]), "Number of individuals in beagle and reference ID file do not match!"
+    af, iters = emMAF.emMAF_windowed(args.beagle, IDs, args.maf_iter, args.maf_tole, W, out=args.out + ".pop_af.npy", ctx=ctx, keep=keep_ref)
+    _say_converged(iters, say)
+    del af
+    _save_names(args, pops, say)
+    _loo_windowed(args, ctx, W, IDs, pops, sample_names, iters, say, keep_ref, keep_ds)
+
+
+def _run_z_windowed(args, flavour, ctx, plan, IDs, group_of, say, summary):
+    """--get_assignment_z_score or --get_reference_z_score alone (flavour: "assignment" / "reference") on files that do not fit (or
+    WGSASSIGN_Z_WINDOW_SITES / WGSASSIGN_ZREF_WINDOW_SITES): passes over the Beagle file and the depth file in site windows; the
+    checks, lines and file of the resident run in their order."""
     import numpy as np
 
     from . import reader_cy, zscore
     W, batch = plan
+    assignment = flavour == "assignment"
     index, _, m = reader_cy.ensure_index(args.beagle)
     with reader_cy.BeagleStream(args.beagle, threads=1) as st:
         n = st.n
     assert os.path.isfile(args.pop_af_IDs), "Population ID file does not exist!!"
+    if assignment:
+        IDs = np.loadtxt(args.pop_af_IDs, delimiter="\t", dtype="str")
+        A = np.load(args.pop_af_file, mmap_mode="r")
     majmin = None
     if args.ind_counts_file:
         majmin = zscore.read_majmin(args.ind_majmin_file)
@@ -522,34 +478,48 @@ def _run_zref_windowed(args, comm, ctx, plan, IDs, group_of, say, summary):
     else:
         assert os.path.isfile(args.ind_ad_file), "Individual allele depths file does not exist!"
     assert os.path.isfile(args.pop_names), "Population names file does not exist!!"
+    if assignment:
+        pops = np.loadtxt(args.pop_names, dtype="str")
     assert (n == IDs.shape[0]), "Number of individuals in beagle and reference ID file do not match!"
     if args.allele_count_threshold is not None:
         assert (args.allele_count_threshold >= 0), "Allele count threshold needs to be greater than/equal to 0!"
-    allele_count_threshold = args.allele_count_threshold or 0
+    thresholds = (args.allele_count_threshold or 0, args.single_read_threshold)
     ind_start, ind_end = zscore.ind_range(n, args.ind_start, args.ind_end)
     lines = []
-    z_out = zscore.reference_z_scores_windowed(args.beagle, args.ind_counts_file or args.ind_ad_file, IDs, group_of, args.maf_iter,
-                                               args.maf_tole, allele_count_threshold, args.single_read_threshold, ind_start, ind_end,
-                                               window_sites=W, say=lines.append, counts=majmin is not None, majmin=majmin, batch=batch,
-                                               ctx=ctx)
-    info, stats = zscore.reference_z_scores_windowed.info, zscore.reference_z_scores_windowed.stats
+    windowed = dict(window_sites=W, say=lines.append, counts=majmin is not None, majmin=majmin, batch=batch, ctx=ctx)
+    depth_file = args.ind_counts_file or args.ind_ad_file
+    if assignment:
+        run = zscore.assignment_z_scores_windowed
+        z_out = run(args.beagle, depth_file, A, IDs, np.atleast_1d(pops), *thresholds, ind_start, ind_end, **windowed)
+    else:
+        run = zscore.reference_z_scores_windowed
+        z_out = run(args.beagle, depth_file, IDs, group_of, args.maf_iter, args.maf_tole, *thresholds, ind_start, ind_end, **windowed)
+    info, stats = run.info, run.stats
     say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
     summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
     say("Parsing population ID file.")
+    if assignment:
+        say("Parsing population allele frequency file.")
     say("Parsing individual allele depths file.")
     for ln in lines:
         say(ln)
-    print("wgsassign_amd: reference z-scores in %d rounds of individuals, %d passes over %d windows of %d sites (%d bytes downloaded)" %
-          (stats["rounds"], stats["passes"], stats["windows"], stats["window_sites"], stats["downloaded_bytes"]), file=sys.stderr, flush=True)
-    np.savetxt(args.out + ".reference_z_ind.txt", z_out, fmt="%.7f")
-    say("Saved " + str(ind_end - ind_start) + " individual z-scores as " + str(args.out) + ".reference_z_ind.txt (text)")
+    if assignment:
+        print("wgsassign_amd: z-scores in %d rounds of 2 passes over %d windows of %d sites (%d bytes downloaded)" %
+              (stats["rounds"], stats["windows"], stats["window_sites"], stats["downloaded_bytes"]), file=sys.stderr, flush=True)
+    else:
+        print("wgsassign_amd: reference z-scores in %d rounds of individuals, %d passes over %d windows of %d sites (%d bytes downloaded)" %
+              (stats["rounds"], stats["passes"], stats["windows"], stats["window_sites"], stats["downloaded_bytes"]), file=sys.stderr, flush=True)
+    name = ".z_ind.txt" if assignment else ".reference_z_ind.txt"
+    np.savetxt(args.out + name, z_out, fmt="%.7f")
+    say("Saved " + str(ind_end - ind_start) + " individual z-scores as " + str(args.out) + name + " (text)")
 
 
 def _run(args, comm):
     """The hot-path options on device-resident data.  Under torchrun (one process per GPU) the SNPs are
     sharded over the ranks: every rank parses and holds only its contiguous SNP range; the EM convergence sums,
     the serial-chain carry and the n x K log-likelihood sums cross ranks through one sum
-    all-reduce (RCCL); rank 0 writes the reference's output files."""
+    all-reduce (RCCL); rank 0 writes the reference's output files.  On one rank, options that a windowed route covers
+    (ROUTES) run in site windows when their files do not fit the device or their variable asks for it."""
     import numpy as np
 
     from . import emMAF, fisher, glassy, reader_cy, utils
@@ -583,105 +553,21 @@ def _run(args, comm):
 
     W = _window_sites(args, comm, ctx)
     if W is not None:
-        # --get_pop_like alone on a file that does not fit (or WGSASSIGN_WINDOW_SITES): scored window by window; the lines of the
-        # resident run in their order, and one more on stderr
-        A = np.load(args.pop_af_file, mmap_mode="r")
-        out = glassy.assignLL_windowed(args.beagle, A, W, ctx=ctx)
-        info, stats = glassy.assignLL_windowed.info, glassy.assignLL_windowed.stats
-        say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
-        summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
-        say("Parsing population allele frequency file.")
-        say("Calculating likelihood of population assignment")
-        say(str(info["n"]) + " individuals to assign to " + str(A.shape[1]) + " populations")
-        print("wgsassign_amd: scored in %d windows of %d sites" % (stats["windows"], stats["window_sites"]), file=sys.stderr, flush=True)
-        np.savetxt(args.out + ".pop_like.txt", out.astype(np.float32), fmt="%.7f")
-        say("Saved population assignment log likelihoods as " + str(args.out) + ".pop_like.txt (text)")
+        _run_score_windowed(args, ctx, W, say, summary)
         comm.barrier()
         return
-
-    W = _fit_window_sites(args, comm, ctx)
-    W_loo = _loo_window_sites(args, comm, ctx) if W is None else None
-    W_ne = _ne_window_sites(args, comm, ctx) if W is None and W_loo is None else None
-    if W is not None or W_loo is not None or W_ne is not None:
-        # --get_reference_af alone on a file that does not fit (or WGSASSIGN_WINDOW_SITES): fitted window by window in rounds; the
-        # lines and files of the resident run, and one more line on stderr.  With --loo beside it (a file that does not fit, or
-        # WGSASSIGN_LOO_WINDOW_SITES) the leave-one-out run follows in the same windows, on the frequencies just written.  With
-        # --ne_obs (a file that does not fit, or WGSASSIGN_NE_WINDOW_SITES) one pass for the Fisher information comes between them.
-        W = W if W is not None else W_loo if W_loo is not None else W_ne
-        af, iters = emMAF.emMAF_windowed(args.beagle, IDs, args.maf_iter, args.maf_tole, W, out=args.out + ".pop_af.npy", ctx=ctx)
-        info, stats = emMAF.emMAF_windowed.info, emMAF.emMAF_windowed.stats
-        say("Loaded " + str(info["m"]) + " sites and " + str(info["n"]) + " individuals.")
-        summary(info["sample_names"], info["m"], [(info["site_names"][:4], info["site_names"][-4:])])
-        say("Parsing reference population ID file.")
-        for it in iters:
-            if it > 0:
-                say("EM (MAF) converged at iteration: " + str(int(it)))
-        print("wgsassign_amd: fitted in %d rounds of %d windows of %d sites" % (stats["rounds"], stats["windows"], stats["window_sites"]),
-              file=sys.stderr, flush=True)
-        del af
-        say("Saved reference population allele frequencies as " + str(args.out) + ".pop_af.npy (Binary - np.float32)\n")
-        say("Column order of populations is: " + str(pops))
-        np.savetxt(args.out + ".pop_names.txt", pops, fmt="%s")
-        say("Saved reference population names as " + str(args.out) +
-            ".pop_names.txt (String: Order of pops for .pop_af.npy, .ne_obs.npy, and fisher_obs.npy files)\n")
-        if W_ne is not None:
-            say("Estimating Fisher information.")
-            A = np.load(args.out + ".pop_af.npy", mmap_mode="r")
-            f_obs, ne_obs, ne_obs_mean, ne_ind = fisher.fisher_obs_windowed(args.beagle, A, IDs, W, out=args.out, ctx=ctx)
-            del A, f_obs, ne_obs
-            stats = fisher.fisher_obs_windowed.stats
-            print("wgsassign_amd: Fisher information in %d windows of %d sites" % (stats["windows"], stats["window_sites"]), file=sys.stderr,
-                  flush=True)
-            say("Saved reference population observed Fisher information per locus as " + str(args.out) +
-                ".fisher_obs.npy (Binary - np.float32)\n")
-            say("Saved reference population effective sample size estimates per locus as " + str(args.out) +
-                ".ne_obs.npy (Binary - np.float32)\n")
-            ne_obs_mean_out = np.empty((2, len(pops)), dtype=np.dtype('U25'))
-            ne_obs_mean_out[0, :] = pops
-            ne_obs_mean_out[1, :] = ne_obs_mean
-            np.savetxt(args.out + ".ne_obs.txt", ne_obs_mean_out, fmt="%s")
-            say("Saved reference population effective sample size estimates as " + str(args.out) +
-                ".ne_obs.txt (String - np.U25)\n")
-            say("Estimating individual effective sample sizes.")
-            np.savetxt(args.out + ".ne_ind.txt", ne_ind.reshape(-1, 1), fmt="%.7f")
-            say("Save individual effective sample sizes as " + str(args.out) + ".ne_ind.txt")
-        if W_loo is not None or (W_ne is not None and args.loo):
-            P = args.partition_sites
-            say("Performing leave-one-out cross validation.")
-            say(str(info["n"]) + " individuals to assign to " + str(len(pops)) + " populations")
-            A = np.load(args.out + ".pop_af.npy", mmap_mode="r")
-            ll, parts, loo_iters = glassy.loo_windowed(args.beagle, A, IDs, args.maf_iter, args.maf_tole, W, P, need_parts=P > 1,
-                                                       pop_iters=iters, ctx=ctx)
-            del A
-            stats = glassy.loo_windowed.stats
-            for it in loo_iters:
-                if it > 0:
-                    say("EM (MAF) converged at iteration: " + str(int(it)))
-            print("wgsassign_amd: leave-one-out in %d rounds of %d windows of %d sites" % (stats["rounds"], stats["windows"], stats["window_sites"]),
-                  file=sys.stderr, flush=True)
-            outfile = f"{args.out}.pop_like_LOO.tsv"
-            partfile = f"{args.out}.pop_like_LOO_partitions_{P}.tsv.gz"
-            utils.write_ass_mats(outfile, ll, info["sample_names"], pops, print_part_column=False, sample_locations=IDs[:, 1], doing_LOO=True)
-            say(f"Saved leave-one-out cross validation log likelihoods as {outfile}")
-            if P > 1:
-                utils.write_ass_mats(partfile, parts, info["sample_names"], pops, partition_count=P, print_part_column=True,
-                                     sample_locations=IDs[:, 1], doing_LOO=True)
-                say(f"Saved leave-one-out cross validation log likelihoods from partitioned sites as {partfile}")
-            say(f"Column order of populations is: {pops}")
-        comm.barrier()
-        return
-
-    z_plan = _z_window_sites(args, comm, ctx)
-    if z_plan is not None:
-        _run_z_windowed(args, comm, ctx, z_plan, say, summary)
-        comm.barrier()
-        return
-
-    zref_plan = _zref_window_sites(args, comm, ctx)
-    if zref_plan is not None:
-        _run_zref_windowed(args, comm, ctx, zref_plan, IDs, group_of, say, summary)
-        comm.barrier()
-        return
+    for ask in (_fit_window_sites, _loo_window_sites, _ne_window_sites):     # (each asked only when those before it said None)
+        W = ask(args, comm, ctx)
+        if W is not None:
+            _run_fit_windowed(args, ctx, W, IDs, pops, say, summary)
+            comm.barrier()
+            return
+    for flavour, ask in (("assignment", _z_window_sites), ("reference", _zref_window_sites)):
+        plan = ask(args, comm, ctx)
+        if plan is not None:
+            _run_z_windowed(args, flavour, ctx, plan, IDs, group_of, say, summary)
+            comm.barrier()
+            return
 
     scored = None
     if args.loo_downsampled_beagle:
@@ -713,9 +599,7 @@ def _run(args, comm):
             raise ValueError("Site names in full and downsampled Beagle do not match after filtering.")
         W_ds = _loo_ds_window_sites(args, comm, ctx, m_kept=len(kept_ref))
         if W_ds is not None:
-            # --get_reference_af --loo --loo_downsampled_beagle on files that do not fit (or WGSASSIGN_LOO_DS_WINDOW_SITES): both files
-            # in windows of kept sites; the names of both files still live on the host
-            del names_ref, names_ds, kept_ref
+            del names_ref, names_ds, kept_ref       # (the names of both files still live on the host)
             _run_loo_ds_windowed(args, ctx, W_ds, IDs, pops, sample_names, keep_ref, keep_ds, say)
             comm.barrier()
             return
@@ -725,20 +609,13 @@ def _run(args, comm):
             scored, _, _, _ = reader_cy.stream_to_device(args.loo_downsampled_beagle, group_of, n_groups, ctx=ctx,
                                                          rank=comm.rank, world=comm.world, keep=keep_ds, comm=comm)
         except RuntimeError as e:
-            hinted = with_windows_hint(e, loo_ds_candidate=windowed_loo_ds_candidate(args, comm.world))
-            if hinted is e:
-                raise
-            raise hinted from e
+            _raise_hinted(e, args, comm.world)
     else:
         try:
             beagle, sample_names, site_names, m = reader_cy.stream_to_device(
                 args.beagle, group_of, n_groups, ctx=ctx, rank=comm.rank, world=comm.world, comm=comm, names="ends")
         except RuntimeError as e:
-            hinted = with_windows_hint(e, windowed_candidate(args, comm.world), windowed_z_candidate(args, comm.world),
-                                       zref_candidate=windowed_zref_candidate(args, comm.world))
-            if hinted is e:
-                raise
-            raise hinted from e
+            _raise_hinted(e, args, comm.world)
         n = beagle.n
         say("Loaded " + str(m) + " sites and " + str(n) + " individuals.")
         ends = comm.allgather_object((site_names[:4], site_names[-4:]))
@@ -758,37 +635,15 @@ def _run(args, comm):
         af_full = comm.gather_rows(af)
         if root:
             np.save(args.out + ".pop_af", af_full)
-        say("Saved reference population allele frequencies as " + str(args.out) + ".pop_af.npy (Binary - np.float32)\n")
-        say("Column order of populations is: " + str(pops))
-        if root:
-            np.savetxt(args.out + ".pop_names.txt", pops, fmt="%s")
-        say("Saved reference population names as " + str(args.out) +
-            ".pop_names.txt (String: Order of pops for .pop_af.npy, .ne_obs.npy, and fisher_obs.npy files)\n")
+        _save_names(args, pops, say, root)
         if args.ne_obs:                      # per-SNP quantities shard trivially; rank 0 assembles and writes
             say("Estimating Fisher information.")
             f_loc, ne_loc = fisher.fisher_obs(None, af, IDs, args.threads, beagle=beagle)
             f_obs, ne_obs = comm.gather_rows(f_loc), comm.gather_rows(ne_loc)
-            if root:
-                np.save(args.out + ".fisher_obs", f_obs)
-            say("Saved reference population observed Fisher information per locus as " + str(args.out) +
-                ".fisher_obs.npy (Binary - np.float32)\n")
-            if root:
-                np.save(args.out + ".ne_obs", ne_obs)
-            say("Saved reference population effective sample size estimates per locus as " + str(args.out) +
-                ".ne_obs.npy (Binary - np.float32)\n")
-            if root:
-                ne_obs_mean_out = np.empty((2, len(pops)), dtype=np.dtype('U25'))
-                ne_obs_mean_out[0, :] = pops
-                ne_obs_mean_out[1, :] = np.mean(ne_obs, axis=0)
-                np.savetxt(args.out + ".ne_obs.txt", ne_obs_mean_out, fmt="%s")
-            say("Saved reference population effective sample size estimates as " + str(args.out) +
-                ".ne_obs.txt (String - np.U25)\n")
-            say("Estimating individual effective sample sizes.")
             # np.mean's running float32 total is handed from SNP shard to SNP shard (fisher.fisher_obs_ind)
-            ne_ind_full = fisher.fisher_obs_ind(None, af, IDs, args.threads, beagle=beagle, comm=comm, m_total=m)
-            if root:
-                np.savetxt(args.out + ".ne_ind.txt", ne_ind_full.reshape(-1, 1), fmt="%.7f")
-            say("Save individual effective sample sizes as " + str(args.out) + ".ne_ind.txt")
+            _save_ne_obs(args, pops, say, np.mean(ne_obs, axis=0) if root else None,
+                         lambda: fisher.fisher_obs_ind(None, af, IDs, args.threads, beagle=beagle, comm=comm, m_total=m),
+                         per_locus=(f_obs, ne_obs), root=root)
 
         if args.loo:
             say("Performing leave-one-out cross validation.")
@@ -802,17 +657,7 @@ def _run(args, comm):
                                               args.partition_sites, comm=comm, need_parts=args.partition_sites > 1)
             if root:
                 sys.stdout.write(buf.getvalue())
-                suffix = "_downsampled" if scored is not None else ""
-                outfile = f"{args.out}.pop_like_LOO{suffix}.tsv"
-                partfile = f"{args.out}.pop_like_LOO{suffix}_partitions_{args.partition_sites}.tsv.gz"
-                utils.write_ass_mats(outfile, ll, sample_names, pops, print_part_column=False,
-                                     sample_locations=IDs[:, 1], doing_LOO=True)
-                print(f"Saved leave-one-out cross validation log likelihoods as {outfile}")
-                if args.partition_sites > 1:
-                    utils.write_ass_mats(partfile, parts, sample_names, pops, partition_count=args.partition_sites,
-                                         print_part_column=True, sample_locations=IDs[:, 1], doing_LOO=True)
-                    print(f"Saved leave-one-out cross validation log likelihoods from partitioned sites as {partfile}")
-                print(f"Column order of populations is: {pops}")
+                _save_loo(args, ll, parts, sample_names, pops, IDs, say, "_downsampled" if scored is not None else "")
 
     if args.get_pop_like:
         say("Parsing population allele frequency file.")

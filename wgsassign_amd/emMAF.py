@@ -120,14 +120,11 @@ def emMAF_windowed(path, IDs, maf_iter, tole, window_sites=None, out=None, ctx=N
     them -- m, the rows of af, the windows and the names are those of kept sites (reader_cy.stream_windows)."""
     import time
 
-    from . import reader_cy, windowed_fit, windows
+    from . import reader_cy, utils, windowed_fit, windows
     from .device import EMStream, get_context
     ctx = ctx or get_context()
     t0 = time.perf_counter()
-    IDs = np.asarray(IDs)
-    pops = np.unique(IDs[:, 1])
-    group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
-    counts = np.bincount(group_of, minlength=len(pops))
+    pops, group_of, counts = utils.population_groups(np.asarray(IDs))
     K = len(pops)
     index, _, m = reader_cy.ensure_index(path)
     if keep is not None:
@@ -140,17 +137,10 @@ def emMAF_windowed(path, IDs, maf_iter, tole, window_sites=None, out=None, ctx=N
     if window_sites is None:
         W = windows.env_window_sites()
         if W is None:
-            W = windows.plan_fit(m, len(group_of), K, ctx.mem_info()[0]) or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN
+            W = windows.plan_fit(m, len(group_of), K, ctx.mem_info()[0]) or windows.whole_file_window(m)
     else:
-        if int(window_sites) < windows.ALIGN:
-            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
-        W = int(window_sites) // windows.ALIGN * windows.ALIGN
-
-    def groups(sample_names):
-        if len(sample_names) != len(group_of):
-            raise AssertionError("Number of individuals in beagle and reference ID file do not match!")
-        return group_of, K
-
+        W = windows.explicit_window(window_sites)
+    groups = utils.checked_groups(group_of, K)
     af = np.empty((m, K), dtype=np.float32) if out is None else np.lib.format.open_memmap(out, mode="w+", dtype=np.float32, shape=(m, K))
     info, stats = {}, {"round_seconds": []}
     stream = EMStream(K, maf_iter, m, ctx)

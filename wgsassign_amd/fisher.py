@@ -145,14 +145,11 @@ def fisher_obs_windowed(path, af, IDs, window_sites=None, out=None, ctx=None):
     fisher_obs_windowed.info: n, m, sample_names, site_names (the first and last four), pops."""
     import time
 
-    from . import reader_cy, windows
+    from . import reader_cy, utils, windows
     from .device import FisherStream, get_context
     ctx = ctx or get_context()
     t0 = time.perf_counter()
-    IDs = np.asarray(IDs)
-    pops = np.unique(IDs[:, 1])
-    group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
-    counts = np.bincount(group_of, minlength=len(pops))
+    pops, group_of, counts = utils.population_groups(np.asarray(IDs))
     K = len(pops)
     if af.ndim != 2 or af.shape[1] != K:
         raise ValueError("the allele frequencies must be an (m, %d) matrix" % K)
@@ -164,17 +161,10 @@ def fisher_obs_windowed(path, af, IDs, window_sites=None, out=None, ctx=None):
     if window_sites is None:
         W = windows.env_window_sites(name=windows.ENV_NE)
         if W is None:
-            W = (windows.plan_ne(m, len(group_of), K, ctx.mem_info()[0], counts=counts)
-                 or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN)
+            W = windows.plan_ne(m, len(group_of), K, ctx.mem_info()[0], counts=counts) or windows.whole_file_window(m)
     else:
-        if int(window_sites) < windows.ALIGN:
-            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
-        W = int(window_sites) // windows.ALIGN * windows.ALIGN
-
-    def groups(sample_names):
-        if len(sample_names) != len(group_of):
-            raise AssertionError("Number of individuals in beagle and reference ID file do not match!")
-        return group_of, K
+        W = windows.explicit_window(window_sites)
+    groups = utils.checked_groups(group_of, K)
 
     def result(suffix):
         if out is None:

@@ -53,11 +53,9 @@ def assignLL_windowed(path, A, window_sites=None, ctx=None, mode=None):
             index, _, m = reader_cy.ensure_index(path)
             with reader_cy.BeagleStream(path, threads=1, index=index, first_row=0) as st:
                 n = st.n
-            W = windows.plan(m, n, K, ctx.mem_info()[0]) or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN
+            W = windows.plan(m, n, K, ctx.mem_info()[0]) or windows.whole_file_window(m)
     else:
-        if int(window_sites) < windows.ALIGN:
-            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
-        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+        W = windows.explicit_window(window_sites)
     info, stream = {}, None
     gen = reader_cy.stream_windows(path, W, ctx=ctx, info=info)
     try:
@@ -356,14 +354,11 @@ def loo_windowed(path, af, IDs, maf_iter, maf_tole, window_sites=None, num_parti
     loo_windowed.info: n, m, sample_names, site_names (the first and last four), pops."""
     import time
 
-    from . import reader_cy, windowed_fit, windows
+    from . import reader_cy, utils, windowed_fit, windows
     from .device import EMStream, LooStream, default_mode, get_context
     ctx = ctx or get_context()
     t0 = time.perf_counter()
-    IDs = np.asarray(IDs)
-    pops = np.unique(IDs[:, 1])
-    group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
-    counts = np.bincount(group_of, minlength=len(pops))
+    pops, group_of, counts = utils.population_groups(np.asarray(IDs))
     n, K, P = len(group_of), len(pops), int(num_partitions)
     if af.ndim != 2 or af.shape[1] != K:
         raise ValueError("the allele frequencies must be an (m, %d) matrix" % K)
@@ -401,19 +396,12 @@ def loo_windowed(path, af, IDs, maf_iter, maf_tole, window_sites=None, num_parti
         W = windows.env_window_sites(name=windows.ENV_LOO_DS if scored_path is not None else windows.ENV_LOO)
         if W is None:
             planned = (windows.plan_loo_ds if scored_path is not None else windows.plan_loo)(m, n, K, ctx.mem_info()[0], counts=counts, P=P)
-            W = planned or max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN
+            W = planned or windows.whole_file_window(m)
     else:
-        if int(window_sites) < windows.ALIGN:
-            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
-        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+        W = windows.explicit_window(window_sites)
     if first_iters is None and pop_iters is not None:
         first_iters = loo_first_iters(group_of, pop_iters, maf_iter)
-
-    def groups(sample_names):
-        if len(sample_names) != n:
-            raise AssertionError("Number of individuals in beagle and reference ID file do not match!")
-        return group_of, K
-
+    groups = utils.checked_groups(group_of, K)
     info, info_scored, stats = {}, {}, {"round_seconds": []}
     stream = EMStream(n, maf_iter, m, ctx)
     loo_stream = LooStream(n, K, m, P if exact_parts else 0, ctx)

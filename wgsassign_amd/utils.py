@@ -37,6 +37,24 @@ def filter_sites_to_common(L, site_names, site_names_target):
     return L[mask, :], names[mask].tolist()
 
 
+def population_groups(IDs):
+    """(pops, group_of, counts) of an ID table: the sorted population names of its second column, every individual's index among them
+    (int32) and the individuals of every population."""
+    pops = np.unique(IDs[:, 1])
+    group_of = np.searchsorted(pops, IDs[:, 1]).astype(np.int32)
+    return pops, group_of, np.bincount(group_of, minlength=len(pops))
+
+
+def checked_groups(group_of, n_groups):
+    """The group_of argument of reader_cy.stream_windows for an ID table's groups: called with the file's sample names, it refuses a
+    file with another number of individuals and hands out (group_of, n_groups)."""
+    def groups(sample_names):
+        if len(sample_names) != len(group_of):
+            raise AssertionError("Number of individuals in beagle and reference ID file do not match!")
+        return group_of, n_groups
+    return groups
+
+
 def partition_loglikes(per_site_ll, partition_count):
     """utils.py:129-151: sums of a per-site vector by label = site index % partition_count
     (sequential float32 accumulation, like np.add.at)."""

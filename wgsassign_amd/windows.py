@@ -19,8 +19,8 @@ RESERVE (4 GiB, at most a quarter of the free memory: the ingest's text and line
 when the device inflates -- the block sums of a sweep, the context's workspace).  A resident matrix needs m sites of it;
 windowed scoring holds TWO windows (the one being scored and the one being filled), each with its frequencies and codes.
 
-The other windowed routes have their own arithmetic below (fit_site_bytes, loo_site_bytes, loo_ds_site_bytes, ne_site_bytes,
-z_site_bytes, zref_site_bytes) and, but for the fit, a variable of their own.
+The other windowed routes, each with its options, variable, planner and driver, are in the table at the head of DESIGN.md
+section 5.1; their arithmetic follows below.
 """
 import os
 
@@ -80,21 +80,50 @@ def window_count(m, W):
     return (int(m) + int(W) - 1) // int(W)
 
 
+def explicit_window(window_sites):
+    """The window a driver was asked for outright: `window_sites` rounded down to a multiple of 8192; fewer is an error."""
+    if int(window_sites) < ALIGN:
+        raise ValueError("a window holds at least %d sites, not %d" % (ALIGN, int(window_sites)))
+    return int(window_sites) // ALIGN * ALIGN
+
+
+def whole_file_window(m):
+    """The one window that holds all m sites: what a driver runs in when its planner says that everything fits."""
+    return max(1, window_count(m, ALIGN)) * ALIGN
+
+
+def _plan_two_windows(forced, fits, per_site, free_bytes, message, **named):
+    """What plan, plan_fit, plan_loo, plan_loo_ds and plan_ne share: `forced` (the route's variable) when it is set, None when the
+    resident run `fits`, else the largest multiple of 8192 sites of which two windows of `per_site` bytes a site fit the budget.
+    None fits: MemoryError with the route's `message`, filled with sites, bytes (of the two smallest windows), usable, free and
+    whatever is `named`."""
+    if forced is not None:
+        return forced
+    if fits:
+        return None
+    W = budget(free_bytes) // (2 * per_site) // ALIGN * ALIGN
+    if W < ALIGN:
+        raise MemoryError(message % dict(named, sites=ALIGN, bytes=2 * ALIGN * per_site, usable=max(0, budget(free_bytes)), free=free_bytes))
+    return W
+
+
 def plan(m, n, K, free_bytes, environ=None):
     """The window for scoring m sites x n individuals against K populations with `free_bytes` of device memory free:
     None when the resident matrix fits and WGSASSIGN_WINDOW_SITES does not ask for windows, else W (a multiple of 8192;
     the last window may be shorter).  Too little memory for two windows of 8192 sites is an error."""
-    forced = env_window_sites(environ)
-    if forced is not None:
-        return forced
-    if fits_resident(m, n, K, free_bytes):
-        return None
-    W = budget(free_bytes) // (2 * site_bytes(n, K)) // ALIGN * ALIGN
-    if W < ALIGN:
-        raise MemoryError("windowed scoring needs two windows of %d sites x %d individuals on the device (%d bytes with their "
-                          "frequencies and class codes); %d of the %d free bytes can be used" %
-                          (ALIGN, n, 2 * ALIGN * site_bytes(n, K), max(0, budget(free_bytes)), free_bytes))
-    return W
+    return _plan_two_windows(env_window_sites(environ), fits_resident(m, n, K, free_bytes), site_bytes(n, K), free_bytes,
+                             "windowed scoring needs two windows of %(sites)d sites x %(n)d individuals on the device (%(bytes)d bytes "
+                             "with their frequencies and class codes); %(usable)d of the %(free)d free bytes can be used", n=n)
+
+
+def _slab_pairs(n, K, counts=None):
+    """float4 columns of the population slabs: per population one per pair of its individuals (fit_site_bytes)."""
+    return sum((int(c) + 1) // 2 for c in counts) if counts is not None else (int(n) + int(K)) // 2
+
+
+def _slab_quads(n, K, counts=None):
+    """Code words of the population slabs: per population one per four of its individuals (fit_site_bytes)."""
+    return sum((int(c) + 3) // 4 for c in counts) if counts is not None else (int(n) + 3 * int(K)) // 4
 
 
 def fit_site_bytes(n, K, counts=None):
@@ -114,11 +143,7 @@ def fit_site_bytes(n, K, counts=None):
     The stopping test's tables (wgs_em_stream: maf_iter x K float64 and float32) and the chains' workspace (60 bytes per fit and
     4096 sites) do not grow with the window worth mentioning and come out of RESERVE."""
     n, K = int(n), int(K)
-    if counts is not None:
-        pairs = sum((int(c) + 1) // 2 for c in counts)
-        quads = sum((int(c) + 3) // 4 for c in counts)
-    else:
-        pairs, quads = (n + K) // 2, (n + 3 * K) // 4
+    pairs, quads = _slab_pairs(n, K, counts), _slab_quads(n, K, counts)
     return 16 * pairs + 8 * K + (8 * K + 63) // 64 + (1 + 8 * 254 + 8) + 8 * quads + K * (1 + 8 * 254)
 
 
@@ -130,18 +155,10 @@ def fits_resident_fit(m, n, K, free_bytes, counts=None):
 def plan_fit(m, n, K, free_bytes, environ=None, counts=None):
     """plan() for --get_reference_af: None when the resident fit fits and WGSASSIGN_WINDOW_SITES does not ask for windows, else W (a
     multiple of 8192).  Two windows are held, each with its EM batch and codes."""
-    forced = env_window_sites(environ)
-    if forced is not None:
-        return forced
-    if fits_resident_fit(m, n, K, free_bytes, counts):
-        return None
-    per_site = fit_site_bytes(n, K, counts)
-    W = budget(free_bytes) // (2 * per_site) // ALIGN * ALIGN
-    if W < ALIGN:
-        raise MemoryError("a windowed fit needs two windows of %d sites x %d individuals on the device (%d bytes with their "
-                          "frequency buffers and class codes); %d of the %d free bytes can be used" %
-                          (ALIGN, n, 2 * ALIGN * per_site, max(0, budget(free_bytes)), free_bytes))
-    return W
+    return _plan_two_windows(env_window_sites(environ), fits_resident_fit(m, n, K, free_bytes, counts), fit_site_bytes(n, K, counts),
+                             free_bytes,
+                             "a windowed fit needs two windows of %(sites)d sites x %(n)d individuals on the device (%(bytes)d bytes "
+                             "with their frequency buffers and class codes); %(usable)d of the %(free)d free bytes can be used", n=n)
 
 
 def loo_site_bytes(n, K, counts=None, P=1):
@@ -170,18 +187,11 @@ def plan_loo(m, n, K, free_bytes, environ=None, counts=None, P=1):
     """plan() for --get_reference_af --loo: None when the resident matrix fits (the resident run batches its re-fits by what is
     left and needs only the matrix: fits_resident_fit) and WGSASSIGN_LOO_WINDOW_SITES does not ask for windows, else W (a
     multiple of 8192) for two windows, each with its batch of n re-fits."""
-    forced = env_window_sites(environ, ENV_LOO)
-    if forced is not None:
-        return forced
-    if fits_resident_fit(m, n, K, free_bytes, counts):
-        return None
-    per_site = loo_site_bytes(n, K, counts, P)
-    W = budget(free_bytes) // (2 * per_site) // ALIGN * ALIGN
-    if W < ALIGN:
-        raise MemoryError("a windowed leave-one-out run needs two windows of %d sites x %d individuals on the device (%d bytes with "
-                          "their %d re-fits, class codes and scoring tables); %d of the %d free bytes can be used" %
-                          (ALIGN, n, 2 * ALIGN * per_site, n, max(0, budget(free_bytes)), free_bytes))
-    return W
+    return _plan_two_windows(env_window_sites(environ, ENV_LOO), fits_resident_fit(m, n, K, free_bytes, counts),
+                             loo_site_bytes(n, K, counts, P), free_bytes,
+                             "a windowed leave-one-out run needs two windows of %(sites)d sites x %(n)d individuals on the device "
+                             "(%(bytes)d bytes with their %(n)d re-fits, class codes and scoring tables); %(usable)d of the %(free)d "
+                             "free bytes can be used", n=n)
 
 
 def loo_ds_site_bytes(n, K, counts=None, P=1):
@@ -197,11 +207,7 @@ def loo_ds_site_bytes(n, K, counts=None, P=1):
 
     The re-fits never look at the scored matrix, so it carries no EM batch."""
     n, K = int(n), int(K)
-    if counts is not None:
-        pairs = sum((int(c) + 1) // 2 for c in counts)
-        quads = sum((int(c) + 3) // 4 for c in counts)
-    else:
-        pairs, quads = (n + K) // 2, (n + 3 * K) // 4
+    pairs, quads = _slab_pairs(n, K, counts), _slab_quads(n, K, counts)
     return loo_site_bytes(n, K, counts, P) + 16 * pairs + (1 + 8 * 254 + 8) + 4 * quads + K
 
 
@@ -215,18 +221,11 @@ def plan_loo_ds(m_kept, n, K, free_bytes, environ=None, counts=None, P=1):
     """plan() for --get_reference_af --loo --loo_downsampled_beagle over m_kept kept sites: None when two resident matrices fit
     (fits_resident_loo_ds) and WGSASSIGN_LOO_DS_WINDOW_SITES does not ask for windows, else W (a multiple of 8192 KEPT sites) for
     two windows of each file, the reference file's with their batches of n re-fits."""
-    forced = env_window_sites(environ, ENV_LOO_DS)
-    if forced is not None:
-        return forced
-    if fits_resident_loo_ds(m_kept, n, K, free_bytes, counts):
-        return None
-    per_site = loo_ds_site_bytes(n, K, counts, P)
-    W = budget(free_bytes) // (2 * per_site) // ALIGN * ALIGN
-    if W < ALIGN:
-        raise MemoryError("a windowed leave-one-out run on downsampled likelihoods needs two windows of %d sites x %d individuals of both "
-                          "files on the device (%d bytes with their %d re-fits, class codes and scoring tables); %d of the %d free bytes "
-                          "can be used" % (ALIGN, n, 2 * ALIGN * per_site, n, max(0, budget(free_bytes)), free_bytes))
-    return W
+    return _plan_two_windows(env_window_sites(environ, ENV_LOO_DS), fits_resident_loo_ds(m_kept, n, K, free_bytes, counts),
+                             loo_ds_site_bytes(n, K, counts, P), free_bytes,
+                             "a windowed leave-one-out run on downsampled likelihoods needs two windows of %(sites)d sites x %(n)d "
+                             "individuals of both files on the device (%(bytes)d bytes with their %(n)d re-fits, class codes and scoring "
+                             "tables); %(usable)d of the %(free)d free bytes can be used", n=n)
 
 
 def kept_windows(keep, W):
@@ -258,8 +257,7 @@ def ne_site_bytes(n, K, counts=None):
     The row matrix of the file's last, shorter chunk (n x at most 8191 float32), its leaf sums, the plans and the stream's totals do
     not grow with the window and come out of RESERVE."""
     n, K = int(n), int(K)
-    pairs = sum((int(c) + 1) // 2 for c in counts) if counts is not None else (n + K) // 2
-    return 16 * pairs + 4 * K + 12 * K + (4 * n + 127) // 128
+    return 16 * _slab_pairs(n, K, counts) + 4 * K + 12 * K + (4 * n + 127) // 128
 
 
 def plan_ne(m, n, K, free_bytes, environ=None, counts=None, loo=False, P=1):
@@ -267,20 +265,13 @@ def plan_ne(m, n, K, free_bytes, environ=None, counts=None, loo=False, P=1):
     WGSASSIGN_NE_WINDOW_SITES does not ask for windows, else W (a multiple of 8192) for two windows: the fit's (plan_fit's
     arithmetic), or the Fisher pass's when that is smaller.  loo: --loo runs beside it in the same windows, so the window is the
     smaller of this and what plan_loo derives."""
-    forced = env_window_sites(environ, ENV_NE)
-    if forced is not None:
-        return forced
-    if fits_resident_fit(m, n, K, free_bytes, counts):
-        return None
     per_site = max(fit_site_bytes(n, K, counts), ne_site_bytes(n, K, counts))
     if loo:
         per_site = max(per_site, loo_site_bytes(n, K, counts, P))
-    W = budget(free_bytes) // (2 * per_site) // ALIGN * ALIGN
-    if W < ALIGN:
-        raise MemoryError("a windowed --ne_obs run needs two windows of %d sites x %d individuals on the device (%d bytes with their "
-                          "frequency buffers, class codes and Fisher results); %d of the %d free bytes can be used" %
-                          (ALIGN, n, 2 * ALIGN * per_site, max(0, budget(free_bytes)), free_bytes))
-    return W
+    return _plan_two_windows(env_window_sites(environ, ENV_NE), fits_resident_fit(m, n, K, free_bytes, counts), per_site, free_bytes,
+                             "a windowed --ne_obs run needs two windows of %(sites)d sites x %(n)d individuals on the device (%(bytes)d "
+                             "bytes with their frequency buffers, class codes and Fisher results); %(usable)d of the %(free)d free bytes "
+                             "can be used", n=n)
 
 
 Z_RESIDENT_BATCH = 64           # individuals per launch of the resident z-score path (zscore.assignment_z_scores)
@@ -315,13 +306,47 @@ def fits_resident_z(m, n, K, count, free_bytes):
     return int(m) * z_site_bytes(n, K, min(int(count), Z_RESIDENT_BATCH)) <= budget(free_bytes)
 
 
+def _round_batch(W, count, state_bytes, window_bytes, free_bytes):
+    """What z_batch and zref_batch share: all `count` individuals when state_bytes(batch) and W sites of window_bytes(batch) each fit
+    the budget, else the largest half, quarter, ... of them that does (at least one)."""
+    batch = max(1, int(count))
+    while batch > 1 and state_bytes(batch) + int(W) * window_bytes(batch) > budget(free_bytes):
+        batch = (batch + 1) // 2
+    return batch
+
+
+def _plan_rounds(forced, fits, count, state_bytes, window_bytes, free_bytes, message, **named):
+    """What plan_z and plan_zref share: None when the route's variable is not set (`forced` is None) and the resident run `fits`; with
+    the variable set (forced, _round_batch(forced, ...)), whether or not that fits; else (W, batch) with batch = count halved until a
+    window of 8192 sites of window_bytes(batch) each fits beside state_bytes(batch), and W the largest multiple of 8192 that does.
+    Not even one individual: MemoryError with the route's `message`, filled with sites, bytes (of the smallest window), state (of one
+    individual), usable, free and whatever is `named`."""
+    if forced is not None:
+        return forced, _round_batch(forced, count, state_bytes, window_bytes, free_bytes)
+    if fits:
+        return None
+    batch = count
+    while True:
+        room = budget(free_bytes) - state_bytes(batch)
+        W = room // window_bytes(batch) // ALIGN * ALIGN if room > 0 else 0
+        if W >= ALIGN or batch == 1:
+            break
+        batch = (batch + 1) // 2
+    if W < ALIGN:
+        raise MemoryError(message % dict(named, sites=ALIGN, bytes=ALIGN * window_bytes(batch), state=state_bytes(1),
+                                         usable=max(0, budget(free_bytes)), free=free_bytes))
+    return W, batch
+
+
+def _z_window_bytes(n, K, batch):
+    """Per site of a window with the second matrix beside it."""
+    return z_site_bytes(n, K, batch) + 16 * ((int(n) + 1) // 2)
+
+
 def z_batch(W, n, K, count, free_bytes):
     """Individuals per round for windows of W sites: all `count` when their state and one window's objects fit beside the second
     matrix, else the largest half, quarter, ... of them that does (at least one)."""
-    batch = max(1, int(count))
-    while batch > 1 and z_state_bytes(batch) + int(W) * (z_site_bytes(n, K, batch) + 16 * ((int(n) + 1) // 2)) > budget(free_bytes):
-        batch = (batch + 1) // 2
-    return batch
+    return _round_batch(W, count, z_state_bytes, lambda batch: _z_window_bytes(n, K, batch), free_bytes)
 
 
 def plan_z(m, n, K, count, free_bytes, environ=None):
@@ -329,30 +354,12 @@ def plan_z(m, n, K, count, free_bytes, environ=None):
     WGSASSIGN_Z_WINDOW_SITES does not ask for windows, else (W, batch): windows of W sites (a multiple of 8192) and rounds of `batch`
     individuals.  batch = count -- one round, two passes over the files -- whenever the state of all of them (z_state_bytes) leaves
     room for a window of 8192 sites beside the second matrix; otherwise the largest half, quarter, ... of them that does."""
-    forced = env_window_sites(environ, ENV_Z)
     m, n, K, count = int(m), int(n), int(K), int(count)
-    if forced is None and fits_resident_z(m, n, K, count, free_bytes):
-        return None
-    batch = count
-    while True:
-        per_site = z_site_bytes(n, K, batch) + 16 * ((n + 1) // 2)
-        room = budget(free_bytes) - z_state_bytes(batch)
-        W = room // per_site // ALIGN * ALIGN if room > 0 else 0
-        if W >= ALIGN or batch == 1:
-            break
-        batch = (batch + 1) // 2
-    if forced is not None:
-        return forced, z_batch(forced, n, K, count, free_bytes)
-    if W < ALIGN:
-        raise MemoryError("windowed z-scores need two windows of %d sites x %d individuals on the device (%d bytes with the depths, "
-                          "frequencies, masks and statistics of one) and %d bytes of state per individual; %d of the %d free bytes can be "
-                          "used" % (ALIGN, n, ALIGN * per_site, z_state_bytes(1), max(0, budget(free_bytes)), free_bytes))
-    return W, batch
-
-
-def _slab_pairs(n, K, counts=None):
-    """float4 columns of the population slabs: per population one per pair of its individuals (fit_site_bytes)."""
-    return sum((int(c) + 1) // 2 for c in counts) if counts is not None else (int(n) + int(K)) // 2
+    return _plan_rounds(env_window_sites(environ, ENV_Z), fits_resident_z(m, n, K, count, free_bytes), count, z_state_bytes,
+                        lambda batch: _z_window_bytes(n, K, batch), free_bytes,
+                        "windowed z-scores need two windows of %(sites)d sites x %(n)d individuals on the device (%(bytes)d bytes with the "
+                        "depths, frequencies, masks and statistics of one) and %(state)d bytes of state per individual; %(usable)d of the "
+                        "%(free)d free bytes can be used", n=n)
 
 
 def _zref_fits_bytes(count):
@@ -402,32 +409,17 @@ def _zref_window_bytes(n, K, batch, counts=None):
 def zref_batch(W, n, K, count, free_bytes, maf_iter=200, counts=None):
     """Individuals per round for windows of W sites: all `count` when their state and the two windows' objects fit, else the largest
     half, quarter, ... of them that does (at least one)."""
-    batch = max(1, int(count))
-    while batch > 1 and zref_state_bytes(batch, maf_iter) + int(W) * _zref_window_bytes(n, K, batch, counts) > budget(free_bytes):
-        batch = (batch + 1) // 2
-    return batch
+    return _round_batch(W, count, lambda batch: zref_state_bytes(batch, maf_iter), lambda batch: _zref_window_bytes(n, K, batch, counts),
+                        free_bytes)
 
 
 def plan_zref(m, n, K, count, free_bytes, maf_iter=200, environ=None, counts=None):
     """plan() for --get_reference_z_score of `count` individuals: None when the resident objects fit (fits_resident_zref) and
     WGSASSIGN_ZREF_WINDOW_SITES does not ask for windows, else (W, batch): windows of W sites (a multiple of 8192) and rounds of `batch`
     individuals, halved as plan_z halves them until a window of 8192 sites fits beside their state."""
-    forced = env_window_sites(environ, ENV_ZREF)
     m, n, K, count = int(m), int(n), int(K), int(count)
-    if forced is None and fits_resident_zref(m, n, K, count, free_bytes, counts):
-        return None
-    batch = count
-    while True:
-        per_site = _zref_window_bytes(n, K, batch, counts)
-        room = budget(free_bytes) - zref_state_bytes(batch, maf_iter)
-        W = room // per_site // ALIGN * ALIGN if room > 0 else 0
-        if W >= ALIGN or batch == 1:
-            break
-        batch = (batch + 1) // 2
-    if forced is not None:
-        return forced, zref_batch(forced, n, K, count, free_bytes, maf_iter, counts)
-    if W < ALIGN:
-        raise MemoryError("windowed reference z-scores need two windows of %d sites x %d individuals on the device (%d bytes with the "
-                          "depths, masks, statistics and masked fits of one) and %d bytes of state per individual; %d of the %d free bytes "
-                          "can be used" % (ALIGN, n, ALIGN * per_site, zref_state_bytes(1, maf_iter), max(0, budget(free_bytes)), free_bytes))
-    return W, batch
+    return _plan_rounds(env_window_sites(environ, ENV_ZREF), fits_resident_zref(m, n, K, count, free_bytes, counts), count,
+                        lambda batch: zref_state_bytes(batch, maf_iter), lambda batch: _zref_window_bytes(n, K, batch, counts), free_bytes,
+                        "windowed reference z-scores need two windows of %(sites)d sites x %(n)d individuals on the device (%(bytes)d bytes "
+                        "with the depths, masks, statistics and masked fits of one) and %(state)d bytes of state per individual; "
+                        "%(usable)d of the %(free)d free bytes can be used", n=n)

@@ -929,11 +929,9 @@ def assignment_z_scores_windowed(path, depth_path, A, IDs, pops, n_threshold=0, 
     total = ind_end - ind_start
     if window_sites is None:
         planned = windows.plan_z(m, n, A.shape[1], total, ctx.mem_info()[0])
-        W, batch = planned if planned is not None else (max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN, batch)
+        W, batch = planned if planned is not None else (windows.whole_file_window(m), batch)
     else:
-        if int(window_sites) < windows.ALIGN:
-            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
-        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+        W = windows.explicit_window(window_sites)
     batch = windows.z_batch(W, n, A.shape[1], total, ctx.mem_info()[0]) if not batch else min(int(batch), total)
     rounds = list(_batches(ind_start, ind_end, batch))
     if len(rounds) > 1:
@@ -1132,11 +1130,9 @@ def reference_z_scores_windowed(path, depth_path, IDs, group_of, maf_iter=200, m
     free = ctx.mem_info()[0]
     if window_sites is None:
         planned = windows.plan_zref(m, n, n_groups, total, free, maf_iter, counts=sizes)
-        W, batch = planned if planned is not None else (max(1, windows.window_count(m, windows.ALIGN)) * windows.ALIGN, batch)
+        W, batch = planned if planned is not None else (windows.whole_file_window(m), batch)
     else:
-        if int(window_sites) < windows.ALIGN:
-            raise ValueError("a window holds at least %d sites, not %d" % (windows.ALIGN, int(window_sites)))
-        W = int(window_sites) // windows.ALIGN * windows.ALIGN
+        W = windows.explicit_window(window_sites)
     batch = windows.zref_batch(W, n, n_groups, total, free, maf_iter, sizes) if not batch else min(int(batch), total)
     rounds = list(_batches(ind_start, ind_end, batch))
     if len(rounds) > 1:
