@@ -295,13 +295,8 @@ def test_one_body_behind_both_entry_points():
 
 
 def test_scored_window_checks_under_the_sanitizers(tmp_path):
-    """csrc/loo_stream_checks.h is host-only: tests/c_abi/loo_stream_scored_checks_check.cpp drives what wgs_loo_stream_push_scored
-    refuses of the scored window under AddressSanitizer + UBSan, as a program of its own."""
-    import subprocess
-    exe = str(tmp_path / "loo_stream_scored_checks_check")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                        "-I", os.path.join(ROOT, "wgsassign_amd", "csrc"), "-o", exe,
-                        os.path.join(ROOT, "tests", "c_abi", "loo_stream_scored_checks_check.cpp")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    """csrc/stream_checks.h is host-only: the `scored` part of tests/c_abi/stream_checks_check.cpp drives what
+    wgs_loo_stream_push_scored refuses of the scored window under AddressSanitizer + UBSan, as a program of its own."""
+    import sanitized
+    r = sanitized.run(tmp_path, "stream_checks_check.cpp", "scored")
     assert r.returncode == 0 and r.stdout.startswith("ok ") and int(r.stdout.split()[1]) > 100, (r.stdout[-2000:], r.stderr[-3000:])

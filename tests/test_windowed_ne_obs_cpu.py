@@ -154,17 +154,12 @@ def test_new_symbols_are_declared_bound_and_exported():
     version = int(re.search(r"#define WGS_ABI_VERSION (\d+)", header).group(1))
     assert version == 4 == _lib.ABI_VERSION == lib.wgs_version()
     assert "`WGS_ABI_VERSION` (4)" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    assert "fisher_stream_checks.h" in open(os.path.join(ROOT, "wgsassign_amd", "build.py")).read()
+    assert '"stream_checks.h"' in open(os.path.join(ROOT, "wgsassign_amd", "build.py")).read()
 
 
 def test_push_checks_under_the_sanitizers(tmp_path):
-    """csrc/fisher_stream_checks.h is host-only: tests/c_abi/fisher_stream_checks_check.cpp drives what wgs_fisher_stream_push and
-    wgs_fisher_stream_finish refuse, and the accepted sequences, under AddressSanitizer + UBSan, as a program of its own."""
-    import subprocess
-    exe = str(tmp_path / "fisher_stream_checks_check")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                        "-I", os.path.join(ROOT, "wgsassign_amd", "csrc"), "-o", exe,
-                        os.path.join(ROOT, "tests", "c_abi", "fisher_stream_checks_check.cpp")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    """csrc/stream_checks.h is host-only: the `fisher` part of tests/c_abi/stream_checks_check.cpp drives what wgs_fisher_stream_push
+    and wgs_fisher_stream_finish refuse, and the accepted sequences, under AddressSanitizer + UBSan, as a program of its own."""
+    import sanitized
+    r = sanitized.run(tmp_path, "stream_checks_check.cpp", "fisher")
     assert r.returncode == 0 and r.stdout.startswith("ok ") and int(r.stdout.split()[1]) > 100, (r.stdout[-2000:], r.stderr[-3000:])

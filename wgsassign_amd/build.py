@@ -53,7 +53,7 @@ def source_ids():
 
 def build(force=False, verbose=False):
     cc = hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "em_state.h"), os.path.join(CSRC, "em_fit_ledger.h"), os.path.join(CSRC, "em_stream_checks.h"), os.path.join(CSRC, "em_stream_masked_checks.h"), os.path.join(CSRC, "loo_stream_checks.h"), os.path.join(CSRC, "fisher_stream_checks.h"), os.path.join(CSRC, "log_table.h"), os.path.join(CSRC, "fast_math.h"), os.path.join(CSRC, "reader_text.h"), os.path.join(CSRC, "zscore.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "em_state.h"), os.path.join(CSRC, "em_fit_ledger.h"), os.path.join(CSRC, "stream_checks.h"), os.path.join(CSRC, "streams.h"), os.path.join(CSRC, "log_table.h"), os.path.join(CSRC, "fast_math.h"), os.path.join(CSRC, "reader_text.h"), os.path.join(CSRC, "zscore.h"),
                os.path.join(HERE, "..", "include", "wgsassign_hip.h")]
     id_header = os.path.join(CSRC, "build_id.h")
     text = '#define WGS_BUILD_ID "%s"\n#define WGS_KERNELS_ID "%s"\n#define WGS_INGEST_KERNELS_ID "%s"\n' % source_ids()

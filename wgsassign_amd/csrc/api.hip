@@ -13,7 +13,8 @@
 #include "build_id.h"
 #include "common.h"
 #include "em_state.h"
-#include "fisher_stream_checks.h"
+#include "stream_checks.h"
+#include "streams.h"
 
 static thread_local std::string g_err;
 
@@ -82,9 +83,10 @@ void wgs_live_destroy_children(void *parent)
         }
         if (!e.obj) return;
         if (e.kind == WGS_LIVE_EM) wgs_em_destroy(reinterpret_cast<wgs_em *>(e.obj));
+        else if (e.kind == WGS_LIVE_SCORE) wgs_score_destroy(reinterpret_cast<wgs_score *>(e.obj));
         else if (e.kind == WGS_LIVE_DEPTH) wgs_depth_destroy(reinterpret_cast<wgs_depth *>(e.obj));
         else if (e.kind == WGS_LIVE_ZKEEP) wgs_zkeep_destroy(reinterpret_cast<wgs_zkeep *>(e.obj));
-        else wgs_score_destroy(reinterpret_cast<wgs_score *>(e.obj));
+        else wgs_live_remove(e.obj);        // a kind that is nobody's child today (streams.h): forgotten, never cast to a guess
     }
 }
 
@@ -792,17 +794,13 @@ static int fisher_ind_reduce(wgs_beagle *b, wgs_afset *a, int32_t i0, int32_t co
  * individual np.mean's running float32 total (PairwisePlan above) is continued: a window starts at a multiple of 8192 sites, so its
  * full chunks are NumPy's own, each a regular tree of 64 leaves of 128 sites -- fisher_window_kernel forms those leaf sums in the same
  * sweep that gives f_obs and ne_obs, without a row matrix -- and the file's last, shorter chunk, whose leaves are irregular, takes the
- * row route of fisher_ind_reduce (at most n x 8191 floats).  The totals (n floats, by individual in file order; two buffers in
- * alternation) stay on the device between the pushes. */
-constexpr int WGS_LIVE_FISHER_STREAM = 8;   // kind in the live-object registry (5, 6, 7: the other streams): only its liveness is kept
-struct wgs_fisher_stream {
-    wgs_ctx *ctx = nullptr;
-    int device = 0;
-    int64_t n = 0, m_total = 0, pushed = 0;
+ * row route of fisher_ind_reduce (at most n x 8191 floats).  The totals (n floats, by individual in file order) stay on the device
+ * between the pushes. */
+struct wgs_fisher_stream : StreamCursor {
+    int64_t n = 0;
     int32_t K = 0;
     bool finished = false;
-    float *d_total[2] = {nullptr, nullptr};
-    int cur = 0;                            // d_total[cur]: the totals over the sites pushed so far (pushed > 0)
+    RunningPair<float> total;               // the n totals over the sites pushed so far
     int32_t *d_row_of = nullptr;            // [n] individual -> row of the leaf sums (slab after slab, column after column)
     std::vector<int32_t> row_of;            // what d_row_of holds
     hipEvent_t ev0 = nullptr, ev1 = nullptr;    // bracket the fused sweep of the last push
@@ -811,10 +809,9 @@ struct wgs_fisher_stream {
 
 void wgs_fisher_stream_destroy(wgs_fisher_stream *st)
 {
-    if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
-    (void)hipSetDevice(st->device);
-    for (void *p : {(void *)st->d_total[0], (void *)st->d_total[1], (void *)st->d_row_of})
-        if (p) (void)hipFree(p);
+    if (!stream_retire(st)) return;
+    st->total.release();
+    if (st->d_row_of) (void)hipFree(st->d_row_of);
     if (st->ev0) (void)hipEventDestroy(st->ev0);
     if (st->ev1) (void)hipEventDestroy(st->ev1);
     delete st;
@@ -827,15 +824,11 @@ int wgs_fisher_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total
                 (long long)m_total);
     WGS_REQUIRE(n < (1ll << 31), "%lld individuals are too many for one Fisher stream", (long long)n);
     HIP_TRY(hipSetDevice(ctx->device));
-    wgs_fisher_stream *st = new wgs_fisher_stream();
-    wgs_live_add(st, WGS_LIVE_FISHER_STREAM, nullptr);
+    wgs_fisher_stream *st = stream_new<wgs_fisher_stream>(ctx, m_total, WGS_LIVE_FISHER_STREAM);
     auto guard = on_failure([&] { wgs_fisher_stream_destroy(st); });
-    st->ctx = ctx;
-    st->device = ctx->device;
     st->n = n;
     st->K = K;
-    st->m_total = m_total;
-    for (float *&p : st->d_total) HIP_TRY(wgs_malloc(&p, sizeof(float) * (size_t)n));
+    HIP_TRY(st->total.allocate((size_t)n));
     HIP_TRY(wgs_malloc(&st->d_row_of, sizeof(int32_t) * (size_t)n));
     HIP_TRY(hipEventCreate(&st->ev0));
     HIP_TRY(hipEventCreate(&st->ev1));
@@ -847,20 +840,16 @@ int wgs_fisher_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total
 /* One window: f_obs_rows / ne_obs_rows (host, rows x K float32, site-major) receive the window's rows of .fisher_obs.npy / .ne_obs.npy;
  * the per-individual totals go on from where the window before left them.  The window rules of wgs_score_stream_push hold, the window
  * has the stream's n and K and one slab per population, none of them empty: anything else is rc 2 and a message, nothing launched
- * (fisher_stream_checks.h).  Returns when the device is done with the window. */
+ * (stream_checks.h).  Returns when the device is done with the window. */
 int wgs_fisher_stream_push(wgs_fisher_stream *st, wgs_beagle *window, wgs_afset *window_af, float *f_obs_rows, float *ne_obs_rows)
 {
     WGS_REQUIRE(st && window && window_af && f_obs_rows && ne_obs_rows, "null argument");
     WGS_REQUIRE(window->ctx == st->ctx && window_af->ctx == st->ctx, "the window belongs to another context than the Fisher stream");
-    char why[256];
     std::vector<int32_t> slab_cols(window->n_groups);
     for (int g = 0; g < window->n_groups; ++g) slab_cols[g] = window->slabs[g].ncols;
-    if (fisher_stream_shape_refusal(window->n, window->n_groups, slab_cols.data(), window_af->K, window_af->m, window->m, st->n, st->K, why,
-                                    sizeof why) ||
-        fisher_stream_window_refusal(window->site0, window->m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, st->finished, why, sizeof why)) {
-        wgs_set_error("%s", why);
-        return 2;
-    }
+    STREAM_TRY(fisher_stream_shape_refusal(window->n, window->n_groups, slab_cols.data(), window_af->K, window_af->m, window->m, st->n, st->K, why,
+                                           sizeof why) ||
+               fisher_stream_window_refusal(window->site0, window->m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, st->finished, why, sizeof why));
     wgs_ctx *ctx = st->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     const int K = st->K;
@@ -937,12 +926,11 @@ int wgs_fisher_stream_push(wgs_fisher_stream *st, wgs_beagle *window, wgs_afset 
     HIP_TRY(hipEventRecord(st->ev0, ctx->stream));
     if (launch_fisher_window(ctx, d_descs, K, m, full)) return 1;
     HIP_TRY(hipEventRecord(st->ev1, ctx->stream));
-    int cur = st->cur;
+    RunningPair<float> run = st->total;                      // (flipped up to twice; the stream takes it over when the push has succeeded)
     if (full) {
-        if (launch_fisher_stream_combine(ctx, d_sums, (int)nleaf, st->d_row_of, d_prog, (int)nprog, (int)n, st->pushed ? st->d_total[cur] : nullptr,
-                                         st->d_total[cur ^ 1]))
+        if (launch_fisher_stream_combine(ctx, d_sums, (int)nleaf, st->d_row_of, d_prog, (int)nprog, (int)n, run.before(st->pushed > 0), run.next()))
             return 1;
-        cur ^= 1;
+        run.flip();
     }
     if (tail) {
         constexpr int64_t ROWS_PER_LAUNCH = 32768;           // (the individual is the grid's y)
@@ -957,10 +945,10 @@ int wgs_fisher_stream_push(wgs_fisher_stream *st, wgs_beagle *window, wgs_afset 
             if (launch_pairwise_leaves(ctx, d_rows + (size_t)r0 * tail, (int)std::min<int64_t>(ROWS_PER_LAUNCH, n - r0), tail, d_lo, d_len, (int)nleaf_t,
                                        d_tsums + (size_t)r0 * nleaf_t))
                 return 1;
-        if (launch_fisher_stream_combine(ctx, d_tsums, (int)nleaf_t, st->d_row_of, d_tprog, (int)nprog_t, (int)n,
-                                         st->pushed + full > 0 ? st->d_total[cur] : nullptr, st->d_total[cur ^ 1]))
+        if (launch_fisher_stream_combine(ctx, d_tsums, (int)nleaf_t, st->d_row_of, d_tprog, (int)nprog_t, (int)n, run.before(st->pushed + full > 0),
+                                         run.next()))
             return 1;
-        cur ^= 1;
+        run.flip();
     }
     if (launch_transpose_Km_to_mK(ctx, d_f, d_t, m, K)) return 1;
     HIP_TRY(hipMemcpyAsync(f_obs_rows, d_t, mk * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -969,7 +957,7 @@ int wgs_fisher_stream_push(wgs_fisher_stream *st, wgs_beagle *window, wgs_afset 
     HIP_TRY(hipMemcpyAsync(ne_obs_rows, d_t, mk * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (hipEventElapsedTime(&st->last_ms, st->ev0, st->ev1) != hipSuccess) st->last_ms = 0.0f;
-    st->cur = cur;
+    st->total = run;
     st->pushed += m;
     return 0;
 }
@@ -987,15 +975,11 @@ int wgs_fisher_stream_sweep_ms(wgs_fisher_stream *st, float *ms)
 int wgs_fisher_stream_finish(wgs_fisher_stream *st, float *ne_ind_out)
 {
     WGS_REQUIRE(st && ne_ind_out, "null argument");
-    char why[256];
-    if (fisher_stream_finish_refusal(st->pushed, st->m_total, st->finished, why, sizeof why)) {
-        wgs_set_error("%s", why);
-        return 2;
-    }
+    STREAM_TRY(fisher_stream_finish_refusal(st->pushed, st->m_total, st->finished, why, sizeof why));
     wgs_ctx *ctx = st->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    float *d_means = st->d_total[st->cur ^ 1];
-    if (launch_fisher_stream_means(ctx, st->d_total[st->cur], (int)st->n, st->m_total, d_means)) return 1;
+    float *d_means = st->total.next();
+    if (launch_fisher_stream_means(ctx, st->total.current(), (int)st->n, st->m_total, d_means)) return 1;
     HIP_TRY(hipMemcpyAsync(ne_ind_out, d_means, sizeof(float) * (size_t)st->n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     st->finished = true;

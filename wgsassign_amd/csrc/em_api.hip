@@ -11,8 +11,8 @@
 
 #include "common.h"
 #include "em_state.h"
-#include "em_stream_checks.h"
-#include "em_stream_masked_checks.h"
+#include "stream_checks.h"
+#include "streams.h"
 #include "zscore.h"
 
 // Enqueues `units` fits or fit groups as launch(first, count) over slices of at most `per_launch` of them.
@@ -758,13 +758,9 @@ const float *wgs_em_f_dev(wgs_em *em, int32_t fit)
  * and fits whose stopping iteration is known stop there, are clamped and handed out.  S and C stay on the device from push to push;
  * the host reads them once per round (wgs_em_stream_read) and decides with the rule of wgs_em_fit (em_band / em_classify /
  * em_chain_converged; wgsassign_amd/windowed_fit.py keeps the rounds).  Nothing is read back while a window is fitted. */
-constexpr int WGS_LIVE_EM_STREAM = 6;   // kind in the live-object registry (score_api.hip: 5): no parent, only its liveness is kept
 constexpr int EM_STREAM_SLOTS = 256;    // sweeps a push enqueues before it waits for the device once (their descriptors stay pinned until then)
-struct wgs_em_stream {
-    wgs_ctx *ctx = nullptr;
-    int device = 0;
+struct wgs_em_stream : StreamCursor {   // (pushed: in this round)
     int32_t n_fits = 0, max_iter = 0;
-    int64_t m_total = 0, pushed = 0;
     int32_t rounds = 0;                 // rounds read so far
     double *d_S = nullptr;              // [max_iter][n_fits] sums of squared differences over the sites pushed in the accumulating round(s)
     float *d_C = nullptr;               // [max_iter][n_fits] float32 carries of the chains of this round
@@ -789,8 +785,7 @@ struct wgs_em_stream {
 
 void wgs_em_stream_destroy(wgs_em_stream *st)
 {
-    if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
-    (void)hipSetDevice(st->device);
+    if (!stream_retire(st)) return;
     for (void *p : {(void *)st->d_S, (void *)st->d_C, (void *)st->d_win, (void *)st->d_descs, (void *)st->d_groups, (void *)st->d_jobs,
                     (void *)st->d_cell, (void *)st->d_chain_out, st->d_chain_work, (void *)st->d_from, (void *)st->d_ca, (void *)st->d_cb, (void *)st->d_cjobs})
         if (p) (void)hipFree(p);
@@ -806,14 +801,10 @@ int wgs_em_stream_create(wgs_ctx *ctx, int32_t n_fits, int32_t max_iter, int64_t
                 max_iter, (long long)m_total);
     WGS_REQUIRE((int64_t)n_fits * std::max(1, max_iter) < (1ll << 30), "%d fits x %d iterations are too many for one fit stream", n_fits, max_iter);
     HIP_TRY(hipSetDevice(ctx->device));
-    wgs_em_stream *st = new wgs_em_stream();
-    wgs_live_add(st, WGS_LIVE_EM_STREAM, nullptr);
+    wgs_em_stream *st = stream_new<wgs_em_stream>(ctx, m_total, WGS_LIVE_EM_STREAM);
     auto guard = on_failure([&] { wgs_em_stream_destroy(st); });
-    st->ctx = ctx;
-    st->device = ctx->device;
     st->n_fits = n_fits;
     st->max_iter = max_iter;
-    st->m_total = m_total;
     const size_t n = (size_t)n_fits, cells = n * (size_t)std::max(1, max_iter);
     st->slots = std::max(1, std::min(max_iter, EM_STREAM_SLOTS));
     HIP_TRY(wgs_malloc(&st->d_S, sizeof(double) * cells));
@@ -924,15 +915,11 @@ static int em_stream_push_window(wgs_em_stream *st, wgs_em *em, const int32_t *r
     const int64_t m = window->m;
     int32_t T = 0;
     bool any_final = false;
-    char why[256];
-    if (em_stream_window_refusal(window->site0, m, em->cap_m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why) ||
-        em_stream_plan_refusal(n, st->max_iter, run_iters, final, clamp_lo && clamp_hi, keep || f_out != nullptr, keep ? m : f_stride, m, chain_fit,
-                               chain_iter, n_chain, &T, &any_final, why, sizeof why) ||
-        (sums_from && em_stream_sums_from_refusal(n, run_iters, sums_from, why, sizeof why)) ||
-        (zk && em_stream_masked_refusal(window, zk->b, n, zk->count, fit_slot, why, sizeof why))) {
-        wgs_set_error("%s", why);
-        return 2;
-    }
+    STREAM_TRY(em_stream_window_refusal(window->site0, m, em->cap_m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why) ||
+               em_stream_plan_refusal(n, st->max_iter, run_iters, final, clamp_lo && clamp_hi, keep || f_out != nullptr, keep ? m : f_stride, m,
+                                      chain_fit, chain_iter, n_chain, &T, &any_final, why, sizeof why) ||
+               (sums_from && em_stream_sums_from_refusal(n, run_iters, sums_from, why, sizeof why)) ||
+               (zk && em_stream_masked_refusal(window, zk->b, n, zk->count, fit_slot, why, sizeof why)));
     const EmSwitches sw;
     wgs_ctx *ctx = st->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1051,7 +1038,7 @@ int wgs_em_stream_push_masked(wgs_em_stream *st, wgs_em *em, wgs_zkeep *zk, cons
 int wgs_em_stream_read(wgs_em_stream *st, double *S_host, float *C_host)
 {
     WGS_REQUIRE(st, "null argument");
-    WGS_REQUIRE(st->pushed == st->m_total, "only %lld of the %lld sites were pushed", (long long)st->pushed, (long long)st->m_total);
+    STREAM_TRY(stream_all_pushed_refusal(st->pushed, st->m_total, why, sizeof why));
     HIP_TRY(hipSetDevice(st->ctx->device));
     const size_t cells = (size_t)st->n_fits * st->max_iter;
     if (S_host && cells) HIP_TRY(hipMemcpyAsync(S_host, st->d_S, sizeof(double) * cells, hipMemcpyDeviceToHost, st->ctx->stream));

@@ -9,7 +9,8 @@
 
 #include "common.h"
 #include "em_state.h"
-#include "loo_stream_checks.h"
+#include "stream_checks.h"
+#include "streams.h"
 
 struct wgs_score {
     wgs_beagle *b = nullptr;
@@ -496,24 +497,18 @@ int wgs_score_totals_all(wgs_score *sc, wgs_comm *comm, double *totals_out, doub
 
 /* ---- windowed scoring: one GPU walks the sites of a file window by window.  What the relay above does
  * across ranks -- np.sum's running float64 total continued from one site range to the next over the range's 8192-site chunk sums --
- * happens here in time: the total stays in device memory between the pushes (two buffers in alternation: the kernel reads one and
- * writes the other) and crosses to the host once, in wgs_score_stream_finish. */
-constexpr int WGS_LIVE_STREAM = 5;      // kind in the live-object registry (common.h: 1, 2; zscore.h: 3, 4): a stream has no parent, only its liveness is kept
-struct wgs_score_stream {
-    wgs_ctx *ctx = nullptr;
-    int device = 0;
-    int64_t n = 0, m_total = 0, pushed = 0, cells = 0;
+ * happens here in time: the total stays in device memory between the pushes (streams.h: RunningPair) and crosses to the host once,
+ * in wgs_score_stream_finish. */
+struct wgs_score_stream : StreamCursor {
+    int64_t n = 0, cells = 0;
     int32_t K = 0;
-    double *d_run[2] = {nullptr, nullptr};
-    int cur = 0;                      // d_run[cur]: the totals over the sites pushed so far (pushed > 0)
+    RunningPair<double> run;          // the n x K totals over the sites pushed so far
 };
 
 void wgs_score_stream_destroy(wgs_score_stream *st)
 {
-    if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
-    (void)hipSetDevice(st->device);
-    for (double *p : st->d_run)
-        if (p) (void)hipFree(p);                      // (plain allocations, not the context's pool: the handle may outlive its context)
+    if (!stream_retire(st)) return;
+    st->run.release();
     delete st;
 }
 
@@ -523,55 +518,40 @@ int wgs_score_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total,
     WGS_REQUIRE(n > 0 && K > 0 && m_total > 0, "a score stream needs individuals, populations and sites (%lld x %d over %lld sites)",
                 (long long)n, K, (long long)m_total);
     HIP_TRY(hipSetDevice(ctx->device));
-    wgs_score_stream *st = new wgs_score_stream();
-    wgs_live_add(st, WGS_LIVE_STREAM, nullptr);
+    wgs_score_stream *st = stream_new<wgs_score_stream>(ctx, m_total, WGS_LIVE_SCORE_STREAM);
     auto guard = on_failure([&] { wgs_score_stream_destroy(st); });
-    st->ctx = ctx;
-    st->device = ctx->device;
     st->n = n;
     st->K = K;
-    st->m_total = m_total;
     st->cells = n * (int64_t)K;
-    for (double *&p : st->d_run) HIP_TRY(wgs_malloc(&p, sizeof(double) * (size_t)st->cells));
+    HIP_TRY(st->run.allocate((size_t)st->cells));
     guard.dismiss();
     *out = st;
     return 0;
 }
 
-/* One window: its first site must be the number of sites pushed so far and a multiple of WGS_WINDOW_ALIGN (8192, the sites of one
- * addend of NumPy's running total: a window that began elsewhere would regroup them), and every window but the last must hold a
- * multiple of 8192 sites.  Anything else is refused before a kernel is launched.  The window is swept by the path wgs_score_sums
- * takes; its chunk sums are folded onto the running total by the code behind wgs_score_total_from.  Returns when the device is done with the
- * window -- its matrix and frequencies may be refilled -- but reads nothing back.  wgs_assign_last_ms: this window's sweep. */
+/* One window, under the window rule (stream_checks.h): a window that breaks it, or has another n or K, is refused before a kernel is
+ * launched.  The window is swept by the path wgs_score_sums takes; its chunk sums are folded onto the running total by the code behind
+ * wgs_score_total_from.  Returns when the device is done with the window -- its matrix and frequencies may be refilled -- but reads
+ * nothing back.  wgs_assign_last_ms: this window's sweep. */
 int wgs_score_stream_push(wgs_score_stream *st, wgs_beagle *window, wgs_afset *window_af, int mode)
 {
     WGS_REQUIRE(st && window && window_af, "null argument");
     WGS_REQUIRE(mode == WGS_MODE_EXACT || mode == WGS_MODE_FAST, "unknown mode %d", mode);
     WGS_REQUIRE(window->ctx == st->ctx && window_af->ctx == st->ctx, "the window belongs to another context than the score stream");
-    WGS_REQUIRE(window->n == st->n && window_af->K == st->K, "the window is %lld individuals x %d populations, the score stream %lld x %d",
-                (long long)window->n, window_af->K, (long long)st->n, st->K);
-    WGS_REQUIRE(window->m > 0, "an empty window");
-    WGS_REQUIRE(window_af->m == window->m, "allele frequencies cover %lld SNPs, the window %lld", (long long)window_af->m, (long long)window->m);
-    WGS_REQUIRE(window->site0 % WGS_WINDOW_ALIGN == 0, "the window starts at site %lld, which is not a multiple of %d", (long long)window->site0,
-                WGS_WINDOW_ALIGN);
-    WGS_REQUIRE(window->site0 == st->pushed, "the window starts at site %lld, but %lld sites were pushed so far", (long long)window->site0,
-                (long long)st->pushed);
-    WGS_REQUIRE(st->pushed + window->m <= st->m_total, "the window's %lld sites after %lld pushed exceed the %lld sites of the score stream",
-                (long long)window->m, (long long)st->pushed, (long long)st->m_total);
-    WGS_REQUIRE(st->pushed + window->m == st->m_total || window->m % WGS_WINDOW_ALIGN == 0,
-                "a window of %lld sites that is not the last one (not a multiple of %d)", (long long)window->m, WGS_WINDOW_ALIGN);
+    STREAM_TRY(score_stream_shape_refusal(window->n, window_af->K, window_af->m, window->m, st->n, st->K, why, sizeof why) ||
+               stream_window_refusal("score stream", window->site0, window->m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why));
     wgs_ctx *ctx = st->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     wgs_score *sc = nullptr;
     auto guard = on_failure([&] { wgs_score_destroy(sc); });
     if (int rc = wgs_score_create(window, window_af, nullptr, 0, (int32_t)window->n, &sc)) return rc;
     if (score_sums_enqueue(sc, mode)) return 1;
-    if (score_total_enqueue(sc, st->pushed ? st->d_run[st->cur] : nullptr, st->d_run[st->cur ^ 1])) return 1;
+    if (score_total_enqueue(sc, st->run.before(st->pushed > 0), st->run.next())) return 1;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     guard.dismiss();
     wgs_score_destroy(sc);
     ctx->assign_ms_pending = true;
-    st->cur ^= 1;
+    st->run.flip();
     st->pushed += window->m;
     return 0;
 }
@@ -579,9 +559,9 @@ int wgs_score_stream_push(wgs_score_stream *st, wgs_beagle *window, wgs_afset *w
 int wgs_score_stream_finish(wgs_score_stream *st, double *out_nK)
 {
     WGS_REQUIRE(st && out_nK, "null argument");
-    WGS_REQUIRE(st->pushed == st->m_total, "only %lld of the %lld sites were pushed", (long long)st->pushed, (long long)st->m_total);
+    STREAM_TRY(stream_all_pushed_refusal(st->pushed, st->m_total, why, sizeof why));
     HIP_TRY(hipSetDevice(st->ctx->device));
-    HIP_TRY(hipMemcpyAsync(out_nK, st->d_run[st->cur], sizeof(double) * (size_t)st->cells, hipMemcpyDeviceToHost, st->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out_nK, st->run.current(), sizeof(double) * (size_t)st->cells, hipMemcpyDeviceToHost, st->ctx->stream));
     HIP_TRY(hipStreamSynchronize(st->ctx->stream));
     return 0;
 }
@@ -1029,28 +1009,23 @@ static int parts_exact_literal(wgs_beagle *b, wgs_afset *a, const float *const *
 /* ---- the leave-one-out run in site windows ("leave-one-out in windows").  What wgs_loo does on one resident
  * matrix after its re-fits -- the column table of glassy.py:87-105, the per-individual sweep, np.sum's float64 totals, the serial float32
  * partition sums -- happens here window by window, on the window's batch of n re-fits that the last round of a windowed fit left
- * clamped on the device (wgs_em_stream_push_keep).  Between the pushes the stream keeps the n x K running totals (two buffers in
- * alternation, as wgs_score_stream) and the n x P x K float32 partition carries on the device; a window continues both exactly as the
+ * clamped on the device (wgs_em_stream_push_keep).  Between the pushes the stream keeps the n x K running totals (as wgs_score_stream
+ * does) and the n x P x K float32 partition carries on the device; a window continues both exactly as the
  * SNP shard of a rank > 0 continues them in wgs_loo: the totals over its 8192-site chunk sums, the chains from the carries with the
  * totals before the window as `start`.  wgs_loo_stream_finish is the one read-back. */
-constexpr int WGS_LIVE_LOO_STREAM = 7;  // kind in the live-object registry (5: score stream, 6: fit stream): only its liveness is kept
-struct wgs_loo_stream {
-    wgs_ctx *ctx = nullptr;
-    int device = 0;
-    int64_t n = 0, m_total = 0, pushed = 0, cells = 0;
+struct wgs_loo_stream : StreamCursor {
+    int64_t n = 0, cells = 0;
     int32_t K = 0, P = 0;               // P == 0: no partition sums
-    double *d_run[2] = {nullptr, nullptr};
-    int cur = 0;                        // d_run[cur]: the totals over the sites pushed so far (pushed > 0)
+    RunningPair<double> run;            // the n x K totals over the sites pushed so far
     float *d_carry = nullptr;           // [n * P * K] the partition sums over the sites pushed so far
     std::vector<float> h_carry, h_parts;    // the literal chains (P too large for the block-parallel ones) take and give host arrays
 };
 
 void wgs_loo_stream_destroy(wgs_loo_stream *st)
 {
-    if (!st || !wgs_live_remove(st)) return;          // (destroyed already)
-    (void)hipSetDevice(st->device);
-    for (void *p : {(void *)st->d_run[0], (void *)st->d_run[1], (void *)st->d_carry})
-        if (p) (void)hipFree(p);
+    if (!stream_retire(st)) return;
+    st->run.release();
+    if (st->d_carry) (void)hipFree(st->d_carry);
     delete st;
 }
 
@@ -1063,17 +1038,13 @@ int wgs_loo_stream_create(wgs_ctx *ctx, int64_t n, int32_t K, int64_t m_total, i
     WGS_REQUIRE(n * (int64_t)K * std::max(1, P) < (1ll << 31), "%lld individuals x %d populations x %d partitions are too many for one stream",
                 (long long)n, K, P);
     HIP_TRY(hipSetDevice(ctx->device));
-    wgs_loo_stream *st = new wgs_loo_stream();
-    wgs_live_add(st, WGS_LIVE_LOO_STREAM, nullptr);
+    wgs_loo_stream *st = stream_new<wgs_loo_stream>(ctx, m_total, WGS_LIVE_LOO_STREAM);
     auto guard = on_failure([&] { wgs_loo_stream_destroy(st); });
-    st->ctx = ctx;
-    st->device = ctx->device;
     st->n = n;
     st->K = K;
     st->P = P;
-    st->m_total = m_total;
     st->cells = n * (int64_t)K;
-    for (double *&p : st->d_run) HIP_TRY(wgs_malloc(&p, sizeof(double) * (size_t)st->cells));
+    HIP_TRY(st->run.allocate((size_t)st->cells));
     if (P > 0) HIP_TRY(wgs_malloc(&st->d_carry, sizeof(float) * (size_t)st->cells * P));
     guard.dismiss();
     *out = st;
@@ -1104,17 +1075,14 @@ int wgs_loo_stream_push_scored(wgs_loo_stream *st, wgs_em *window_em, wgs_beagle
     wgs_beagle *window = window_em->b;
     WGS_REQUIRE(window->ctx == st->ctx && window_af->ctx == st->ctx, "the window belongs to another context than the leave-one-out stream");
     WGS_REQUIRE(scored_window->ctx == st->ctx, "the scored window belongs to another context than the leave-one-out stream");
-    char why[256];
-    if (loo_stream_shape_refusal(window->n, window->n_groups, window_em->n_fits, window_af->K, window_af->m, window->m, st->n, st->K, why,
-                                 sizeof why) ||
-        loo_stream_fits_refusal(st->n, window_em->group.data(), window_em->skip_local.data(), window->group_of.data(), why, sizeof why) ||
-        loo_stream_window_refusal(window->site0, window->m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why) ||
-        (scored_window != window &&
-         loo_stream_scored_refusal(scored_window->n, scored_window->m, scored_window->site0, scored_window->n_groups, scored_window->group_of.data(),
-                                   window->n, window->m, window->site0, window->n_groups, window->group_of.data(), why, sizeof why))) {
-        wgs_set_error("%s", why);
-        return 2;
-    }
+    STREAM_TRY(loo_stream_shape_refusal(window->n, window->n_groups, window_em->n_fits, window_af->K, window_af->m, window->m, st->n, st->K, why,
+                                        sizeof why) ||
+               loo_stream_fits_refusal(st->n, window_em->group.data(), window_em->skip_local.data(), window->group_of.data(), why, sizeof why) ||
+               stream_window_refusal("leave-one-out stream", window->site0, window->m, st->pushed, st->m_total, WGS_WINDOW_ALIGN, why, sizeof why) ||
+               (scored_window != window &&
+                loo_stream_scored_refusal(scored_window->n, scored_window->m, scored_window->site0, scored_window->n_groups,
+                                          scored_window->group_of.data(), window->n, window->m, window->site0, window->n_groups,
+                                          window->group_of.data(), why, sizeof why)));
     wgs_ctx *ctx = st->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     const int64_t n = st->n;
@@ -1132,8 +1100,8 @@ int wgs_loo_stream_push_scored(wgs_loo_stream *st, wgs_em *window_em, wgs_beagle
     if (int rc = wgs_score_create(scored_window, window_af, colptr.data(), 0, (int32_t)n, &sc)) return rc;
     if (score_sums_enqueue(sc, P > 0 ? WGS_MODE_EXACT : mode)) return 1;
     sc->have_prefix = P > 0;
-    const double *before = st->pushed ? st->d_run[st->cur] : nullptr;      // the totals over the windows before this one
-    if (score_total_enqueue(sc, before, st->d_run[st->cur ^ 1])) return 1;
+    const double *before = st->run.before(st->pushed > 0);                  // the totals over the windows before this one
+    if (score_total_enqueue(sc, before, st->run.next())) return 1;
     const size_t chains = cells * (size_t)std::max(1, P);
     if (P > 0 && P <= WGS_MAX_BLOCK_PARALLEL_PARTS && chains_block_parallel(sc->plan, sc->cells, P)) {
         if (chains_prepare_enqueue(sc, P, before, true)) return 1;
@@ -1155,7 +1123,7 @@ int wgs_loo_stream_push_scored(wgs_loo_stream *st, wgs_em *window_em, wgs_beagle
     guard.dismiss();
     wgs_score_destroy(sc);
     ctx->assign_ms_pending = true;
-    st->cur ^= 1;
+    st->run.flip();
     st->pushed += window->m;
     return 0;
 }
@@ -1165,10 +1133,10 @@ int wgs_loo_stream_push_scored(wgs_loo_stream *st, wgs_em *window_em, wgs_beagle
 int wgs_loo_stream_finish(wgs_loo_stream *st, double *ll_out, float *parts_out)
 {
     WGS_REQUIRE(st && ll_out, "null argument");
-    WGS_REQUIRE(st->pushed == st->m_total, "only %lld of the %lld sites were pushed", (long long)st->pushed, (long long)st->m_total);
+    STREAM_TRY(stream_all_pushed_refusal(st->pushed, st->m_total, why, sizeof why));
     WGS_REQUIRE(!parts_out || st->P > 0, "the leave-one-out stream keeps no partition sums");
     HIP_TRY(hipSetDevice(st->ctx->device));
-    HIP_TRY(hipMemcpyAsync(ll_out, st->d_run[st->cur], sizeof(double) * (size_t)st->cells, hipMemcpyDeviceToHost, st->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ll_out, st->run.current(), sizeof(double) * (size_t)st->cells, hipMemcpyDeviceToHost, st->ctx->stream));
     if (parts_out)
         HIP_TRY(hipMemcpyAsync(parts_out, st->d_carry, sizeof(float) * (size_t)st->cells * st->P, hipMemcpyDeviceToHost, st->ctx->stream));
     HIP_TRY(hipStreamSynchronize(st->ctx->stream));

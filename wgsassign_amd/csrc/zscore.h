@@ -1,6 +1,7 @@
 // Internal declarations of the z-score path (zscore_kernels.hip, zscore_api.hip).
 #pragma once
 #include "common.h"
+#include "streams.h"       // the kinds of the live-object registry: WGS_LIVE_DEPTH, WGS_LIVE_ZKEEP, WGS_LIVE_ZSUM
 
 constexpr int WGS_Z_MAXD = 21;                                        // largest depth Ar + Aa with a class of its own
 constexpr int WGS_Z_NKEYS = (WGS_Z_MAXD + 1) * (WGS_Z_MAXD + 2) / 2;  // 253 classes: one per thread of a 256-thread workgroup
@@ -9,9 +10,6 @@ constexpr int WGS_Z_NKEYS = (WGS_Z_MAXD + 1) * (WGS_Z_MAXD + 2) / 2;  // 253 cla
 // kept-site set may carry a deep table in global memory: per individual a map depth -> first row (-1: depth not kept), and per kept
 // depth d the rows a = 0 .. d of {component, mean of class (d - a, a) | AD_like[0..2], AD_factorial[0..2] at AD_index[a, d - a]}.
 constexpr int WGS_Z_DEEP_MAP = 511, WGS_Z_DEEP_ROW = 8;
-
-// kinds of the live-object registry (common.h: WGS_LIVE_EM = 1, WGS_LIVE_SCORE = 2): the depth table and the kept-site sets
-constexpr int WGS_LIVE_DEPTH = 3, WGS_LIVE_ZKEEP = 4;
 
 struct ZInd {                  // one individual as the sweeps see it
     const float4 *slab;
@@ -50,7 +48,6 @@ struct wgs_zkeep {
 // np.sum's float32 order continued from site window to site window (zscore_kernels.hip: zsum_*): per (individual, array) the running
 // float32 over the closed 8192-element chunks and the elements of the open one.  Also the class sweep's running sums of a windowed pass.
 constexpr int WGS_ZSUM_CHUNK = 8192, WGS_ZSUM_ARRAYS = 3;
-constexpr int WGS_LIVE_ZSUM = 6;          // (score_api.hip: 5) no parent, only its liveness is kept
 struct ZSumJob {
     const float *x;            // the window's compacted array of this (individual, array): k elements
     float *tail, *run;         // the open chunk (WGS_ZSUM_CHUNK floats) and the running value

@@ -22,15 +22,53 @@ _live = weakref.WeakSet()       # device objects that still own library handles
 
 @atexit.register
 def _close_all():
-    """Release every device object before the interpreter tears modules down: children (scores, EM batches)
-    before the matrices they refer to, so no destructor runs against a freed parent or an unloaded library."""
-    order = {"Score": 0, "ScoreStream": 0, "EMStream": 0, "LooStream": 0, "EMBatch": 1, "AFSet": 2, "DeviceBeagle": 3}
-    for obj in sorted(list(_live), key=lambda o: order.get(type(o).__name__, 9)):
+    """Release every device object before the interpreter tears modules down, so no destructor runs against an unloaded library.
+    In whatever order: an object's close() closes what was made from it first."""
+    for obj in list(_live):
         try:
             obj.close()
         except Exception:
             pass
 
+
+class Handle:
+    """An object that owns one handle of the library.  A subclass names the symbol that destroys the handle; objects made from this
+    one register with it (_own) and are closed before it, whatever order a collector picks."""
+
+    _destroy = None         # the library's destroy symbol
+    _at_exit = True         # kept in _live: closed at the interpreter's exit if still open
+    _h = None
+    _children = ()
+
+    def _own(self, h, *parents, children=False):
+        """Takes the handle `h` over, as a child of `parents`; children: objects will be made from this one."""
+        self._h = h
+        if children:
+            self._children = weakref.WeakSet()
+        for p in parents:
+            p._children.add(self)
+        if self._at_exit:
+            _live.add(self)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _release(self, h):
+        getattr(_lib.load(), self._destroy)(h)
+
+    def close(self):
+        if self._h:
+            for child in list(self._children):
+                child.close()
+            self._release(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _mode_from(var):
@@ -79,8 +117,11 @@ def default_device_index():
     return local_rank
 
 
-class Context:
-    """One HIP device + stream (wgs_ctx)."""
+class Context(Handle):
+    """One HIP device + stream (wgs_ctx).  Only close() destroys it: the library's objects keep a pointer to their context, so it is
+    never destroyed behind them by a collector or at the interpreter's exit."""
+
+    _destroy, _at_exit = "wgs_ctx_destroy", False
 
     def __init__(self, device=None):
         lib = _lib.load()
@@ -88,13 +129,11 @@ class Context:
             device = default_device_index()
         h = ctypes.c_void_p()
         check(lib.wgs_ctx_create(int(device), ctypes.byref(h)))
-        self._h = h
+        self._own(h, children=True)             # the streams of this context: closed before it
         self.device = int(device)
-        self._children = weakref.WeakSet()      # score streams of this context: closed before it
 
-    @property
-    def handle(self):
-        return self._h
+    def __del__(self):
+        pass
 
     def sync(self):
         check(_lib.load().wgs_ctx_sync(self._h))
@@ -116,13 +155,6 @@ class Context:
         check(_lib.load().wgs_ctx_info(self._h, name, 256, ctypes.byref(cus), ctypes.byref(mem)))
         return {"name": name.value.decode(), "cus": cus.value, "mem_bytes": mem.value}
 
-    def close(self):
-        if self._h:
-            for child in list(self._children):
-                child.close()
-            _lib.load().wgs_ctx_destroy(self._h)
-            self._h = None
-
 
 def get_context():
     global _default_ctx
@@ -131,13 +163,15 @@ def get_context():
     return _default_ctx
 
 
-class DeviceBeagle:
+class DeviceBeagle(Handle):
     """Genotype-likelihood matrix (one SNP shard) as population slabs in HBM (wgs_beagle).
 
     group_of: int array (n,) with the group (population column) of every individual, or None for
     a single group.  Groups keep individuals in file order, as the reference's sorted column
     gather does (WGSassign.py:227-233).
     """
+
+    _destroy = "wgs_beagle_destroy"
 
     def __init__(self, m, n, group_of=None, n_groups=1, site0=0, ctx=None):
         self.ctx = ctx or get_context()
@@ -154,9 +188,7 @@ class DeviceBeagle:
         self.n_groups = n_groups
         h = ctypes.c_void_p()
         check(_lib.load().wgs_beagle_create(self.ctx.handle, self.m, self.n, gp, n_groups, self.site0, ctypes.byref(h)))
-        self._h = h
-        self._children = weakref.WeakSet()      # EM batches and scores over this matrix: closed before it, whatever order a collector picks
-        _live.add(self)
+        self._own(h, children=True)             # EM batches, scores and depth tables over this matrix: closed before it
 
     @classmethod
     def from_host(cls, L, group_of=None, n_groups=1, site0=0, ctx=None):
@@ -166,10 +198,6 @@ class DeviceBeagle:
         b = cls(L.shape[0], L.shape[1] // 2, group_of, n_groups, site0, ctx)
         b.upload_rows(L, 0)
         return b
-
-    @property
-    def handle(self):
-        return self._h
 
     def upload_rows(self, rows, row0=0):
         rows = _as_f32c(rows, "rows")
@@ -278,31 +306,18 @@ class DeviceBeagle:
         return {"hash_slots": slots, "dict_rows": drows, "em_table_rows": lrows, "score_batch_snps": batch, "slab_numbering": bool(local),
                 "tile_rows_bytes": trb, "batch_rows_cap": cap, "ncls": ncls, "dict": dic, "slabs": slabs}
 
-    def close(self):
-        if self._h:
-            for child in list(self._children):
-                child.close()
-            _lib.load().wgs_beagle_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class AFSet:
+class AFSet(Handle):
     """K allele-frequency vectors of m SNPs on the device (the (m, K) `.pop_af.npy` matrix)."""
+
+    _destroy = "wgs_afset_destroy"
 
     def __init__(self, m, K, ctx=None):
         self.ctx = ctx or get_context()
         self.m, self.K = int(m), int(K)
         h = ctypes.c_void_p()
         check(_lib.load().wgs_afset_create(self.ctx.handle, self.m, self.K, ctypes.byref(h)))
-        self._h = h
-        self._children = weakref.WeakSet()      # scores over these columns
-        _live.add(self)
+        self._own(h, children=True)             # scores over these columns
 
     @classmethod
     def from_host(cls, A, ctx=None):
@@ -310,10 +325,6 @@ class AFSet:
         a = cls(A.shape[0], A.shape[1], ctx)
         check(_lib.load().wgs_afset_upload(a._h, f32p(A)))
         return a
-
-    @property
-    def handle(self):
-        return self._h
 
     def to_host(self):
         out = np.empty((self.m, self.K), dtype=np.float32)
@@ -326,27 +337,15 @@ class AFSet:
     def col_dev(self, col):
         return _lib.load().wgs_afset_col_dev(self._h, int(col))
 
-    def close(self):
-        if self._h:
-            for child in list(self._children):
-                child.close()
-            _lib.load().wgs_afset_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class EMBatch:
+class EMBatch(Handle):
     """A batch of EM fits over the slabs of one DeviceBeagle (wgs_em).
 
     fit j uses the individuals of group groups[j], leaving out individual skips[j] (global
     index) when >= 0 -- the leave-one-out re-fit of glassy.py:65-78.
     """
 
+    _destroy = "wgs_em_destroy"
     GUARD = 0.0    # floor of the band in which the exact serial chain decides (see guard_band)
 
     def __init__(self, beagle, groups, skips=None, mode=None):
@@ -357,14 +356,8 @@ class EMBatch:
         s = np.ascontiguousarray(skips if skips is not None else np.full(self.n_fits, -1), dtype=np.int32)
         h = ctypes.c_void_p()
         check(_lib.load().wgs_em_create(beagle.handle, self.n_fits, i32p(g), i32p(s), self.mode, ctypes.byref(h)))
-        self._h = h
-        beagle._children.add(self)
-        _live.add(self)
+        self._own(h, beagle)
         self.active = np.ones(self.n_fits, dtype=bool)
-
-    @property
-    def handle(self):
-        return self._h
 
     # ---- primitives (one C-ABI call each)
     def step(self):
@@ -464,17 +457,6 @@ class EMBatch:
         out = (ctypes.c_int64 * 4)()
         check(_lib.load().wgs_debug_em_sweep_paths(self._h, out))
         return [int(x) for x in out]
-
-    def close(self):
-        if self._h:
-            _lib.load().wgs_em_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def guard_band(m_total, guard=0.0):
@@ -613,10 +595,12 @@ def last_assign_ms(ctx):
 MAX_BLOCK_PARALLEL_PARTS = 64     # beyond this the chains are many and short: literal one-lane chains
 
 
-class Score:
+class Score(Handle):
     """The scoring step of glassy.py:31-42 / 92-109 on device-resident data (wgs_score): the n x K float64
     sums of the individuals [rows) in one reproducible sweep, and the reference's serial float32
     partition sums (utils.py:147-149) from block functions prepared in parallel on every SNP shard."""
+
+    _destroy = "wgs_score_destroy"
 
     def __init__(self, beagle, afset, colptr=None, rows=None):
         self.b, self.K, self.n = beagle, afset.K, beagle.n
@@ -625,10 +609,7 @@ class Score:
         self._keep, cp = _colptr_arg(colptr, self.n, self.K)
         h = ctypes.c_void_p()
         check(_lib.load().wgs_score_create(beagle.handle, afset.handle, cp, lo, hi, ctypes.byref(h)))
-        self._h = h
-        beagle._children.add(self)
-        afset._children.add(self)
-        _live.add(self)
+        self._own(h, beagle, afset)
         self.local = None
         self.ms = {}
 
@@ -709,21 +690,12 @@ class Score:
         k = _lib.load().wgs_score_last_serial_blocks(self._h, ctypes.byref(tot))
         return k, tot.value
 
-    def close(self):
-        if self._h:
-            _lib.load().wgs_score_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ScoreStream:
+class ScoreStream(Handle):
     """The accumulator of windowed scoring (wgs_score_stream): the n x K float64 totals over m_total sites from consecutive
     windows, np.sum's running total staying on the device from push to push -- bit for bit what one resident matrix gives."""
+
+    _destroy = "wgs_score_stream_destroy"
 
     def __init__(self, n, K, m_total, ctx=None):
         self.ctx = ctx or get_context()
@@ -732,13 +704,7 @@ class ScoreStream:
         self.sweep_ms = []                      # kernel time of every window's sweep
         h = ctypes.c_void_p()
         check(_lib.load().wgs_score_stream_create(self.ctx.handle, self.n, self.K, self.m_total, ctypes.byref(h)))
-        self._h = h
-        self.ctx._children.add(self)
-        _live.add(self)
-
-    @property
-    def handle(self):
-        return self._h
+        self._own(h, self.ctx)
 
     def push(self, beagle, afset, mode=None):
         """Scores one window: beagle.site0 must be the number of sites pushed so far (a multiple of 8192)."""
@@ -753,21 +719,12 @@ class ScoreStream:
         check(_lib.load().wgs_score_stream_finish(self._h, f64p(out)))
         return out
 
-    def close(self):
-        if self._h:
-            _lib.load().wgs_score_stream_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class EMStream:
+class EMStream(Handle):
     """The tables of a windowed fit (wgs_em_stream): S (maf_iter x n_fits float64 sums) and C (float32 chain carries) stay on the
     device from window to window; a round pushes every window once and reads them back once (windowed_fit.py keeps the rounds)."""
+
+    _destroy = "wgs_em_stream_destroy"
 
     def __init__(self, n_fits, maf_iter, m_total, ctx=None):
         self.ctx = ctx or get_context()
@@ -775,81 +732,53 @@ class EMStream:
         self.windows = 0
         h = ctypes.c_void_p()
         check(_lib.load().wgs_em_stream_create(self.ctx.handle, self.n_fits, self.maf_iter, self.m_total, ctypes.byref(h)))
-        self._h = h
-        self.ctx._children.add(self)
-        _live.add(self)
+        self._own(h, self.ctx)
 
-    @property
-    def handle(self):
-        return self._h
+    def _marshal(self, run_iters, final, clamp_lo, clamp_hi, chains, named="final and the clamps", fit_slot=None, sums_from=None):
+        """What every push hands the library, checked: ([run_iters, final, clamp_lo, clamp_hi, chain fits, chain iterations, number of
+        chains], fit_slot, sums_from), each a pointer (which keeps its array alive) or None where nothing was given.  `named`: what
+        the ValueError calls the arrays after run_iters and fit_slot."""
+        def ptr(values, dtype, as_ptr):
+            a = None if values is None else np.ascontiguousarray(values, dtype=dtype)
+            return a, (None if a is None or not a.size else as_ptr(a))
+        shape = (self.n_fits,)
+        (run, run_p), (slot, slot_p) = ptr(run_iters, np.int32, i32p), ptr(fit_slot, np.int32, i32p)
+        if run.shape != shape or (slot is not None and slot.shape != shape):
+            raise ValueError("%s must have one entry per fit" % ("run_iters" if slot is None else "run_iters and fit_slot"))
+        rest = [ptr(final, np.int32, i32p), ptr(clamp_lo, np.float32, f32p), ptr(clamp_hi, np.float32, f32p), ptr(sums_from, np.int32, i32p)]
+        if any(a is not None and a.shape != shape for a, _ in rest):
+            raise ValueError("%s must have one entry per fit" % named)
+        (_, fin_p), (_, lo_p), (_, hi_p), (_, from_p) = rest
+        (cf, cf_p), (_, ci_p) = ptr([c[0] for c in chains], np.int32, i32p), ptr([c[1] for c in chains], np.int32, i32p)
+        return [run_p, fin_p, lo_p, hi_p, cf_p, ci_p, len(cf)], slot_p, from_p
 
     def push(self, em, run_iters, final=None, clamp_lo=None, clamp_hi=None, chains=(), add_sums=False, f_out=None):
         """One window through its EMBatch: em.b.site0 must be the number of sites pushed so far in this round.  chains: (fit,
         iteration) pairs sorted by iteration; f_out: (n_fits, >= window rows) float32 that receives the final fits' rows."""
-        run = np.ascontiguousarray(run_iters, dtype=np.int32)
-        if run.shape != (self.n_fits,):
-            raise ValueError("run_iters must have one entry per fit")
-        fin = None if final is None else np.ascontiguousarray(final, dtype=np.int32)
-        lo = None if clamp_lo is None else np.ascontiguousarray(clamp_lo, dtype=np.float32)
-        hi = None if clamp_hi is None else np.ascontiguousarray(clamp_hi, dtype=np.float32)
-        for a in (fin, lo, hi):
-            if a is not None and a.shape != (self.n_fits,):
-                raise ValueError("final and the clamps must have one entry per fit")
-        cf = np.ascontiguousarray([c[0] for c in chains], dtype=np.int32)
-        ci = np.ascontiguousarray([c[1] for c in chains], dtype=np.int32)
+        plan, _, _ = self._marshal(run_iters, final, clamp_lo, clamp_hi, chains)
         stride = 0
         if f_out is not None:
             f_out = _as_f32c(f_out, "f_out")
             if f_out.ndim != 2 or f_out.shape[0] != self.n_fits:
                 raise ValueError("f_out must be (n_fits, rows)")
             stride = f_out.shape[1]
-        check(_lib.load().wgs_em_stream_push(self._h, em.handle, i32p(run), None if fin is None else i32p(fin),
-                                             None if lo is None else f32p(lo), None if hi is None else f32p(hi),
-                                             i32p(cf) if len(cf) else None, i32p(ci) if len(ci) else None, len(cf), int(bool(add_sums)),
-                                             None if f_out is None else f32p(f_out), int(stride)))
+        check(_lib.load().wgs_em_stream_push(self._h, em.handle, *plan, int(bool(add_sums)), None if f_out is None else f32p(f_out), int(stride)))
         self.windows += 1
 
     def push_keep(self, em, run_iters, final=None, clamp_lo=None, clamp_hi=None, chains=(), sums_from=None):
         """push() for fits the host does not want (wgs_em_stream_push_keep): a final fit is clamped and stays in `em` (em.f_dev),
         no frequencies are copied.  sums_from (n_fits,) or None (no sums): the sum of iteration t of fit k joins S for
         t > sums_from[k] only."""
-        run = np.ascontiguousarray(run_iters, dtype=np.int32)
-        if run.shape != (self.n_fits,):
-            raise ValueError("run_iters must have one entry per fit")
-        fin = None if final is None else np.ascontiguousarray(final, dtype=np.int32)
-        lo = None if clamp_lo is None else np.ascontiguousarray(clamp_lo, dtype=np.float32)
-        hi = None if clamp_hi is None else np.ascontiguousarray(clamp_hi, dtype=np.float32)
-        frm = None if sums_from is None else np.ascontiguousarray(sums_from, dtype=np.int32)
-        for a in (fin, lo, hi, frm):
-            if a is not None and a.shape != (self.n_fits,):
-                raise ValueError("final, the clamps and sums_from must have one entry per fit")
-        cf = np.ascontiguousarray([c[0] for c in chains], dtype=np.int32)
-        ci = np.ascontiguousarray([c[1] for c in chains], dtype=np.int32)
-        check(_lib.load().wgs_em_stream_push_keep(self._h, em.handle, i32p(run), None if fin is None else i32p(fin),
-                                                  None if lo is None else f32p(lo), None if hi is None else f32p(hi),
-                                                  i32p(cf) if len(cf) else None, i32p(ci) if len(ci) else None, len(cf),
-                                                  None if frm is None else i32p(frm)))
+        plan, _, from_p = self._marshal(run_iters, final, clamp_lo, clamp_hi, chains, "final, the clamps and sums_from", sums_from=sums_from)
+        check(_lib.load().wgs_em_stream_push_keep(self._h, em.handle, *plan, from_p))
         self.windows += 1
 
     def push_masked(self, em, keep, fit_slot, run_iters, final=None, clamp_lo=None, clamp_hi=None, chains=()):
         """push_keep() without sums for fits whose stopping test runs over a site subset (wgs_em_stream_push_masked): the chain of
         (fit, iteration) runs over the sites slot fit_slot[fit] of the zscore.KeepSet `keep` kept in this window; a fit that kept
         nothing here hands its carry on.  keep must have been made from em's matrix."""
-        run = np.ascontiguousarray(run_iters, dtype=np.int32)
-        slot = np.ascontiguousarray(fit_slot, dtype=np.int32)
-        if run.shape != (self.n_fits,) or slot.shape != (self.n_fits,):
-            raise ValueError("run_iters and fit_slot must have one entry per fit")
-        fin = None if final is None else np.ascontiguousarray(final, dtype=np.int32)
-        lo = None if clamp_lo is None else np.ascontiguousarray(clamp_lo, dtype=np.float32)
-        hi = None if clamp_hi is None else np.ascontiguousarray(clamp_hi, dtype=np.float32)
-        for a in (fin, lo, hi):
-            if a is not None and a.shape != (self.n_fits,):
-                raise ValueError("final and the clamps must have one entry per fit")
-        cf = np.ascontiguousarray([c[0] for c in chains], dtype=np.int32)
-        ci = np.ascontiguousarray([c[1] for c in chains], dtype=np.int32)
-        check(_lib.load().wgs_em_stream_push_masked(self._h, em.handle, keep.handle, i32p(slot), i32p(run), None if fin is None else i32p(fin),
-                                                    None if lo is None else f32p(lo), None if hi is None else f32p(hi),
-                                                    i32p(cf) if len(cf) else None, i32p(ci) if len(ci) else None, len(cf)))
+        plan, slot_p, _ = self._marshal(run_iters, final, clamp_lo, clamp_hi, chains, fit_slot=fit_slot)
+        check(_lib.load().wgs_em_stream_push_masked(self._h, em.handle, keep.handle, slot_p, *plan))
         self.windows += 1
 
     def read(self):
@@ -865,22 +794,13 @@ class EMStream:
         check(_lib.load().wgs_em_stream_read(self._h, None, f32p(C) if C.size else None))
         return C
 
-    def close(self):
-        if self._h:
-            _lib.load().wgs_em_stream_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LooStream:
+class LooStream(Handle):
     """The accumulator of the leave-one-out run in site windows (wgs_loo_stream): np.sum's n x K float64 totals and, for P > 0,
     the n x P x K serial float32 partition sums stay on the device from push to push -- bit for bit what glassy.loo_device gives
     on one resident matrix."""
+
+    _destroy = "wgs_loo_stream_destroy"
 
     def __init__(self, n, K, m_total, P=0, ctx=None):
         self.ctx = ctx or get_context()
@@ -888,13 +808,7 @@ class LooStream:
         self.windows = 0
         h = ctypes.c_void_p()
         check(_lib.load().wgs_loo_stream_create(self.ctx.handle, self.n, self.K, self.m_total, self.P, ctypes.byref(h)))
-        self._h = h
-        self.ctx._children.add(self)
-        _live.add(self)
-
-    @property
-    def handle(self):
-        return self._h
+        self._own(h, self.ctx)
 
     def push(self, em, afset, mode=None, scored=None):
         """Scores one window: `em` holds its n re-fits at their stopping iterations, clamped (EMStream.push_keep); afset the
@@ -915,22 +829,13 @@ class LooStream:
         check(_lib.load().wgs_loo_stream_finish(self._h, f64p(out), f32p(parts) if parts is not None else None))
         return out, parts
 
-    def close(self):
-        if self._h:
-            _lib.load().wgs_loo_stream_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FisherStream:
+class FisherStream(Handle):
     """--ne_obs in site windows (wgs_fisher_stream): every push gives the window's rows of f_obs and ne_obs; np.mean's running float32
     total of every individual's per-site terms stays on the device from push to push -- bit for bit what fisher.fisher_obs and
     fisher.fisher_obs_ind give on one resident matrix."""
+
+    _destroy = "wgs_fisher_stream_destroy"
 
     def __init__(self, n, K, m_total, ctx=None):
         self.ctx = ctx or get_context()
@@ -939,13 +844,7 @@ class FisherStream:
         self.sweep_ms = []                      # kernel time of every window's fused sweep
         h = ctypes.c_void_p()
         check(_lib.load().wgs_fisher_stream_create(self.ctx.handle, self.n, self.K, self.m_total, ctypes.byref(h)))
-        self._h = h
-        self.ctx._children.add(self)
-        _live.add(self)
-
-    @property
-    def handle(self):
-        return self._h
+        self._own(h, self.ctx)
 
     def push(self, beagle, afset):
         """One window (population slabs; beagle.site0 must be the number of sites pushed so far, a multiple of 8192): its
@@ -964,17 +863,6 @@ class FisherStream:
         out = np.zeros(self.n, dtype=np.float32)
         check(_lib.load().wgs_fisher_stream_finish(self._h, f32p(out)))
         return out
-
-    def close(self):
-        if self._h:
-            _lib.load().wgs_fisher_stream_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def partition_sums_exact(beagle, afset, colptr=None, P=1, comm=None, literal=False):

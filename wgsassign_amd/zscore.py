@@ -38,6 +38,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f32p, i32p
+from .device import Handle, get_context
 
 N_CLASSES = 253      # = WGS_Z_CLASSES: depth pairs (Ar, Aa) with Ar + Aa <= 21, class index d (d + 1) / 2 + Aa -- the dense tier
 MAX_DENSE = 21       # = wgs_zscore_max_depth()
@@ -162,15 +163,16 @@ def class_index(Ar, Aa):
 
 
 # ---------------------------------------------------------------- device objects
-class DepthTable:
+class DepthTable(Handle):
     """The allele-depth table of a DeviceBeagle's SNP shard on the device (wgs_depth)."""
+
+    _destroy, _at_exit = "wgs_depth_destroy", False       # (its matrix closes it)
 
     def __init__(self, beagle, AD=None, chunk_rows=None):
         self.b = beagle
         h = ctypes.c_void_p()
         check(_lib.load().wgs_depth_create(beagle.handle, ctypes.byref(h)))
-        self._h = h
-        beagle._children.add(self)
+        self._own(h, beagle)
         if AD is not None:
             check_depths(AD, beagle.m, beagle.n)
             step = chunk_rows or max(1, (64 << 20) // (8 * beagle.n))
@@ -206,10 +208,6 @@ class DepthTable:
             raise
         return t
 
-    @property
-    def handle(self):
-        return self._h
-
     def upload_rows(self, rows, row0=0):
         rows = np.ascontiguousarray(rows[:, :2 * self.b.n], dtype=np.int32)
         check(_lib.load().wgs_depth_upload_rows(self._h, i32p(rows), int(row0), rows.shape[0]))
@@ -220,20 +218,11 @@ class DepthTable:
         check(_lib.load().wgs_depth_download_rows(self._h, i32p(out), int(row0), int(nrows)))
         return out
 
-    def close(self):
-        if self._h:
-            _lib.load().wgs_depth_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class KeepSet:
+class KeepSet(Handle):
     """L_keep of individuals [i0, i0 + count) on the device (wgs_zkeep); .kept[j] = sites kept."""
+
+    _destroy, _at_exit = "wgs_zkeep_destroy", False       # (its table's matrix closes it)
 
     def __init__(self, depth, i0, key_mean, key_comp, deep_map=None, deep_rows=None):
         count = key_mean.shape[0]
@@ -251,12 +240,7 @@ class KeepSet:
             assert deep_map.shape == (count, DEEP_MAX + 1) and deep_rows.ndim == 2 and deep_rows.shape[1] == DEEP_ROW
             check(_lib.load().wgs_zkeep_create_deep(depth.handle, self.i0, count, f32p(key_mean), i32p(key_comp), i32p(deep_map),
                                                     f32p(deep_rows), deep_rows.shape[0], kept_p, ctypes.byref(h)))
-        self._h = h
-        depth.b._children.add(self)
-
-    @property
-    def handle(self):
-        return self._h
+        self._own(h, depth.b)
 
     def sites(self, slot):
         out = np.empty(int(self.kept[slot]), dtype=np.int32)
@@ -282,17 +266,6 @@ class KeepSet:
         dev, total = ctypes.c_void_p(), ctypes.c_int64()
         check(_lib.load().wgs_zscore_stats_dev(self._h, f32p(tables), ptrs, ctypes.byref(dev), ctypes.byref(total)))
         return dev, int(total.value)
-
-    def close(self):
-        if self._h:
-            _lib.load().wgs_zkeep_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------- the reference's functions, a batch of individuals at a time
@@ -620,24 +593,20 @@ def reference_z_scores(beagle, depth, IDs, group_of, maf_iter=200, maf_tole=1e-4
 
 
 # ---------------------------------------------------------------- --get_assignment_z_score in site windows
-class ZSum:
+class ZSum(Handle):
     """What a batch of individuals carries from site window to site window on the device (wgs_zsum): the class sweep's running sums
     and, per (individual, array) of the three per-site arrays, np.sum's float32 order -- the running value over the closed
     8192-element chunks and the open chunk."""
 
+    _destroy, _at_exit = "wgs_zsum_destroy", False        # (its context closes it)
+
     def __init__(self, count, ctx=None):
-        from .device import get_context
         self.ctx = ctx or get_context()
         self.count = int(count)
         self.downloaded = 0                          # bytes that crossed to the host through this object
         h = ctypes.c_void_p()
         check(_lib.load().wgs_zsum_create(self.ctx.handle, self.count, ctypes.byref(h)))
-        self._h = h
-        self.ctx._children.add(self)
-
-    @property
-    def handle(self):
-        return self._h
+        self._own(h, self.ctx)
 
     def classes(self, depth, i0):
         """The class sweep over the next window (wgs_zscore_classes_carry): counts, first sites (LOCAL, -1: none) and `over` of this
@@ -692,30 +661,17 @@ class ZSum:
                     sums[j, a] = run[j, a] + np.sum(tails[j][a]) if tails[j][a].size else run[j, a]
         return totals, sums
 
-    def close(self):
-        if self._h:
-            _lib.load().wgs_zsum_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class _ShapeTable:
+class _ShapeTable(Handle):
     """A depth table of its own shape (wgs_depth_create_shape): the landing place of a depth file's chunks."""
+
+    _destroy, _at_exit = "wgs_depth_destroy", False       # (the DepthWindows that made it closes it, else its context)
 
     def __init__(self, ctx, rows, n):
         h = ctypes.c_void_p()
         check(_lib.load().wgs_depth_create_shape(ctx.handle, int(rows), int(n), ctypes.byref(h)))
-        self.handle, self.rows = h, int(rows)
-
-    def close(self):
-        if self.handle:
-            _lib.load().wgs_depth_destroy(self.handle)
-            self.handle = None
+        self._own(h, ctx)
+        self.ctx, self.rows = ctx, int(rows)
 
 
 DEPTH_WINDOW_CHUNK = 8 << 20         # text bytes per chunk of a windowed depth pass
