@@ -1,7 +1,8 @@
-// Sanitizer driver for csrc/reader.cpp (host code only): index, indexed opens at several rows and thread counts,
+// Sanitizer driver for csrc/reader*.cpp (host code only): index, indexed opens at several rows and thread counts,
 // full reads; prints a checksum per configuration -- all must agree.  Then the two hand-overs of the device ingest, whose
 // producer threads run beside the consumer: inflated text (wgs_debug_reader_text_rows) and, for BGZF files, compressed
-// members (wgs_debug_reader_comp_text), both with small buffers so that many chunks change hands.
+// members (wgs_debug_reader_comp_text), both with small buffers so that many chunks change hands.  Last the early exits of
+// their chunk queue (csrc/reader_text.h): every stop must return, whatever the producer is doing.
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -9,6 +10,7 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include "reader_text.h"
 #include "wgsassign_hip.h"
 #include "wgsassign_hip_debug.h"
 
@@ -40,6 +42,46 @@ static uint64_t read_all(wgs_reader *r, int64_t chunk, int64_t *rows_out)
     }
     *rows_out = total;
     return h;
+}
+
+static TextAllocator heap()
+{
+    TextAllocator a;
+    a.alloc = [](size_t n, void *) { return malloc(n); };
+    a.release = [](void *p, void *) { free(p); };
+    return a;
+}
+
+// A hand-over stopped at once (take 0), with one chunk taken and never released (take 1, nbuf 2), and while the producer
+// waits for a free chunk that the consumer holds (take 1, nbuf 1).  comp: the compressed hand-over, which plain gzip refuses.
+static int stop_early(const char *path, bool comp, int nbuf, int take)
+{
+    wgs_reader *r = nullptr;
+    if (wgs_reader_open(path, 3, &r)) return 2;
+    int rc = comp ? reader_comp_start(r, 1, 1, nbuf, heap()) : reader_text_start(r, 1, nbuf, heap(), -1);
+    if (rc == 0 && take) {
+        TextChunk *t = nullptr;
+        CompChunk *c = nullptr;
+        rc = comp ? reader_comp_next(r, &c, nullptr) : reader_text_next(r, &t, nullptr);
+        if (rc == 0 && !t && !c) rc = 9;
+    }
+    if (comp) reader_comp_stop(r);
+    else reader_text_stop(r);
+    wgs_reader_close(r);
+    return comp && rc == 2 && strstr(g_err, "bad argument") ? 0 : rc;
+}
+
+// a row limit that ends inside the first chunk: those rows, then the end
+static int stop_at_limit(const char *path)
+{
+    wgs_reader *r = nullptr;
+    if (wgs_reader_open(path, 3, &r)) return 2;
+    int rc = reader_text_start(r, 1, 2, heap(), 3);
+    int64_t rows = 0;
+    for (TextChunk *c = nullptr; rc == 0 && (rc = reader_text_next(r, &c, nullptr)) == 0 && c; reader_text_release(r, c)) rows += (int64_t)c->begin.size();
+    reader_text_stop(r);
+    wgs_reader_close(r);
+    return rc ? rc : rows == 3 ? 0 : 9;
 }
 
 int main(int argc, char **argv)
@@ -103,6 +145,12 @@ int main(int argc, char **argv)
             return 8;
         }
     }
+    for (int comp = 0; comp < 2; ++comp) {
+        const int plan[3][2] = {{2, 0}, {2, 1}, {1, 1}};           // nbuf, chunks taken
+        for (const auto &q : plan)
+            if (int rc = stop_early(path, comp != 0, q[0], q[1])) { fprintf(stderr, "early stop (%s, %d buffers, %d taken): rc %d %s\n", comp ? "compressed" : "text", q[0], q[1], rc, g_err); return 9; }
+    }
+    if (int rc = stop_at_limit(path)) { fprintf(stderr, "row limit inside the first chunk: rc %d %s\n", rc, g_err); return 9; }
     printf("ok\n");
     return 0;
 }

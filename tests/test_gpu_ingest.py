@@ -1,5 +1,5 @@
 """The device-side ingest (csrc/ingest.hip: Beagle text tokenised on the MI355X straight into the population slabs)
-against the host parser (csrc/reader.cpp, itself pinned to the reference's parse by tests/test_reader_cpu.py) and the
+against the host parser (csrc/reader.cpp: parse_line, itself pinned to the reference's parse by tests/test_reader_cpu.py) and the
 golden parse of the bundled files (reader_cy.pyx:16-77)."""
 import gzip
 import os

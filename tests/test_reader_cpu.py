@@ -1,4 +1,4 @@
-"""CPU-only: the native streamed Beagle reader (csrc/reader.cpp) against the reference's parsing
+"""CPU-only: the native streamed Beagle reader (csrc/reader*.cpp) against the reference's parsing
 rules (reader_cy.pyx:16-77) -- golden parse of the bundled files, a pure-Python restatement,
 awkward tokens, chunking."""
 import gzip
@@ -343,7 +343,7 @@ def test_bgzf_parallel_index_and_block_parallel_inflate(tmp_path, monkeypatch, v
 
 
 def test_reader_clean_under_address_and_thread_sanitizers():
-    """csrc/reader.cpp is host code with worker threads (parallel parse, BGZF blocks, gzip stretches between access
+    """csrc/reader*.cpp is host code with worker threads (parallel parse, BGZF blocks, gzip stretches between access
     points): tools/reader_sanitize.sh builds it with -fsanitize=address,undefined and with -fsanitize=thread and drives
     the index pass, indexed opens at several rows and thread counts, and full reads whose checksums must agree."""
     import subprocess
@@ -685,7 +685,7 @@ def _comp_text(path, comp_bytes, text_cap, nbuf=2, threads=3, index=None, first_
 
 @pytest.mark.parametrize("block", [900, 60000])
 def test_compressed_hand_over_delivers_the_rest_of_the_file(tmp_path, monkeypatch, block):
-    """What the device-resident ingest consumes (reader.cpp: comp_producer): the text the header calls had inflated
+    """What the device-resident ingest consumes (reader_pipes.cpp: comp_producer): the text the header calls had inflated
     already, then whole BGZF members in staging buffers -- together exactly the file's text behind the header, whatever
     the staging and text limits (one buffer or two, slices that end inside members, limits below one slice), from the
     start and from a row in the middle through the index."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Host side of the device ingest alone (no GPU): the text hand-over of csrc/reader.cpp -- inflate ahead into buffers, cut at
+"""Host side of the device ingest alone (no GPU): the text hand-over of csrc/reader_pipes.cpp -- inflate ahead into buffers, cut at
 newlines, list the lines -- drained without parsing, with ordinary (not page-locked) buffers, per thread count.
    python tools/bench_inflate.py --inds 2000 --sites 100000 [--threads 4,8,16,32]"""
 import argparse

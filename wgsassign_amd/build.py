@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwgsassign_hip.so")
-SOURCES = ["api.hip", "em_api.hip", "score_api.hip", "codes.hip", "codes_kernels.hip", "em_kernels.hip", "assign_kernels.hip", "beagle_kernels.hip", "ingest.hip", "inflate.hip", "rccl_comm.hip", "zscore_api.hip", "zscore_kernels.hip", "reader.cpp"]
+SOURCES = ["api.hip", "em_api.hip", "score_api.hip", "codes.hip", "codes_kernels.hip", "em_kernels.hip", "assign_kernels.hip", "beagle_kernels.hip", "ingest.hip", "inflate.hip", "rccl_comm.hip", "zscore_api.hip", "zscore_kernels.hip", "reader.cpp", "reader_index.cpp", "reader_pipes.cpp"]
 # -ffp-contract=off: the exact-mode kernels restate the reference's rounding sequence operation by
 # operation; hipcc's default (fast) contraction would fuse a*b+c and change results.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"] + os.environ.get("WGSASSIGN_BUILD_DEFINES", "").split()
@@ -53,7 +53,7 @@ def source_ids():
 
 def build(force=False, verbose=False):
     cc = hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "em_state.h"), os.path.join(CSRC, "em_fit_ledger.h"), os.path.join(CSRC, "stream_checks.h"), os.path.join(CSRC, "streams.h"), os.path.join(CSRC, "log_table.h"), os.path.join(CSRC, "fast_math.h"), os.path.join(CSRC, "reader_text.h"), os.path.join(CSRC, "zscore.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "em_state.h"), os.path.join(CSRC, "em_fit_ledger.h"), os.path.join(CSRC, "stream_checks.h"), os.path.join(CSRC, "streams.h"), os.path.join(CSRC, "log_table.h"), os.path.join(CSRC, "fast_math.h"), os.path.join(CSRC, "reader_text.h"), os.path.join(CSRC, "reader_impl.h"), os.path.join(CSRC, "gz_source.h"), os.path.join(CSRC, "bgzf.h"), os.path.join(CSRC, "zscore.h"),
                os.path.join(HERE, "..", "include", "wgsassign_hip.h")]
     id_header = os.path.join(CSRC, "build_id.h")
     text = '#define WGS_BUILD_ID "%s"\n#define WGS_KERNELS_ID "%s"\n#define WGS_INGEST_KERNELS_ID "%s"\n' % source_ids()

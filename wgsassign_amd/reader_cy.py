@@ -1,5 +1,5 @@
 """Beagle reader: drop-in for `reader_cy.readBeagle` (reader_cy.pyx:16-77), backed by the
-native streamed reader of libwgsassign_hip.so (csrc/reader.cpp; host code, needs no GPU).
+native streamed reader of libwgsassign_hip.so (csrc/reader*.cpp; host code, needs no GPU).
 
 Header: every 3rd token after the first three is a sample name; per line token 0 is the site
 name, two allele columns are skipped, GL0 and GL1 are kept and GL2 dropped; values are
